@@ -34,26 +34,30 @@ espflix_amd/gen/libefx_gen.so: espflix_amd/gen/efx_gen.cpp $(CSRC)/mpeg1_codeboo
 
 # TEST: the reference's UNMODIFIED host player (src/espflix.cpp) and platform layer (src/streamer.cpp) built against
 # libefx's drop-in headers instead of src/player.h / src/video.h -- player.cpp and video.cpp are not in the build.
-# Only where the reference tree exists (the build container); the binaries travel to the GPU box like the .so files.
+# Only where the reference tree exists.  Everything it makes lies under oracle/_ref/dropin, beside the other binaries
+# built from the reference, and nothing under tests/.
 REF ?= /root/reference
 DROPIN_FLAGS = -std=c++14 -O1 -w -fpermissive -pthread -Iinclude/espflix_dropin -Iinclude -I$(REF)/src
-DROPIN_LIBS  = -Lespflix_amd -lefx -Wl,-rpath,'$$ORIGIN/../../espflix_amd' -Wl,-rpath,/opt/rocm/lib -L/opt/rocm/lib -lamdhip64
+DROPIN_LIBS  = -Lespflix_amd -lefx -Wl,-rpath,'$$ORIGIN/../../../espflix_amd' -Wl,-rpath,/opt/rocm/lib -L/opt/rocm/lib -lamdhip64
 # (a quoted #include looks in the including file's own directory first, so the reference sources are reached through
 # symbolic links in a scratch directory that holds neither player.h nor video.h: those two -- and only those -- come
-# from include/espflix_dropin; a maintainer simply replaces the two files in src/)
-DROPIN_SRC = tests/_build/dropin_src
-dropin: tests/_build/espflix_dropin tests/_build/espflix_dropin_long
-$(DROPIN_SRC)/espflix.cpp:
-	mkdir -p $(DROPIN_SRC)
-	ln -sf $(REF)/src/espflix.cpp $(DROPIN_SRC)/espflix.cpp
-	ln -sf $(REF)/src/streamer.cpp $(DROPIN_SRC)/streamer.cpp
-tests/_build/espflix_dropin: $(DROPIN_SRC)/espflix.cpp tests/dropin_main.cpp include/efx_player.hpp include/espflix_dropin/player.h espflix_amd/libefx.so
-	g++ $(DROPIN_FLAGS) tests/dropin_main.cpp $(DROPIN_SRC)/espflix.cpp $(DROPIN_SRC)/streamer.cpp $(DROPIN_LIBS) -o $@
+# from include/espflix_dropin; a maintainer simply replaces the two files in src/.  Each recipe makes its own scratch
+# directory, $@.src, and removes it once the binary is linked)
+DROPIN      = oracle/_ref/dropin
+DROPIN_REF  = $(REF)/src/espflix.cpp $(REF)/src/streamer.cpp
+DROPIN_LINK = rm -rf $@.src && mkdir -p $@.src && ln -s $(DROPIN_REF) $@.src/
+dropin: $(DROPIN)/espflix_dropin $(DROPIN)/espflix_dropin_long
+$(DROPIN)/espflix_dropin: $(DROPIN_REF) tests/dropin_main.cpp include/efx_player.hpp include/espflix_dropin/player.h espflix_amd/libefx.so
+	$(DROPIN_LINK)
+	g++ $(DROPIN_FLAGS) tests/dropin_main.cpp $@.src/espflix.cpp $@.src/streamer.cpp $(DROPIN_LIBS) -o $@
+	rm -rf $@.src
 # the same unmodified code playing a 1008-picture synthetic stream: src/splash.h is shadowed by a generated header
-tests/_build/dropin_long/splash.h: tests/make_dropin_long.py espflix_amd/gen/libefx_gen.so
-	python3 tests/make_dropin_long.py tests/_build/dropin_long
-tests/_build/espflix_dropin_long: tests/_build/dropin_long/splash.h $(DROPIN_SRC)/espflix.cpp tests/dropin_main.cpp include/efx_player.hpp espflix_amd/libefx.so
-	g++ -Itests/_build/dropin_long $(DROPIN_FLAGS) tests/dropin_main.cpp $(DROPIN_SRC)/espflix.cpp $(DROPIN_SRC)/streamer.cpp $(DROPIN_LIBS) -o $@
+$(DROPIN)/long/splash.h: tests/make_dropin_long.py espflix_amd/gen/libefx_gen.so
+	python3 tests/make_dropin_long.py $(DROPIN)/long
+$(DROPIN)/espflix_dropin_long: $(DROPIN)/long/splash.h $(DROPIN_REF) tests/dropin_main.cpp include/efx_player.hpp espflix_amd/libefx.so
+	$(DROPIN_LINK)
+	g++ -I$(DROPIN)/long $(DROPIN_FLAGS) tests/dropin_main.cpp $@.src/espflix.cpp $@.src/streamer.cpp $(DROPIN_LIBS) -o $@
+	rm -rf $@.src
 
 # the C++ scaling harness over the multi-device C-ABI (efx_multi_*), RCCL for the gather of the chain hashes
 scale: tools/efx_scale

@@ -12,15 +12,22 @@ max-over-ranks time, the all-gather of per-stream frame-chain hashes and the cou
 
     python bench.py --gpus N --steps K --warmup W       N > 1 without a torchrun environment re-launches
                                                          itself under torch.distributed.run (one rank per GPU)
+                    [--full] [--dump-outputs DIR]
 
-Parity gate: BEFORE the timed region every stream of the shard is decoded
+A plain run does only what the headline figure needs: it generates and uploads the batch, warms up (one untimed call + W),
+times K calls and prints the result line (metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds per
+timed call, and the timed region's stage times).  --dump-outputs DIR writes what the last timed call left a caller
+(dump_outputs): the same arguments give the same inputs, so two builds can be compared output for output.  Everything
+else below -- parity gate, the other legs, roofline, CPU baselines -- runs with --full.
+
+Parity gate (--full): BEFORE the timed region every stream of the shard is decoded
 with all pictures kept and every picture's frame hash is compared with tests/golden/bench_*.u64 --
 the output of the unmodified reference decoder on the same streams (tests/golden/make_bench_golden.py).
 After the timed region the two frames left in the double buffer are compared again, the per-stream
 chain hashes are all-gathered and rank 0 checks the whole job against the golden table.  A mismatch
 aborts the run: no number is printed for a decoder that differs from the reference.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  Extra objects of a --full run:
   roofline          dominant kernel's algorithmic GB/s vs the 8 TB/s HBM peak (HIP-event stage times
                     measured inside the timed region on the kernels' own streams)
   cpu_baseline      the unmodified reference decoder (oracle/_ref, kind "reference") -- or the C
@@ -575,12 +582,11 @@ def timed_region(job, dec, steps, warmup, overlap=True):
 _GEN_CACHE = {}  # --soak: a leg is repeated with the same streams
 
 
-def run_workload(job, args, workload, S, ids, gen_threads, steps, warmup, want_serial=True, sustained_steps=0):
-    """Generate, gate, time one workload on this rank.  Returns a dict of rank-local + job results."""
-    from espflix_amd import dist as edist
+def generate_streams(args, workload, S, ids, gen_threads):
+    """The streams of `ids` for `workload` (deterministic: the same ids give the same bytes).  Returns (batches, streams,
+    seconds)."""
     from espflix_amd import gen
     flags, _, _, P = WORKLOADS[workload][:4]
-    golden = load_golden(workload)
     t_gen = time.perf_counter()
     # ids are contiguous per rank (or wrapped for the small tables): generate in runs of consecutive ids
     key = (workload, S, int(ids[0]), int(ids[-1]))
@@ -599,7 +605,56 @@ def run_workload(job, args, workload, S, ids, gen_threads, steps, warmup, want_s
             start = end
         if getattr(args, "soak", None):
             _GEN_CACHE[key] = (batches, streams)
-    t_gen = time.perf_counter() - t_gen
+    return batches, streams, time.perf_counter() - t_gen
+
+
+def pin_launch_structure(dec, args):
+    """The launch structure is pinned for the timed steps (efx_set_option): ONE reconstruction group per call -- what back-to-back
+    calls run as anyway, except that the FIRST call after a synchronisation finds the GPU idle and could be split -- so all K
+    calls are the same k_index ... k_recon launches and the per-launch figures are exact.  The parse kernel's residency cap
+    stays automatic: the first call's parser, with nothing to run beside, may have the whole chip (0.84 instead of 1.38 ms
+    of pipeline fill: 2 % of a 20-step region); `launch_structure.parse_cap` says so.  Returns whether it pinned."""
+    pinned = hasattr(dec, "set_option") and not args.no_overlap
+    if pinned:
+        import espflix_amd as efx
+        dec.set_option(efx.OPT_GROUPS, 1)
+        dec.set_option(efx.OPT_PARSE_CAP, 1 if args.pin_parse_cap else 0)
+    return pinned
+
+
+DUMP_STREAMS, DUMP_SEED = 32, 20260  # --dump-outputs: frames of a fixed, seeded sample of the job's streams (26 MB as float32)
+
+
+def dump_outputs(dec, S, P, ids, out_dir, rank, world):
+    """--dump-outputs DIR: what a caller of the timed path holds after its last step, as DIR/<name>.npy (float32 / float64;
+    rank r > 0 appends _rank<r>).  The ring holds pictures P-2 and P-1 of every stream: their frames (Y plane then the two
+    chroma planes, 101376 bytes) for a fixed sample of the streams, and for every stream their device-computed FNV-1a-64
+    hashes (split into exact 32-bit halves), its picture count and its status word."""
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "" if rank == 0 else f"_rank{rank}"
+    slots = [dec.picture_slot(p) for p in (P - 2, P - 1)]
+    hashes = dec.frame_hashes()[:, slots]
+    n = min(S, max(1, DUMP_STREAMS // world))
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(S, n, replace=False))
+    arrays = {
+        "frames": np.stack([np.stack([dec.download_frame(int(i), s) for s in slots]) for i in pick]).astype(np.float32),
+        "frame_stream_ids": np.asarray(ids)[pick].astype(np.float64),
+        "frame_hash_hi": (hashes >> np.uint64(32)).astype(np.float64),
+        "frame_hash_lo": (hashes & np.uint64(0xFFFFFFFF)).astype(np.float64),
+        "picture_counts": np.array([dec.picture_count(i) for i in range(S)], dtype=np.float64),
+        "stream_status": np.array([dec.stream_status(i) for i in range(S)], dtype=np.float64),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + sfx + ".npy"), a)
+    log(f"outputs of the last timed step: {', '.join(arrays)} in {out_dir} ({sum(a.nbytes for a in arrays.values()) / 1e6:.1f} MB)")
+
+
+def run_workload(job, args, workload, S, ids, gen_threads, steps, warmup, want_serial=True, sustained_steps=0, dump_dir=None):
+    """Generate, gate, time one workload on this rank.  Returns a dict of rank-local + job results."""
+    from espflix_amd import dist as edist
+    flags, _, _, P = WORKLOADS[workload][:4]
+    golden = load_golden(workload)
+    batches, streams, t_gen = generate_streams(args, workload, S, ids, gen_threads)
     es_bytes = int(sum(s.size for s in streams))
     n_i = S * ((P + 11) // 12)
     n_p = S * P - n_i
@@ -611,18 +666,11 @@ def run_workload(job, args, workload, S, ids, gen_threads, steps, warmup, want_s
 
     dec.upload(streams, 0)  # bitstreams resident in HBM from here on
     dec.set_timing(True)
-    # The launch structure is pinned for the timed steps (efx_set_option): ONE reconstruction group per call -- what back-to-back
-    # calls run as anyway, except that the FIRST call after a synchronisation finds the GPU idle and could be split -- so all K
-    # calls are the same k_index ... k_recon launches and the per-launch figures are exact.  The parse kernel's residency cap
-    # stays automatic: the first call's parser, with nothing to run beside, may have the whole chip (0.84 instead of 1.38 ms
-    # of pipeline fill: 2 % of a 20-step region); `launch_structure.parse_cap` says so.
-    pinned = hasattr(dec, "set_option") and not args.no_overlap
-    if pinned:
-        import espflix_amd as efx
-        dec.set_option(efx.OPT_GROUPS, 1)
-        dec.set_option(efx.OPT_PARSE_CAP, 1 if args.pin_parse_cap else 0)
+    pinned = pin_launch_structure(dec, args)
     elapsed = timed_region(job, dec, steps, warmup, overlap=not args.no_overlap)
     t = dec.timing()
+    if dump_dir:
+        dump_outputs(dec, S, P, ids, dump_dir, job.rank, job.world)
     stage_ms = np.array([t.index_ms, t.parse_ms, t.recon_ms])
     timed_calls = t.timed_calls
     groups = max(1, int(getattr(t, "groups", 1)))  # reconstruction groups of a call
@@ -719,6 +767,7 @@ def run_workload(job, args, workload, S, ids, gen_threads, steps, warmup, want_s
                 "efx_upload_done() of the one before; the arena's content is laid out once (a receiver fills it by DMA)")
 
     if pinned:
+        import espflix_amd as efx
         dec.set_option(efx.OPT_GROUPS, 0)
         dec.set_option(efx.OPT_PARSE_CAP, 0)
     serial_ms = None
@@ -820,17 +869,75 @@ def soak(job, args):
     log(f"SOAK_OK {leg} {n}")
 
 
+def headline(job, args, S, P, job_pictures, elapsed, es_bytes, n_coefs):
+    """The keys of the result line that a plain run and a --full run share: the metric of the primary timed region."""
+    world, steps = job.world, args.steps
+    return {
+        "metric": "MPEG-1 352x192 frames/s", "value": job_pictures * steps / elapsed, "unit": "frames/s", "n_gpus": world,
+        "steps": steps, "warmup": args.warmup, "ms_per_step": elapsed / steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8/int32", "data": "synthetic",
+        "config": {"workload": f"{S} streams/GPU x GOP(12) I+11P, 352x192 MPEG-1 ES resident in HBM, ids rank*{S}.. per rank "
+                               f"(BASELINE configs[2]; at 8 GPUs = configs[4], stream k on rank floor(k*8/8192))",
+                   "streams_per_gpu": S, "streams_total": S * world, "pictures_per_stream": P, "es_bytes_per_gpu": es_bytes,
+                   "mean_bytes_per_picture": es_bytes / (S * P), "parallelism": f"stream-partition x{world}",
+                   "coefficients_per_gpu": n_coefs, "ring_depth": 2},
+    }
+
+
+def primary_ids(job, S):
+    from espflix_amd import dist as edist
+    first, _ = edist.shard(job.rank, job.world, S)
+    return np.arange(first, first + S)
+
+
+def run_plain(job, args):
+    """A plain run (no --full): only what the headline figure needs.  The primary workload's batch is generated, uploaded
+    and timed exactly as the --full run's primary timed region times it (launch structure pinned, stage timing on, W warm-up
+    + K timed calls, barrier + synchronize on both sides, max over ranks); --dump-outputs writes what the last timed call
+    left.  No parity gate and no other leg: they are --full."""
+    from espflix_amd import dist as edist
+    S = args.streams
+    ids = primary_ids(job, S)
+    threads = max(1, usable_cores() // max(1, job.local_world))
+    P = WORKLOADS["gop12"][3]
+    _, streams, t_gen = generate_streams(args, "gop12", S, ids, threads)
+    es_bytes = int(sum(s.size for s in streams))
+    dec = job.make_decoder(S, P, 2, es_bytes + 64 * S)
+    dec.upload(streams, 0)
+    dec.set_timing(True)
+    pinned = pin_launch_structure(dec, args)
+    # the --full run's timed steps follow the parity gate's decode of this batch (the kernels loaded and run once): one
+    # untimed call here, so that the W warm-up calls and the K timed ones start from the same state
+    dec.decode()
+    elapsed = timed_region(job, dec, args.steps, args.warmup, overlap=not args.no_overlap)
+    t = dec.timing()
+    if args.dump_outputs:
+        dump_outputs(dec, S, P, ids, args.dump_outputs, job.rank, job.world)
+    totals = edist.sum_over_ranks([S * P], job.dist, job.device)
+    dec.close()
+    if job.rank != 0:
+        return None
+    out = headline(job, args, S, P, totals[0], elapsed, es_bytes, int(t.coefficients))
+    out["stage_ms"] = {"k_index(+scan,emit)": float(t.index_ms), "k_parse": float(t.parse_ms), "k_recon": float(t.recon_ms)}
+    out["launch_structure"] = {"pinned": bool(pinned), "mixed": int(getattr(t, "mixed", 0)), "timed_calls_averaged": t.timed_calls}
+    out["gen_seconds"] = t_gen
+    out["full"] = False
+    return out
+
+
 def run(job, args):
     from espflix_amd import dist as edist
     rank, world = job.rank, job.world
     S = args.streams
     threads = max(1, usable_cores() // max(1, job.local_world))
-    first, _ = edist.shard(rank, world, S)
-    ids = np.arange(first, first + S)
+    ids = primary_ids(job, S)
     if world > 1 and rank == 0:
         log(f"{'RCCL' if job.device == 'cuda' else 'gloo'} saw {world} ranks")
+    if not args.full:
+        return run_plain(job, args)
 
-    r = run_workload(job, args, "gop12", S, ids, threads, args.steps, args.warmup, sustained_steps=args.sustained_steps)
+    r = run_workload(job, args, "gop12", S, ids, threads, args.steps, args.warmup, sustained_steps=args.sustained_steps,
+                     dump_dir=args.dump_outputs)
     P = r["P"]
 
     # SURVEY 8d config 5 as written: the FIXED 8192-stream batch, stream k on rank floor(k*N/8192)
@@ -893,7 +1000,6 @@ def run(job, args):
     if rank != 0:
         return None
     steps = args.steps
-    value = r["job_pictures"] * steps / r["elapsed"]
     stage_ms = r["stage_ms"]
     names = ["k_index(+scan,emit)", "k_parse", "k_recon x%d" % P]
     alg = algorithmic_bytes(r["es_bytes"], r["n_i"], r["n_p"])
@@ -933,15 +1039,8 @@ def run(job, args):
                  "source": "profiles/r6_issue_floor.json (tools/issue_floor.py)"}
         # what the numbers say: the larger of the two fractions names the nearer roof
         bound = "valu_issue" if issue["frac"] > achieved / HBM_PEAK_GBS else "hbm"
-    out = {
-        "metric": "MPEG-1 352x192 frames/s", "value": value, "unit": "frames/s", "n_gpus": world,
-        "steps": steps, "warmup": args.warmup, "ms_per_step": r["elapsed"] / steps * 1e3,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8/int32", "data": "synthetic",
-        "config": {"workload": f"{S} streams/GPU x GOP(12) I+11P, 352x192 MPEG-1 ES resident in HBM, ids rank*{S}.. per rank "
-                               f"(BASELINE configs[2]; at 8 GPUs = configs[4], stream k on rank floor(k*8/8192))",
-                   "streams_per_gpu": S, "streams_total": S * world, "pictures_per_stream": P, "es_bytes_per_gpu": r["es_bytes"],
-                   "mean_bytes_per_picture": r["es_bytes"] / (S * P), "parallelism": f"stream-partition x{world}",
-                   "coefficients_per_gpu": r["n_coefs"], "ring_depth": 2},
+    out = headline(job, args, S, P, r["job_pictures"], r["elapsed"], r["es_bytes"], r["n_coefs"])
+    out.update({
         "roofline": {"bound": bound, "bound_note": "achieved / peak / frac are SURVEY 8d's algorithmic bytes against the HBM roofline, as the "
                      "contract asks; the resource this kernel is nearest to is vector-instruction ISSUE (`issue`): its arithmetic at the "
                      "measured opcode rates (profiles/r6_valu_rates.md) fills issue.frac of the chip's SIMD cycles in the timed region and "
@@ -983,7 +1082,8 @@ def run(job, args):
         "video_out": video_out,
         "cpu_baseline": cpu,
         "cpu_baseline_o3": cpu_o3,
-    }
+        "full": True,
+    })
     return out
 
 
@@ -1005,6 +1105,10 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--streams", type=int, default=1024, help="streams per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: parity gate, sustained / ingest / one-call-at-a-time legs, roofline, "
+                         "fixed batch, other workloads, video out, CPU baselines (the --no-* options below select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy")
     ap.add_argument("--fixed-batch", type=int, default=FIXED_BATCH, help="streams of the fixed (strong-scaling) batch")
     ap.add_argument("--no-fixed-batch", action="store_true")
     ap.add_argument("--no-other-workloads", action="store_true")

@@ -53,7 +53,7 @@ def _run_job(world, extra, port):
 
 
 def test_two_rank_gloo_job_runs_the_bench_control_flow():
-    p = _run_job(2, ["--streams", "3", "--steps", "2", "--warmup", "1", "--fixed-batch", "9", "--cpu-baseline-seconds", "0.2"], 29533)
+    p = _run_job(2, ["--full", "--streams", "3", "--steps", "2", "--warmup", "1", "--fixed-batch", "9", "--cpu-baseline-seconds", "0.2"], 29533)
     assert p.returncode == 0, p.stderr[-3000:]
     assert "gloo saw 2 ranks" in p.stderr
     out = json.loads([l for l in p.stdout.splitlines() if l.startswith("RESULT ")][0][7:])
@@ -70,10 +70,26 @@ def test_two_rank_gloo_job_runs_the_bench_control_flow():
     # value = pictures of ALL ranks / max-over-ranks time
     assert abs(out["value"] * out["ms_per_step"] / 1e3 - 6 * 12) < 1e-6
     # the same job in one process: same per-stream hashes, hence the same checksum of checksums
-    q = _run_job(1, ["--streams", "6", "--steps", "1", "--warmup", "0", "--no-fixed-batch", "--no-other-workloads", "--no-cpu-baseline"], 29534)
+    q = _run_job(1, ["--full", "--streams", "6", "--steps", "1", "--warmup", "0", "--no-fixed-batch", "--no-other-workloads", "--no-cpu-baseline"],
+                 29534)
     assert q.returncode == 0, q.stderr[-3000:]
     one = json.loads([l for l in q.stdout.splitlines() if l.startswith("RESULT ")][0][7:])
     assert one["checksum_of_checksums"] == out["checksum_of_checksums"]
+
+
+def test_plain_run_reports_only_the_headline():
+    # without --full: the timed region and the result line, nothing else (no gate, no other leg)
+    p = _run_job(2, ["--streams", "3", "--steps", "3", "--warmup", "1"], 29536)
+    assert p.returncode == 0, p.stderr[-3000:]
+    out = json.loads([l for l in p.stdout.splitlines() if l.startswith("RESULT ")][0][7:])
+    assert out["full"] is False and out["steps"] == 3 and out["warmup"] == 1 and out["n_gpus"] == 2
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in out
+    assert out["launch_structure"]["timed_calls_averaged"] == 3       # exactly --steps calls were timed
+    assert abs(out["value"] * out["ms_per_step"] / 1e3 - 6 * 12) < 1e-6
+    for k in ("roofline", "parity_gate", "fixed_batch_8192", "other_workloads", "cpu_baseline", "sustained", "ingest"):
+        assert k not in out
+    assert "leg:" not in p.stderr
 
 
 def test_bench_aborts_when_a_stream_differs_from_the_reference(tmp_path):
@@ -92,7 +108,7 @@ def test_bench_aborts_when_a_stream_differs_from_the_reference(tmp_path):
         "dist_worker.main()\n")
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29535")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", "29535", str(worker), "--gpus", "2", "--streams", "2", "--steps", "1", "--warmup", "0",
+           "--master-port", "29535", str(worker), "--gpus", "2", "--full", "--streams", "2", "--steps", "1", "--warmup", "0",
            "--no-fixed-batch", "--no-cpu-baseline"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode != 0

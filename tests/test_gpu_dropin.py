@@ -1,5 +1,5 @@
 """The real binding: the reference's UNMODIFIED host player src/espflix.cpp and platform layer src/streamer.cpp,
-compiled (by `make dropin`, in the build container, where the reference tree is) against libefx's drop-in
+compiled (by `make dropin`, where the reference tree is, into oracle/_ref/dropin) against libefx's drop-in
 headers include/espflix_dropin/{player,video}.h instead of src/player.h / src/video.h -- src/player.cpp and
 src/video.cpp are not in the build.  ESPFlix::run() -> play_rom(splash_ts) (src/espflix.cpp:1043-1058) then
 drives MpegDecoder exactly as on the device; every push_video() up-call must carry the frame and PTS the
@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 
 
 def run_dropin(name, tmp_path):
-    exe = os.path.join(ROOT, "tests", "_build", name)
+    exe = os.path.join(ROOT, "oracle", "_ref", "dropin", name)
     if not os.path.exists(exe):
         pytest.skip(f"{exe} was not built (`make dropin` needs the reference tree)")
     log = str(tmp_path / "dropin.log")
@@ -49,7 +49,7 @@ def test_unmodified_espflix_plays_the_splash_clip(tmp_path, golden):
 
 def test_unmodified_espflix_plays_a_thousand_pictures(tmp_path):
     frames, done, err = run_dropin("espflix_dropin_long", tmp_path)
-    path = os.path.join(ROOT, "tests", "_build", "dropin_long", "long.ts")
+    path = os.path.join(ROOT, "oracle", "_ref", "dropin", "long", "long.ts")
     ts = np.fromfile(path, dtype=np.uint8)
     n, h, pts, _ = oracle.decode(ts, 1, flush_last=False, max_frames=1100)
     assert n == 1007 and len(frames) == n

@@ -10,10 +10,10 @@ out=gpurun_out/prof_$1; mkdir -p $out
 # --timed-only + 200 steps: 2400 of the 2436 k_recon launches of the process (12 per step: one group of 1024 streams x 12
 # picture indexes, pinned) belong to the timed region, so the average rocprofv3 reports is the one bench.py measures with HIP
 # events (roofline.avg_launch_ms)
-B="python bench.py --steps 200 --warmup 3 --no-cpu-baseline --no-fixed-batch --no-other-workloads --no-video-out --timed-only"
+B="python bench.py --full --steps 200 --warmup 3 --no-cpu-baseline --no-fixed-batch --no-other-workloads --no-video-out --timed-only"
 timeout 150 rocprofv3 --kernel-trace --stats --output-format csv -d $out -o pipelined -- $B > $out/bench_pipelined.log 2>&1
 timeout 150 rocprofv3 --kernel-trace --stats --output-format csv -d $out -o serial -- $B --no-overlap > $out/bench_serial.log 2>&1
-S="python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-fixed-batch --no-other-workloads --no-video-out --no-overlap"
+S="python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-fixed-batch --no-other-workloads --no-video-out --no-overlap"
 for c in FETCH_SIZE WRITE_SIZE; do
   EFX_FORCE_PARSE_CAP=1 timeout 120 rocprofv3 --pmc $c --output-format csv -d $out/pmc_$c -o p -- $S > /dev/null 2>&1
   EFX_FORCE_PARSE_CAP=2 timeout 120 rocprofv3 --pmc $c --output-format csv -d $out/pmcu_$c -o p -- $S > /dev/null 2>&1

@@ -1,7 +1,7 @@
 #!/bin/bash
 # development aid: instruction-fetch counters of k_recon / k_parse (serial mode: counter collection serialises dispatches)
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
-S="python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-fixed-batch --no-other-workloads --no-video-out --no-overlap"
+S="python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-fixed-batch --no-other-workloads --no-video-out --no-overlap"
 run() { name=$1; shift; timeout 120 rocprofv3 --pmc "$@" --output-format csv -d gpurun_out/pmci_$name -o p -- $S > gpurun_out/pmci_$name.log 2>&1; echo "$name rc=$?"; }
 run ic SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_BUSY_CYCLES
 run if SQ_IFETCH SQ_IFETCH_LEVEL SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES

@@ -1,7 +1,7 @@
 #!/bin/bash
 # development aid: memory REQUEST counters of k_recon / k_parse (serial mode: counter collection serialises dispatches)
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
-S="python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-fixed-batch --no-other-workloads --no-video-out --no-overlap"
+S="python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-fixed-batch --no-other-workloads --no-video-out --no-overlap"
 run() { name=$1; shift; timeout 120 rocprofv3 --pmc "$@" --output-format csv -d gpurun_out/pmcm_$name -o p -- $S > gpurun_out/pmcm_$name.log 2>&1; echo "$name rc=$?"; }
 run tcc TCC_REQ_sum TCC_READ_sum TCC_WRITE_sum TCC_HIT_sum TCC_MISS_sum
 run tcp TCP_TCC_READ_REQ_sum TCP_TCC_WRITE_REQ_sum TCP_PENDING_STALL_CYCLES_sum TCP_GATE_EN1_sum

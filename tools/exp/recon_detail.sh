@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 for v in "$@"; do
 export EFX_LIB=$GRAFT_REPO_ROOT/espflix_amd/libefx_$v.so
-B="python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-overlap --no-fixed-batch --no-other-workloads"
+B="python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-overlap --no-fixed-batch --no-other-workloads"
 timeout 120 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/rd_$v -o s -- $B > gpurun_out/rd_$v.log 2>&1
 timeout 120 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --output-format csv -d gpurun_out/rdp_$v -o p -- $B > /dev/null 2>&1
 timeout 120 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VALU SQ_INST_CYCLES_VMEM --output-format csv -d gpurun_out/rdq_$v -o p -- $B > /dev/null 2>&1

@@ -2,7 +2,7 @@
 # development aid: rocprofv3 kernel-trace stats of a short serial bench run
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 tag=${1:-x}; shift
-B="python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-fixed-batch --no-other-workloads $@"
+B="python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-fixed-batch --no-other-workloads $@"
 timeout 150 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/st_$tag -o s -- $B > gpurun_out/st_$tag.log 2>&1
 f=$(find gpurun_out/st_$tag -name "*kernel_stats.csv" | head -1)
 python - <<P
