@@ -25,6 +25,10 @@ FRAME_BYTES = 101376
 
 OPT_GROUPS, OPT_PARSE_CAP, OPT_RECON_MODE, OPT_RECON_WAVES, OPT_RECON_SPINS, OPT_RECON_ITEMS, OPT_SBC_SERIAL, OPT_DEMUX_FUSED = 1, 2, 3, 4, 5, 6, 7, 8   # efx_option
 SBC_PROBE_FIRST = 1
+PIX_I420, PIX_RGB24, PIX_RGBP = 0, 1, 2     # efx_pixel_format
+CHROMA_NEAREST, CHROMA_BILINEAR = 0, 1
+_PIX_FORMATS = {"i420": PIX_I420, "rgb24": PIX_RGB24, "rgbp": PIX_RGBP}
+_CHROMA_MODES = {"nearest": CHROMA_NEAREST, "bilinear": CHROMA_BILINEAR}
 FORMAT_ES = 0
 FORMAT_TS = 1
 
@@ -68,6 +72,11 @@ class _FieldOpts(C.Structure):
     _fields_ = [("first_stream", C.c_int), ("n_streams", C.c_int), ("slot", C.c_int), ("other_slot", C.c_int),
                 ("ntsc", C.c_int), ("frame_counter", C.c_int), ("hscroll", C.c_int), ("overlay", C.c_void_p),
                 ("overlay_stride", C.c_size_t), ("overlay_blend", C.c_int), ("overlay_progress", C.c_int)]
+
+
+class _ExportOpts(C.Structure):
+    _fields_ = [("first_stream", C.c_int), ("n_streams", C.c_int), ("slot", C.c_int), ("picture", C.c_int), ("format", C.c_int),
+                ("chroma", C.c_int), ("full_range", C.c_int), ("dst_stride", C.c_size_t)]
 
 
 class _IdxRec(C.Structure):
@@ -120,6 +129,8 @@ _SYMBOLS = {
     "efx_frame_hashes": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "efx_upload_frame": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "efx_video_get_params": (C.c_int, [C.c_int, C.POINTER(_VideoParams)]),
+    "efx_export_bytes": (C.c_size_t, [C.c_int]),
+    "efx_export_frames": (C.c_int, [_P, C.POINTER(_ExportOpts), _P]),
     "efx_composite_fields": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "efx_composite_fields_ex": (C.c_int, [_P, C.POINTER(_FieldOpts), _P]),
     "efx_demux_audio": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(C.c_size_t), _P, C.c_size_t, _P]),
@@ -203,6 +214,26 @@ def idx_pts2pts(idx: bytes, pts: int, speed: int) -> int:
     return int(load_library().efx_idx_pts2pts(h.ctypes.data, pts, speed))
 
 
+def export_bytes(fmt) -> int:
+    """Bytes of one exported image ("i420", "rgb24", "rgbp" or an EFX_PIX_* value; 0 for an unknown format)."""
+    return int(load_library().efx_export_bytes(_PIX_FORMATS[fmt] if isinstance(fmt, str) else int(fmt)))
+
+
+def _export_shape(fmt: str, n: int):
+    return {"i420": (n, FRAME_BYTES), "rgb24": (n, FRAME_HEIGHT, FRAME_WIDTH, 3), "rgbp": (n, 3, FRAME_HEIGHT, FRAME_WIDTH)}[fmt]
+
+
+def i420_planes(t):
+    """(Y, U, V) views of exported I420 images: a flat (n, 101376) tensor / array -> (n, 192, 352), (n, 96, 176) twice
+    (a single image of 101376 bytes -> the same without the leading axis).  U is Cb, V is Cr."""
+    lead = tuple(t.shape[:-1])
+    y_bytes, c_bytes = FRAME_WIDTH * FRAME_HEIGHT, FRAME_WIDTH * FRAME_HEIGHT // 4
+    y = t[..., :y_bytes].reshape(lead + (FRAME_HEIGHT, FRAME_WIDTH))
+    u = t[..., y_bytes:y_bytes + c_bytes].reshape(lead + (FRAME_HEIGHT // 2, FRAME_WIDTH // 2))
+    v = t[..., y_bytes + c_bytes:].reshape(lead + (FRAME_HEIGHT // 2, FRAME_WIDTH // 2))
+    return y, u, v
+
+
 def sbc_state_bytes() -> int:
     return int(load_library().efx_sbc_state_bytes())
 
@@ -278,6 +309,7 @@ class Decoder:
         cfg = _Config(device, max_streams, max_pictures, ring_depth, max_stream_bytes, hip_stream or None)
         _check(None, self._lib.efx_create(C.byref(cfg), C.byref(self._ctx)))
         self.max_streams, self.max_pictures, self.ring_depth = max_streams, max_pictures, max(2, ring_depth)
+        self.device = device
         self.n_streams = 0
 
     def close(self):
@@ -443,6 +475,79 @@ class Decoder:
         out = np.empty((n, self.ring_depth), dtype=np.uint64)
         _check(self._ctx, self._lib.efx_frame_hashes(self._ctx, first_stream, n, out.ctypes.data))
         return out
+
+    # -- pictures out (efx_export_frames) ---------------------------------------------------
+    def _export_opts(self, fmt, first_stream, n_streams, picture, slot, chroma, full_range, dst_stride=0):
+        if fmt not in _PIX_FORMATS:
+            raise ValueError(f"unknown format {fmt!r}: one of {sorted(_PIX_FORMATS)}")
+        if chroma not in _CHROMA_MODES:
+            raise ValueError(f"unknown chroma mode {chroma!r}: one of {sorted(_CHROMA_MODES)}")
+        if picture is not None and slot is not None:
+            raise ValueError("give picture= (of the most recent decode) or slot= (a ring slot), not both")
+        if slot is None and picture is None:
+            picture = 0
+        n = (self.n_streams - first_stream) if n_streams is None else n_streams
+        return n, _ExportOpts(first_stream, n, -1 if slot is None else slot, 0 if picture is None else picture,
+                              _PIX_FORMATS[fmt], _CHROMA_MODES[chroma], 1 if full_range else 0, dst_stride)
+
+    def export_to(self, dst: DeviceBuffer | int, fmt: str = "rgb24", *, first_stream: int = 0, n_streams: int | None = None,
+                  picture: int | None = None, slot: int | None = None, chroma: str = "bilinear", full_range: bool = False,
+                  dst_stride: int = 0):
+        """efx_export_frames into raw device memory (a DeviceBuffer or a pointer), asynchronous on the library's stream:
+        image i at dst + i * dst_stride (0 = packed).  Arguments as export()."""
+        _, o = self._export_opts(fmt, first_stream, n_streams, picture, slot, chroma, full_range, dst_stride)
+        ptr = dst.ptr if isinstance(dst, DeviceBuffer) else dst
+        _check(self._ctx, self._lib.efx_export_frames(self._ctx, C.byref(o), ptr))
+
+    def export(self, fmt: str = "rgb24", *, first_stream: int = 0, n_streams: int | None = None, picture: int | None = None,
+               slot: int | None = None, chroma: str = "bilinear", full_range: bool = False, out=None, sync: bool = True):
+        """Decoded pictures as a torch uint8 tensor on the decoder's device, converted there (no host round trip):
+        fmt "rgb24" -> (n, 192, 352, 3), "rgbp" -> (n, 3, 192, 352), "i420" -> (n, 101376) (i420_planes() splits it).
+        Streams first_stream ... + n_streams (default: the rest of the last upload); picture p of the most recent decode
+        (picture=, the default: p = 0) or ring slot k of every stream (slot=).  chroma "bilinear" (MPEG-1 siting) or
+        "nearest"; full_range False = BT.601 studio swing (what MPEG-1 carries).  out: a preallocated contiguous uint8
+        tensor of that size on this device, or a DeviceBuffer (then returned as is).
+
+        The kernel runs on the library's stream.  sync=True (default) waits for it, so the tensor is ready for any torch
+        stream.  sync=False is only safe when the decoder was created with
+        hip_stream=torch.cuda.current_stream().cuda_stream and that stream is a torch.cuda.Stream(), not the default
+        stream (whose handle, 0, makes the library create a private stream) -- the tensor is then ordered like any torch
+        op on that stream -- or when the caller calls sync() before using the tensor."""
+        import torch
+
+        n, o = self._export_opts(fmt, first_stream, n_streams, picture, slot, chroma, full_range)
+        shape = _export_shape(fmt, n)
+        nbytes = n * export_bytes(fmt)
+        if isinstance(out, DeviceBuffer):
+            if out.nbytes < nbytes:
+                raise ValueError(f"out holds {out.nbytes} bytes, the export needs {nbytes}")
+            result, ptr = out, out.ptr
+        else:
+            device = torch.device("cuda", self.device)
+            if out is None:
+                out = torch.empty(shape, dtype=torch.uint8, device=device)
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != device:
+                raise ValueError(f"out must be a uint8 tensor on {device}")
+            if not out.is_contiguous() or out.numel() != nbytes:
+                raise ValueError(f"out must be contiguous with {nbytes} elements (shape {shape})")
+            result, ptr = out.view(shape), out.data_ptr()
+        _check(self._ctx, self._lib.efx_export_frames(self._ctx, C.byref(o), ptr))
+        if sync:
+            self.sync()
+        return result
+
+    def export_host(self, fmt: str = "rgb24", *, first_stream: int = 0, n_streams: int | None = None,
+                    picture: int | None = None, slot: int | None = None, chroma: str = "bilinear",
+                    full_range: bool = False) -> np.ndarray:
+        """export() for callers without torch: converted on the device, returned as a NumPy array of the same shape."""
+        n, o = self._export_opts(fmt, first_stream, n_streams, picture, slot, chroma, full_range)
+        buf = DeviceBuffer(self, n * export_bytes(fmt))
+        try:
+            _check(self._ctx, self._lib.efx_export_frames(self._ctx, C.byref(o), buf.ptr))
+            self.sync()
+            return buf.download(np.uint8, buf.nbytes).reshape(_export_shape(fmt, n))
+        finally:
+            buf.free()
 
     # -- video / audio out ----------------------------------------------------------------
     def alloc(self, nbytes: int) -> DeviceBuffer:

@@ -48,6 +48,8 @@ __global__ void k_frame_hash(const uint8_t*, int, uint64_t*);
 __global__ void k_fill(uint32_t*, uint32_t, size_t);
 __global__ void k_composite(const uint8_t*, const VideoTables*, const VideoLineTemplates*, FieldArgs, uint16_t*);
 __global__ void k_pdm(const int16_t*, int, int, int32_t*, uint16_t*);
+template <int FMT, int CHROMA>
+__global__ void k_export(const uint8_t*, int, ExportArgs);  // (k_export.hip: the five (format, chroma) instances)
 __global__ void k_sbc(const uint8_t*, size_t, int, int, SbcState*, const SbcTables*, int16_t*, size_t, uint32_t*, uint32_t*, int);
 __global__ void k_sbc_frames(const uint8_t*, size_t, int, int, SbcFrameInfo*, uint32_t*, uint32_t*, SbcQueues*);
 __global__ void k_sbc_plan(const SbcFrameInfo*, int, int, const SbcState*, SbcFramePlan*, uint32_t*, SbcQueues*, uint32_t*, int, int, uint32_t*,
@@ -76,6 +78,7 @@ using namespace efx;
 #endif
 constexpr int kParseStreams = EFX_PARSE_STREAMS;  // parse halves in flight at once (latency-bound kernels: two overlap well)
 constexpr int kMaxGroups = 16;      // an efx_decode call parses its streams in up to this many parse halves
+static_assert(kMaxGroups <= kExportMaxGroups, "k_export takes every reconstruction group of a call");
 #ifndef EFX_RECON_MERGE
 #define EFX_RECON_MERGE 1
 #endif
@@ -1653,6 +1656,85 @@ int efx_composite_fields(efx_ctx* ctx, int first_stream, int n_streams, int slot
     o.ntsc = ntsc;
     o.frame_counter = frame_counter;
     return efx_composite_fields_ex(ctx, &o, dst_device);
+}
+
+size_t efx_export_bytes(int format)
+{
+    switch (format) {
+    case EFX_PIX_I420: return (size_t)kFrameBytes;  // 352 x 192 x 3 / 2: the same count as the strip layout
+    case EFX_PIX_RGB24:
+    case EFX_PIX_RGBP: return (size_t)3 * EFX_FRAME_WIDTH * EFX_FRAME_HEIGHT;
+    default: return 0;
+    }
+}
+
+int efx_export_frames(efx_ctx* ctx, const efx_export_opts* o, void* dst_device)
+{
+    bind_device(ctx);
+    if (!ctx || !o)
+        return EFX_ERR_ARG;
+    const size_t image = efx_export_bytes(o->format);
+    if (!dst_device || ((uintptr_t)dst_device & 15))
+        return fail(ctx, EFX_ERR_ARG, "efx_export_frames: dst_device must be a 16-byte aligned device pointer");
+    if (!image)
+        return fail(ctx, EFX_ERR_ARG, "efx_export_frames: unknown format");
+    if (o->format != EFX_PIX_I420 && o->chroma != EFX_CHROMA_NEAREST && o->chroma != EFX_CHROMA_BILINEAR)
+        return fail(ctx, EFX_ERR_ARG, "efx_export_frames: unknown chroma mode");
+    const size_t stride = o->dst_stride ? o->dst_stride : image;
+    if (stride < image || (stride & 15))
+        return fail(ctx, EFX_ERR_ARG, "efx_export_frames: dst_stride must be a multiple of 16 and hold an image");
+    if (o->first_stream < 0 || o->n_streams <= 0 || o->first_stream > ctx->cfg.max_streams - o->n_streams)
+        return fail(ctx, EFX_ERR_ARG, "efx_export_frames: stream range outside max_streams");
+    if (o->slot < -1 || o->slot >= ctx->cfg.ring_depth)
+        return fail(ctx, EFX_ERR_ARG, "efx_export_frames: slot outside the ring");
+    ExportArgs a{};
+    a.first_stream = o->first_stream;
+    a.ring_depth = ctx->cfg.ring_depth;
+    a.slot = o->slot;
+    a.full_range = o->full_range ? 1 : 0;
+    a.dst = static_cast<uint8_t*>(dst_device);
+    a.dst_stride = stride;
+    if (o->slot < 0) {
+        if (o->picture < 0 || o->picture >= ctx->cfg.max_pictures)
+            return fail(ctx, EFX_ERR_ARG, "efx_export_frames: picture outside [0, max_pictures)");
+        if (!ctx->decoded || ctx->n_groups < 1)
+            return fail(ctx, EFX_ERR_STATE, "efx_export_frames: picture mode before any decode");
+        if (o->first_stream + o->n_streams > ctx->last_n_streams)
+            return fail(ctx, EFX_ERR_STATE, "efx_export_frames: stream range beyond the most recent decode's streams");
+        // every reconstruction group of that call left its streams' ring positions in its own hand-over slot
+        a.picture = o->picture;
+        a.n_groups = ctx->n_groups;
+        for (int g = 0; g < ctx->n_groups; g++) {
+            a.group_first[g] = ctx->groups[g].first;
+            a.call_pos[g] = ctx->slot[ctx->groups[g].slot].d_call_pos;
+        }
+    }
+    const unsigned blocks = (unsigned)(((size_t)o->n_streams * kExportItemsPerPicture + kExportItemsPerBlock - 1) / kExportItemsPerBlock);
+    const bool bilinear = o->chroma == EFX_CHROMA_BILINEAR;
+    const uint8_t* frames = ctx->d_frames;
+    if (o->format == EFX_PIX_I420)
+        hipLaunchKernelGGL((k_export<EFX_PIX_I420, EFX_CHROMA_NEAREST>), dim3(blocks), dim3(256), 0, ctx->stream, frames, o->n_streams, a);
+    else if (o->format == EFX_PIX_RGB24 && bilinear)
+        hipLaunchKernelGGL((k_export<EFX_PIX_RGB24, EFX_CHROMA_BILINEAR>), dim3(blocks), dim3(256), 0, ctx->stream, frames, o->n_streams, a);
+    else if (o->format == EFX_PIX_RGB24)
+        hipLaunchKernelGGL((k_export<EFX_PIX_RGB24, EFX_CHROMA_NEAREST>), dim3(blocks), dim3(256), 0, ctx->stream, frames, o->n_streams, a);
+    else if (bilinear)
+        hipLaunchKernelGGL((k_export<EFX_PIX_RGBP, EFX_CHROMA_BILINEAR>), dim3(blocks), dim3(256), 0, ctx->stream, frames, o->n_streams, a);
+    else
+        hipLaunchKernelGGL((k_export<EFX_PIX_RGBP, EFX_CHROMA_NEAREST>), dim3(blocks), dim3(256), 0, ctx->stream, frames, o->n_streams, a);
+    EFX_HIP(hipGetLastError());
+    if (o->slot < 0) {
+        // A hand-over slot is recycled by the decode kSlots groups later once its recon_done fires (efx_decode_range):
+        // move the event of every slot whose call record the export reads behind the export.  The newest group's event
+        // stays last_recon_done -- it now marks the export, which is queued after that group.
+        for (int g = 0; g < ctx->n_groups; g++) {
+            const efx_ctx::Group& gr = ctx->groups[g];
+            if (gr.count > 0 && gr.first < o->first_stream + o->n_streams && gr.first + gr.count > o->first_stream)
+                EFX_HIP(hipEventRecord(ctx->slot[gr.slot].recon_done, ctx->stream));
+        }
+        ctx->last_recon_done = ctx->slot[ctx->groups[ctx->n_groups - 1].slot].recon_done;
+    }
+    return EFX_OK;
 }
 
 int efx_pdm(efx_ctx* ctx, int n_streams, const int16_t* pcm_device, int n_samples, int32_t* state_device, uint16_t* dst_device)

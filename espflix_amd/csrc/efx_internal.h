@@ -129,6 +129,27 @@ struct VideoLineTemplates {
 };
 void build_video_line_templates(const VideoTables* v, VideoLineTemplates* out);
 
+// k_export (k_export.hip): one item = 16 luma columns x 2 rows of one picture (the two rows share one chroma row), 22 x 96
+// items per picture; a workgroup converts kExportItemsPerBlock consecutive items (4 passes of 256 threads)
+constexpr int kExportItemsPerPicture = 22 * 96;
+constexpr int kExportItemsPerBlock = 1024;
+constexpr int kExportMaxGroups = 16;  // reconstruction groups of one efx_decode (efx_api.hip: kMaxGroups)
+
+// k_export launch arguments (by value)
+struct ExportArgs {
+    int first_stream, ring_depth;
+    int slot;     // >= 0: this ring slot of every stream; < 0: picture `picture` of the most recent efx_decode
+    int picture;
+    // picture mode: streams [group_first[g], group_first[g + 1]) of that call left their ring positions in call_pos[g]
+    // (k_advance: call_pos[2 s] = frame index before the call, call_pos[2 s + 1] = first picture with a PTS or -1)
+    int n_groups;
+    int group_first[kExportMaxGroups];
+    const int32_t* call_pos[kExportMaxGroups];
+    int full_range;
+    uint8_t* dst;
+    size_t dst_stride;
+};
+
 // per-stream result of k_ts_sequences
 struct IdxInfo {
     int64_t first_pts, last_pts;  // origin (PTS of the first sequence start), PTS of the last video PES

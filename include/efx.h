@@ -209,6 +209,53 @@ int efx_frame_hashes(efx_ctx* ctx, int first_stream, int n, uint64_t* out);
 /* Overwrite one ring frame from host memory (tests, poster upload). Synchronous. */
 int efx_upload_frame(efx_ctx* ctx, int stream, int slot, const uint8_t* src);
 
+/* -- pictures out in standard pixel formats (k_export) ----------------------------------- */
+/* The ring frames above keep the reference's strip layout, which nothing outside this library reads.  efx_export_frames
+ * turns ring frames of a contiguous range of streams into one image per stream, on the device, in one launch:
+ *
+ *   EFX_PIX_I420   Y 192 x 352, then U (Cb) 96 x 176, then V (Cr) 96 x 176, planar, rows packed: 101 376 bytes
+ *   EFX_PIX_RGB24  192 x 352 x 3 (HWC), R G B interleaved: 202 752 bytes
+ *   EFX_PIX_RGBP   3 x 192 x 352 (CHW), the planes R, G, B (torchvision's layout): 202 752 bytes
+ *
+ * Plane mapping.  Strip rows 0-7 of the strip layout carry Cb (U) and rows 8-15 Cr (V).  The reference calls rows 0-7
+ * "cr" (Frame::get_cr, src/player.cpp:38-46), but they hold MPEG-1 block 4 (cr_addr, player.cpp:830-831,1129-1130),
+ * which its decoder predicts from cr_dc (player.cpp:1037,1060): block 4 is Cb in ISO 11172-2 2.4.3.7, and the
+ * reference's own display path reads those rows as u_ptr (src/video.cpp:695-696).  I420's U plane is rows 0-7.
+ *
+ * RGB is exact integer arithmetic (espflix_amd/csrc/export_px.h), bit-reproducible anywhere:
+ *   chroma at luma resolution, for luma column x, row y:
+ *     EFX_CHROMA_NEAREST   C[y >> 1][x >> 1]
+ *     EFX_CHROMA_BILINEAR  MPEG-1 siting (a chroma sample centred between its 2 x 2 luma samples):
+ *                          cx0 = x >> 1, cx1 = clamp(cx0 + (x & 1 ? 1 : -1), 0, 175), likewise cy0 / cy1 in 0 .. 95,
+ *                          c = (9 C[cy0][cx0] + 3 C[cy0][cx1] + 3 C[cy1][cx0] + C[cy1][cx1] + 8) >> 4
+ *   matrix, u = U - 128, v = V - 128, t = cy (Y - y0) + 128, >> arithmetic, results clamped to 0 .. 255:
+ *     R = (t + rv v) >> 8,  G = (t + gu u + gv v) >> 8,  B = (t + bu u) >> 8
+ *     BT.601 studio swing (full_range 0, what MPEG-1 carries): cy 298, y0 16, rv 409, gu -100, gv -208, bu 516
+ *     BT.601 full range   (full_range 1):                      cy 256, y0 0,  rv 359, gu -88,  gv -183, bu 454 */
+typedef enum efx_pixel_format { EFX_PIX_I420 = 0, EFX_PIX_RGB24 = 1, EFX_PIX_RGBP = 2 } efx_pixel_format;
+#define EFX_CHROMA_NEAREST 0
+#define EFX_CHROMA_BILINEAR 1
+typedef struct efx_export_opts {
+    int first_stream, n_streams;
+    int slot;          /* >= 0: this ring slot of every selected stream; -1: use `picture` */
+    int picture;       /* slot < 0: picture `picture` of the most recent efx_decode* of each stream */
+    int format;        /* efx_pixel_format */
+    int chroma;        /* EFX_CHROMA_*; ignored for I420 */
+    int full_range;    /* 0 = BT.601 studio swing (MPEG-1), 1 = full range */
+    size_t dst_stride; /* bytes from one stream's image to the next; 0 = efx_export_bytes(format) */
+} efx_export_opts;
+/* bytes of one image in `format`; 0 for an unknown format.  Host only. */
+size_t efx_export_bytes(int format);
+/* Stream first_stream + i goes to dst_device + i * dst_stride (device memory, 16-byte aligned; stride a multiple of 16
+ * and at least the image; the bytes between images are not written).  Asynchronous, on the context's stream: queued
+ * behind the decodes before it, it reads what they reconstruct.  Picture mode (slot = -1) needs no synchronisation: the
+ * ring slot of each stream (efx_stream_picture_slot's arithmetic) is read on the device from the record the most
+ * recent decode left -- streams of one batch may sit in different slots.
+ * EFX_ERR_ARG: dst_device NULL or not 16-byte aligned, unknown format or chroma mode, a bad dst_stride, the stream range
+ * outside max_streams, slot >= ring_depth or < -1, picture outside [0, max_pictures).  EFX_ERR_STATE (picture mode):
+ * no decode yet, or the stream range beyond the stream count of the most recent decode. */
+int efx_export_frames(efx_ctx* ctx, const efx_export_opts* opts, void* dst_device);
+
 /* -- composite video out (video_init / video_isr, src/video.cpp:572-630,1122-1198) -------- */
 typedef struct efx_video_params {
     int line_width, line_count;        /* samples per line, lines per field */
