@@ -41,6 +41,7 @@ STREAM_COEF_OVERRUN = 32
 STREAM_SERIAL_HUNT = 64   # the reference would misread bits between two start codes (its marker hunt is bit-serial): see efx.h
 STREAM_INTERNAL = 256     # never expected: a lost hand-over inside the reconstruction kernel (efx.h)
 STREAM_SLICE_ORDER = 128  # slice start codes of a picture not strictly rising in bitstream order: see efx.h
+ENCODE_FULL = 512         # efx_encode: the stream's output region filled up (efx.h)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EFX_LIB") or os.path.join(_HERE, "libefx.so")  # EFX_LIB: development builds
@@ -77,6 +78,19 @@ class _FieldOpts(C.Structure):
 class _ExportOpts(C.Structure):
     _fields_ = [("first_stream", C.c_int), ("n_streams", C.c_int), ("slot", C.c_int), ("picture", C.c_int), ("format", C.c_int),
                 ("chroma", C.c_int), ("full_range", C.c_int), ("dst_stride", C.c_size_t)]
+
+
+class _EncodeOpts(C.Structure):
+    _fields_ = [("n_streams", C.c_int), ("n_pictures", C.c_int), ("format", C.c_int), ("qscale", C.c_int), ("gop", C.c_int),
+                ("search", C.c_int), ("cont", C.c_int), ("first_pts", C.c_int64), ("src_stride", C.c_size_t),
+                ("dst_stride", C.c_size_t)]
+
+
+@dataclass
+class EncodeResult:
+    streams: list          # bytes written per stream by the call
+    status: np.ndarray     # EFX_ENCODE_* bits per stream
+    recon: object = None   # (n, P, 101376) reconstruction (torch tensor or NumPy array), when asked for
 
 
 class _IdxRec(C.Structure):
@@ -131,6 +145,8 @@ _SYMBOLS = {
     "efx_video_get_params": (C.c_int, [C.c_int, C.POINTER(_VideoParams)]),
     "efx_export_bytes": (C.c_size_t, [C.c_int]),
     "efx_export_frames": (C.c_int, [_P, C.POINTER(_ExportOpts), _P]),
+    "efx_encode": (C.c_int, [_P, C.POINTER(_EncodeOpts), _P, _P, _P, _P, _P]),
+    "efx_encode_bound": (C.c_size_t, [C.c_int, C.c_int]),
     "efx_composite_fields": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "efx_composite_fields_ex": (C.c_int, [_P, C.POINTER(_FieldOpts), _P]),
     "efx_demux_audio": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(C.c_size_t), _P, C.c_size_t, _P]),
@@ -232,6 +248,11 @@ def i420_planes(t):
     u = t[..., y_bytes:y_bytes + c_bytes].reshape(lead + (FRAME_HEIGHT // 2, FRAME_WIDTH // 2))
     v = t[..., y_bytes + c_bytes:].reshape(lead + (FRAME_HEIGHT // 2, FRAME_WIDTH // 2))
     return y, u, v
+
+
+def encode_bound(fmt: int, n_pictures: int) -> int:
+    """Worst-case bytes of one encoded stream of n_pictures pictures (efx_encode_bound; 0 for invalid arguments)."""
+    return int(load_library().efx_encode_bound(fmt, n_pictures))
 
 
 def sbc_state_bytes() -> int:
@@ -548,6 +569,88 @@ class Decoder:
             return buf.download(np.uint8, buf.nbytes).reshape(_export_shape(fmt, n))
         finally:
             buf.free()
+
+    # -- MPEG-1 encode (efx_encode) ------------------------------------------------------------
+    def encode_to(self, src: DeviceBuffer | int, dst: DeviceBuffer | int, length: DeviceBuffer | int,
+                  status: DeviceBuffer | int, *, n_streams: int, n_pictures: int, qscale: int = 8, gop: int = 12,
+                  search: int = 7, fmt: int = FORMAT_TS, cont: bool = False, first_pts: int = 0, src_stride: int = 0,
+                  dst_stride: int = 0, recon: DeviceBuffer | int | None = None):
+        """efx_encode on raw device memory (DeviceBuffers or pointers), asynchronous on the library's stream: stream i's
+        pictures at src + i * src_stride (0 = packed), its bytes appended to dst + i * dst_stride (0 = efx_encode_bound),
+        uint32 byte counts and status bits to length / status, the reconstruction to recon (optional)."""
+        g = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else b)
+        o = _EncodeOpts(n_streams, n_pictures, fmt, qscale, gop, search, 1 if cont else 0, first_pts,
+                        src_stride or n_pictures * FRAME_BYTES, dst_stride or encode_bound(fmt, n_pictures))
+        _check(self._ctx, self._lib.efx_encode(self._ctx, C.byref(o), g(src), g(dst), g(length), g(status), g(recon)))
+        return o.dst_stride
+
+    def encode(self, pictures, *, qscale: int = 8, gop: int = 12, search: int = 7, fmt: int = FORMAT_TS, cont: bool = False,
+               first_pts: int = 0, recon: bool = False, dst_stride: int = 0) -> EncodeResult:
+        """Encode (n, P, 101376) I420 pictures (the layout export("i420") writes) into n MPEG-1 streams of P pictures: a uint8
+        torch tensor on the decoder's device or a NumPy array.  Stream i takes the pictures of row i (the order export()
+        gives streams).  Returns each stream's bytes, its status bits and, with recon=True, what a decoder reconstructs
+        (a tensor on the device for tensor input, else an array).  cont=True continues the streams of the previous encode
+        (qscale and search may change).  Synchronises: torch's current stream before (tensor input), the library's after.
+
+        dst_stride: bytes of device memory for each stream's output, 0 = encode_bound(fmt, P), the size that can never fill
+        up -- about 357 kB (ES) / 365 kB (TS) per picture, 10 to 100 times what a picture usually takes: 1024 streams x 24
+        TS pictures reserve some 9 GB for the call.  A smaller region is fine where the caller knows its content; a stream
+        that does not fit ends after its last whole picture with status ENCODE_FULL (its bytes so far are returned) and can
+        only be encoded again from the start (cont=False), with a larger dst_stride."""
+        lead = tuple(pictures.shape[:-1])
+        if len(lead) != 2 or pictures.shape[-1] != FRAME_BYTES:
+            raise ValueError(f"pictures must have shape (n, P, {FRAME_BYTES}), got {tuple(pictures.shape)}")
+        n, P = lead
+        bufs = []
+        try:
+            rec_t = None
+            if isinstance(pictures, np.ndarray):
+                src = DeviceBuffer(self, max(1, pictures.size))
+                bufs.append(src)
+                src.upload(np.ascontiguousarray(pictures, dtype=np.uint8))
+                src_ptr = src.ptr
+            else:
+                import torch
+                device = torch.device("cuda", self.device)
+                if pictures.dtype != torch.uint8 or pictures.device != device:
+                    raise ValueError(f"pictures must be a uint8 tensor on {device} (or a NumPy array)")
+                pictures = pictures.contiguous()
+                torch.cuda.current_stream(device).synchronize()
+                src_ptr = pictures.data_ptr()
+                if recon:
+                    rec_t = torch.empty((n, P, FRAME_BYTES), dtype=torch.uint8, device=device)
+            stride = dst_stride or encode_bound(fmt, P)
+            dst, meta = DeviceBuffer(self, n * stride), DeviceBuffer(self, 2 * 4 * n + 16)
+            bufs += [dst, meta]
+            rec_ptr = None
+            if recon and rec_t is None:
+                rec_buf = DeviceBuffer(self, n * P * FRAME_BYTES)
+                bufs.append(rec_buf)
+                rec_ptr = rec_buf.ptr
+            elif rec_t is not None:
+                rec_ptr = rec_t.data_ptr()
+            status_off = (4 * n + 15) // 16 * 16
+            self.encode_to(src_ptr, dst, meta.ptr, meta.ptr + status_off, n_streams=n, n_pictures=P, qscale=qscale, gop=gop,
+                           search=search, fmt=fmt, cont=cont, first_pts=first_pts, dst_stride=stride, recon=rec_ptr)
+            self.sync()
+            lens = meta.download(np.uint32, n)
+            st = np.empty(n, dtype=np.uint32)
+            _check(self._ctx, self._lib.efx_memcpy_d2h(self._ctx, st.ctypes.data, meta.ptr + status_off, 4 * n))
+            streams = []
+            for i in range(n):
+                b = np.empty(int(lens[i]), dtype=np.uint8)
+                if b.size:
+                    _check(self._ctx, self._lib.efx_memcpy_d2h(self._ctx, b.ctypes.data, dst.ptr + i * stride, b.size))
+                streams.append(b.tobytes())
+            out_rec = None
+            if rec_t is not None:
+                out_rec = rec_t
+            elif recon:
+                out_rec = bufs[-1].download(np.uint8, n * P * FRAME_BYTES).reshape(n, P, FRAME_BYTES)
+            return EncodeResult(streams, st, out_rec)
+        finally:
+            for b in bufs:
+                b.free()
 
     # -- video / audio out ----------------------------------------------------------------
     def alloc(self, nbytes: int) -> DeviceBuffer:

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <memory>
 #include <mutex>
 #include <thread>
 
@@ -17,6 +18,7 @@
 
 #include "efx.h"
 #include "efx_internal.h"
+#include "enc_core.h"
 #include "parse_tm.h"
 
 namespace efx {
@@ -50,6 +52,9 @@ __global__ void k_composite(const uint8_t*, const VideoTables*, const VideoLineT
 __global__ void k_pdm(const int16_t*, int, int, int32_t*, uint16_t*);
 template <int FMT, int CHROMA>
 __global__ void k_export(const uint8_t*, int, ExportArgs);  // (k_export.hip: the five (format, chroma) instances)
+__global__ void k_enc_begin(EncArgs);
+__global__ void k_enc_rows(EncArgs);
+__global__ void k_enc_pack(EncArgs);
 __global__ void k_sbc(const uint8_t*, size_t, int, int, SbcState*, const SbcTables*, int16_t*, size_t, uint32_t*, uint32_t*, int);
 __global__ void k_sbc_frames(const uint8_t*, size_t, int, int, SbcFrameInfo*, uint32_t*, uint32_t*, SbcQueues*);
 __global__ void k_sbc_plan(const SbcFrameInfo*, int, int, const SbcState*, SbcFramePlan*, uint32_t*, SbcQueues*, uint32_t*, int, int, uint32_t*,
@@ -243,6 +248,20 @@ struct efx_ctx {
     int opt_demux_fused = 0;             // 1 = TS input through the one-pass demultiplexer (k_demux_fused: measured slower, kept as an option)
     bool sbc_flags_clean = false;        // d_sbc_flags[0, n) all kSbcRegularFlag (k_sbc_finish leaves them so)
     uint64_t* d_hash = nullptr;
+
+    // efx_encode's state and scratch (allocated at the first call, for max_streams streams)
+    EncState* d_enc_state = nullptr;
+    uint8_t* d_enc_pics = nullptr;       // two I420 reconstruction buffers per stream
+    uint8_t* d_enc_slices = nullptr;     // 12 slices of enc::kSliceCap bytes per stream
+    uint32_t* d_enc_slice_len = nullptr;
+    enc::Tables* d_enc_tables = nullptr;
+    std::unique_ptr<enc::Tables> h_enc_tables;  // the source of d_enc_tables' upload
+    uint32_t* h_enc_full = nullptr;      // host-mapped: enc_generation of the streams when one of them last filled its region
+    uint32_t* d_enc_full = nullptr;      // ... its device address
+    bool enc_ready = false;              // every buffer above exists
+    bool enc_started = false;            // streams exist that cont = 1 may continue
+    uint32_t enc_generation = 0;         // fresh efx_encode calls so far: the value a call writes to *h_enc_full when a stream fills up
+    int enc_n_streams = 0, enc_format = 0, enc_gop = 0;  // of the call that started them
 
     // results of the last decode (fetch_results)
     int n_streams = 0;  // streams of the batch the last decode read
@@ -683,7 +702,10 @@ void efx_destroy(efx_ctx* ctx)
     }
     void* bufs[] = {ctx->d_tables, ctx->d_tm_tables, ctx->d_sbc_flags, ctx->d_sbc_next, ctx->d_sbc_info, ctx->d_sbc_plan, ctx->d_sbc_extra, ctx->d_sbc_cover, ctx->d_state, ctx->d_frames, ctx->d_video[0],  ctx->d_video[1], ctx->d_video_lines[0],
                     ctx->d_video_lines[1], ctx->d_hash, ctx->d_ts, ctx->d_demux_chunks, ctx->d_sbc_tables, ctx->d_idx_info, ctx->d_ts_off, ctx->d_idx_len,
-                    ctx->d_idx_base, ctx->d_idx_seq};
+                    ctx->d_idx_base, ctx->d_idx_seq, ctx->d_enc_state, ctx->d_enc_pics, ctx->d_enc_slices, ctx->d_enc_slice_len,
+                    ctx->d_enc_tables};
+    if (ctx->h_enc_full)
+        (void)hipHostFree(ctx->h_enc_full);
     for (auto& te : ctx->timing_ring)
         for (auto& ev : te.ev)
             if (ev)
@@ -1733,6 +1755,128 @@ int efx_export_frames(efx_ctx* ctx, const efx_export_opts* o, void* dst_device)
                 EFX_HIP(hipEventRecord(ctx->slot[gr.slot].recon_done, ctx->stream));
         }
         ctx->last_recon_done = ctx->slot[ctx->groups[ctx->n_groups - 1].slot].recon_done;
+    }
+    return EFX_OK;
+}
+
+size_t efx_encode_bound(int format, int n_pictures)
+{
+    if ((format != EFX_FORMAT_ES && format != EFX_FORMAT_TS) || n_pictures < 1 || n_pictures > 255)
+        return 0;
+    const size_t es = (size_t)enc::kHdrCap + (size_t)kMbH * enc::kSliceCap;  // headers + 12 worst-case slices
+    const size_t pic = format == EFX_FORMAT_TS ? (size_t)enc::ts_packets((uint32_t)(es + enc::kPesHdrBytes)) * 188 : es;
+    return (pic * (size_t)n_pictures + 15) / 16 * 16;
+}
+
+int efx_encode(efx_ctx* ctx, const efx_encode_opts* o, const uint8_t* src_device, uint8_t* dst_device, uint32_t* len_device,
+               uint32_t* status_device, uint8_t* recon_device)
+{
+    bind_device(ctx);
+    if (!ctx || !o)
+        return EFX_ERR_ARG;
+    auto misaligned = [](const void* p) { return !p || ((uintptr_t)p & 15); };
+    if (o->n_streams < 1 || o->n_streams > ctx->cfg.max_streams)
+        return fail(ctx, EFX_ERR_ARG, "efx_encode: n_streams outside 1 .. max_streams");
+    if (o->n_pictures < 1 || o->n_pictures > 255)
+        return fail(ctx, EFX_ERR_ARG, "efx_encode: n_pictures outside 1 .. 255");
+    if (o->format != EFX_FORMAT_ES && o->format != EFX_FORMAT_TS)
+        return fail(ctx, EFX_ERR_ARG, "efx_encode: unknown format");
+    if (o->qscale < 1 || o->qscale > 31)
+        return fail(ctx, EFX_ERR_ARG, "efx_encode: qscale outside 1 .. 31");
+    if (o->gop < 1 || o->gop > 255)
+        return fail(ctx, EFX_ERR_ARG, "efx_encode: gop outside 1 .. 255");
+    if (o->search < 0 || o->search > enc::kMaxSearch)
+        return fail(ctx, EFX_ERR_ARG, "efx_encode: search outside 0 .. 15");
+    if (o->cont != 0 && o->cont != 1)
+        return fail(ctx, EFX_ERR_ARG, "efx_encode: cont must be 0 or 1");
+    if (o->first_pts < 0 || o->first_pts >= (1ll << 33))
+        return fail(ctx, EFX_ERR_ARG, "efx_encode: first_pts outside 0 .. 2^33-1");
+    if (o->src_stride < (size_t)o->n_pictures * kFrameBytes || (o->src_stride & 15))
+        return fail(ctx, EFX_ERR_ARG, "efx_encode: src_stride must be a multiple of 16 and hold n_pictures pictures");
+    if (o->dst_stride & 15)
+        return fail(ctx, EFX_ERR_ARG, "efx_encode: dst_stride must be a multiple of 16");
+    if (misaligned(src_device) || misaligned(dst_device) || misaligned(len_device) || misaligned(status_device) ||
+        (recon_device && ((uintptr_t)recon_device & 15)))
+        return fail(ctx, EFX_ERR_ARG, "efx_encode: src, dst, len and status must be 16-byte aligned device pointers (recon too, unless NULL)");
+    if (o->cont) {
+        if (!ctx->enc_started)
+            return fail(ctx, EFX_ERR_STATE, "efx_encode: cont without a previous efx_encode");
+        if (o->n_streams != ctx->enc_n_streams || o->format != ctx->enc_format || o->gop != ctx->enc_gop)
+            return fail(ctx, EFX_ERR_STATE, "efx_encode: cont with n_streams, format or gop other than the call that started the streams");
+        if (*(volatile uint32_t*)ctx->h_enc_full == ctx->enc_generation)
+            return fail(ctx, EFX_ERR_STATE, "efx_encode: cont after a stream filled its output region");
+    }
+    if (!ctx->enc_ready) {
+        // all or nothing: a context whose encoder scratch could not be allocated in full holds none of it
+        const size_t n = (size_t)ctx->cfg.max_streams;
+        hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&ctx->h_enc_full), 16, hipHostMallocMapped);
+        if (e == hipSuccess) {
+            *ctx->h_enc_full = 0;
+            e = hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->d_enc_full), ctx->h_enc_full, 0);
+        }
+        if (e == hipSuccess) e = dalloc(&ctx->d_enc_state, n);
+        if (e == hipSuccess) e = dalloc(&ctx->d_enc_pics, 2 * n * kFrameBytes);
+        if (e == hipSuccess) e = dalloc(&ctx->d_enc_slices, n * kMbH * enc::kSliceCap);
+        if (e == hipSuccess) e = dalloc(&ctx->d_enc_slice_len, n * kMbH);
+        if (e == hipSuccess) e = dalloc(&ctx->d_enc_tables, 1);
+        if (e == hipSuccess) {
+            ctx->h_enc_tables.reset(new enc::Tables);
+            enc::build_tables(ctx->h_enc_tables.get());
+            e = hipMemcpyAsync(ctx->d_enc_tables, ctx->h_enc_tables.get(), sizeof(enc::Tables), hipMemcpyHostToDevice, ctx->stream);
+        }
+        if (e != hipSuccess) {
+            void* bufs[] = {ctx->d_enc_state, ctx->d_enc_pics, ctx->d_enc_slices, ctx->d_enc_slice_len, ctx->d_enc_tables};
+            for (void* b : bufs)
+                (void)dev_free(b);
+            if (ctx->h_enc_full)
+                (void)hipHostFree(ctx->h_enc_full);
+            ctx->d_enc_state = nullptr;
+            ctx->d_enc_pics = ctx->d_enc_slices = nullptr;
+            ctx->d_enc_slice_len = ctx->h_enc_full = ctx->d_enc_full = nullptr;
+            ctx->d_enc_tables = nullptr;
+            (void)hipGetLastError();
+            return fail(ctx, EFX_ERR_DEVICE, "efx_encode: cannot allocate the encoder's state and scratch", e);
+        }
+        ctx->enc_ready = true;
+    }
+    if (!o->cont)
+        ctx->enc_generation = ctx->enc_generation + 1 ? ctx->enc_generation + 1 : 1;  // (0: no call has filled a region)
+    EncArgs a{};
+    a.src = src_device;
+    a.src_stride = o->src_stride;
+    a.dst = dst_device;
+    a.dst_stride = o->dst_stride;
+    a.len = len_device;
+    a.status = status_device;
+    a.recon = recon_device;
+    a.st = ctx->d_enc_state;
+    a.pics = ctx->d_enc_pics;
+    a.slices = ctx->d_enc_slices;
+    a.slice_len = ctx->d_enc_slice_len;
+    a.tab = ctx->d_enc_tables;
+    a.full_flag = ctx->d_enc_full;
+    a.generation = ctx->enc_generation;
+    a.first_pts = o->first_pts;
+    a.n_streams = o->n_streams;
+    a.n_pictures = o->n_pictures;
+    a.qscale = o->qscale;
+    a.gop = o->gop;
+    a.search = o->search;
+    a.format = o->format;
+    a.f_code = o->search <= 7 ? 1 : 2;
+    a.cont = o->cont;
+    hipLaunchKernelGGL(k_enc_begin, dim3((unsigned)((o->n_streams + 63) / 64)), dim3(64), 0, ctx->stream, a);
+    for (int p = 0; p < o->n_pictures; p++) {
+        a.picture = p;
+        hipLaunchKernelGGL(k_enc_rows, dim3((unsigned)o->n_streams * kMbH), dim3(64), 0, ctx->stream, a);
+        hipLaunchKernelGGL(k_enc_pack, dim3((unsigned)o->n_streams), dim3(256), 0, ctx->stream, a);
+    }
+    EFX_HIP(hipGetLastError());
+    if (!o->cont) {
+        ctx->enc_started = true;
+        ctx->enc_n_streams = o->n_streams;
+        ctx->enc_format = o->format;
+        ctx->enc_gop = o->gop;
     }
     return EFX_OK;
 }

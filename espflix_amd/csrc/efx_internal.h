@@ -247,6 +247,40 @@ struct SbcState {
 };
 static_assert(sizeof(SbcState) == 2192, "SbcState layout");
 
+// efx_encode (k_encode.hip): per-stream state that carries from call to call (continuation), in HBM
+namespace enc {
+struct Tables;
+}
+struct EncState {
+    uint32_t pictures;  // pictures encoded since the stream started: GOP phase, temporal_reference, PTS
+    uint32_t cc;        // TS continuity counter of the next packet
+    uint32_t cur;       // which of the stream's two reconstruction buffers holds the newest picture
+    uint32_t full;      // the output region of a call filled up: nothing more is written until the stream starts afresh
+    uint32_t out_len;   // bytes written by the current call
+    uint32_t status;    // EFX_ENCODE_* bits of the current call
+    int64_t first_pts;  // PTS of picture 0
+};
+
+// k_encode launch arguments (by value)
+struct EncArgs {
+    const uint8_t* src;  // I420 pictures: stream i, picture p at src + i * src_stride + p * 101376
+    size_t src_stride;
+    uint8_t* dst;  // output region of stream i at dst + i * dst_stride
+    size_t dst_stride;
+    uint32_t* len;
+    uint32_t* status;
+    uint8_t* recon;           // may be null: reconstruction of (stream i, picture p) at recon + (i * n_pictures + p) * 101376
+    EncState* st;
+    uint8_t* pics;            // two I420 reconstruction buffers per stream
+    uint8_t* slices;          // per (stream, row): the coded slice, enc::kSliceCap bytes apart
+    uint32_t* slice_len;
+    const enc::Tables* tab;
+    uint32_t* full_flag;      // host-mapped: set to `generation` when a stream fills its region (efx_encode's continuation check)
+    uint32_t generation;      // of the streams: counts the fresh efx_encode calls of the context
+    int64_t first_pts;
+    int n_streams, n_pictures, picture, qscale, gop, search, format, f_code, cont;
+};
+
 void build_sbc_tables(SbcTables* t);
 void build_parse_tables(ParseTables* t);
 void build_video_tables(int ntsc, VideoTables* t);

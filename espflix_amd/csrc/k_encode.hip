@@ -1,0 +1,255 @@
+// k_encode.hip -- batched MPEG-1 I/P encoder (efx_encode): every stream advances one picture per pair of launches.
+//
+//   k_enc_begin   one lane per stream: fresh streams get their state reset, every stream its per-call output counters
+//   k_enc_rows    one wave per (stream, macroblock row): for each of the row's 22 macroblocks, full-pel search over the
+//                 previous reconstruction staged in LDS (v_sad_u8, one candidate vector per lane), the 8 half-pel
+//                 neighbours of the best one, the intra / inter decision, then transform, quantisation and reconstruction
+//                 with one lane per block (enc_core.h).  The levels stay in LDS; at the end of the row one lane codes the
+//                 slice into the stream's slice scratch.  Rows are independent: reconstruction does not depend on the
+//                 coding order (a skipped macroblock reconstructs like "motion compensated, not coded" with vector 0).
+//   k_enc_pack    one workgroup per stream: picture headers, then the picture's slices (ES) or its PES in 188-byte
+//                 packets (TS) appended to the stream's output region, or EFX_ENCODE_FULL when it does not fit
+//
+// Every store is a vector store (global / LDS); the only serial part is the bit writer of a slice.
+#include <hip/hip_runtime.h>
+
+#include "efx.h"
+#include "efx_internal.h"
+#include "enc_core.h"
+
+namespace efx {
+
+__global__ void k_enc_begin(EncArgs a)
+{
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= a.n_streams)
+        return;
+    EncState S = a.st[s];
+    if (!a.cont) {
+        S.pictures = 0;
+        S.cc = 0;
+        S.cur = 0;
+        S.full = 0;
+        S.first_pts = a.first_pts;
+    }
+    S.out_len = 0;
+    S.status = S.full ? EFX_ENCODE_FULL : 0u;
+    a.st[s] = S;
+    a.len[s] = 0;
+    a.status[s] = S.status;
+}
+
+__device__ inline uint32_t wave_min(uint32_t v)
+{
+    for (int off = 32; off > 0; off >>= 1)
+        v = min(v, (uint32_t)__shfl_xor((int)v, off, 64));
+    return v;
+}
+
+__device__ inline int wave_sum(int v)
+{
+    for (int off = 32; off > 0; off >>= 1)
+        v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(64) void k_enc_rows(EncArgs a)
+{
+    using namespace enc;
+    const int row = blockIdx.x % kMbRows, s = blockIdx.x / kMbRows, lane = threadIdx.x;
+    const Tables& T = *a.tab;
+    const EncState S = a.st[s];
+    const int type = (S.pictures % (uint32_t)a.gop) == 0 ? 1 : 2;
+    const uint8_t* src = a.src + (size_t)s * a.src_stride + (size_t)a.picture * kPicBytes;
+    const uint8_t* ref = a.pics + ((size_t)s * 2 + S.cur) * kPicBytes;
+    uint8_t* rec = a.pics + ((size_t)s * 2 + (S.cur ^ 1)) * kPicBytes;
+    uint8_t* rec_out = a.recon ? a.recon + ((size_t)s * a.n_pictures + a.picture) * kPicBytes : nullptr;
+
+    __shared__ Mb mbs[kMbCols];
+    __shared__ uint32_t cur_w[64];                      // the macroblock's luma, 16 rows x 4 words
+    __shared__ uint32_t win_w[kWin * kWinStride / 4 + 4];  // search window
+    __shared__ int best_sad;
+    uint8_t* win = reinterpret_cast<uint8_t*>(win_w);
+    const int R = a.search, side = 2 * R + 1, wn = 2 * R + 18;
+
+    for (int mbx = 0; mbx < kMbCols; mbx++) {
+        cur_w[lane] = *reinterpret_cast<const uint32_t*>(src + (row * 16 + (lane >> 2)) * kW + mbx * 16 + (lane & 3) * 4);
+        int h = 0, v = 0;
+        bool intra = type == 1;
+        if (type == 2) {
+            const int wx0 = mbx * 16 - R - 1, wy0 = row * 16 - R - 1;
+            for (int i = lane; i < wn * wn; i += 64) {
+                const int wy = i / wn, wx = i - wy * wn, gx = wx0 + wx, gy = wy0 + wy;
+                win[wy * kWinStride + wx] = (gx >= 0 && gx < kW && gy >= 0 && gy < kH) ? ref[gy * kW + gx] : 0;
+            }
+            __syncthreads();
+            // full-pel search: one candidate per lane, 16 x 4 byte-quad SADs against the uniform current rows
+            uint32_t best = 0xFFFFFFFFu;
+            for (int c = lane; c < side * side; c += 64) {
+                const int dy = c / side - R, dx = c - (c / side) * side - R;
+                if (!mv_ok(mbx, row, 2 * dx, 2 * dy))
+                    continue;
+                const int base = (dy + R + 1) * kWinStride + dx + R + 1;
+                uint32_t sad = 0;
+                for (int y = 0; y < 16; y++) {
+                    const int o = base + y * kWinStride;
+                    const int w0 = o >> 2, sh = o & 3;
+                    const uint32_t q0 = win_w[w0], q1 = win_w[w0 + 1], q2 = win_w[w0 + 2], q3 = win_w[w0 + 3], q4 = win_w[w0 + 4];
+                    sad = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(q1, q0, sh), cur_w[y * 4 + 0], sad);
+                    sad = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(q2, q1, sh), cur_w[y * 4 + 1], sad);
+                    sad = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(q3, q2, sh), cur_w[y * 4 + 2], sad);
+                    sad = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(q4, q3, sh), cur_w[y * 4 + 3], sad);
+                }
+                best = min(best, search_key(search_cost((int)sad, dx, dy), dx, dy, c));
+            }
+            best = wave_min(best);
+            const int bc = (int)(best & 1023), bdy = bc / side - R, bdx = bc - (bc / side) * side - R;
+            // the best vector and its 8 half-pel neighbours, with the decoder's interpolation (search 0: the zero vector
+            // only, lane 4 alone, for its SAD)
+            uint32_t key2 = 0xFFFFFFFFu;
+            int sad2 = 0;
+            if (lane < 9 && (R > 0 || lane == 4)) {
+                const int hh = 2 * bdx + lane % 3 - 1, vv = 2 * bdy + lane / 3 - 1;
+                if (mv_ok(mbx, row, hh, vv)) {
+                    const int px = (mbx << 5) + hh, py = (row << 5) + vv;
+                    const uint8_t* w = win + ((py >> 1) - wy0) * kWinStride + (px >> 1) - wx0;
+                    const uint8_t* cur = reinterpret_cast<const uint8_t*>(cur_w);
+                    for (int y = 0; y < 16; y++)
+                        for (int x = 0; x < 16; x++) {
+                            const int p = interp(w + y * kWinStride + x, kWinStride, px & 1, py & 1);
+                            const int d = p - cur[y * 16 + x];
+                            sad2 += d < 0 ? -d : d;
+                        }
+                    const int cost = lane == 4 ? search_cost(sad2, bdx, bdy) : sad2;
+                    key2 = ((uint32_t)cost << 4) | (lane == 4 ? 0u : (uint32_t)lane + 1);
+                }
+            }
+            const uint32_t win2 = wave_min(key2);
+            const int bl = (int)(win2 & 15) == 0 ? 4 : (int)(win2 & 15) - 1;
+            if (lane < 9 && key2 == win2)
+                best_sad = sad2;
+            h = 2 * bdx + bl % 3 - 1;
+            v = 2 * bdy + bl / 3 - 1;
+            // intra cost: the luma's deviation from its own mean
+            const uint32_t wv = cur_w[lane];
+            const int sum = wave_sum((int)((wv & 255) + ((wv >> 8) & 255) + ((wv >> 16) & 255) + (wv >> 24)));
+            const int mean = (sum + 128) >> 8;
+            int dev = 0;
+            for (int k = 0; k < 4; k++) {
+                const int d = (int)((wv >> (8 * k)) & 255) - mean;
+                dev += d < 0 ? -d : d;
+            }
+            dev = wave_sum(dev);
+            __syncthreads();
+            intra = choose_intra(dev, best_sad);
+            if (intra)
+                h = v = 0;
+        }
+        // one lane per block: prediction, transform, quantisation, reconstruction
+        int coded = 0;
+        if (lane < 6) {
+            uint8_t blk[64];
+            if (!intra)
+                predict_block(ref, lane, mbx, row, h, v, blk);
+            int pitch;
+            const uint8_t* sb = block_ptr(src, lane, mbx, row, &pitch);
+            coded = code_block(sb, pitch, intra, a.qscale, T, blk, mbs[mbx].lev[lane]);
+            uint8_t* rb = const_cast<uint8_t*>(block_ptr(rec, lane, mbx, row, &pitch));
+            for (int y = 0; y < 8; y++) {
+                uint2 w;
+                w.x = blk[y * 8] | blk[y * 8 + 1] << 8 | blk[y * 8 + 2] << 16 | (uint32_t)blk[y * 8 + 3] << 24;
+                w.y = blk[y * 8 + 4] | blk[y * 8 + 5] << 8 | blk[y * 8 + 6] << 16 | (uint32_t)blk[y * 8 + 7] << 24;
+                *reinterpret_cast<uint2*>(rb + y * pitch) = w;
+                if (rec_out)
+                    *reinterpret_cast<uint2*>(rec_out + (rb - rec) + y * pitch) = w;
+            }
+        }
+        const uint64_t cm = __ballot(lane < 6 && coded);
+        if (lane == 0) {
+            int cbp = 0;
+            for (int b = 0; b < 6; b++)
+                if ((cm >> b) & 1)
+                    cbp |= 0x20 >> b;
+            mbs[mbx].h = (int8_t)h;
+            mbs[mbx].v = (int8_t)v;
+            mbs[mbx].intra = intra ? 1 : 0;
+            mbs[mbx].cbp = (uint8_t)(intra ? 0 : cbp);
+        }
+        __syncthreads();
+    }
+    if (lane == 0)
+        a.slice_len[(size_t)s * kMbRows + row] =
+            write_slice(a.slices + ((size_t)s * kMbRows + row) * kSliceCap, row, a.qscale, type, a.f_code, mbs, T);
+}
+
+__global__ __launch_bounds__(256) void k_enc_pack(EncArgs a)
+{
+    using namespace enc;
+    const int s = blockIdx.x, tid = threadIdx.x;
+    __shared__ uint8_t hdr[kHdrCap];
+    __shared__ uint32_t seg[kMbRows + 2];  // ES offsets: headers, then slice k at seg[k + 1]
+    __shared__ uint32_t sh_bytes, sh_ok;
+    EncState S = a.st[s];
+    const uint32_t phase = S.pictures % (uint32_t)a.gop;
+    const int type = phase == 0 ? 1 : 2;
+    const bool ts = a.format == EFX_FORMAT_TS;
+    if (tid == 0) {
+        seg[0] = 0;
+        seg[1] = write_headers(hdr, phase == 0, S.pictures, (int)phase, type, a.f_code);
+        for (int k = 0; k < kMbRows; k++)
+            seg[k + 2] = seg[k + 1] + a.slice_len[(size_t)s * kMbRows + k];
+        const uint32_t es = seg[kMbRows + 1];
+        const uint32_t bytes = ts ? ts_packets(es + kPesHdrBytes) * 188 : es;
+        sh_bytes = bytes;
+        sh_ok = !S.full && (uint64_t)S.out_len + bytes <= a.dst_stride;
+    }
+    __syncthreads();
+    const uint32_t bytes = sh_bytes, es_len = seg[kMbRows + 1];
+    const int64_t pts = (S.first_pts + 3003 * (int64_t)S.pictures) & ((1ll << 33) - 1);
+    if (sh_ok) {
+        uint8_t* out = a.dst + (size_t)s * a.dst_stride + S.out_len;
+        const uint8_t* sl = a.slices + (size_t)s * kMbRows * kSliceCap;
+        for (uint32_t o = tid; o < bytes; o += 256) {
+            int64_t e = o;
+            uint8_t b = 0;
+            if (ts) {
+                int64_t pp;
+                b = ts_byte(o, es_len + kPesHdrBytes, S.cc, &pp);
+                e = pp < kPesHdrBytes ? -1 : pp - kPesHdrBytes;
+                if (pp >= 0 && pp < kPesHdrBytes)
+                    b = pes_header_byte((int)pp, pts);
+            }
+            if (e >= 0) {
+                const uint32_t u = (uint32_t)e;
+                if (u < seg[1])
+                    b = hdr[u];
+                else {
+                    int k = 0;
+                    while (u >= seg[k + 2])
+                        k++;
+                    b = sl[(size_t)k * kSliceCap + (u - seg[k + 1])];
+                }
+            }
+            out[o] = b;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        if (sh_ok) {
+            S.out_len += bytes;
+            if (ts)
+                S.cc = (S.cc + ts_packets(es_len + kPesHdrBytes)) & 15;
+        } else if (!S.full) {
+            S.full = 1;
+            S.status |= EFX_ENCODE_FULL;
+            *(volatile uint32_t*)a.full_flag = a.generation;
+        }
+        S.pictures++;
+        S.cur ^= 1;
+        a.st[s] = S;
+        a.len[s] = S.out_len;
+        a.status[s] = S.status;
+    }
+}
+
+}  // namespace efx

@@ -256,6 +256,64 @@ size_t efx_export_bytes(int format);
  * no decode yet, or the stream range beyond the stream count of the most recent decode. */
 int efx_export_frames(efx_ctx* ctx, const efx_export_opts* opts, void* dst_device);
 
+/* -- MPEG-1 encode on the device (k_encode) ---------------------------------------------- */
+/* The reference plays titles that were "encoded with ffmpeg at around 1.5MBits" (README.md:87) ahead of time; nothing in it
+ * writes a stream.  efx_encode turns I420 pictures in device memory (the layout efx_export_frames writes: Y 192 x 352, then
+ * Cb 96 x 176, then Cr 96 x 176, 101 376 bytes) into MPEG-1 video that the reference player plays, for n_streams streams
+ * at once; with decode and I420 export it makes an on-device transcode.
+ *
+ * The streams honour every constraint of the reference decoder: 352 x 192, I and P pictures only, a sequence header and a
+ * closed GOP header before every I picture (default quantiser matrices; what the trick-play index seeks to), temporal_reference
+ * = pictures since the GOP header, vbv_delay 0xFFFF, full_pel_forward_vector 0 and forward_f_code 1 (search <= 7) or 2; one
+ * slice per macroblock row at quantiser_scale `qscale`; a P macroblock is intra, coded with or without motion compensation,
+ * motion compensated and not coded, or skipped -- never the first or last of its slice; every vector keeps its luma and
+ * chroma fetches inside the picture; every level is at most 255 in magnitude (8- and 16-bit escapes, player.cpp:1092-1099)
+ * and every value the decoder clamps stays in -256..511 (levels are halved until a block fits).  TS output: PID 0x100, one
+ * PES (stream id E0, PTS only) per picture, 188-byte packets, the last of a PES padded with adaptation-field stuffing; no
+ * sequence_end_code, so that streams can be continued.
+ *
+ * Motion search: exhaustive over every full-pel vector within +-search that keeps the fetches inside the picture, then the
+ * 8 half-pel neighbours of the best one with the decoder's interpolation; search 0 = the zero vector only.
+ *
+ * Reconstruction contract: recon_device (may be NULL) receives, in I420, exactly what a decoder holds after each picture --
+ * dequantisation, the one-coefficient shortcut with its unclamped intra DC, the reference's IDCT rounding, the clamp to 0..248
+ * -- at recon_device + (i * n_pictures + p) * 101376.  P pictures are predicted from it.
+ *
+ * Asynchronous on the context's stream, no host synchronisation, 1 + 2 x n_pictures launches whatever n_streams is.  Stream i
+ * appends to dst_device + i * dst_stride and writes nothing outside that region; len_device[i] gets the bytes written by the
+ * call, status_device[i] its EFX_ENCODE_* bits (both valid after efx_sync).  A picture that does not fit ends the stream's
+ * output after the last whole picture and sets EFX_ENCODE_FULL; other streams go on.  dst_stride >= efx_encode_bound(format,
+ * n_pictures) never sets it.  A stream's bytes depend only on its pictures, the options and its continuation state.
+ *
+ * cont = 1 continues the streams of the previous call: the outputs of the calls concatenated are one stream (the first picture
+ * is predicted from the previous call's last reconstruction; GOP phase, temporal_reference, PTS and continuity counter carry
+ * on).  qscale and search may change; EFX_ERR_STATE when there was no previous call, n_streams, format or gop differ from
+ * the call that started the streams, or a stream of the previous call hit EFX_ENCODE_FULL (known to the host once that call
+ * has completed, e.g. after efx_sync; a full stream is never continued on the device either).  Only the streams that cont
+would continue count: a region filled before the latest cont = 0 call never refuses it, whether that call has run or not.
+ *
+ * The encoder's state and scratch (two pictures and twelve worst-case slices per stream) are allocated at the context's first
+ * efx_encode, for max_streams streams, and freed by efx_destroy; encoding touches nothing of the decoder.
+ * EFX_ERR_ARG: a field out of range, a NULL or misaligned (16 bytes) src / dst / len / status / recon pointer, src_stride
+ * below n_pictures x 101376 or not a multiple of 16, dst_stride not a multiple of 16. */
+#define EFX_ENCODE_FULL 512u  /* status_device bit: the output region filled up (see above) */
+typedef struct efx_encode_opts {
+    int n_streams;      /* streams 0 .. n_streams-1 of the context, 1 .. max_streams */
+    int n_pictures;     /* pictures per stream in this call, 1 .. 255 */
+    int format;         /* EFX_FORMAT_ES or EFX_FORMAT_TS */
+    int qscale;         /* quantiser_scale of every slice, 1 .. 31 */
+    int gop;            /* an I picture every `gop` pictures of a stream, 1 .. 255 (1 = I pictures only) */
+    int search;         /* full-pel motion search radius 0 .. 15; 0 = the zero vector only */
+    int cont;           /* 0: every stream starts afresh; 1: continue the streams of the previous efx_encode */
+    int64_t first_pts;  /* TS, fresh streams: PTS of picture 0 (90 kHz, 0 .. 2^33-1); picture k carries first_pts + 3003 k */
+    size_t src_stride;  /* bytes from one stream's pictures to the next (>= n_pictures * 101376, multiple of 16) */
+    size_t dst_stride;  /* bytes of output region per stream (multiple of 16) */
+} efx_encode_opts;
+int efx_encode(efx_ctx* ctx, const efx_encode_opts* opts, const uint8_t* src_device, uint8_t* dst_device, uint32_t* len_device,
+               uint32_t* status_device, uint8_t* recon_device);
+/* Worst-case bytes of one stream of n_pictures pictures in `format` (0 for invalid arguments).  Host only. */
+size_t efx_encode_bound(int format, int n_pictures);
+
 /* -- composite video out (video_init / video_isr, src/video.cpp:572-630,1122-1198) -------- */
 typedef struct efx_video_params {
     int line_width, line_count;        /* samples per line, lines per field */
