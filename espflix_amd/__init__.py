@@ -42,6 +42,9 @@ STREAM_SERIAL_HUNT = 64   # the reference would misread bits between two start c
 STREAM_INTERNAL = 256     # never expected: a lost hand-over inside the reconstruction kernel (efx.h)
 STREAM_SLICE_ORDER = 128  # slice start codes of a picture not strictly rising in bitstream order: see efx.h
 ENCODE_FULL = 512         # efx_encode: the stream's output region filled up (efx.h)
+MUX_FULL = 1024           # efx_mux_av: the stream's output region is too small, nothing written (efx.h)
+MUX_BAD_VIDEO = 2048      # efx_mux_av: the video input is not a transport stream of PID 0x100 that starts with a PES (efx.h)
+PCM_FRAME_PLANAR, PCM_INTERLEAVED = 0, 1   # efx_sbc_encode_opts.pcm_layout
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EFX_LIB") or os.path.join(_HERE, "libefx.so")  # EFX_LIB: development builds
@@ -84,6 +87,19 @@ class _EncodeOpts(C.Structure):
     _fields_ = [("n_streams", C.c_int), ("n_pictures", C.c_int), ("format", C.c_int), ("qscale", C.c_int), ("gop", C.c_int),
                 ("search", C.c_int), ("cont", C.c_int), ("first_pts", C.c_int64), ("src_stride", C.c_size_t),
                 ("dst_stride", C.c_size_t)]
+
+
+class _SbcEncodeOpts(C.Structure):
+    _fields_ = [("n_streams", C.c_int), ("n_frames", C.c_int), ("frequency", C.c_int), ("blocks", C.c_int), ("mode", C.c_int),
+                ("allocation", C.c_int), ("bitpool", C.c_int), ("pcm_layout", C.c_int), ("pcm_stride", C.c_size_t),
+                ("frame_stride", C.c_size_t)]
+
+
+class _MuxOpts(C.Structure):
+    _fields_ = [("n_streams", C.c_int), ("audio_pid", C.c_int), ("frame_bytes", C.c_int), ("n_frames", C.c_int),
+                ("frames_per_pes", C.c_int), ("samples_per_frame", C.c_int), ("sample_rate", C.c_int),
+                ("audio_first_pts", C.c_int64), ("audio_first_frame", C.c_int64), ("audio_cc", C.c_int),
+                ("video_stride", C.c_size_t), ("audio_stride", C.c_size_t), ("dst_stride", C.c_size_t)]
 
 
 @dataclass
@@ -156,6 +172,12 @@ _SYMBOLS = {
     "efx_idx_pts2pts": (C.c_int64, [_P, C.c_int64, C.c_int]),
     "efx_sbc_state_bytes": (C.c_size_t, []),
     "efx_sbc_decode": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.c_int, C.c_int, _P, _P, C.c_size_t, _P, _P, C.c_int]),
+    "efx_sbc_frame_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "efx_sbc_enc_state_bytes": (C.c_size_t, []),
+    "efx_sbc_encode": (C.c_int, [_P, C.POINTER(_SbcEncodeOpts), _P, _P, _P]),
+    "efx_mux_av": (C.c_int, [_P, C.POINTER(_MuxOpts), _P, _P, _P, _P, _P, _P]),
+    "efx_mux_bound": (C.c_size_t, [C.c_size_t, C.c_int, C.c_int, C.c_int]),
+    "efx_mux_audio_packets": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "efx_pdm": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P]),
     "efx_set_timing": (C.c_int, [_P, C.c_int]),
     "efx_get_timing": (C.c_int, [_P, C.POINTER(_Timing)]),
@@ -257,6 +279,25 @@ def encode_bound(fmt: int, n_pictures: int) -> int:
 
 def sbc_state_bytes() -> int:
     return int(load_library().efx_sbc_state_bytes())
+
+
+def sbc_frame_bytes(blocks: int, channels: int, bitpool: int) -> int:
+    """Bytes of an SBC frame of 8 subbands (efx_sbc_frame_bytes; 0 for arguments efx_sbc_encode rejects)."""
+    return int(load_library().efx_sbc_frame_bytes(blocks, channels, bitpool))
+
+
+def sbc_enc_state_bytes() -> int:
+    return int(load_library().efx_sbc_enc_state_bytes())
+
+
+def mux_bound(video_bytes: int, n_frames: int, frame_bytes: int, frames_per_pes: int) -> int:
+    """A dst_stride with which efx_mux_av never reports MUX_FULL (efx_mux_bound; 0 for invalid arguments)."""
+    return int(load_library().efx_mux_bound(video_bytes, n_frames, frame_bytes, frames_per_pes))
+
+
+def mux_audio_packets(n_frames: int, frame_bytes: int, frames_per_pes: int) -> int:
+    """Audio packets efx_mux_av writes per stream: add to audio_cc (mod 16) for the next call."""
+    return int(load_library().efx_mux_audio_packets(n_frames, frame_bytes, frames_per_pes))
 
 
 def _check(ctx, status: int):
@@ -703,6 +744,175 @@ class Decoder:
         g = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else b)
         _check(self._ctx, self._lib.efx_sbc_decode(self._ctx, n_streams, g(frames), stream_stride, frame_bytes, n_frames,
                                                    g(state), g(pcm), pcm_stride, g(ret), g(pcm_count), 1 if probe_first else 0))
+
+    # -- SBC encode (efx_sbc_encode) and A/V multiplexing (efx_mux_av) ------------------------------
+    def sbc_encode_to(self, pcm: DeviceBuffer | int, state: DeviceBuffer | int, frames: DeviceBuffer | int, *, n_streams: int,
+                      n_frames: int, blocks: int = 16, mode: int = 0, allocation: int = 0, bitpool: int = 28, frequency: int = 3,
+                      pcm_layout: int = PCM_FRAME_PLANAR, pcm_stride: int = 0, frame_stride: int = 0) -> int:
+        """efx_sbc_encode on raw device memory, asynchronous on the library's stream: stream i's int16 PCM at pcm + i x
+        pcm_stride elements (0 = packed), its frames back to back from frames + i x frame_stride bytes (0 = the frames'
+        size rounded up to 16), the encoders' states (sbc_enc_state_bytes() each, zeros = fresh) updated in place.  Returns
+        the frame stride used."""
+        g = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
+        ch = 2 if mode else 1
+        fb = sbc_frame_bytes(blocks, ch, bitpool)
+        o = _SbcEncodeOpts(n_streams, n_frames, frequency, blocks, mode, allocation, bitpool, pcm_layout,
+                           pcm_stride or n_frames * blocks * 8 * ch, frame_stride or (n_frames * fb + 15) // 16 * 16)
+        _check(self._ctx, self._lib.efx_sbc_encode(self._ctx, C.byref(o), g(pcm), g(state), g(frames)))
+        return o.frame_stride
+
+    def sbc_encode(self, pcm, *, blocks: int = 16, mode: int = 0, allocation: int = 0, bitpool: int = 28, frequency: int = 3,
+                   pcm_layout: int = PCM_FRAME_PLANAR, cont: bool = False):
+        """Encode int16 PCM [n_streams, samples] (a NumPy array, or a torch tensor on the decoder's device) into SBC frames:
+        a uint8 torch tensor [n_streams, n_frames, frame_bytes] on the device (samples must be a whole number of frames:
+        blocks x 8 x channels values each).  cont=True continues the streams of the previous sbc_encode of this object (the
+        analysis filter's memory is kept on the device); otherwise the encoders start afresh.  Synchronises torch's current
+        stream before and the library's after."""
+        import torch
+        device = torch.device("cuda", self.device)
+        if isinstance(pcm, np.ndarray):
+            pcm = torch.from_numpy(np.ascontiguousarray(pcm, dtype=np.int16)).to(device)
+        if pcm.dtype != torch.int16 or pcm.device != device or pcm.dim() != 2:
+            raise ValueError(f"pcm must be an int16 [n_streams, samples] tensor on {device} (or a NumPy array)")
+        pcm = pcm.contiguous()
+        ch = 2 if mode else 1
+        n, per = pcm.shape[0], blocks * 8 * ch
+        if pcm.shape[1] == 0 or pcm.shape[1] % per:
+            raise ValueError(f"samples per stream must be a positive multiple of {per}")
+        n_frames = pcm.shape[1] // per
+        fb = sbc_frame_bytes(blocks, ch, bitpool)
+        if not fb:
+            raise ValueError("blocks, mode or bitpool out of range")
+        st = getattr(self, "_sbc_enc_state", None)
+        if not cont or st is None or st.shape[0] != n:
+            if cont:
+                raise EfxError(-5, "sbc_encode: cont without a previous sbc_encode of as many streams")
+            st = torch.zeros((n, sbc_enc_state_bytes()), dtype=torch.uint8, device=device)
+        stride = (n_frames * fb + 15) // 16 * 16
+        out = torch.empty((n, stride), dtype=torch.uint8, device=device)
+        torch.cuda.current_stream(device).synchronize()
+        self.sbc_encode_to(pcm.data_ptr(), st.data_ptr(), out.data_ptr(), n_streams=n, n_frames=n_frames, blocks=blocks, mode=mode,
+                           allocation=allocation, bitpool=bitpool, frequency=frequency, pcm_layout=pcm_layout,
+                           pcm_stride=pcm.shape[1], frame_stride=stride)
+        self.sync()
+        self._sbc_enc_state = st
+        return out[:, :n_frames * fb].reshape(n, n_frames, fb)
+
+    def mux_to(self, video: DeviceBuffer | int, video_len: DeviceBuffer | int, audio: DeviceBuffer | int | None,
+               dst: DeviceBuffer | int, length: DeviceBuffer | int, status: DeviceBuffer | int, *, n_streams: int, frame_bytes: int,
+               n_frames: int, video_stride: int, audio_stride: int, dst_stride: int, frames_per_pes: int = 8,
+               audio_pid: int = 0x101, samples_per_frame: int = 128, sample_rate: int = 48000, audio_first_pts: int = 0,
+               audio_first_frame: int = 0, audio_cc: int = 0):
+        """efx_mux_av on raw device memory, asynchronous on the library's stream: video / video_len are what encode_to left in
+        dst / length, so encode_to -> sbc_encode_to -> mux_to needs no synchronisation in between."""
+        g = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else b)
+        o = _MuxOpts(n_streams, audio_pid, frame_bytes, n_frames, frames_per_pes, samples_per_frame, sample_rate, audio_first_pts,
+                     audio_first_frame, audio_cc, video_stride, audio_stride, dst_stride)
+        _check(self._ctx, self._lib.efx_mux_av(self._ctx, C.byref(o), g(video), g(video_len), g(audio), g(dst), g(length), g(status)))
+
+    def mux(self, video_streams, frames, *, frames_per_pes: int = 8, audio_pid: int = 0x101, samples_per_frame: int = 128,
+            sample_rate: int = 48000, audio_first_pts: int = 0, audio_first_frame: int = 0, audio_cc: int = 0,
+            dst_stride: int = 0):
+        """Multiplex video transport streams (a list of bytes / uint8 arrays, as encode(fmt=FORMAT_TS) returns them) with SBC
+        frames (uint8 [n_streams, n_frames, frame_bytes]: a NumPy array or a torch tensor as sbc_encode returns it; n_frames
+        may be 0).  Returns (titles: list of bytes, status: uint32 array of MUX_* bits).  Synchronises."""
+        n = len(video_streams)
+        arrs = [np.frombuffer(v, dtype=np.uint8) if isinstance(v, (bytes, bytearray, memoryview))
+                else np.ascontiguousarray(v, dtype=np.uint8) for v in video_streams]
+        if not isinstance(frames, np.ndarray):
+            frames = frames.cpu().numpy()
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        if frames.ndim != 3 or frames.shape[0] != n:
+            raise ValueError("frames must have shape (n_streams, n_frames, frame_bytes)")
+        n_frames, fb = frames.shape[1], frames.shape[2]
+        r16 = lambda v: (v + 15) // 16 * 16
+        v_stride = r16(max(1, max(a.size for a in arrs)))
+        a_stride = r16(max(1, n_frames * fb))
+        stride = dst_stride or mux_bound(v_stride, n_frames, fb, frames_per_pes)
+        bufs = []
+        try:
+            d_v, d_a, d_dst = (DeviceBuffer(self, n * v_stride), DeviceBuffer(self, n * a_stride), DeviceBuffer(self, n * stride))
+            d_meta = DeviceBuffer(self, 3 * r16(4 * n))
+            bufs += [d_v, d_a, d_dst, d_meta]
+            host_v = np.zeros((n, v_stride), dtype=np.uint8)
+            for i, a in enumerate(arrs):
+                host_v[i, :a.size] = a
+            d_v.upload(host_v)
+            host_a = np.zeros((n, a_stride), dtype=np.uint8)
+            host_a[:, :n_frames * fb] = frames.reshape(n, -1)
+            d_a.upload(host_a)
+            d_meta.upload(np.array([a.size for a in arrs], dtype=np.uint32))
+            p_len, p_st = d_meta.ptr + r16(4 * n), d_meta.ptr + 2 * r16(4 * n)
+            self.mux_to(d_v, d_meta.ptr, d_a, d_dst, p_len, p_st, n_streams=n, frame_bytes=fb, n_frames=n_frames,
+                        video_stride=v_stride, audio_stride=a_stride, dst_stride=stride, frames_per_pes=frames_per_pes,
+                        audio_pid=audio_pid, samples_per_frame=samples_per_frame, sample_rate=sample_rate,
+                        audio_first_pts=audio_first_pts, audio_first_frame=audio_first_frame, audio_cc=audio_cc)
+            self.sync()
+            return self._download_streams(d_dst.ptr, stride, p_len, p_st, n)
+        finally:
+            for b in bufs:
+                b.free()
+
+    def _download_streams(self, dst_ptr: int, stride: int, len_ptr: int, status_ptr: int, n: int):
+        lens, st = np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint32)
+        _check(self._ctx, self._lib.efx_memcpy_d2h(self._ctx, lens.ctypes.data, len_ptr, 4 * n))
+        _check(self._ctx, self._lib.efx_memcpy_d2h(self._ctx, st.ctypes.data, status_ptr, 4 * n))
+        out = []
+        for i in range(n):
+            b = np.empty(int(lens[i]), dtype=np.uint8)
+            if b.size:
+                _check(self._ctx, self._lib.efx_memcpy_d2h(self._ctx, b.ctypes.data, dst_ptr + i * stride, b.size))
+            out.append(b.tobytes())
+        return out, st
+
+    def encode_av(self, pictures, pcm, *, qscale: int = 8, gop: int = 12, search: int = 7, first_pts: int = 0, blocks: int = 16,
+                  allocation: int = 0, bitpool: int = 28, frequency: int = 3, sample_rate: int = 48000, frames_per_pes: int = 8,
+                  audio_pid: int = 0x101):
+        """Pictures + PCM -> complete titles: encode (transport streams) -> sbc_encode (mono) -> mux, queued back to back on
+        the library's stream with nothing synchronised in between.  pictures: (n, P, 101376) I420 as for encode(); pcm: int16
+        [n, samples], a whole number of frames of blocks x 8 samples; the audio starts at the first picture's PTS.  Every
+        stream starts afresh.  Returns (titles: list of bytes, status: uint32 array of ENCODE_* | MUX_* bits)."""
+        import torch
+        device = torch.device("cuda", self.device)
+        to_dev = lambda t, dt: torch.from_numpy(np.ascontiguousarray(t)).to(device) if isinstance(t, np.ndarray) else t
+        pictures, pcm = to_dev(pictures, np.uint8), to_dev(pcm, np.int16)
+        if pictures.dtype != torch.uint8 or pictures.dim() != 3 or pictures.shape[-1] != FRAME_BYTES or pictures.device != device:
+            raise ValueError(f"pictures must be uint8 (n, P, {FRAME_BYTES}) on {device}")
+        n, P = int(pictures.shape[0]), int(pictures.shape[1])
+        if pcm.dtype != torch.int16 or pcm.dim() != 2 or pcm.shape[0] != n or pcm.device != device or pcm.shape[1] % (blocks * 8):
+            raise ValueError("pcm must be int16 [n, samples], samples a multiple of blocks x 8")
+        pictures, pcm = pictures.contiguous(), pcm.contiguous()
+        n_frames = int(pcm.shape[1]) // (blocks * 8)
+        fb = sbc_frame_bytes(blocks, 1, bitpool)
+        r16 = lambda v: (v + 15) // 16 * 16
+        v_stride = encode_bound(FORMAT_TS, P)
+        a_stride = r16(max(1, n_frames * fb))
+        stride = mux_bound(v_stride, n_frames, fb, frames_per_pes)
+        bufs = []
+        try:
+            d_v, d_a, d_dst = DeviceBuffer(self, n * v_stride), DeviceBuffer(self, n * a_stride), DeviceBuffer(self, n * stride)
+            d_meta, d_state = DeviceBuffer(self, 4 * r16(4 * n)), DeviceBuffer(self, n * sbc_enc_state_bytes())
+            bufs += [d_v, d_a, d_dst, d_meta, d_state]
+            d_state.upload(np.zeros(n * sbc_enc_state_bytes(), dtype=np.uint8))
+            p_vlen, p_vst, p_len, p_st = (d_meta.ptr + k * r16(4 * n) for k in range(4))
+            torch.cuda.current_stream(device).synchronize()
+            self.encode_to(pictures.data_ptr(), d_v, p_vlen, p_vst, n_streams=n, n_pictures=P, qscale=qscale, gop=gop, search=search,
+                           fmt=FORMAT_TS, first_pts=first_pts, dst_stride=v_stride)
+            if n_frames:
+                self.sbc_encode_to(pcm.data_ptr(), d_state, d_a, n_streams=n, n_frames=n_frames, blocks=blocks, mode=0,
+                                   allocation=allocation, bitpool=bitpool, frequency=frequency, pcm_stride=int(pcm.shape[1]),
+                                   frame_stride=a_stride)
+            self.mux_to(d_v, p_vlen, d_a, d_dst, p_len, p_st, n_streams=n, frame_bytes=fb, n_frames=n_frames, video_stride=v_stride,
+                        audio_stride=a_stride, dst_stride=stride, frames_per_pes=frames_per_pes, audio_pid=audio_pid,
+                        samples_per_frame=blocks * 8, sample_rate=sample_rate, audio_first_pts=first_pts)
+            self.sync()
+            titles, st = self._download_streams(d_dst.ptr, stride, p_len, p_st, n)
+            vst = np.empty(n, dtype=np.uint32)
+            _check(self._ctx, self._lib.efx_memcpy_d2h(self._ctx, vst.ctypes.data, p_vst, 4 * n))
+            return titles, st | vst
+        finally:
+            for b in bufs:
+                b.free()
 
     def pdm(self, n_streams: int, pcm: DeviceBuffer | int, n_samples: int, state: DeviceBuffer | int,
             dst: DeviceBuffer | int):

@@ -20,6 +20,7 @@
 #include "efx_internal.h"
 #include "enc_core.h"
 #include "parse_tm.h"
+#include "sbc_enc_core.h"
 
 namespace efx {
 // kernels (k_demux.hip, k_index.hip, k_parse.hip, k_recon.hip, k_video.hip)
@@ -67,6 +68,9 @@ __global__ void k_sbc_gen(const uint8_t*, size_t, int, int, const SbcState*, Sbc
                           const SbcFramePlan*, int16_t*, size_t, int, SbcQueues*, const uint32_t*, int, const uint8_t*, int);
 __global__ void k_sbc_finish(const uint8_t*, size_t, int, int, SbcState*, const SbcState*, const SbcTables*, int16_t*, size_t, uint32_t*,
                              uint32_t*, int, uint32_t*);
+__global__ void k_sbc_enc(SbcEncArgs);
+__global__ void k_sbc_enc_state(SbcEncArgs);
+__global__ void k_mux(MuxArgs);
 }  // namespace efx
 
 using namespace efx;
@@ -223,6 +227,9 @@ struct efx_ctx {
     VideoTables* d_video[2] = {nullptr, nullptr};  // [0] PAL, [1] NTSC
     VideoLineTemplates* d_video_lines[2] = {nullptr, nullptr};
     SbcTables* d_sbc_tables = nullptr;
+    sbcenc::Tables* d_sbc_enc_tables = nullptr;  // efx_sbc_encode's window and matrix (sbc_enc_core.h)
+    uint32_t* d_mux_before = nullptr;            // efx_mux_av's scratch: per (stream, audio PES) the video packets in front of it
+    size_t mux_before_cap = 0;
     int parse_wg_cap = 0;  // k_parse workgroups resident per parse kernel while reconstruction launches are queued (0: no cap); EFX_PARSE_WG_CAP
     // launch structure (efx_set_option; the environment variables of the same names, upper case with EFX_, set the defaults)
     int opt_groups = 0;        // reconstruction groups per call: 0 = one group behind a busy reconstruction stream, groups of
@@ -609,6 +616,7 @@ int efx_create(const efx_config* cfg, efx_ctx** out)
     A(dalloc(&ctx->d_video_lines[1], 1));
     A(dalloc(&ctx->d_hash, n * D));
     A(dalloc(&ctx->d_sbc_tables, 1));
+    A(dalloc(&ctx->d_sbc_enc_tables, 1));
     if (e != hipSuccess) {
         fprintf(stderr, "efx_create: %s\n", hipGetErrorString(e));
         return bail(EFX_ERR_DEVICE);
@@ -663,6 +671,9 @@ int efx_create(const efx_config* cfg, efx_ctx** out)
         SbcTables st;
         build_sbc_tables(&st);
         A(hipMemcpy(ctx->d_sbc_tables, &st, sizeof(st), hipMemcpyHostToDevice));
+        sbcenc::Tables et;
+        sbcenc::build_tables(&et);
+        A(hipMemcpy(ctx->d_sbc_enc_tables, &et, sizeof(et), hipMemcpyHostToDevice));
     }
     A(hipMemset(ctx->d_frames, 0, n * D * kFrameBytes));
     for (auto& sl : ctx->slot) {
@@ -703,7 +714,7 @@ void efx_destroy(efx_ctx* ctx)
     void* bufs[] = {ctx->d_tables, ctx->d_tm_tables, ctx->d_sbc_flags, ctx->d_sbc_next, ctx->d_sbc_info, ctx->d_sbc_plan, ctx->d_sbc_extra, ctx->d_sbc_cover, ctx->d_state, ctx->d_frames, ctx->d_video[0],  ctx->d_video[1], ctx->d_video_lines[0],
                     ctx->d_video_lines[1], ctx->d_hash, ctx->d_ts, ctx->d_demux_chunks, ctx->d_sbc_tables, ctx->d_idx_info, ctx->d_ts_off, ctx->d_idx_len,
                     ctx->d_idx_base, ctx->d_idx_seq, ctx->d_enc_state, ctx->d_enc_pics, ctx->d_enc_slices, ctx->d_enc_slice_len,
-                    ctx->d_enc_tables};
+                    ctx->d_enc_tables, ctx->d_sbc_enc_tables, ctx->d_mux_before};
     if (ctx->h_enc_full)
         (void)hipHostFree(ctx->h_enc_full);
     for (auto& te : ctx->timing_ring)
@@ -2209,6 +2220,157 @@ int efx_sbc_decode(efx_ctx* ctx, int n_streams, const uint8_t* frames_device, si
                        ctx->d_sbc_next, ctx->d_sbc_tables, pcm_device, pcm_stride, ret_device, pcm_count_device, flags, d_how);
     EFX_HIP(hipGetLastError());
     ctx->sbc_flags_clean = true;
+    return EFX_OK;
+}
+
+// ---- SBC encode (k_sbc_enc.hip) -------------------------------------------------------------------------------------------------
+size_t efx_sbc_frame_bytes(int blocks, int channels, int bitpool)
+{
+    if ((blocks != 4 && blocks != 8 && blocks != 12 && blocks != 16) || channels < 1 || channels > 2 || bitpool < 2 || bitpool > 128)
+        return 0;
+    return sbcenc::frame_bytes(blocks, channels, bitpool);
+}
+
+size_t efx_sbc_enc_state_bytes(void) { return sbcenc::kStateBytes; }
+
+int efx_sbc_encode(efx_ctx* ctx, const efx_sbc_encode_opts* o, const int16_t* pcm_device, void* state_device, uint8_t* frames_device)
+{
+    bind_device(ctx);
+    if (!ctx || !o)
+        return EFX_ERR_ARG;
+    auto misaligned = [](const void* p) { return !p || ((uintptr_t)p & 15); };
+    if (o->n_streams < 1 || o->n_streams > ctx->cfg.max_streams)
+        return fail(ctx, EFX_ERR_ARG, "efx_sbc_encode: n_streams outside 1 .. max_streams");
+    if (o->frequency < 0 || o->frequency > 3)
+        return fail(ctx, EFX_ERR_ARG, "efx_sbc_encode: frequency outside 0 .. 3");
+    if (o->blocks != 4 && o->blocks != 8 && o->blocks != 12 && o->blocks != 16)
+        return fail(ctx, EFX_ERR_ARG, "efx_sbc_encode: blocks must be 4, 8, 12 or 16");
+    if (o->mode != 0 && o->mode != 1)
+        return fail(ctx, EFX_ERR_ARG, "efx_sbc_encode: mode must be 0 (mono) or 1 (dual channel): the reference decodes no joint stereo, and its stereo is not the standard's");
+    if (o->allocation != 0 && o->allocation != 1)
+        return fail(ctx, EFX_ERR_ARG, "efx_sbc_encode: allocation must be 0 (loudness) or 1 (SNR)");
+    if (o->bitpool < 2 || o->bitpool > 128)
+        return fail(ctx, EFX_ERR_ARG, "efx_sbc_encode: bitpool outside 2 .. 128");
+    if (o->pcm_layout != EFX_PCM_FRAME_PLANAR && o->pcm_layout != EFX_PCM_INTERLEAVED)
+        return fail(ctx, EFX_ERR_ARG, "efx_sbc_encode: unknown pcm_layout");
+    const int channels = o->mode ? 2 : 1, spf = o->blocks * 8;
+    if (o->n_frames < 1 || (long long)o->n_frames * spf >= (1ll << 31))
+        return fail(ctx, EFX_ERR_ARG, "efx_sbc_encode: n_frames must be >= 1 and n_frames x samples per frame below 2^31");
+    const size_t fb = sbcenc::frame_bytes(o->blocks, channels, o->bitpool);
+    if (o->pcm_stride < (size_t)o->n_frames * spf * channels)
+        return fail(ctx, EFX_ERR_ARG, "efx_sbc_encode: pcm_stride does not hold n_frames frames");
+    if (o->frame_stride < (size_t)o->n_frames * fb || (o->frame_stride & 15))
+        return fail(ctx, EFX_ERR_ARG, "efx_sbc_encode: frame_stride must be a multiple of 16 and hold n_frames frames");
+    if (misaligned(pcm_device) || misaligned(state_device) || misaligned(frames_device))
+        return fail(ctx, EFX_ERR_ARG, "efx_sbc_encode: pcm, state and frames must be 16-byte aligned device pointers");
+    SbcEncArgs a{};
+    a.pcm = pcm_device;
+    a.state = static_cast<int16_t*>(state_device);
+    a.frames = frames_device;
+    a.tables = ctx->d_sbc_enc_tables;
+    a.pcm_stride = o->pcm_stride;
+    a.frame_stride = o->frame_stride;
+    a.frame_bytes = (uint32_t)fb;
+    a.n_streams = o->n_streams;
+    a.n_frames = o->n_frames;
+    a.n_groups = (o->n_frames + 3) / 4;
+    a.frequency = o->frequency;
+    a.blocks = o->blocks;
+    a.mode = o->mode;
+    a.allocation = o->allocation;
+    a.bitpool = o->bitpool;
+    a.layout = o->pcm_layout;
+    // (both grid dimensions are strided over by the kernel: the caps only bound the launch)
+    const dim3 grid((unsigned)std::min(a.n_groups, 1 << 20), (unsigned)std::min(a.n_streams, 65535));
+    hipLaunchKernelGGL(k_sbc_enc, grid, dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL(k_sbc_enc_state, dim3((unsigned)a.n_streams), dim3(192), 0, ctx->stream, a);
+    EFX_HIP(hipGetLastError());
+    return EFX_OK;
+}
+
+// ---- A/V multiplexer (k_mux.hip) ------------------------------------------------------------------------------------------------
+int efx_mux_audio_packets(int n_frames, int frame_bytes, int frames_per_pes)
+{
+    if (n_frames < 0 || frame_bytes < 1 || frames_per_pes < 1 || (long long)frames_per_pes * frame_bytes > 2048)
+        return -1;
+    const long long full = n_frames / frames_per_pes, rest = n_frames % frames_per_pes;
+    long long n = full * enc::ts_packets((uint32_t)(14 + frames_per_pes * frame_bytes));
+    if (rest)
+        n += enc::ts_packets((uint32_t)(14 + rest * frame_bytes));
+    return n > 0x7FFFFFFF ? -1 : (int)n;
+}
+
+size_t efx_mux_bound(size_t video_bytes, int n_frames, int frame_bytes, int frames_per_pes)
+{
+    const int ap = efx_mux_audio_packets(n_frames, frame_bytes, frames_per_pes);
+    if (ap < 0)
+        return 0;
+    return (video_bytes + (size_t)ap * 188 + 15) / 16 * 16;
+}
+
+int efx_mux_av(efx_ctx* ctx, const efx_mux_opts* o, const uint8_t* video_ts_device, const uint32_t* video_len_device,
+               const uint8_t* audio_frames_device, uint8_t* dst_device, uint32_t* len_device, uint32_t* status_device)
+{
+    bind_device(ctx);
+    if (!ctx || !o)
+        return EFX_ERR_ARG;
+    auto misaligned = [](const void* p) { return !p || ((uintptr_t)p & 15); };
+    if (o->n_streams < 1 || o->n_streams > ctx->cfg.max_streams)
+        return fail(ctx, EFX_ERR_ARG, "efx_mux_av: n_streams outside 1 .. max_streams");
+    if (o->audio_pid != 0x101 && o->audio_pid != 0x102)
+        return fail(ctx, EFX_ERR_ARG, "efx_mux_av: audio_pid must be 0x101 or 0x102");
+    if (o->frame_bytes < 1 || o->n_frames < 0 || o->frames_per_pes < 1 || (long long)o->frames_per_pes * o->frame_bytes > 2048)
+        return fail(ctx, EFX_ERR_ARG, "efx_mux_av: frame_bytes >= 1, n_frames >= 0, frames_per_pes >= 1 and frames_per_pes x frame_bytes <= 2048");
+    if (o->samples_per_frame < 1 || o->sample_rate < 1)
+        return fail(ctx, EFX_ERR_ARG, "efx_mux_av: samples_per_frame and sample_rate must be positive");
+    if (o->audio_first_pts < 0 || o->audio_first_pts >= (1ll << 33) || o->audio_first_frame < 0 || o->audio_first_frame >= (1ll << 31))
+        return fail(ctx, EFX_ERR_ARG, "efx_mux_av: audio_first_pts outside 0 .. 2^33-1 or audio_first_frame outside 0 .. 2^31-1");
+    if (o->audio_cc < 0 || o->audio_cc > 15)
+        return fail(ctx, EFX_ERR_ARG, "efx_mux_av: audio_cc outside 0 .. 15");
+    if ((o->video_stride & 15) || (o->audio_stride & 15) || (o->dst_stride & 15) || o->dst_stride >= (1ull << 32) ||
+        o->audio_stride < (size_t)o->n_frames * o->frame_bytes)
+        return fail(ctx, EFX_ERR_ARG, "efx_mux_av: strides must be multiples of 16, audio_stride hold n_frames frames, dst_stride be below 2^32");
+    const int ap = efx_mux_audio_packets(o->n_frames, o->frame_bytes, o->frames_per_pes);
+    if (ap < 0)
+        return fail(ctx, EFX_ERR_ARG, "efx_mux_av: too many audio packets for one call");
+    if (misaligned(video_ts_device) || misaligned(video_len_device) || misaligned(dst_device) || misaligned(len_device) ||
+        misaligned(status_device) || (o->n_frames > 0 && misaligned(audio_frames_device)))
+        return fail(ctx, EFX_ERR_ARG, "efx_mux_av: video, video_len, dst, len and status (and audio, with frames) must be 16-byte aligned device pointers");
+    MuxArgs a{};
+    a.n_pes = (o->n_frames + o->frames_per_pes - 1) / o->frames_per_pes;
+    const size_t need = (size_t)o->n_streams * (size_t)std::max(a.n_pes, 1);
+    if (need > ctx->mux_before_cap) {
+        if (ctx->d_mux_before)
+            (void)dev_free(ctx->d_mux_before);
+        ctx->d_mux_before = nullptr;
+        ctx->mux_before_cap = 0;
+        EFX_HIP(dalloc(&ctx->d_mux_before, need));
+        ctx->mux_before_cap = need;
+    }
+    a.video = video_ts_device;
+    a.video_len = video_len_device;
+    a.audio = audio_frames_device;
+    a.dst = dst_device;
+    a.len = len_device;
+    a.status = status_device;
+    a.video_before = ctx->d_mux_before;
+    a.video_stride = o->video_stride;
+    a.audio_stride = o->audio_stride;
+    a.dst_stride = o->dst_stride;
+    a.first_pts = o->audio_first_pts;
+    a.first_frame = o->audio_first_frame;
+    a.n_streams = o->n_streams;
+    a.pid = o->audio_pid;
+    a.frame_bytes = o->frame_bytes;
+    a.n_frames = o->n_frames;
+    a.frames_per_pes = o->frames_per_pes;
+    a.samples_per_frame = o->samples_per_frame;
+    a.sample_rate = o->sample_rate;
+    a.cc = o->audio_cc;
+    a.pes_packets = (int)enc::ts_packets((uint32_t)(14 + o->frames_per_pes * o->frame_bytes));
+    a.audio_packets = ap;
+    hipLaunchKernelGGL(k_mux, dim3((unsigned)a.n_streams), dim3(256), 0, ctx->stream, a);
+    EFX_HIP(hipGetLastError());
     return EFX_OK;
 }
 

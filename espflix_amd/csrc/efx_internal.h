@@ -281,6 +281,36 @@ struct EncArgs {
     int n_streams, n_pictures, picture, qscale, gop, search, format, f_code, cont;
 };
 
+// k_sbc_enc launch arguments (by value): efx_sbc_encode_opts, checked, with the context's tables
+namespace sbcenc {
+struct Tables;
+}
+struct SbcEncArgs {
+    const int16_t* pcm;   // stream i at pcm + i * pcm_stride
+    int16_t* state;       // stream i: 2 x 72 samples at state + i * 144 (k_sbc_enc reads, k_sbc_enc_state writes)
+    uint8_t* frames;      // stream i, frame f at frames + i * frame_stride + f * frame_bytes
+    const sbcenc::Tables* tables;
+    size_t pcm_stride, frame_stride;
+    uint32_t frame_bytes;
+    int n_streams, n_frames, n_groups;  // n_groups: workgroups' worth of frames per stream (four frames each)
+    int frequency, blocks, mode, allocation, bitpool, layout;
+};
+
+// k_mux launch arguments (by value): efx_mux_opts, checked
+struct MuxArgs {
+    const uint8_t* video;      // stream i's transport stream at video + i * video_stride, video_len[i] bytes
+    const uint32_t* video_len;
+    const uint8_t* audio;      // stream i's frames at audio + i * audio_stride
+    uint8_t* dst;
+    uint32_t* len;
+    uint32_t* status;
+    uint32_t* video_before;    // scratch, per (stream, audio PES): video packets in front of it
+    size_t video_stride, audio_stride, dst_stride;
+    int64_t first_pts, first_frame;
+    int n_streams, pid, frame_bytes, n_frames, frames_per_pes, samples_per_frame, sample_rate, cc;
+    int n_pes, pes_packets, audio_packets;  // audio PES of a stream, packets of a full one, audio packets of a stream
+};
+
 void build_sbc_tables(SbcTables* t);
 void build_parse_tables(ParseTables* t);
 void build_video_tables(int ntsc, VideoTables* t);

@@ -421,6 +421,91 @@ int efx_sbc_decode(efx_ctx* ctx, int n_streams, const uint8_t* frames_device, si
                    int n_frames, void* state_device, int16_t* pcm_device, size_t pcm_stride, uint32_t* ret_device,
                    uint32_t* pcm_count_device, int flags);
 
+/* -- SBC audio encode: PCM -> frames the reference decodes (espflix_amd/csrc/k_sbc_enc.hip, sbc_enc_core.h) -- */
+/* The inverse of efx_sbc_decode for what the reference decoder accepts and plays like every other SBC decoder: 8 subbands
+ * (src/sbc_decoder.cpp:291-292), mono or dual channel.  Not offered: joint stereo (rejected there) and mode 2 "stereo" --
+ * its bit_allocation gives every channel the whole bitpool (src/sbc_decoder.cpp:151-232), so a mode-2 frame it plays is
+ * not one other decoders play.  The player itself decodes mono frames of at most 16 blocks into a 128-sample buffer
+ * (src/video.cpp:978-985) and expects 48 kHz, 16 blocks, 64-byte frames (src/video.cpp:953-987): bitpool 28.
+ * A frame: 9C, frequency / blocks / mode / allocation / subbands, bitpool, CRC-8 (x^8+x^4+x^3+x^2+1, initial value 0x0F,
+ * over bytes 1 and 2 and the scale factors; the reference ignores it, other decoders check it), 4-bit scale factors, the
+ * quantised samples block-major, channel, subband, most significant bit first (get_samples, src/sbc_decoder.cpp:273-341).
+ * The analysis is A2DP Appendix B's with the subband samples halved, which is the reference's amplitude convention
+ * (a sample is reconstructed inside (-2^scale, 2^scale), src/sbc_decoder.cpp:257-264,330-334): PCM encoded here and decoded
+ * by it (or by efx_sbc_decode) returns at unity gain, 73 samples late.  All integer; tests/sbc_enc_model_main.cpp writes
+ * the same bytes on the host. */
+#define EFX_PCM_FRAME_PLANAR 0  /* what efx_sbc_decode writes: per frame, channel 0's blocks x 8 samples, then channel 1's */
+#define EFX_PCM_INTERLEAVED  1  /* L R L R ...; the same as FRAME_PLANAR for mono */
+typedef struct efx_sbc_encode_opts {
+    int n_streams;     /* 1 .. max_streams */
+    int n_frames;      /* frames per stream in this call, >= 1; n_frames x samples per frame < 2^31 */
+    int frequency;     /* header field 0..3 = 16 / 32 / 44.1 / 48 kHz (selects the loudness offsets) */
+    int blocks;        /* 4, 8, 12, 16 */
+    int mode;          /* 0 mono, 1 dual channel */
+    int allocation;    /* 0 loudness, 1 SNR */
+    int bitpool;       /* 2 .. 128 (above 128 the reference hangs) */
+    int pcm_layout;    /* EFX_PCM_* */
+    size_t pcm_stride;    /* int16 elements from one stream's PCM to the next, >= n_frames x blocks x 8 x channels */
+    size_t frame_stride;  /* bytes from one stream's frames to the next, >= n_frames x frame bytes, a multiple of 16 */
+} efx_sbc_encode_opts;
+/* 4 + 4 channels + ceil(blocks x channels x bitpool / 8); 0 for arguments efx_sbc_encode rejects.  Host only. */
+size_t efx_sbc_frame_bytes(int blocks, int channels, int bitpool);
+/* Bytes of encoder state per stream: the last 72 samples of each channel.  All zero = a fresh encoder.  Host only. */
+size_t efx_sbc_enc_state_bytes(void);
+/* n_streams independent encoders.  pcm (device): stream i at pcm + i x pcm_stride; state (device, updated): n_streams x
+ * efx_sbc_enc_state_bytes(); frames (device): stream i's n_frames frames back to back from frames + i x frame_stride --
+ * the layout efx_sbc_decode reads (frames, stream_stride, frame_bytes), so one call's output is the other's input.  Bytes
+ * between the streams' regions are left alone.  Asynchronous on the context's stream, two launches whatever the counts;
+ * touches nothing of the video decoder, the video encoder or the SBC decoder.  A longer stream takes several calls, the
+ * state carries the analysis filter's memory over: the frames are those of one long call.
+ * EFX_ERR_ARG: a field out of range, mode 2 or 3, a NULL or misaligned (16 bytes) pcm / state / frames pointer, a stride
+ * too small or (frame_stride) not a multiple of 16. */
+int efx_sbc_encode(efx_ctx* ctx, const efx_sbc_encode_opts* opts, const int16_t* pcm_device, void* state_device,
+                   uint8_t* frames_device);
+
+/* -- A/V multiplexer: video transport stream + SBC frames -> a title (espflix_amd/csrc/k_mux.hip) -- */
+/* The reference player takes its audio from PES packets on PID 0x101 / 0x102 of the transport stream that carries the
+ * video on PID 0x100 (MpegDecoder::demux, src/player.cpp:421-433).  Output, byte for byte (tests/mux_model.py restates it):
+ *  - audio PES: 00 00 01 C0, PES_packet_length = 8 + payload (the player compares it with what arrived,
+ *    src/player.cpp:390-396,431-432), 80 80 05, the 5-byte PTS of the PES's first frame, then frames_per_pes frames (the
+ *    last PES of a call may hold fewer); 188-byte packets on audio_pid, payload_unit_start on the first, the continuity
+ *    counter running on from audio_cc, the last packet padded with adaptation-field stuffing as efx_encode pads video;
+ *  - the unit of interleaving is a PES: its packets stay together, video packets are copied unchanged.  Units appear in
+ *    PTS order, audio first at equal PTS, the order inside each kind kept; a video PES without PTS counts as having its
+ *    predecessor's (before the first PTS: as earlier than all audio); audio later than the last video PES follows it.
+ *    PTS are compared as written, without unwrapping at 2^33;
+ *  - no PAT / PMT: the reference player does not read them (its own clips carry them on PIDs 0 and 0x1000, it skips them). */
+#define EFX_MUX_FULL      1024u  /* status bit: the output region is too small; the stream's length is 0 */
+#define EFX_MUX_BAD_VIDEO 2048u  /* status bit: video_len not a multiple of 188, a packet without 0x47 or not on PID 0x100,
+                                    or a first packet that does not start a PES; the stream's length is 0 */
+typedef struct efx_mux_opts {
+    int n_streams;            /* 1 .. max_streams */
+    int audio_pid;            /* 0x101 or 0x102 (the reference's own clips use 0x102) */
+    int frame_bytes;          /* SBC frame size */
+    int n_frames;             /* audio frames per stream in this call, >= 0 */
+    int frames_per_pes;       /* >= 1; frames_per_pes x frame_bytes <= 2048: half the player's 4 KiB audio ring (src/video.cpp:957) */
+    int samples_per_frame;    /* blocks x 8 */
+    int sample_rate;          /* Hz */
+    int64_t audio_first_pts;  /* 90 kHz PTS of frame 0 of the title */
+    int64_t audio_first_frame;/* index in the title of this call's first frame: frame k of the call carries
+                                 audio_first_pts + floor((audio_first_frame + k) x samples_per_frame x 90000 / sample_rate) */
+    int audio_cc;             /* continuity counter of the first audio packet, 0..15 */
+    size_t video_stride, audio_stride, dst_stride;   /* bytes between streams; multiples of 16 */
+} efx_mux_opts;
+/* video_ts / video_len (device) are what efx_encode(EFX_FORMAT_TS) left in dst_device / len_device: the lengths are read on
+ * the device, so encode -> mux needs no host synchronisation.  audio_frames (device): stream i's frames at
+ * audio_frames + i x audio_stride (may be NULL when n_frames is 0).  The title of stream i goes to dst + i x dst_stride, its
+ * length to len[i], EFX_MUX_* bits (0 = fine) to status[i]; a stream with a status bit set has length 0 and its region is not
+ * written.  Stateless: a title made in several calls passes audio_first_frame and audio_cc on (efx_mux_audio_packets).
+ * Asynchronous on the context's stream, one launch.  EFX_ERR_ARG: a field out of range, a stride that is not a multiple of
+ * 16 (dst_stride: or 2^32 and above), audio_stride below n_frames x frame_bytes, a NULL or misaligned (16 bytes) pointer. */
+int efx_mux_av(efx_ctx* ctx, const efx_mux_opts* opts, const uint8_t* video_ts_device, const uint32_t* video_len_device,
+               const uint8_t* audio_frames_device, uint8_t* dst_device, uint32_t* len_device, uint32_t* status_device);
+/* A dst_stride that never gives EFX_MUX_FULL for video_bytes of video (0 for invalid arguments).  Host only. */
+size_t efx_mux_bound(size_t video_bytes, int n_frames, int frame_bytes, int frames_per_pes);
+/* Audio packets efx_mux_av writes per stream: add to audio_cc (mod 16) for the next call (-1 for invalid arguments).  Host only. */
+int efx_mux_audio_packets(int n_frames, int frame_bytes, int frames_per_pes);
+
 /* -- measurement -------------------------------------------------------------------------- */
 typedef struct efx_timing {
     float index_ms, parse_ms, recon_ms, total_ms; /* HIP-event stage times, mean over the efx_decode calls
