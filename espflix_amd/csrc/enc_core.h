@@ -213,16 +213,11 @@ EFX_ENC_HD inline void fdct8(const int* in, int* out, const Tables& T)
         }
 }
 
-// Code one block: the source block (8 x 8) minus the prediction in blk (inter), transformed and quantised (intra AC:
-// rounded; non-intra: truncated, a dead zone), |level| <= 255, then halved until the decoder's clamp stays inside its
-// domain; blk gets the reconstruction and lev_out the levels.  Returns 1 when the block has a level to code (intra: 1).
-EFX_ENC_HD inline int code_block(const uint8_t* src, int pitch, bool intra, int q, const Tables& T, uint8_t* blk, int16_t* lev_out)
+// Quantise the coefficients F (raster order, fdct8's units) into levels in scan order: intra DC the rounded mean 0..255,
+// intra AC rounded, non-intra truncated (a dead zone), |level| <= 255.  Returns whether a level other than the intra DC
+// is non-zero.
+EFX_ENC_HD inline bool quantise(const int* F, bool intra, int q, const Tables& T, int* lev)
 {
-    int pix[64], F[64], lev[64];
-    for (int y = 0; y < 8; y++)
-        for (int x = 0; x < 8; x++)
-            pix[y * 8 + x] = (int)src[y * pitch + x] - (intra ? 0 : (int)blk[y * 8 + x]);
-    fdct8(pix, F, T);
     bool any = false;
     for (int n = 0; n < 64; n++) {
         const int zz = T.zz[n];
@@ -240,6 +235,20 @@ EFX_ENC_HD inline int code_block(const uint8_t* src, int pitch, bool intra, int 
         lev[n] = l;
         any |= l != 0 && !(intra && n == 0);
     }
+    return any;
+}
+
+// Code one block: the source block (8 x 8) minus the prediction in blk (inter), transformed and quantised, then the
+// levels halved until the decoder's clamp stays inside its domain; blk gets the reconstruction and lev_out the levels.
+// Returns 1 when the block has a level to code (intra: 1).
+EFX_ENC_HD inline int code_block(const uint8_t* src, int pitch, bool intra, int q, const Tables& T, uint8_t* blk, int16_t* lev_out)
+{
+    int pix[64], F[64], lev[64];
+    for (int y = 0; y < 8; y++)
+        for (int x = 0; x < 8; x++)
+            pix[y * 8 + x] = (int)src[y * pitch + x] - (intra ? 0 : (int)blk[y * 8 + x]);
+    fdct8(pix, F, T);
+    bool any = quantise(F, intra, q, T, lev);
     while (!reconstruct(lev, intra, q, T, blk, false)) {
         any = false;
         for (int n = intra ? 1 : 0; n < 64; n++) {

@@ -35,6 +35,43 @@ def encode(exe: str, pics, gop=12, qscale=8, search=7, fmt=1, first_pts=0):
         return open(out, "rb").read(), np.fromfile(rec, dtype=np.uint8).reshape(-1, PIC)
 
 
+def build_blocks(out_dir: str) -> str:
+    """tests/enc_blocks_main.cpp: enc_core.h's fdct8 and code_block on single blocks."""
+    cxx = shutil.which("g++") or shutil.which("c++")
+    assert cxx, "a host C++ compiler is needed to build enc_core.h"
+    exe = os.path.join(out_dir, "enc_blocks")
+    subprocess.run([cxx, "-O2", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "espflix_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "enc_blocks_main.cpp"), "-o", exe], check=True)
+    return exe
+
+
+def _run_blocks(exe: str, mode: str, data: np.ndarray, width: int) -> np.ndarray:
+    with tempfile.TemporaryDirectory() as td:
+        src, out = os.path.join(td, "in.bin"), os.path.join(td, "out.bin")
+        data.tofile(src)
+        subprocess.run([exe, mode, src, out], check=True, timeout=600)
+        return np.fromfile(out, dtype=np.int32).reshape(-1, width)
+
+
+def fdct_blocks(exe: str, blocks) -> np.ndarray:
+    """fdct8 of (n, 8, 8) integer blocks: (n, 8, 8) int32, 8 x the standard 2-D DCT."""
+    blocks = np.ascontiguousarray(blocks, dtype=np.int32).reshape(-1, 64)
+    return _run_blocks(exe, "fdct", blocks, 64).reshape(-1, 8, 8)
+
+
+def code_blocks(exe: str, intra, q, src, pred):
+    """code_block on n blocks (intra / q per block, src / pred (n, 8, 8) uint8): fdct8's output (n, 8, 8), the levels in
+    scan order (n, 64) and whether the halving loop ran (n)."""
+    n = len(src)
+    rec = np.empty((n, 130), dtype=np.uint8)
+    rec[:, 0] = intra
+    rec[:, 1] = q
+    rec[:, 2:66] = np.asarray(src, dtype=np.uint8).reshape(n, 64)
+    rec[:, 66:] = np.asarray(pred, dtype=np.uint8).reshape(n, 64)
+    out = _run_blocks(exe, "code", rec, 129)
+    return out[:, :64].reshape(n, 8, 8), out[:, 64:128], out[:, 128].astype(bool)
+
+
 def luma_psnr(src, recon) -> float:
     """Mean luma PSNR of recon against src, source values above 248 taken as 248 (the decoder's clamp)."""
     y0 = np.minimum(np.asarray(src).reshape(-1, PIC)[:, :W * H].astype(np.float64), 248)
@@ -111,3 +148,72 @@ def checkerboard(n: int) -> np.ndarray:
 
 def flat(n: int, value: int) -> np.ndarray:
     return np.full((n, PIC), value, dtype=np.uint8)
+
+
+def noise(seed: int = 11) -> np.ndarray:
+    """Two pictures of full-range random bytes."""
+    import common
+    return common.random_frames(seed).reshape(2, -1)[:, :PIC]
+
+
+# -- checks shared by the host-model tests (test_encode_yardstick.py) and the device tests (test_gpu_encode.py) -----------
+
+def mb_tables(stream: bytes, fmt: int) -> dict:
+    """{picture: (intra, h, v)} of the P pictures of a stream, (12, 22) arrays from the oracle's parse trace; a skipped
+    macroblock is inter with the zero vector, the vector of an intra macroblock reads 0."""
+    out = {}
+    for pic, addr, intra, _skipped, h, v in p_vectors(stream, fmt):
+        t = out.setdefault(pic, tuple(np.full((12, 22), -99, dtype=np.int64) for _ in range(3)))
+        t[0][addr // 22, addr % 22] = intra
+        t[1][addr // 22, addr % 22] = 0 if intra else h
+        t[2][addr // 22, addr % 22] = 0 if intra else v
+    return out
+
+
+def check_decisions(stream: bytes, fmt: int, pics, recon, gop: int, search: int) -> int:
+    """Every macroblock of every P picture carries the (intra, h, v) the exhaustive search model (encode_float.decisions)
+    derives from the source picture and the encoder's own previous reconstruction.  Exact.  Returns the macroblocks
+    compared."""
+    import encode_float as F
+    tables = mb_tables(stream, fmt)
+    want_pics = [p for p in range(len(pics)) if p % gop]
+    assert sorted(tables) == want_pics, (sorted(tables), want_pics)
+    for p in want_pics:
+        got = tables[p]
+        assert (got[0] >= 0).all(), f"picture {p}: the stream lacks macroblocks"
+        want = F.decisions(pics[p], recon[p - 1], search)
+        for name, g, w in zip(("intra", "h", "v"), got, want):
+            bad = np.argwhere(g != w)
+            assert not len(bad), (f"search {search} picture {p}: {name} differs from the search model in {len(bad)} macroblocks; "
+                                  f"first (row, column) {tuple(bad[0])}: encoder (intra, h, v) = "
+                                  f"{tuple(int(t[tuple(bad[0])]) for t in got)}, model {tuple(int(t[tuple(bad[0])]) for t in want)}")
+    return 264 * len(want_pics)
+
+
+PSNR_JSON = os.path.join(ROOT, "tests", "golden", "encode_psnr.json")
+QUALITY_Q = (1, 2, 4, 8, 16, 31)
+QUALITY_GOP, QUALITY_SEARCH = 4, 7
+
+
+def quality_sources(clip_i420: dict) -> dict:
+    """The three 12-picture sources of the quality check; clip_i420: every picture of the two clips as I420."""
+    return {"splash": clip_i420["splash"][14:26], "vmedia": clip_i420["vmedia"][14:26], "moving": moving(12)}
+
+
+def neighbour_q(q: int) -> int:
+    return q + 1 if q < 31 else 30
+
+
+def check_quality(record: dict, name: str, q: int, pics, recon, what: str) -> list:
+    """The encoder's mean luma PSNR of the I pictures and of the P pictures is at least the float yardstick's
+    (tests/golden/encode_psnr.json) less the recorded margin, a quarter of the yardstick's own step to the neighbouring
+    qscale.  Returns the failures (and prints every figure)."""
+    import encode_float as F
+    got = F.psnr_by_type(pics, recon, QUALITY_GOP)
+    rec = record["cases"][f"{name}_q{q}"]
+    failures = []
+    for t, g in zip("IP", got):
+        print(f"{what} {name:7s} q {q:2d} {t}: {g:7.3f} dB, yardstick {rec[t]:7.3f} dB ({g - rec[t]:+.3f}), margin {rec[t + '_margin']:.3f}")
+        if not g >= rec[t] - rec[t + "_margin"]:
+            failures.append((name, q, t, round(g, 3), rec[t], rec[t + "_margin"]))
+    return failures

@@ -1,7 +1,10 @@
 """efx_encode (k_encode): I420 pictures in device memory -> MPEG-1 ES / TS on the device.  Every stream must decode with
 efx_decode, the test oracle and (where built) the reference to exactly the reconstruction the encoder reports, and its bytes
-must be those of the host build of the encoder's arithmetic (tests/encode_model.py)."""
+must be those of the host build of the encoder's arithmetic (tests/encode_model.py) at every search radius.  Its search and
+mode decisions must be those of the exhaustive search model and its quality that of the float64 yardstick encoder
+(tests/encode_float.py; tests/test_encode_yardstick.py holds the same checks for the host build)."""
 import ctypes as C
+import json
 import os
 import subprocess
 import sys
@@ -11,6 +14,7 @@ import numpy as np
 import pytest
 
 import common
+import encode_float as F
 import encode_model as E
 import export_model as M
 import oracle
@@ -142,6 +146,60 @@ def test_search_finds_motion(efx, model):
     v7 = [(h, v) for _, _, intra, _, h, v in E.p_vectors(r7.streams[0], 0) if not intra]
     assert v0 and all(h == 0 and v == 0 for h, v in v0)
     assert all(abs(h) <= 15 and abs(v) <= 15 for h, v in v7) and any(h & 1 or v & 1 for h, v in v7)
+
+
+@pytest.mark.parametrize("search", range(16))
+def test_radius_matrix(efx, model, search):
+    """Every search radius (each gives k_enc_rows another window side, fill width and lane stride; 8 switches to
+    forward_f_code 2) at qscale 1, 5 and 31 on the source whose vectors reach the window's edge, and the noise pictures
+    at qscale 5: the device's bytes and reconstruction are the host model's, the oracle decodes the stream to the
+    reconstruction, and the largest |h| and |v| of the inter macroblocks are 2 R + 1 (search 0: the zero vector)."""
+    big = F.big_motion(5)
+    dec = efx.Decoder(1, 1)
+    for name, pics, q, fmt in (("big_motion", big, 1, 0), ("big_motion", big, 5, 1), ("big_motion", big, 31, 0),
+                               ("noise", E.noise(), 5, 1)):
+        r = dec.encode(pics[None], qscale=q, gop=12, search=search, fmt=fmt, first_pts=PTS0, recon=True)
+        assert r.status[0] == 0
+        want, want_rec = E.encode(model, pics, gop=12, qscale=q, search=search, fmt=fmt, first_pts=PTS0)
+        assert r.streams[0] == want, f"{name} q {q}: device and host streams differ"
+        assert np.array_equal(r.recon[0], want_rec), f"{name} q {q}: device and host reconstructions differ"
+        oracle_check(r.streams[0], fmt, r.recon[0])
+        if name == "big_motion":
+            vec = [(h, v) for _, _, intra, _, h, v in E.p_vectors(r.streams[0], fmt) if not intra]
+            reach = 2 * search + 1 if search else 0
+            assert vec and max(abs(h) for h, _ in vec) == reach and max(abs(v) for _, v in vec) == reach, (q, reach)
+    dec.close()
+
+
+@pytest.mark.parametrize("search", [1, 6, 8, 14, 15])
+def test_search_decisions_are_the_models(efx, search):
+    """Every macroblock of every P picture of the device's streams: (intra, h, v) equals the exhaustive search model's
+    (encode_float.decisions), with the device's own previous reconstruction as the reference picture.  Exact."""
+    dec = efx.Decoder(1, 1)
+    total = 0
+    for pics in (F.big_motion(5), E.checkerboard(3), E.flat(3, 90)):
+        r = dec.encode(pics[None], qscale=5, gop=len(pics), search=search, fmt=0, recon=True)
+        assert r.status[0] == 0
+        total += E.check_decisions(r.streams[0], 0, pics, r.recon[0], len(pics), search)
+    dec.close()
+    assert total == 264 * 8
+
+
+@pytest.mark.parametrize("q", E.QUALITY_Q)
+def test_quality_against_the_float_yardstick(efx, clip_pictures, q):
+    """splash and vmedia (pictures 14..25) and the moving texture in one batch call, gop 4: the device's mean luma PSNR of
+    the I pictures and of the P pictures is at least the float64 yardstick's (tests/golden/encode_psnr.json) less the
+    recorded margin, a quarter of the yardstick's own step to the neighbouring qscale."""
+    record = json.load(open(E.PSNR_JSON))
+    sources = E.quality_sources(clip_pictures)
+    dec = efx.Decoder(len(sources), 1)
+    r = dec.encode(np.stack(list(sources.values())), qscale=q, gop=E.QUALITY_GOP, search=E.QUALITY_SEARCH, fmt=0, recon=True)
+    dec.close()
+    assert (r.status == 0).all()
+    failures = []
+    for i, (name, pics) in enumerate(sources.items()):
+        failures += E.check_quality(record, name, q, pics, r.recon[i], "device")
+    assert not failures, failures
 
 
 @pytest.mark.parametrize("name", ["checker_q1", "noise", "flat0", "flat255"])
