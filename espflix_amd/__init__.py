@@ -42,6 +42,7 @@ STREAM_SERIAL_HUNT = 64   # the reference would misread bits between two start c
 STREAM_INTERNAL = 256     # never expected: a lost hand-over inside the reconstruction kernel (efx.h)
 STREAM_SLICE_ORDER = 128  # slice start codes of a picture not strictly rising in bitstream order: see efx.h
 ENCODE_FULL = 512         # efx_encode: the stream's output region filled up (efx.h)
+ENCODE_VBV = 4096         # efx_encode_rc: the buffer model's level went below zero during the call (efx.h)
 MUX_FULL = 1024           # efx_mux_av: the stream's output region is too small, nothing written (efx.h)
 MUX_BAD_VIDEO = 2048      # efx_mux_av: the video input is not a transport stream of PID 0x100 that starts with a PES (efx.h)
 PCM_FRAME_PLANAR, PCM_INTERLEAVED = 0, 1   # efx_sbc_encode_opts.pcm_layout
@@ -89,6 +90,10 @@ class _EncodeOpts(C.Structure):
                 ("dst_stride", C.c_size_t)]
 
 
+class _EncodeRate(C.Structure):
+    _fields_ = [("bitrate", C.c_int), ("vbv_bits", C.c_int), ("qmin", C.c_int), ("qmax", C.c_int)]
+
+
 class _SbcEncodeOpts(C.Structure):
     _fields_ = [("n_streams", C.c_int), ("n_frames", C.c_int), ("frequency", C.c_int), ("blocks", C.c_int), ("mode", C.c_int),
                 ("allocation", C.c_int), ("bitpool", C.c_int), ("pcm_layout", C.c_int), ("pcm_stride", C.c_size_t),
@@ -107,6 +112,7 @@ class EncodeResult:
     streams: list          # bytes written per stream by the call
     status: np.ndarray     # EFX_ENCODE_* bits per stream
     recon: object = None   # (n, P, 101376) reconstruction (torch tensor or NumPy array), when asked for
+    qscales: object = None  # (n, P) uint8 array: every picture's quantiser_scale (0 = not written), when bitrate is given
 
 
 class _IdxRec(C.Structure):
@@ -162,6 +168,7 @@ _SYMBOLS = {
     "efx_export_bytes": (C.c_size_t, [C.c_int]),
     "efx_export_frames": (C.c_int, [_P, C.POINTER(_ExportOpts), _P]),
     "efx_encode": (C.c_int, [_P, C.POINTER(_EncodeOpts), _P, _P, _P, _P, _P]),
+    "efx_encode_rc": (C.c_int, [_P, C.POINTER(_EncodeOpts), C.POINTER(_EncodeRate), _P, _P, _P, _P, _P, _P]),
     "efx_encode_bound": (C.c_size_t, [C.c_int, C.c_int]),
     "efx_composite_fields": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "efx_composite_fields_ex": (C.c_int, [_P, C.POINTER(_FieldOpts), _P]),
@@ -615,18 +622,29 @@ class Decoder:
     def encode_to(self, src: DeviceBuffer | int, dst: DeviceBuffer | int, length: DeviceBuffer | int,
                   status: DeviceBuffer | int, *, n_streams: int, n_pictures: int, qscale: int = 8, gop: int = 12,
                   search: int = 7, fmt: int = FORMAT_TS, cont: bool = False, first_pts: int = 0, src_stride: int = 0,
-                  dst_stride: int = 0, recon: DeviceBuffer | int | None = None):
+                  dst_stride: int = 0, recon: DeviceBuffer | int | None = None, bitrate: int | None = None,
+                  vbv_bits: int = 250_000, qmin: int = 3, qmax: int = 31, qscale_out: DeviceBuffer | int | None = None):
         """efx_encode on raw device memory (DeviceBuffers or pointers), asynchronous on the library's stream: stream i's
         pictures at src + i * src_stride (0 = packed), its bytes appended to dst + i * dst_stride (0 = efx_encode_bound),
-        uint32 byte counts and status bits to length / status, the reconstruction to recon (optional)."""
+        uint32 byte counts and status bits to length / status, the reconstruction to recon (optional).
+
+        bitrate (bit/s): efx_encode_rc instead -- every picture's quantiser chosen on the device under the buffer model
+        of efx.h (vbv_bits, qmin, qmax; qscale is the first picture's), the n_streams x n_pictures quantisers to
+        qscale_out (optional).  The defaults are the profile of the reference's indexer."""
         g = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else b)
         o = _EncodeOpts(n_streams, n_pictures, fmt, qscale, gop, search, 1 if cont else 0, first_pts,
                         src_stride or n_pictures * FRAME_BYTES, dst_stride or encode_bound(fmt, n_pictures))
-        _check(self._ctx, self._lib.efx_encode(self._ctx, C.byref(o), g(src), g(dst), g(length), g(status), g(recon)))
+        if bitrate is None:
+            _check(self._ctx, self._lib.efx_encode(self._ctx, C.byref(o), g(src), g(dst), g(length), g(status), g(recon)))
+        else:
+            r = _EncodeRate(bitrate, vbv_bits, qmin, qmax)
+            _check(self._ctx, self._lib.efx_encode_rc(self._ctx, C.byref(o), C.byref(r), g(src), g(dst), g(length), g(status),
+                                                      g(recon), g(qscale_out)))
         return o.dst_stride
 
     def encode(self, pictures, *, qscale: int = 8, gop: int = 12, search: int = 7, fmt: int = FORMAT_TS, cont: bool = False,
-               first_pts: int = 0, recon: bool = False, dst_stride: int = 0) -> EncodeResult:
+               first_pts: int = 0, recon: bool = False, dst_stride: int = 0, bitrate: int | None = None,
+               vbv_bits: int = 250_000, qmin: int = 3, qmax: int = 31) -> EncodeResult:
         """Encode (n, P, 101376) I420 pictures (the layout export("i420") writes) into n MPEG-1 streams of P pictures: a uint8
         torch tensor on the decoder's device or a NumPy array.  Stream i takes the pictures of row i (the order export()
         gives streams).  Returns each stream's bytes, its status bits and, with recon=True, what a decoder reconstructs
@@ -637,7 +655,11 @@ class Decoder:
         up -- about 357 kB (ES) / 365 kB (TS) per picture, 10 to 100 times what a picture usually takes: 1024 streams x 24
         TS pictures reserve some 9 GB for the call.  A smaller region is fine where the caller knows its content; a stream
         that does not fit ends after its last whole picture with status ENCODE_FULL (its bytes so far are returned) and can
-        only be encoded again from the start (cont=False), with a larger dst_stride."""
+        only be encoded again from the start (cont=False), with a larger dst_stride.
+
+        bitrate (bit/s of the bytes in fmt): rate control (efx_encode_rc) under a buffer of vbv_bits bits, quantisers
+        qmin..qmax, qscale for the first picture of a fresh stream; the result's qscales holds every picture's quantiser
+        and status may carry ENCODE_VBV.  cont=True must keep bitrate and vbv_bits."""
         lead = tuple(pictures.shape[:-1])
         if len(lead) != 2 or pictures.shape[-1] != FRAME_BYTES:
             raise ValueError(f"pictures must have shape (n, P, {FRAME_BYTES}), got {tuple(pictures.shape)}")
@@ -663,6 +685,10 @@ class Decoder:
             stride = dst_stride or encode_bound(fmt, P)
             dst, meta = DeviceBuffer(self, n * stride), DeviceBuffer(self, 2 * 4 * n + 16)
             bufs += [dst, meta]
+            q_buf = None
+            if bitrate is not None:
+                q_buf = DeviceBuffer(self, n * P)
+                bufs.append(q_buf)
             rec_ptr = None
             if recon and rec_t is None:
                 rec_buf = DeviceBuffer(self, n * P * FRAME_BYTES)
@@ -672,7 +698,8 @@ class Decoder:
                 rec_ptr = rec_t.data_ptr()
             status_off = (4 * n + 15) // 16 * 16
             self.encode_to(src_ptr, dst, meta.ptr, meta.ptr + status_off, n_streams=n, n_pictures=P, qscale=qscale, gop=gop,
-                           search=search, fmt=fmt, cont=cont, first_pts=first_pts, dst_stride=stride, recon=rec_ptr)
+                           search=search, fmt=fmt, cont=cont, first_pts=first_pts, dst_stride=stride, recon=rec_ptr,
+                           bitrate=bitrate, vbv_bits=vbv_bits, qmin=qmin, qmax=qmax, qscale_out=q_buf)
             self.sync()
             lens = meta.download(np.uint32, n)
             st = np.empty(n, dtype=np.uint32)
@@ -687,8 +714,9 @@ class Decoder:
             if rec_t is not None:
                 out_rec = rec_t
             elif recon:
-                out_rec = bufs[-1].download(np.uint8, n * P * FRAME_BYTES).reshape(n, P, FRAME_BYTES)
-            return EncodeResult(streams, st, out_rec)
+                out_rec = rec_buf.download(np.uint8, n * P * FRAME_BYTES).reshape(n, P, FRAME_BYTES)
+            qs = q_buf.download(np.uint8, n * P).reshape(n, P) if q_buf is not None else None
+            return EncodeResult(streams, st, out_rec, qs)
         finally:
             for b in bufs:
                 b.free()
@@ -867,11 +895,14 @@ class Decoder:
 
     def encode_av(self, pictures, pcm, *, qscale: int = 8, gop: int = 12, search: int = 7, first_pts: int = 0, blocks: int = 16,
                   allocation: int = 0, bitpool: int = 28, frequency: int = 3, sample_rate: int = 48000, frames_per_pes: int = 8,
-                  audio_pid: int = 0x101):
+                  audio_pid: int = 0x101, bitrate: int | None = None, vbv_bits: int = 250_000, qmin: int = 3, qmax: int = 31):
         """Pictures + PCM -> complete titles: encode (transport streams) -> sbc_encode (mono) -> mux, queued back to back on
         the library's stream with nothing synchronised in between.  pictures: (n, P, 101376) I420 as for encode(); pcm: int16
         [n, samples], a whole number of frames of blocks x 8 samples; the audio starts at the first picture's PTS.  Every
-        stream starts afresh.  Returns (titles: list of bytes, status: uint32 array of ENCODE_* | MUX_* bits)."""
+        stream starts afresh.  Returns (titles: list of bytes, status: uint32 array of ENCODE_* | MUX_* bits).
+
+        bitrate: rate control of the video leg only, as for encode(): the rate and the buffer model cover the video PID's
+        packets; the audio packets the multiplexer adds are outside the model."""
         import torch
         device = torch.device("cuda", self.device)
         to_dev = lambda t, dt: torch.from_numpy(np.ascontiguousarray(t)).to(device) if isinstance(t, np.ndarray) else t
@@ -897,7 +928,8 @@ class Decoder:
             p_vlen, p_vst, p_len, p_st = (d_meta.ptr + k * r16(4 * n) for k in range(4))
             torch.cuda.current_stream(device).synchronize()
             self.encode_to(pictures.data_ptr(), d_v, p_vlen, p_vst, n_streams=n, n_pictures=P, qscale=qscale, gop=gop, search=search,
-                           fmt=FORMAT_TS, first_pts=first_pts, dst_stride=v_stride)
+                           fmt=FORMAT_TS, first_pts=first_pts, dst_stride=v_stride, bitrate=bitrate, vbv_bits=vbv_bits, qmin=qmin,
+                           qmax=qmax)
             if n_frames:
                 self.sbc_encode_to(pcm.data_ptr(), d_state, d_a, n_streams=n, n_frames=n_frames, blocks=blocks, mode=0,
                                    allocation=allocation, bitpool=bitpool, frequency=frequency, pcm_stride=int(pcm.shape[1]),

@@ -54,6 +54,7 @@ __global__ void k_pdm(const int16_t*, int, int, int32_t*, uint16_t*);
 template <int FMT, int CHROMA>
 __global__ void k_export(const uint8_t*, int, ExportArgs);  // (k_export.hip: the five (format, chroma) instances)
 __global__ void k_enc_begin(EncArgs);
+__global__ void k_enc_act(EncArgs);
 __global__ void k_enc_rows(EncArgs);
 __global__ void k_enc_pack(EncArgs);
 __global__ void k_sbc(const uint8_t*, size_t, int, int, SbcState*, const SbcTables*, int16_t*, size_t, uint32_t*, uint32_t*, int);
@@ -261,6 +262,7 @@ struct efx_ctx {
     uint8_t* d_enc_pics = nullptr;       // two I420 reconstruction buffers per stream
     uint8_t* d_enc_slices = nullptr;     // 12 slices of enc::kSliceCap bytes per stream
     uint32_t* d_enc_slice_len = nullptr;
+    uint32_t* d_enc_act = nullptr;       // efx_encode_rc: two activity sums per (stream, macroblock row)
     enc::Tables* d_enc_tables = nullptr;
     std::unique_ptr<enc::Tables> h_enc_tables;  // the source of d_enc_tables' upload
     uint32_t* h_enc_full = nullptr;      // host-mapped: enc_generation of the streams when one of them last filled its region
@@ -269,6 +271,8 @@ struct efx_ctx {
     bool enc_started = false;            // streams exist that cont = 1 may continue
     uint32_t enc_generation = 0;         // fresh efx_encode calls so far: the value a call writes to *h_enc_full when a stream fills up
     int enc_n_streams = 0, enc_format = 0, enc_gop = 0;  // of the call that started them
+    bool enc_rc = false;                 // ... which was efx_encode_rc, at enc_bitrate / enc_vbv_bits
+    int enc_bitrate = 0, enc_vbv_bits = 0;
 
     // results of the last decode (fetch_results)
     int n_streams = 0;  // streams of the batch the last decode read
@@ -714,7 +718,7 @@ void efx_destroy(efx_ctx* ctx)
     void* bufs[] = {ctx->d_tables, ctx->d_tm_tables, ctx->d_sbc_flags, ctx->d_sbc_next, ctx->d_sbc_info, ctx->d_sbc_plan, ctx->d_sbc_extra, ctx->d_sbc_cover, ctx->d_state, ctx->d_frames, ctx->d_video[0],  ctx->d_video[1], ctx->d_video_lines[0],
                     ctx->d_video_lines[1], ctx->d_hash, ctx->d_ts, ctx->d_demux_chunks, ctx->d_sbc_tables, ctx->d_idx_info, ctx->d_ts_off, ctx->d_idx_len,
                     ctx->d_idx_base, ctx->d_idx_seq, ctx->d_enc_state, ctx->d_enc_pics, ctx->d_enc_slices, ctx->d_enc_slice_len,
-                    ctx->d_enc_tables, ctx->d_sbc_enc_tables, ctx->d_mux_before};
+                    ctx->d_enc_act, ctx->d_enc_tables, ctx->d_sbc_enc_tables, ctx->d_mux_before};
     if (ctx->h_enc_full)
         (void)hipHostFree(ctx->h_enc_full);
     for (auto& te : ctx->timing_ring)
@@ -1779,12 +1783,11 @@ size_t efx_encode_bound(int format, int n_pictures)
     return (pic * (size_t)n_pictures + 15) / 16 * 16;
 }
 
-int efx_encode(efx_ctx* ctx, const efx_encode_opts* o, const uint8_t* src_device, uint8_t* dst_device, uint32_t* len_device,
-               uint32_t* status_device, uint8_t* recon_device)
+// efx_encode (rate == nullptr) and efx_encode_rc
+static int encode_impl(efx_ctx* ctx, const efx_encode_opts* o, const efx_encode_rate* rate, const uint8_t* src_device,
+                       uint8_t* dst_device, uint32_t* len_device, uint32_t* status_device, uint8_t* recon_device,
+                       uint8_t* qscale_out_device)
 {
-    bind_device(ctx);
-    if (!ctx || !o)
-        return EFX_ERR_ARG;
     auto misaligned = [](const void* p) { return !p || ((uintptr_t)p & 15); };
     if (o->n_streams < 1 || o->n_streams > ctx->cfg.max_streams)
         return fail(ctx, EFX_ERR_ARG, "efx_encode: n_streams outside 1 .. max_streams");
@@ -1814,6 +1817,10 @@ int efx_encode(efx_ctx* ctx, const efx_encode_opts* o, const uint8_t* src_device
             return fail(ctx, EFX_ERR_STATE, "efx_encode: cont without a previous efx_encode");
         if (o->n_streams != ctx->enc_n_streams || o->format != ctx->enc_format || o->gop != ctx->enc_gop)
             return fail(ctx, EFX_ERR_STATE, "efx_encode: cont with n_streams, format or gop other than the call that started the streams");
+        if ((rate != nullptr) != ctx->enc_rc)
+            return fail(ctx, EFX_ERR_STATE, "efx_encode: cont mixes efx_encode and efx_encode_rc: streams continue through the entry point that started them");
+        if (rate && (rate->bitrate != ctx->enc_bitrate || rate->vbv_bits != ctx->enc_vbv_bits))
+            return fail(ctx, EFX_ERR_STATE, "efx_encode_rc: cont with a bitrate or vbv_bits other than the call that started the streams");
         if (*(volatile uint32_t*)ctx->h_enc_full == ctx->enc_generation)
             return fail(ctx, EFX_ERR_STATE, "efx_encode: cont after a stream filled its output region");
     }
@@ -1829,6 +1836,7 @@ int efx_encode(efx_ctx* ctx, const efx_encode_opts* o, const uint8_t* src_device
         if (e == hipSuccess) e = dalloc(&ctx->d_enc_pics, 2 * n * kFrameBytes);
         if (e == hipSuccess) e = dalloc(&ctx->d_enc_slices, n * kMbH * enc::kSliceCap);
         if (e == hipSuccess) e = dalloc(&ctx->d_enc_slice_len, n * kMbH);
+        if (e == hipSuccess) e = dalloc(&ctx->d_enc_act, n * kMbH * 2);
         if (e == hipSuccess) e = dalloc(&ctx->d_enc_tables, 1);
         if (e == hipSuccess) {
             ctx->h_enc_tables.reset(new enc::Tables);
@@ -1836,14 +1844,15 @@ int efx_encode(efx_ctx* ctx, const efx_encode_opts* o, const uint8_t* src_device
             e = hipMemcpyAsync(ctx->d_enc_tables, ctx->h_enc_tables.get(), sizeof(enc::Tables), hipMemcpyHostToDevice, ctx->stream);
         }
         if (e != hipSuccess) {
-            void* bufs[] = {ctx->d_enc_state, ctx->d_enc_pics, ctx->d_enc_slices, ctx->d_enc_slice_len, ctx->d_enc_tables};
+            void* bufs[] = {ctx->d_enc_state, ctx->d_enc_pics, ctx->d_enc_slices, ctx->d_enc_slice_len, ctx->d_enc_act,
+                            ctx->d_enc_tables};
             for (void* b : bufs)
                 (void)dev_free(b);
             if (ctx->h_enc_full)
                 (void)hipHostFree(ctx->h_enc_full);
             ctx->d_enc_state = nullptr;
             ctx->d_enc_pics = ctx->d_enc_slices = nullptr;
-            ctx->d_enc_slice_len = ctx->h_enc_full = ctx->d_enc_full = nullptr;
+            ctx->d_enc_slice_len = ctx->d_enc_act = ctx->h_enc_full = ctx->d_enc_full = nullptr;
             ctx->d_enc_tables = nullptr;
             (void)hipGetLastError();
             return fail(ctx, EFX_ERR_DEVICE, "efx_encode: cannot allocate the encoder's state and scratch", e);
@@ -1876,9 +1885,21 @@ int efx_encode(efx_ctx* ctx, const efx_encode_opts* o, const uint8_t* src_device
     a.format = o->format;
     a.f_code = o->search <= 7 ? 1 : 2;
     a.cont = o->cont;
+    if (rate) {
+        a.rc = 1;
+        a.rate.cap = (int64_t)rate->vbv_bits * 90000;
+        a.rate.gain = (int64_t)rate->bitrate * enc::kRcTick;
+        a.rate.qmin = rate->qmin;
+        a.rate.qmax = rate->qmax;
+        a.rate.q0 = o->qscale < rate->qmin ? rate->qmin : (o->qscale > rate->qmax ? rate->qmax : o->qscale);
+        a.act = ctx->d_enc_act;
+        a.qscale_out = qscale_out_device;
+    }
     hipLaunchKernelGGL(k_enc_begin, dim3((unsigned)((o->n_streams + 63) / 64)), dim3(64), 0, ctx->stream, a);
     for (int p = 0; p < o->n_pictures; p++) {
         a.picture = p;
+        if (rate)
+            hipLaunchKernelGGL(k_enc_act, dim3((unsigned)o->n_streams * kMbH), dim3(64), 0, ctx->stream, a);
         hipLaunchKernelGGL(k_enc_rows, dim3((unsigned)o->n_streams * kMbH), dim3(64), 0, ctx->stream, a);
         hipLaunchKernelGGL(k_enc_pack, dim3((unsigned)o->n_streams), dim3(256), 0, ctx->stream, a);
     }
@@ -1888,8 +1909,37 @@ int efx_encode(efx_ctx* ctx, const efx_encode_opts* o, const uint8_t* src_device
         ctx->enc_n_streams = o->n_streams;
         ctx->enc_format = o->format;
         ctx->enc_gop = o->gop;
+        ctx->enc_rc = rate != nullptr;
+        ctx->enc_bitrate = rate ? rate->bitrate : 0;
+        ctx->enc_vbv_bits = rate ? rate->vbv_bits : 0;
     }
     return EFX_OK;
+}
+
+int efx_encode(efx_ctx* ctx, const efx_encode_opts* o, const uint8_t* src_device, uint8_t* dst_device, uint32_t* len_device,
+               uint32_t* status_device, uint8_t* recon_device)
+{
+    bind_device(ctx);
+    if (!ctx || !o)
+        return EFX_ERR_ARG;
+    return encode_impl(ctx, o, nullptr, src_device, dst_device, len_device, status_device, recon_device, nullptr);
+}
+
+int efx_encode_rc(efx_ctx* ctx, const efx_encode_opts* o, const efx_encode_rate* rate, const uint8_t* src_device, uint8_t* dst_device,
+                  uint32_t* len_device, uint32_t* status_device, uint8_t* recon_device, uint8_t* qscale_out_device)
+{
+    bind_device(ctx);
+    if (!ctx || !o)
+        return EFX_ERR_ARG;
+    if (!rate)
+        return fail(ctx, EFX_ERR_ARG, "efx_encode_rc: rate is NULL");
+    if (rate->bitrate < 8000 || rate->bitrate > 100000000)
+        return fail(ctx, EFX_ERR_ARG, "efx_encode_rc: bitrate outside 8000 .. 100000000 bit/s");
+    if (rate->vbv_bits < 4000 || rate->vbv_bits > 16000000)
+        return fail(ctx, EFX_ERR_ARG, "efx_encode_rc: vbv_bits outside 4000 .. 16000000");
+    if (rate->qmin < 1 || rate->qmin > rate->qmax || rate->qmax > 31)
+        return fail(ctx, EFX_ERR_ARG, "efx_encode_rc: qmin / qmax must satisfy 1 <= qmin <= qmax <= 31");
+    return encode_impl(ctx, o, rate, src_device, dst_device, len_device, status_device, recon_device, qscale_out_device);
 }
 
 int efx_pdm(efx_ctx* ctx, int n_streams, const int16_t* pcm_device, int n_samples, int32_t* state_device, uint16_t* dst_device)

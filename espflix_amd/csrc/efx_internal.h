@@ -14,6 +14,8 @@
 #pragma once
 #include <cstdint>
 
+#include "enc_rate.h"
+
 namespace efx {
 
 constexpr int kMbW = 22, kMbH = 12, kMbCount = 264;
@@ -251,6 +253,7 @@ static_assert(sizeof(SbcState) == 2192, "SbcState layout");
 namespace enc {
 struct Tables;
 }
+static_assert(sizeof(enc::RateState) == 24, "RateState layout");
 struct EncState {
     uint32_t pictures;  // pictures encoded since the stream started: GOP phase, temporal_reference, PTS
     uint32_t cc;        // TS continuity counter of the next packet
@@ -259,6 +262,7 @@ struct EncState {
     uint32_t out_len;   // bytes written by the current call
     uint32_t status;    // EFX_ENCODE_* bits of the current call
     int64_t first_pts;  // PTS of picture 0
+    enc::RateState rate;  // efx_encode_rc: buffer level and history (enc_rate.h)
 };
 
 // k_encode launch arguments (by value)
@@ -279,6 +283,11 @@ struct EncArgs {
     uint32_t generation;      // of the streams: counts the fresh efx_encode calls of the context
     int64_t first_pts;
     int n_streams, n_pictures, picture, qscale, gop, search, format, f_code, cont;
+    // efx_encode_rc (rc = 1): the quantiser of every picture comes from enc::rate_decide, not from qscale
+    int rc;
+    enc::RateParams rate;
+    uint32_t* act;            // per (stream, row): the row's summed dev and summed min(dev, zero-vector SAD) (k_enc_act)
+    uint8_t* qscale_out;      // may be null: the quantiser of (stream i, picture p) at qscale_out + i * n_pictures + p, 0 = not written
 };
 
 // k_sbc_enc launch arguments (by value): efx_sbc_encode_opts, checked, with the context's tables

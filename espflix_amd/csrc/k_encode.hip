@@ -1,6 +1,9 @@
 // k_encode.hip -- batched MPEG-1 I/P encoder (efx_encode): every stream advances one picture per pair of launches.
 //
 //   k_enc_begin   one lane per stream: fresh streams get their state reset, every stream its per-call output counters
+//   k_enc_act     efx_encode_rc only, before every k_enc_rows: one wave per (stream, macroblock row) sums the activity of the
+//                 row's 22 macroblocks -- the luma's deviation from its own mean, and the smaller of that and the SAD
+//                 against the previous reconstruction at the same place -- with v_sad_u8 on whole 352-byte lines
 //   k_enc_rows    one wave per (stream, macroblock row): for each of the row's 22 macroblocks, full-pel search over the
 //                 previous reconstruction staged in LDS (v_sad_u8, one candidate vector per lane), the 8 half-pel
 //                 neighbours of the best one, the intra / inter decision, then transform, quantisation and reconstruction
@@ -9,6 +12,11 @@
 //                 coding order (a skipped macroblock reconstructs like "motion compensated, not coded" with vector 0).
 //   k_enc_pack    one workgroup per stream: picture headers, then the picture's slices (ES) or its PES in 188-byte
 //                 packets (TS) appended to the stream's output region, or EFX_ENCODE_FULL when it does not fit
+//
+//
+// efx_encode_rc: every wave of k_enc_rows adds the twelve row sums of its stream in row order and evaluates
+// enc::rate_decide (enc_rate.h), a pure function of the stream's state and those sums, so all twelve arrive at the same
+// quantiser; k_enc_pack evaluates it once more, then applies the buffer model to the bytes it wrote.
 //
 // Every store is a vector store (global / LDS); the only serial part is the bit writer of a slice.
 #include <hip/hip_runtime.h>
@@ -31,6 +39,7 @@ __global__ void k_enc_begin(EncArgs a)
         S.cur = 0;
         S.full = 0;
         S.first_pts = a.first_pts;
+        enc::rate_reset(&S.rate, a.rate);  // (not read without rate control)
     }
     S.out_len = 0;
     S.status = S.full ? EFX_ENCODE_FULL : 0u;
@@ -53,6 +62,75 @@ __device__ inline int wave_sum(int v)
     return v;
 }
 
+// 4-lane group sum: lanes 4 m .. 4 m + 3 hold the four words of macroblock m's line
+__device__ inline uint32_t quad_sum(uint32_t v)
+{
+    v += (uint32_t)__shfl_xor((int)v, 1, 64);
+    v += (uint32_t)__shfl_xor((int)v, 2, 64);
+    return v;
+}
+
+// Activity of one macroblock row.  A luma line is 88 words: lane l takes word l of each of the 16 lines, lanes 0 .. 23
+// word 64 + l as well, so every line is read whole, in two coalesced loads.  Sums of bytes, deviations and differences are
+// v_sad_u8 on the packed words; integer adds only, so the order of the reduction does not show in the result.
+__global__ __launch_bounds__(64) void k_enc_act(EncArgs a)
+{
+    using namespace enc;
+    const int row = blockIdx.x % kMbRows, s = blockIdx.x / kMbRows, lane = threadIdx.x;
+    const EncState S = a.st[s];
+    const bool has_ref = S.pictures != 0, tail = lane < kW / 4 - 64;
+    const size_t line0 = (size_t)row * 16 * kW;
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(a.src + (size_t)s * a.src_stride + (size_t)a.picture * kPicBytes + line0);
+    const uint32_t* ref = reinterpret_cast<const uint32_t*>(a.pics + ((size_t)s * 2 + S.cur) * kPicBytes + line0);
+    uint32_t c0[16], c1[16], sum0 = 0, sum1 = 0;
+    for (int y = 0; y < 16; y++) {
+        c0[y] = src[y * (kW / 4) + lane];
+        c1[y] = tail ? src[y * (kW / 4) + 64 + lane] : 0u;
+        sum0 = __builtin_amdgcn_sad_u8(c0[y], 0u, sum0);
+        sum1 = __builtin_amdgcn_sad_u8(c1[y], 0u, sum1);
+    }
+    const uint32_t m0 = ((quad_sum(sum0) + 128) >> 8) * 0x01010101u, m1 = ((quad_sum(sum1) + 128) >> 8) * 0x01010101u;
+    uint32_t dev0 = 0, dev1 = 0, sad0 = 0, sad1 = 0;
+    for (int y = 0; y < 16; y++) {
+        dev0 = __builtin_amdgcn_sad_u8(c0[y], m0, dev0);
+        dev1 = __builtin_amdgcn_sad_u8(c1[y], m1, dev1);
+        if (has_ref) {
+            sad0 = __builtin_amdgcn_sad_u8(c0[y], ref[y * (kW / 4) + lane], sad0);
+            if (tail)
+                sad1 = __builtin_amdgcn_sad_u8(c1[y], ref[y * (kW / 4) + 64 + lane], sad1);
+        }
+    }
+    dev0 = quad_sum(dev0);
+    dev1 = quad_sum(dev1);
+    sad0 = quad_sum(sad0);
+    sad1 = quad_sum(sad1);
+    const bool lead = (lane & 3) == 0;  // one lane per macroblock: 16 in the first set of words, 6 in the second
+    const uint32_t i0 = lead ? dev0 : 0u, i1 = lead && tail ? dev1 : 0u;
+    const uint32_t p0 = has_ref ? min(i0, sad0) : i0, p1 = has_ref ? min(i1, sad1) : i1;
+    const int act_i = wave_sum((int)(i0 + i1)), act_p = wave_sum((int)(p0 + p1));
+    if (lane == 0) {
+        uint2 w;
+        w.x = (uint32_t)act_i;
+        w.y = (uint32_t)act_p;
+        *reinterpret_cast<uint2*>(a.act + ((size_t)s * kMbRows + row) * 2) = w;
+    }
+}
+
+// The picture's quantiser under rate control: the stream's row sums added in row order, then the controller.  Every wave
+// of a stream (and k_enc_pack) gets the same value.
+__device__ inline int rate_q(const EncArgs& a, const EncState& S, int s, uint32_t* act_i, uint32_t* act_p)
+{
+    uint32_t ai = 0, ap = 0;
+    for (int k = 0; k < enc::kMbRows; k++) {
+        const uint2 w = *reinterpret_cast<const uint2*>(a.act + ((size_t)s * enc::kMbRows + k) * 2);
+        ai += w.x;
+        ap += w.y;
+    }
+    *act_i = ai;
+    *act_p = ap;
+    return enc::rate_decide(S.rate, a.rate, S.pictures, (int)(S.pictures % (uint32_t)a.gop), a.gop, ai, ap);
+}
+
 __global__ __launch_bounds__(64) void k_enc_rows(EncArgs a)
 {
     using namespace enc;
@@ -60,6 +138,11 @@ __global__ __launch_bounds__(64) void k_enc_rows(EncArgs a)
     const Tables& T = *a.tab;
     const EncState S = a.st[s];
     const int type = (S.pictures % (uint32_t)a.gop) == 0 ? 1 : 2;
+    int qscale = a.qscale;
+    if (a.rc) {
+        uint32_t act_i, act_p;
+        qscale = rate_q(a, S, s, &act_i, &act_p);
+    }
     const uint8_t* src = a.src + (size_t)s * a.src_stride + (size_t)a.picture * kPicBytes;
     const uint8_t* ref = a.pics + ((size_t)s * 2 + S.cur) * kPicBytes;
     uint8_t* rec = a.pics + ((size_t)s * 2 + (S.cur ^ 1)) * kPicBytes;
@@ -153,7 +236,7 @@ __global__ __launch_bounds__(64) void k_enc_rows(EncArgs a)
                 predict_block(ref, lane, mbx, row, h, v, blk);
             int pitch;
             const uint8_t* sb = block_ptr(src, lane, mbx, row, &pitch);
-            coded = code_block(sb, pitch, intra, a.qscale, T, blk, mbs[mbx].lev[lane]);
+            coded = code_block(sb, pitch, intra, qscale, T, blk, mbs[mbx].lev[lane]);
             uint8_t* rb = const_cast<uint8_t*>(block_ptr(rec, lane, mbx, row, &pitch));
             for (int y = 0; y < 8; y++) {
                 uint2 w;
@@ -179,7 +262,7 @@ __global__ __launch_bounds__(64) void k_enc_rows(EncArgs a)
     }
     if (lane == 0)
         a.slice_len[(size_t)s * kMbRows + row] =
-            write_slice(a.slices + ((size_t)s * kMbRows + row) * kSliceCap, row, a.qscale, type, a.f_code, mbs, T);
+            write_slice(a.slices + ((size_t)s * kMbRows + row) * kSliceCap, row, qscale, type, a.f_code, mbs, T);
 }
 
 __global__ __launch_bounds__(256) void k_enc_pack(EncArgs a)
@@ -235,6 +318,15 @@ __global__ __launch_bounds__(256) void k_enc_pack(EncArgs a)
     }
     __syncthreads();
     if (tid == 0) {
+        if (a.rc) {
+            // a picture that was not written changes nothing of the buffer or the history
+            uint32_t act_i, act_p;
+            const int q = rate_q(a, S, s, &act_i, &act_p);
+            if (sh_ok && rate_update(&S.rate, a.rate, (int)phase, q, bytes, act_i, act_p))
+                S.status |= EFX_ENCODE_VBV;
+            if (a.qscale_out)
+                a.qscale_out[(size_t)s * a.n_pictures + a.picture] = (uint8_t)(sh_ok ? q : 0);
+        }
         if (sh_ok) {
             S.out_len += bytes;
             if (ts)

@@ -1,5 +1,6 @@
 """Measure efx_encode (k_encode): 1024 streams x 12 pictures, GOP 12, qscale 8, TS, at search 7 and 15, and -- to split
-the time -- at search 0 and intra only (GOP 1).  The source is distinct per stream (a moving texture, rotated and xor-ed per
+the time -- at search 0 and intra only (GOP 1), then efx_encode_rc at search 7: 1500 kbit/s under a 250 000-bit buffer, qmin 3 (the
+reference indexer's profile; 1 + 3 x pictures launches, the activity measure included).  The source is distinct per stream (a moving texture, rotated and xor-ed per
 stream).  Prints one JSON line: encoded pictures per second from HIP events recorded on the library's own stream around one
 efx_encode call (the best of --steps timed calls after --warmup, and their mean), bytes per picture and the mean luma PSNR
 of the reconstruction against the source (every 64th stream)."""
@@ -25,6 +26,7 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--searches", default="7,15")
+    ap.add_argument("--legs", default="", help="comma-separated leg names to run (default: all), e.g. rate_1500k for a profile")
     args = ap.parse_args()
     N, P = args.streams, args.pictures
     base = E.moving(P, seed=3)
@@ -45,9 +47,12 @@ def main():
            "one efx_encode call (its 1 + 2 x pictures launches); best and mean of the timed calls"}
     # the issue's two radii, then the parts: search 0 (no search, every P tool else) and GOP 1 (intra only: no search, no
     # prediction) -- the differences split the time between the search and the rest
-    legs = [(f"search{r}", r, 12) for r in (int(x) for x in args.searches.split(","))] + [("search0", 0, 12), ("intra_only", 0, 1)]
-    for name, R, gop in legs:
-        kw = dict(n_streams=N, n_pictures=P, qscale=8, gop=gop, search=R, fmt=efx.FORMAT_TS, dst_stride=stride)
+    legs = [(f"search{r}", r, 12, {}) for r in (int(x) for x in args.searches.split(","))]
+    legs += [("search0", 0, 12, {}), ("intra_only", 0, 1, {})]
+    legs += [("rate_1500k", 7, 12, dict(bitrate=1_500_000, vbv_bits=250_000, qmin=3, qmax=31))]
+    legs = [leg for leg in legs if not args.legs or leg[0] in args.legs.split(",")]
+    for name, R, gop, rate in legs:
+        kw = dict(n_streams=N, n_pictures=P, qscale=8, gop=gop, search=R, fmt=efx.FORMAT_TS, dst_stride=stride, **rate)
         for _ in range(args.warmup):
             dec.encode_to(d_src, d_dst, d_meta.ptr, d_meta.ptr + st_off, recon=d_rec, **kw)
         dec.sync()
@@ -64,13 +69,16 @@ def main():
         lens = d_meta.download(np.uint32, N)
         status = np.empty(N, dtype=np.uint32)
         assert dec._lib.efx_memcpy_d2h(dec._ctx, status.ctypes.data, d_meta.ptr + st_off, 4 * N) == 0
-        assert (status == 0).all(), "a stream filled its output region"
+        assert (status & efx.ENCODE_FULL == 0).all(), "a stream filled its output region"
+        assert rate or (status == 0).all()
         rec = d_rec.download(np.uint8, N * P * efx.FRAME_BYTES).reshape(N, P, -1)
         psnr = float(np.mean([E.luma_psnr(src[i], rec[i]) for i in range(0, N, 64)]))
         best = min(ms)
         out[name] = {"gop": gop, "search": R, "pictures_per_s": N * P / (best / 1e3), "pictures_per_s_mean": N * P / (np.mean(ms) / 1e3),
                      "ms_per_call": best, "ms_mean": float(np.mean(ms)), "bytes_per_picture": float(lens.sum()) / (N * P),
                      "luma_psnr_db": round(psnr, 2)}
+        if rate:  # (this source is noise-like: far more than 1500 kbit/s even at qscale 31, so its streams run into debt)
+            out[name].update(rate, streams_in_debt=int((status & efx.ENCODE_VBV != 0).sum()))
     print(json.dumps(out))
     dec.close()
 
