@@ -84,6 +84,12 @@ class _ExportOpts(C.Structure):
                 ("chroma", C.c_int), ("full_range", C.c_int), ("dst_stride", C.c_size_t)]
 
 
+class _ImportOpts(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("n_images", "format", "width", "height", "crop_x", "crop_y", "crop_w", "crop_h",
+                                       "dst_x", "dst_y", "dst_w", "dst_h", "full_range")] + \
+               [("src_stride", C.c_size_t), ("dst_stride", C.c_size_t)]
+
+
 class _EncodeOpts(C.Structure):
     _fields_ = [("n_streams", C.c_int), ("n_pictures", C.c_int), ("format", C.c_int), ("qscale", C.c_int), ("gop", C.c_int),
                 ("search", C.c_int), ("cont", C.c_int), ("first_pts", C.c_int64), ("src_stride", C.c_size_t),
@@ -167,6 +173,8 @@ _SYMBOLS = {
     "efx_video_get_params": (C.c_int, [C.c_int, C.POINTER(_VideoParams)]),
     "efx_export_bytes": (C.c_size_t, [C.c_int]),
     "efx_export_frames": (C.c_int, [_P, C.POINTER(_ExportOpts), _P]),
+    "efx_import_src_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "efx_import_frames": (C.c_int, [_P, C.POINTER(_ImportOpts), _P, _P]),
     "efx_encode": (C.c_int, [_P, C.POINTER(_EncodeOpts), _P, _P, _P, _P, _P]),
     "efx_encode_rc": (C.c_int, [_P, C.POINTER(_EncodeOpts), C.POINTER(_EncodeRate), _P, _P, _P, _P, _P, _P]),
     "efx_encode_bound": (C.c_size_t, [C.c_int, C.c_int]),
@@ -279,6 +287,54 @@ def i420_planes(t):
     return y, u, v
 
 
+def import_src_bytes(fmt, width: int, height: int) -> int:
+    """Bytes of one source image of efx_import_frames ("i420", "rgb24", "rgbp" or an EFX_PIX_* value); 0 for an unknown
+    format, a width or height outside 2 .. 4096, or an odd I420 size."""
+    code = _PIX_FORMATS.get(fmt, -1) if isinstance(fmt, str) else int(fmt)
+    return int(load_library().efx_import_src_bytes(code, width, height))
+
+
+def letterbox_rect(width: int, height: int):
+    """The destination rectangle (x, y, w, h) of fit="letterbox" for a source (or crop) of width x height: the largest
+    rectangle of that aspect ratio with even sides inside 352 x 192, centred.  Integer rule: where width * 192 >=
+    height * 352 the rectangle is 352 wide and floor(352 * height / width) high, otherwise 192 high and
+    floor(192 * width / height) wide; that side is rounded down to even and is at least 16; x = (352 - w) // 2 and
+    y = (192 - h) // 2, each rounded down to even.  Host only."""
+    if width < 1 or height < 1:
+        raise ValueError("width and height must be positive")
+    if width * FRAME_HEIGHT >= height * FRAME_WIDTH:
+        w, h = FRAME_WIDTH, max(16, (FRAME_WIDTH * height // width) & ~1)
+    else:
+        w, h = max(16, (FRAME_HEIGHT * width // height) & ~1), FRAME_HEIGHT
+    return ((FRAME_WIDTH - w) // 2) & ~1, ((FRAME_HEIGHT - h) // 2) & ~1, w, h
+
+
+def _import_geometry(shape, fmt, width, height):
+    """(fmt, n, width, height) of import_pictures' source from its shape."""
+    shape = tuple(shape)
+    if fmt is None:
+        if len(shape) == 4:
+            fmt = "rgb24" if shape[3] == 3 else "rgbp"
+        elif len(shape) == 2:
+            fmt = "i420"
+        else:
+            raise ValueError(f"cannot infer the pixel format from shape {shape}")
+    if fmt not in _PIX_FORMATS:
+        raise ValueError(f"unknown format {fmt!r}: one of {sorted(_PIX_FORMATS)}")
+    if fmt == "i420":
+        if width is None or height is None:
+            raise ValueError("an i420 source needs width= and height=")
+        if len(shape) != 2 or shape[1] != width * height * 3 // 2:
+            raise ValueError(f"an i420 source must have shape (n, {width * height * 3 // 2}), got {shape}")
+        return fmt, shape[0], width, height
+    if len(shape) != 4 or shape[3 if fmt == "rgb24" else 1] != 3:
+        raise ValueError(f"a {fmt} source must have shape " + ("(n, H, W, 3)" if fmt == "rgb24" else "(n, 3, H, W)") + f", got {shape}")
+    h, w = (shape[1], shape[2]) if fmt == "rgb24" else (shape[2], shape[3])
+    if (width is not None and width != w) or (height is not None and height != h):
+        raise ValueError(f"width= / height= disagree with shape {shape}")
+    return fmt, shape[0], w, h
+
+
 def encode_bound(fmt: int, n_pictures: int) -> int:
     """Worst-case bytes of one encoded stream of n_pictures pictures (efx_encode_bound; 0 for invalid arguments)."""
     return int(load_library().efx_encode_bound(fmt, n_pictures))
@@ -379,6 +435,7 @@ class Decoder:
         _check(None, self._lib.efx_create(C.byref(cfg), C.byref(self._ctx)))
         self.max_streams, self.max_pictures, self.ring_depth = max_streams, max_pictures, max(2, ring_depth)
         self.device = device
+        self.hip_stream = hip_stream
         self.n_streams = 0
 
     def close(self):
@@ -617,6 +674,107 @@ class Decoder:
             return buf.download(np.uint8, buf.nbytes).reshape(_export_shape(fmt, n))
         finally:
             buf.free()
+
+    # -- pictures in (efx_import_frames) ----------------------------------------------------
+    def import_to(self, src: DeviceBuffer | int, dst: DeviceBuffer | int, *, n_images: int, fmt: str, width: int, height: int,
+                  crop=None, dst_rect=None, full_range: bool = False, src_stride: int = 0, dst_stride: int = 0):
+        """efx_import_frames on raw device memory (DeviceBuffers or pointers), asynchronous on the library's stream:
+        source image i (fmt "i420", "rgb24" or "rgbp", width x height) at src + i * src_stride (0 = import_src_bytes()
+        rounded up to 16), its 352 x 192 I420 picture at dst + i * dst_stride (0 = 101376).  crop = (x, y, w, h) of the
+        source (None: all of it), dst_rect = (x, y, w, h) of the output that receives it (None: all of it), the rest is
+        black."""
+        if fmt not in _PIX_FORMATS:
+            raise ValueError(f"unknown format {fmt!r}: one of {sorted(_PIX_FORMATS)}")
+        g = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
+        o = _ImportOpts(n_images, _PIX_FORMATS[fmt], width, height, *(crop or (0, 0, 0, 0)), *(dst_rect or (0, 0, 0, 0)),
+                        1 if full_range else 0, src_stride, dst_stride)
+        _check(self._ctx, self._lib.efx_import_frames(self._ctx, C.byref(o), g(src), g(dst)))
+
+    def import_pictures(self, src, *, fmt: str | None = None, width: int | None = None, height: int | None = None, crop=None,
+                        fit: str = "stretch", full_range: bool = False, out=None, sync: bool = True):
+        """Pictures of any size as (n, 101376) I420 pictures of 352 x 192, the layout encode() takes, cropped, scaled and
+        converted on the device (efx_import_frames; the arithmetic: include/efx.h).  src: a NumPy array, or a uint8
+        torch tensor on the decoder's device, of shape (n, H, W, 3) for "rgb24", (n, 3, H, W) for "rgbp", or
+        (n, H * W * 3 // 2) for "i420" together with width= and height=; fmt=None infers the format from the shape (four
+        axes: rgb24 when the last one is 3, else rgbp; two axes: i420).  crop = (x, y, w, h) of the source.
+        fit="stretch" fills the frame; fit="letterbox" keeps the aspect ratio of the source (of the crop): the picture
+        goes into letterbox_rect(w, h), the largest centred rectangle of that ratio with even sides, and the rest of
+        the frame is black.  full_range: RGB sources only, False = BT.601 studio swing (what MPEG-1 carries).
+
+        Returns a tensor for tensor input and an array for array input.  out: a preallocated contiguous uint8 tensor
+        of n * 101376 elements on this device, or a DeviceBuffer (then returned as is); with out given, array input
+        returns out as well.
+
+        The kernels run on the library's stream.  For tensor input torch's current stream is synchronised first unless
+        it is the decoder's stream (hip_stream=).  sync=True (default) waits for the import.  sync=False is only safe
+        under the conditions export() names: the decoder lives on torch's current stream, or the caller calls sync()
+        before using the result."""
+        if fit not in ("stretch", "letterbox"):
+            raise ValueError(f"unknown fit {fit!r}: 'stretch' or 'letterbox'")
+        fmt, n, width, height = _import_geometry(src.shape, fmt, width, height)
+        image = import_src_bytes(fmt, width, height)
+        if not image or n < 1:
+            raise ValueError(f"{fmt} pictures of {width} x {height} cannot be imported (2 .. 4096, i420: even; n >= 1)")
+        stride = (image + 15) // 16 * 16
+        rect = None
+        if fit == "letterbox":
+            rect = letterbox_rect(*(crop[2:] if crop else (width, height)))
+        nbytes = n * FRAME_BYTES
+        bufs, keep = [], []
+        try:
+            is_array = isinstance(src, np.ndarray)
+            if is_array:
+                host = np.zeros((n, stride), dtype=np.uint8)
+                host[:, :image] = np.ascontiguousarray(src, dtype=np.uint8).reshape(n, image)
+                sbuf = DeviceBuffer(self, n * stride)
+                bufs.append(sbuf)
+                sbuf.upload(host)
+                src_ptr = sbuf.ptr
+            else:
+                import torch
+                device = torch.device("cuda", self.device)
+                if not isinstance(src, torch.Tensor) or src.dtype != torch.uint8 or src.device != device:
+                    raise ValueError(f"src must be a uint8 tensor on {device} (or a NumPy array)")
+                flat = src.contiguous()
+                if stride != image or flat.data_ptr() % 16:
+                    padded = torch.zeros((n, stride), dtype=torch.uint8, device=device)
+                    padded[:, :image] = flat.view(n, image)
+                    flat = padded
+                keep.append(flat)
+                cur = torch.cuda.current_stream(device)
+                if not self.hip_stream or cur.cuda_stream != self.hip_stream:
+                    cur.synchronize()
+                    sync = sync or flat is not src  # (torch may hand a staging copy's memory out again on its own stream)
+                src_ptr = flat.data_ptr()
+            obuf = None
+            if isinstance(out, DeviceBuffer):
+                if out.nbytes < nbytes:
+                    raise ValueError(f"out holds {out.nbytes} bytes, the import needs {nbytes}")
+                result, ptr = out, out.ptr
+            elif out is None and is_array:
+                obuf = DeviceBuffer(self, nbytes)
+                bufs.append(obuf)
+                result, ptr = None, obuf.ptr
+            else:
+                import torch
+                device = torch.device("cuda", self.device)
+                if out is None:
+                    out = torch.empty((n, FRAME_BYTES), dtype=torch.uint8, device=device)
+                if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != device:
+                    raise ValueError(f"out must be a uint8 tensor on {device}")
+                if not out.is_contiguous() or out.numel() != nbytes:
+                    raise ValueError(f"out must be contiguous with {nbytes} elements (shape {(n, FRAME_BYTES)})")
+                result, ptr = out.view(n, FRAME_BYTES), out.data_ptr()
+            self.import_to(src_ptr, ptr, n_images=n, fmt=fmt, width=width, height=height, crop=crop, dst_rect=rect,
+                           full_range=full_range, src_stride=stride)
+            if sync or bufs:
+                self.sync()  # (a staging buffer of this call is freed below)
+            if obuf is not None:
+                result = obuf.download(np.uint8, nbytes).reshape(n, FRAME_BYTES)
+            return result
+        finally:
+            for b in bufs:
+                b.free()
 
     # -- MPEG-1 encode (efx_encode) ------------------------------------------------------------
     def encode_to(self, src: DeviceBuffer | int, dst: DeviceBuffer | int, length: DeviceBuffer | int,

@@ -19,6 +19,7 @@
 #include "efx.h"
 #include "efx_internal.h"
 #include "enc_core.h"
+#include "import_px.h"
 #include "parse_tm.h"
 #include "sbc_enc_core.h"
 
@@ -53,6 +54,8 @@ __global__ void k_composite(const uint8_t*, const VideoTables*, const VideoLineT
 __global__ void k_pdm(const int16_t*, int, int, int32_t*, uint16_t*);
 template <int FMT, int CHROMA>
 __global__ void k_export(const uint8_t*, int, ExportArgs);  // (k_export.hip: the five (format, chroma) instances)
+__global__ void k_import_taps(ImportTap*, ImportArgs);  // (k_import.hip)
+__global__ void k_import(const uint8_t*, uint8_t*, const ImportTap*, ImportArgs);
 __global__ void k_enc_begin(EncArgs);
 __global__ void k_enc_act(EncArgs);
 __global__ void k_enc_rows(EncArgs);
@@ -231,6 +234,7 @@ struct efx_ctx {
     sbcenc::Tables* d_sbc_enc_tables = nullptr;  // efx_sbc_encode's window and matrix (sbc_enc_core.h)
     uint32_t* d_mux_before = nullptr;            // efx_mux_av's scratch: per (stream, audio PES) the video packets in front of it
     size_t mux_before_cap = 0;
+    ImportTap* d_import_taps = nullptr;          // efx_import_frames' tap table: written and read on the device, in stream order
     int parse_wg_cap = 0;  // k_parse workgroups resident per parse kernel while reconstruction launches are queued (0: no cap); EFX_PARSE_WG_CAP
     // launch structure (efx_set_option; the environment variables of the same names, upper case with EFX_, set the defaults)
     int opt_groups = 0;        // reconstruction groups per call: 0 = one group behind a busy reconstruction stream, groups of
@@ -621,6 +625,7 @@ int efx_create(const efx_config* cfg, efx_ctx** out)
     A(dalloc(&ctx->d_hash, n * D));
     A(dalloc(&ctx->d_sbc_tables, 1));
     A(dalloc(&ctx->d_sbc_enc_tables, 1));
+    A(dalloc(&ctx->d_import_taps, kImportTapRows));
     if (e != hipSuccess) {
         fprintf(stderr, "efx_create: %s\n", hipGetErrorString(e));
         return bail(EFX_ERR_DEVICE);
@@ -718,7 +723,7 @@ void efx_destroy(efx_ctx* ctx)
     void* bufs[] = {ctx->d_tables, ctx->d_tm_tables, ctx->d_sbc_flags, ctx->d_sbc_next, ctx->d_sbc_info, ctx->d_sbc_plan, ctx->d_sbc_extra, ctx->d_sbc_cover, ctx->d_state, ctx->d_frames, ctx->d_video[0],  ctx->d_video[1], ctx->d_video_lines[0],
                     ctx->d_video_lines[1], ctx->d_hash, ctx->d_ts, ctx->d_demux_chunks, ctx->d_sbc_tables, ctx->d_idx_info, ctx->d_ts_off, ctx->d_idx_len,
                     ctx->d_idx_base, ctx->d_idx_seq, ctx->d_enc_state, ctx->d_enc_pics, ctx->d_enc_slices, ctx->d_enc_slice_len,
-                    ctx->d_enc_act, ctx->d_enc_tables, ctx->d_sbc_enc_tables, ctx->d_mux_before};
+                    ctx->d_enc_act, ctx->d_enc_tables, ctx->d_sbc_enc_tables, ctx->d_mux_before, ctx->d_import_taps};
     if (ctx->h_enc_full)
         (void)hipHostFree(ctx->h_enc_full);
     for (auto& te : ctx->timing_ring)
@@ -1771,6 +1776,74 @@ int efx_export_frames(efx_ctx* ctx, const efx_export_opts* o, void* dst_device)
         }
         ctx->last_recon_done = ctx->slot[ctx->groups[ctx->n_groups - 1].slot].recon_done;
     }
+    return EFX_OK;
+}
+
+size_t efx_import_src_bytes(int format, int width, int height)
+{
+    if (width < 2 || width > kImportMaxWidth || height < 2 || height > kImportMaxWidth)
+        return 0;
+    switch (format) {
+    case EFX_PIX_I420: return ((width | height) & 1) ? 0 : (size_t)width * height * 3 / 2;
+    case EFX_PIX_RGB24:
+    case EFX_PIX_RGBP: return (size_t)width * height * 3;
+    default: return 0;
+    }
+}
+
+int efx_import_frames(efx_ctx* ctx, const efx_import_opts* o, const void* src_device, uint8_t* dst_device)
+{
+    bind_device(ctx);
+    if (!ctx || !o)
+        return EFX_ERR_ARG;
+    if (!src_device || ((uintptr_t)src_device & 15) || !dst_device || ((uintptr_t)dst_device & 15))
+        return fail(ctx, EFX_ERR_ARG, "efx_import_frames: src_device and dst_device must be 16-byte aligned device pointers");
+    const size_t image = efx_import_src_bytes(o->format, o->width, o->height);
+    if (!image)
+        return fail(ctx, EFX_ERR_ARG, "efx_import_frames: unknown format, or width / height outside 2 .. 4096 (I420: even)");
+    if (o->n_images < 1 || o->n_images > (1 << 24))
+        return fail(ctx, EFX_ERR_ARG, "efx_import_frames: n_images outside 1 .. 2^24");
+    ImportArgs a{};
+    a.format = o->format;
+    a.width = o->width;
+    a.height = o->height;
+    a.full_range = o->full_range ? 1 : 0;
+    const int even = o->format == EFX_PIX_I420 ? 1 : 0;
+    if (o->crop_w == 0) {
+        a.crop_w = o->width;
+        a.crop_h = o->height;
+    } else {
+        a.crop_x = o->crop_x, a.crop_y = o->crop_y, a.crop_w = o->crop_w, a.crop_h = o->crop_h;
+        if (a.crop_x < 0 || a.crop_y < 0 || a.crop_w < 1 || a.crop_h < 1 || a.crop_x > o->width - a.crop_w ||
+            a.crop_y > o->height - a.crop_h)
+            return fail(ctx, EFX_ERR_ARG, "efx_import_frames: crop outside the source picture");
+        if (even && ((a.crop_x | a.crop_y | a.crop_w | a.crop_h) & 1))
+            return fail(ctx, EFX_ERR_ARG, "efx_import_frames: the crop of an I420 source must be even");
+    }
+    if (o->dst_w == 0) {
+        a.dst_w = EFX_FRAME_WIDTH;
+        a.dst_h = EFX_FRAME_HEIGHT;
+    } else {
+        a.dst_x = o->dst_x, a.dst_y = o->dst_y, a.dst_w = o->dst_w, a.dst_h = o->dst_h;
+        if ((a.dst_x | a.dst_y | a.dst_w | a.dst_h) & 1)
+            return fail(ctx, EFX_ERR_ARG, "efx_import_frames: the destination rectangle must be even");
+        if (a.dst_x < 0 || a.dst_y < 0 || a.dst_w < 16 || a.dst_h < 16 || a.dst_x > EFX_FRAME_WIDTH - a.dst_w ||
+            a.dst_y > EFX_FRAME_HEIGHT - a.dst_h)
+            return fail(ctx, EFX_ERR_ARG, "efx_import_frames: destination rectangle below 16 x 16 or outside the 352 x 192 frame");
+    }
+    if (a.crop_w > ipx::kMaxRatio * a.dst_w || a.crop_h > ipx::kMaxRatio * a.dst_h)
+        return fail(ctx, EFX_ERR_ARG, "efx_import_frames: the crop is more than 32 times the destination rectangle");
+    a.src_stride = o->src_stride ? o->src_stride : (image + 15) / 16 * 16;
+    a.dst_stride = o->dst_stride ? o->dst_stride : (size_t)kFrameBytes;
+    if (a.src_stride < image || (a.src_stride & 15))
+        return fail(ctx, EFX_ERR_ARG, "efx_import_frames: src_stride must be a multiple of 16 and hold an image");
+    if (a.dst_stride < (size_t)kFrameBytes || (a.dst_stride & 15))
+        return fail(ctx, EFX_ERR_ARG, "efx_import_frames: dst_stride must be a multiple of 16 and hold an image");
+    // two launches whatever n_images is; the table is written on the device, behind every earlier import's reads
+    hipLaunchKernelGGL(k_import_taps, dim3((kImportTapRows + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_import_taps, a);
+    hipLaunchKernelGGL(k_import, dim3((unsigned)o->n_images * kImportBands), dim3(256), 0, ctx->stream,
+                       static_cast<const uint8_t*>(src_device), dst_device, ctx->d_import_taps, a);
+    EFX_HIP(hipGetLastError());
     return EFX_OK;
 }
 

@@ -152,6 +152,29 @@ struct ExportArgs {
     size_t dst_stride;
 };
 
+// k_import (k_import.hip): the taps of one destination index of one axis, written by k_import_taps (import_px.h: taps())
+constexpr int kImportTapSlots = 132;  // ipx::kMaxTaps rounded up so that a record is a multiple of 16 bytes
+struct ImportTap {
+    int32_t start, count;  // source indices [start, start + count) of the (cropped) plane
+    uint16_t k[kImportTapSlots];
+};
+// the table of a call: luma columns, luma rows, chroma columns, chroma rows of the destination rectangle
+constexpr int kImportTapLX = 0, kImportTapLY = 352, kImportTapCX = 352 + 192, kImportTapCY = 352 + 192 + 176;
+constexpr int kImportTapRows = 352 + 192 + 176 + 96;
+constexpr int kImportBandRows = 8;            // a workgroup makes 8 luma rows and 4 rows of each chroma plane
+constexpr int kImportBands = 192 / kImportBandRows;
+constexpr int kImportMaxWidth = 4096;
+
+// k_import_taps / k_import launch arguments (by value)
+struct ImportArgs {
+    int format;                          // efx_pixel_format of the source
+    int width, height;                   // source picture
+    int crop_x, crop_y, crop_w, crop_h;  // source rectangle
+    int dst_x, dst_y, dst_w, dst_h;      // destination rectangle
+    int full_range;
+    size_t src_stride, dst_stride;
+};
+
 // per-stream result of k_ts_sequences
 struct IdxInfo {
     int64_t first_pts, last_pts;  // origin (PTS of the first sequence start), PTS of the last video PES

@@ -1,0 +1,277 @@
+// k_import.hip -- pictures in: I420 / RGB24 / RGBP pictures of any size cropped, scaled and converted to the 352 x 192
+// I420 layout efx_encode reads (the inverse of k_export).  The arithmetic is import_px.h's: an integer function of the
+// source bytes (the formulas: include/efx.h), the same functions on the host and here.
+//
+// k_import_taps  one lane per axis (luma columns / rows, chroma columns / rows) and destination index: the window and its
+//                u16 coefficients into the context's table.  It runs in stream order in front of k_import, so queued calls
+//                with different geometry never share a table's content.
+// k_import       one workgroup per image and band of 8 luma rows (4 rows of each chroma plane).  It walks the source rows
+//                of the band's vertical support: a row is fetched into LDS with 16-byte loads from the 16-byte piece its
+//                first byte lies in (rows start anywhere; the pieces stay inside the image rounded up to 16 bytes), an RGB
+//                row is converted there into three byte rows, so one read of the source makes all three planes.  A lane
+//                owns destination columns (2 luma columns, 2 chroma columns): it forms the 16-bit horizontal sum of the
+//                row and adds k_y * h into one register per destination row.  The band is assembled in LDS on the border
+//                colour and leaves as 16-byte stores: the whole 101376 bytes of an image are written, nothing else.
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+
+#include "efx.h"
+#include "efx_internal.h"
+#include "import_px.h"
+
+namespace efx {
+
+static_assert(kImportTapSlots >= ipx::kMaxTaps && kImportTapSlots % 4 == 0 && sizeof(ImportTap) % 16 == 0 && offsetof(ImportTap, k) == 8,
+              "a tap record holds every window, its coefficients readable in 8-byte groups");
+
+namespace {
+
+constexpr int kW = EFX_FRAME_WIDTH, kH = EFX_FRAME_HEIGHT;
+constexpr int kYBytes = kW * kH, kCBytes = kYBytes / 4;
+constexpr int kRows = kImportBandRows, kCRows = kImportBandRows / 2;
+constexpr int kRowBuf = kImportMaxWidth + 32;      // a byte row behind its alignment shift (<= 15), read four taps at a time
+constexpr int kRawBuf = 3 * kRowBuf + 16;          // an RGB24 row (3 x 4096 + 15) or three RGBP rows, read 4 pixels at a time
+constexpr int kBandY = kRows * kW, kBandC = kCRows * (kW / 2), kBandBytes = kBandY + 2 * kBandC;
+constexpr int kThreads = 256;
+static_assert(2 * kThreads >= kW, "a lane owns two luma columns and two chroma columns");
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// bytes [off, off + len) of the image into buf (16-byte aligned LDS) as whole 16-byte pieces; the segment starts at
+// buf + the returned shift
+__device__ inline int stage(const uint8_t* __restrict__ img, size_t off, int len, uint8_t* buf)
+{
+    const ipx::Span sp = ipx::span(off, len);
+    for (int i = threadIdx.x; i < sp.pieces; i += kThreads)
+        *reinterpret_cast<u32x4*>(buf + 16 * i) = *reinterpret_cast<const u32x4*>(img + sp.a0 + 16 * (size_t)i);
+    return sp.shift;
+}
+
+// The vertical coefficient of source row s for each of the band's destination rows (wave-uniform)
+template <int R>
+__device__ inline void vcoefs(const ImportTap* __restrict__ ty, int n, int s, int ky[R])
+{
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        ky[r] = 0;
+        if (r < n) {
+            const unsigned i = (unsigned)(s - ty[r].start);
+            if (i < (unsigned)ty[r].count)
+                ky[r] = ty[r].k[i];
+        }
+    }
+}
+
+// One destination column's share of a source row: the horizontal sum, rounded to 16 bits, into the rows' accumulators
+template <int R>
+__device__ inline void accumulate(const uint8_t* row, const ImportTap* __restrict__ tx, const int ky[R], int acc[R])
+{
+    // four taps per step, their coefficients in one 8-byte load: k_import_taps leaves zeros behind a window, and the up
+    // to three bytes read behind it lie inside the row buffer (start + count <= 4096, shift <= 15)
+    const int n = tx->count;
+    const uint8_t* p = row + tx->start;
+    const uint2* k4 = reinterpret_cast<const uint2*>(tx->k);
+    int sum = 0;
+    for (int i = 0; i < n; i += 4) {
+        const uint2 w = k4[i >> 2];
+        sum += (int)(w.x & 0xFFFF) * (int)p[i] + (int)(w.x >> 16) * (int)p[i + 1] + (int)(w.y & 0xFFFF) * (int)p[i + 2] +
+               (int)(w.y >> 16) * (int)p[i + 3];
+    }
+    const int h = ipx::hround(sum);
+#pragma unroll
+    for (int r = 0; r < R; r++)
+        acc[r] += ky[r] * h;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(256) void k_import_taps(ImportTap* __restrict__ table, ImportArgs a)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= kImportTapRows)
+        return;
+    // chroma: an I420 source brings half the crop, an RGB source is converted at full resolution
+    const int half = a.format == EFX_PIX_I420 ? 2 : 1;
+    int d, S, D;
+    if (i < kImportTapLY) {
+        d = i - kImportTapLX, S = a.crop_w, D = a.dst_w;
+    } else if (i < kImportTapCX) {
+        d = i - kImportTapLY, S = a.crop_h, D = a.dst_h;
+    } else if (i < kImportTapCY) {
+        d = i - kImportTapCX, S = a.crop_w / half, D = a.dst_w / 2;
+    } else {
+        d = i - kImportTapCY, S = a.crop_h / half, D = a.dst_h / 2;
+    }
+    if (d >= D)
+        return;
+    int n;
+    table[i].start = ipx::taps(S, D, d, &n, table[i].k);
+    table[i].count = n;
+    for (int j = n; j < kImportTapSlots; j++)
+        table[i].k[j] = 0;  // (k_import reads the coefficients four at a time)
+}
+
+__global__ __launch_bounds__(256) void k_import(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                const ImportTap* __restrict__ taps, ImportArgs a)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t s_raw[kRawBuf];
+    __shared__ __attribute__((aligned(16))) uint8_t s_row[3][kRowBuf];
+    __shared__ __attribute__((aligned(16))) uint8_t s_out[kBandBytes];
+
+    const int tid = threadIdx.x;
+    const int band = (int)(blockIdx.x % kImportBands);
+    const size_t image = blockIdx.x / kImportBands;
+    const uint8_t* img = src + image * a.src_stride;
+    uint8_t* out = dst + image * a.dst_stride;
+    const bool rgb = a.format != EFX_PIX_I420;
+
+    // the band on the border colour
+    {
+        const uint32_t black = (rgb && a.full_range) ? 0u : 0x10101010u;
+        for (int i = tid; i < kBandBytes / 4; i += kThreads)
+            reinterpret_cast<uint32_t*>(s_out)[i] = i < kBandY / 4 ? black : 0x80808080u;
+    }
+
+    // the band's rows inside the destination rectangle, as indices into the rectangle: luma [l0, l0 + nl), chroma
+    // [c0, c0 + nc) (every coordinate of the rectangle is even, so the two agree)
+    const int y0 = band * kRows, cy0 = band * kCRows;
+    const int l0 = max(y0, a.dst_y) - a.dst_y, nl = min(y0 + kRows, a.dst_y + a.dst_h) - a.dst_y - l0;
+    const int c0 = max(cy0, a.dst_y / 2) - a.dst_y / 2, nc = min(cy0 + kCRows, (a.dst_y + a.dst_h) / 2) - a.dst_y / 2 - c0;
+    const ImportTap* tly = taps + kImportTapLY + l0;
+    const ImportTap* tcy = taps + kImportTapCY + c0;
+
+    // this lane's columns: luma tid and tid + 256; chroma items tid and tid + 256 of [Cb columns | Cr columns]
+    const int cw2 = a.dst_w / 2;
+    bool lv[2], cv[2];
+    int cplane[2], ccol[2];
+    const ImportTap* tlx[2];
+    const ImportTap* tcx[2];
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+        const int col = tid + kThreads * j;
+        lv[j] = col < a.dst_w;
+        tlx[j] = taps + kImportTapLX + (lv[j] ? col : 0);
+        cv[j] = col < a.dst_w;
+        cplane[j] = col >= cw2 ? 1 : 0;
+        ccol[j] = cv[j] ? col - cplane[j] * cw2 : 0;
+        tcx[j] = taps + kImportTapCX + ccol[j];
+    }
+    int accl[2][kRows] = {}, accc[2][kCRows] = {};
+
+    if (nl > 0) {  // (nl > 0 exactly when nc > 0)
+        const int ls0 = tly[0].start, ls1 = tly[nl - 1].start + tly[nl - 1].count;  // source rows of the supports
+        const int cs0 = tcy[0].start, cs1 = tcy[nc - 1].start + tcy[nc - 1].count;
+        if (rgb) {
+            const ipx::Matrix m = ipx::matrix(a.full_range);
+            for (int s = min(ls0, cs0); s < max(ls1, cs1); s++) {
+                int sh[3];
+                if (a.format == EFX_PIX_RGB24) {
+                    sh[0] = stage(img, ipx::rgb24_row(a.width, a.crop_x, a.crop_y, s), 3 * a.crop_w, s_raw);
+                } else {
+#pragma unroll
+                    for (int c = 0; c < 3; c++)
+                        sh[c] = stage(img, ipx::rgbp_row(c, a.width, a.height, a.crop_x, a.crop_y, s), a.crop_w, s_raw + c * kRowBuf) +
+                                c * kRowBuf;
+                }
+                __syncthreads();
+                // four pixels per lane and step (the last step may convert up to three stale pixels nobody reads)
+                for (int x = 4 * tid; x < a.crop_w; x += 4 * kThreads) {
+                    uint32_t wy = 0, wu = 0, wv = 0;
+#pragma unroll
+                    for (int q = 0; q < 4; q++) {
+                        int r, g, b;
+                        if (a.format == EFX_PIX_RGB24) {
+                            const uint8_t* p = s_raw + sh[0] + 3 * (x + q);
+                            r = p[0], g = p[1], b = p[2];
+                        } else {
+                            r = s_raw[sh[0] + x + q], g = s_raw[sh[1] + x + q], b = s_raw[sh[2] + x + q];
+                        }
+                        const uint32_t yuv = ipx::ycbcr(m, r, g, b);
+                        wy |= (yuv & 0xFF) << (8 * q);
+                        wu |= ((yuv >> 8) & 0xFF) << (8 * q);
+                        wv |= (yuv >> 16) << (8 * q);
+                    }
+                    *reinterpret_cast<uint32_t*>(&s_row[0][x]) = wy;
+                    *reinterpret_cast<uint32_t*>(&s_row[1][x]) = wu;
+                    *reinterpret_cast<uint32_t*>(&s_row[2][x]) = wv;
+                }
+                __syncthreads();
+                if (s >= ls0 && s < ls1) {
+                    int ky[kRows];
+                    vcoefs<kRows>(tly, nl, s, ky);
+#pragma unroll
+                    for (int j = 0; j < 2; j++)
+                        if (lv[j])
+                            accumulate<kRows>(s_row[0], tlx[j], ky, accl[j]);
+                }
+                if (s >= cs0 && s < cs1) {
+                    int ky[kCRows];
+                    vcoefs<kCRows>(tcy, nc, s, ky);
+#pragma unroll
+                    for (int j = 0; j < 2; j++)
+                        if (cv[j])
+                            accumulate<kCRows>(s_row[1 + cplane[j]], tcx[j], ky, accc[j]);
+                }
+                // (the next row's fetch writes s_raw, which nobody reads any more; its conversion waits at the barrier)
+            }
+        } else {
+            for (int s = ls0; s < ls1; s++) {
+                const int sh = stage(img, ipx::i420_row(0, a.width, a.height, a.crop_x, a.crop_y, s), a.crop_w, s_row[0]);
+                __syncthreads();
+                int ky[kRows];
+                vcoefs<kRows>(tly, nl, s, ky);
+#pragma unroll
+                for (int j = 0; j < 2; j++)
+                    if (lv[j])
+                        accumulate<kRows>(s_row[0] + sh, tlx[j], ky, accl[j]);
+                __syncthreads();
+            }
+            for (int s = cs0; s < cs1; s++) {
+                int sh[2];
+#pragma unroll
+                for (int c = 0; c < 2; c++)
+                    sh[c] = stage(img, ipx::i420_row(1 + c, a.width, a.height, a.crop_x, a.crop_y, s), a.crop_w / 2, s_row[1 + c]);
+                __syncthreads();
+                int ky[kCRows];
+                vcoefs<kCRows>(tcy, nc, s, ky);
+#pragma unroll
+                for (int j = 0; j < 2; j++)
+                    if (cv[j])
+                        accumulate<kCRows>(s_row[1 + cplane[j]] + sh[cplane[j]], tcx[j], ky, accc[j]);
+                __syncthreads();
+            }
+        }
+    }
+    __syncthreads();  // the border is laid out
+
+    // the lanes' columns into the band
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+        const int col = tid + kThreads * j;
+#pragma unroll
+        for (int r = 0; r < kRows; r++)
+            if (lv[j] && r < nl)
+                s_out[(a.dst_y + l0 + r - y0) * kW + a.dst_x + col] = (uint8_t)ipx::vround(accl[j][r]);
+#pragma unroll
+        for (int r = 0; r < kCRows; r++)
+            if (cv[j] && r < nc)
+                s_out[kBandY + cplane[j] * kBandC + (a.dst_y / 2 + c0 + r - cy0) * (kW / 2) + a.dst_x / 2 + ccol[j]] =
+                    (uint8_t)ipx::vround(accc[j][r]);
+    }
+    __syncthreads();
+
+    // a band is contiguous in each plane: 176 + 44 + 44 pieces of 16 bytes
+    for (int i = tid; i < kBandBytes / 16; i += kThreads) {
+        uint8_t* o;
+        if (i < kBandY / 16)
+            o = out + y0 * kW + 16 * i;
+        else if (i < (kBandY + kBandC) / 16)
+            o = out + kYBytes + cy0 * (kW / 2) + 16 * (i - kBandY / 16);
+        else
+            o = out + kYBytes + kCBytes + cy0 * (kW / 2) + 16 * (i - (kBandY + kBandC) / 16);
+        *reinterpret_cast<u32x4*>(o) = *reinterpret_cast<const u32x4*>(s_out + 16 * i);
+    }
+}
+
+}  // namespace efx

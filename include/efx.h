@@ -256,6 +256,63 @@ size_t efx_export_bytes(int format);
  * no decode yet, or the stream range beyond the stream count of the most recent decode. */
 int efx_export_frames(efx_ctx* ctx, const efx_export_opts* opts, void* dst_device);
 
+/* -- pictures in: any size and pixel format to the encoder's 352 x 192 I420 (k_import) ----- */
+/* efx_encode reads 352 x 192 I420 pictures; nobody's source material has that size.  efx_import_frames is the inverse of
+ * efx_export_frames: it crops I420, RGB24 (HWC) or RGBP (CHW) pictures of 2 x 2 to 4096 x 4096 pixels, scales the crop
+ * into a rectangle of the 352 x 192 frame and converts RGB to YCbCr, on the device, for n_images pictures at once -- the
+ * first step of the reference indexer's ffmpeg line (indexer/indexer.cpp:299-309: crop=992:546:144:0 ... -s 352x192).
+ *
+ * Output.  Image k is read at src + k * src_stride and written at dst + k * dst_stride in the layout efx_encode reads:
+ * Y 192 x 352, Cb 96 x 176, Cr 96 x 176.  With dst_stride 101376 and n_images = n_streams x n_pictures the output is an
+ * efx_encode source with packed src_stride.  Pixels outside the destination rectangle are black: Y 16 (Y 0 for an RGB
+ * source with full_range = 1), Cb = Cr = 128.  The bytes between output images are not written.
+ *
+ * The arithmetic (espflix_amd/csrc/import_px.h) is an integer function of the source bytes, bit-reproducible anywhere.
+ *   Planes.  An I420 source brings three byte planes: the crop, and the crop halved for Cb and Cr.  An RGB source is
+ *   converted pixel by pixel, at source resolution, into three planes of the crop's size.  Luma goes from crop_w x crop_h
+ *   to dst_w x dst_h, each chroma plane from its extent to dst_w / 2 x dst_h / 2.  The centre-aligned mapping below puts a
+ *   chroma sample in the middle of its 2 x 2 luma samples, which is MPEG-1's siting.
+ *   RGB -> YCbCr, BT.601, >> arithmetic, results clamped to 0 .. 255:
+ *     studio swing (full_range 0, what MPEG-1 carries)      full range (full_range 1)
+ *     Y  = (( 66 R + 129 G +  25 B + 128) >> 8) + 16        Y  =  ( 77 R + 150 G +  29 B + 128) >> 8
+ *     Cb = ((-38 R -  74 G + 112 B + 128) >> 8) + 128       Cb = ((-43 R -  85 G + 128 B + 128) >> 8) + 128
+ *     Cr = ((112 R -  94 G -  18 B + 128) >> 8) + 128       Cr = ((128 R - 107 G -  21 B + 128) >> 8) + 128
+ *   Taps of one axis, source extent S, destination extent D, M = max(S, D) -- a triangle filter widened by the
+ *   down-scaling ratio: destination index d takes source index s with the raw weight
+ *     u(s) = max(0, 2M - |(2s + 1) D - (2d + 1) S|)
+ *   over every s in [0, S) with u(s) > 0 (samples beyond the edge are dropped, not replicated), with the coefficients
+ *   k(s) = floor(u(s) 16384 / sum of u); what is missing to 16384 goes to the tap with the largest u, the first such tap on
+ *   a tie.  S == D gives the single tap s = d: a same-size import is a copy.
+ *   Two passes, horizontal first:  h = (sum of k_x p + 32) >> 6  (16 bits),  out = (sum of k_y h + 2^21) >> 22.
+ *
+ * Memory contract.  For image k the kernels read only bytes in [src + k * src_stride, src + k * src_stride +
+ * efx_import_src_bytes() rounded up to 16) and write only the 101376 bytes of output image k.  src_device and dst_device
+ * are 16-byte aligned and the strides are multiples of 16; rows inside an image start anywhere (333 x 77 RGB24), they are
+ * fetched in 16-byte pieces aligned down inside that interval. */
+typedef struct efx_import_opts {
+    int n_images;                       /* >= 1 */
+    int format;                         /* efx_pixel_format of the SOURCE: I420, RGB24 (HWC), RGBP (CHW) */
+    int width, height;                  /* source picture, 2 .. 4096 each; I420: both even */
+    int crop_x, crop_y, crop_w, crop_h; /* source rectangle that is used; crop_w == 0: the whole picture; I420: all even */
+    int dst_x, dst_y, dst_w, dst_h;     /* rectangle of the 352 x 192 output that receives it; dst_w == 0: 0, 0, 352, 192;
+                                           all even, dst_w, dst_h >= 16, inside the frame */
+    int full_range;                     /* RGB sources: 0 = write BT.601 studio swing (what MPEG-1 carries), 1 = full range;
+                                           ignored for I420 */
+    size_t src_stride;                  /* bytes from one source image to the next; 0 = efx_import_src_bytes() rounded up to 16 */
+    size_t dst_stride;                  /* bytes from one output image to the next; 0 = 101376 */
+} efx_import_opts;
+/* bytes of one source image; 0 for an unknown format, a width or height outside 2 .. 4096, an odd I420 size.  Host only. */
+size_t efx_import_src_bytes(int format, int width, int height);
+/* Asynchronous on the context's stream: no host synchronisation, two launches whatever n_images is (the tap table is
+ * computed on the device in stream order, so calls with different geometry may be queued back to back), and no decoder,
+ * encoder or SBC state is touched.
+ * EFX_ERR_ARG: a NULL or misaligned (16 bytes) pointer, n_images < 1, an unknown format, width or height out of range, an
+ * odd value where an even one is required, a crop outside the source, a destination rectangle below 16 x 16 or outside
+ * the frame, a stride that is too small or not a multiple of 16, or a down-scaling ratio above 32: crop_w > 32 dst_w or
+ * crop_h > 32 dst_h (a window then has at most 65 taps; 129 for the chroma of an RGB source, which goes from the full
+ * crop to half the rectangle). */
+int efx_import_frames(efx_ctx* ctx, const efx_import_opts* opts, const void* src_device, uint8_t* dst_device);
+
 /* -- MPEG-1 encode on the device (k_encode) ---------------------------------------------- */
 /* The reference plays titles that were "encoded with ffmpeg at around 1.5MBits" (README.md:87) ahead of time; nothing in it
  * writes a stream.  efx_encode turns I420 pictures in device memory (the layout efx_export_frames writes: Y 192 x 352, then
