@@ -7,7 +7,7 @@ HIPCC   ?= /opt/rocm/bin/hipcc
 ARCH    ?= gfx950
 CSRC     = espflix_amd/csrc
 HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude -I$(CSRC) -Wall -Wno-unused-function
-OBJS     = $(CSRC)/efx_api.o $(CSRC)/k_demux.o $(CSRC)/k_index.o $(CSRC)/k_parse.o $(CSRC)/k_recon.o $(CSRC)/k_video.o $(CSRC)/k_sbc.o $(CSRC)/k_tsindex.o $(CSRC)/k_export.o $(CSRC)/k_import.o $(CSRC)/k_encode.o $(CSRC)/k_sbc_enc.o $(CSRC)/k_mux.o $(CSRC)/efx_tables.o $(CSRC)/efx_multi.o
+OBJS     = $(CSRC)/efx_api.o $(CSRC)/k_demux.o $(CSRC)/k_index.o $(CSRC)/k_parse.o $(CSRC)/k_recon.o $(CSRC)/k_video.o $(CSRC)/k_sbc.o $(CSRC)/k_tsindex.o $(CSRC)/k_export.o $(CSRC)/k_import.o $(CSRC)/k_import_pcm.o $(CSRC)/k_encode.o $(CSRC)/k_sbc_enc.o $(CSRC)/k_mux.o $(CSRC)/efx_tables.o $(CSRC)/efx_multi.o
 
 .PHONY: all lib gen oracle ref clean dropin scale harness
 # (`scale` links librccl: built by __graft_entry__.build() and by `make scale`, not by a plain `make`)
@@ -23,9 +23,9 @@ $(CSRC)/k_export.o: $(CSRC)/export_px.h
 $(CSRC)/k_import.o $(CSRC)/efx_api.o: $(CSRC)/import_px.h
 $(CSRC)/k_encode.o $(CSRC)/k_mux.o $(CSRC)/efx_api.o: $(CSRC)/enc_core.h $(CSRC)/mpeg1_codebook.h
 $(CSRC)/k_sbc_enc.o $(CSRC)/efx_api.o: $(CSRC)/sbc_enc_core.h $(CSRC)/sbc_proto.h
-$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/efx_internal.h $(CSRC)/enc_rate.h $(CSRC)/parse_tm.h $(CSRC)/efx_probe.h include/efx.h
+$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/efx_internal.h $(CSRC)/import_pcm.h $(CSRC)/enc_rate.h $(CSRC)/parse_tm.h $(CSRC)/efx_probe.h include/efx.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(CSRC)/efx_tables.o: $(CSRC)/efx_tables.cpp $(CSRC)/efx_internal.h $(CSRC)/enc_rate.h $(CSRC)/parse_tm.h $(CSRC)/mpeg1_codebook.h $(CSRC)/sbc_proto.h
+$(CSRC)/efx_tables.o: $(CSRC)/efx_tables.cpp $(CSRC)/efx_internal.h $(CSRC)/import_pcm.h $(CSRC)/enc_rate.h $(CSRC)/parse_tm.h $(CSRC)/mpeg1_codebook.h $(CSRC)/sbc_proto.h
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 $(CSRC)/efx_multi.o: $(CSRC)/efx_multi.cpp include/efx.h
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
@@ -75,7 +75,7 @@ oracle:
 # TEST: the slice parser of k_parse (csrc/parse_tm.h + the tables of csrc/efx_tables.cpp) compiled for the host and checked,
 # record by record, against the parse trace of the test oracle (tests/test_parse_machine.py; no GPU)
 harness: tests/_build/parse_harness
-tests/_build/parse_harness: tests/parse_harness.cpp $(CSRC)/parse_tm.h $(CSRC)/efx_tables.cpp $(CSRC)/efx_internal.h oracle/efx_oracle.c oracle/efx_oracle.h
+tests/_build/parse_harness: tests/parse_harness.cpp $(CSRC)/parse_tm.h $(CSRC)/efx_tables.cpp $(CSRC)/efx_internal.h $(CSRC)/import_pcm.h oracle/efx_oracle.c oracle/efx_oracle.h
 	mkdir -p tests/_build
 	gcc -O2 -std=c99 -c oracle/efx_oracle.c -o tests/_build/efx_oracle.o
 	$(HIPCC) --offload-arch=$(ARCH) -O2 -std=c++17 -Iinclude -I$(CSRC) -Ioracle -x hip tests/parse_harness.cpp $(CSRC)/efx_tables.cpp \

@@ -46,6 +46,9 @@ ENCODE_VBV = 4096         # efx_encode_rc: the buffer model's level went below z
 MUX_FULL = 1024           # efx_mux_av: the stream's output region is too small, nothing written (efx.h)
 MUX_BAD_VIDEO = 2048      # efx_mux_av: the video input is not a transport stream of PID 0x100 that starts with a PES (efx.h)
 PCM_FRAME_PLANAR, PCM_INTERLEAVED = 0, 1   # efx_sbc_encode_opts.pcm_layout
+PCM_PLANAR = 2                             # efx_import_pcm_opts.layout (or PCM_INTERLEAVED)
+_PCM_LAYOUTS = {"interleaved": PCM_INTERLEAVED, "planar": PCM_PLANAR}
+_SBC_FREQUENCY = {16000: 0, 32000: 1, 44100: 2, 48000: 3}  # the SBC header's code of efx_import_pcm's output rates
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EFX_LIB") or os.path.join(_HERE, "libefx.so")  # EFX_LIB: development builds
@@ -104,6 +107,12 @@ class _SbcEncodeOpts(C.Structure):
     _fields_ = [("n_streams", C.c_int), ("n_frames", C.c_int), ("frequency", C.c_int), ("blocks", C.c_int), ("mode", C.c_int),
                 ("allocation", C.c_int), ("bitpool", C.c_int), ("pcm_layout", C.c_int), ("pcm_stride", C.c_size_t),
                 ("frame_stride", C.c_size_t)]
+
+
+class _ImportPcmOpts(C.Structure):
+    _fields_ = [("n_streams", C.c_int), ("n_in", C.c_int), ("in_rate", C.c_int), ("out_rate", C.c_int), ("channels", C.c_int),
+                ("layout", C.c_int), ("mix_q15", C.c_int * 8), ("first_in", C.c_int64), ("src_stride", C.c_size_t),
+                ("dst_stride", C.c_size_t)]
 
 
 class _MuxOpts(C.Structure):
@@ -190,6 +199,11 @@ _SYMBOLS = {
     "efx_sbc_frame_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "efx_sbc_enc_state_bytes": (C.c_size_t, []),
     "efx_sbc_encode": (C.c_int, [_P, C.POINTER(_SbcEncodeOpts), _P, _P, _P]),
+    "efx_import_pcm": (C.c_int, [_P, C.POINTER(_ImportPcmOpts), _P, _P, _P]),
+    "efx_import_pcm_out_samples": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int]),
+    "efx_import_pcm_delay": (C.c_int, [C.c_int, C.c_int]),
+    "efx_import_pcm_state_bytes": (C.c_size_t, []),
+    "efx_import_pcm_filter": (C.c_int, [_P, C.c_int]),
     "efx_mux_av": (C.c_int, [_P, C.POINTER(_MuxOpts), _P, _P, _P, _P, _P, _P]),
     "efx_mux_bound": (C.c_size_t, [C.c_size_t, C.c_int, C.c_int, C.c_int]),
     "efx_mux_audio_packets": (C.c_int, [C.c_int, C.c_int, C.c_int]),
@@ -351,6 +365,29 @@ def sbc_frame_bytes(blocks: int, channels: int, bitpool: int) -> int:
 
 def sbc_enc_state_bytes() -> int:
     return int(load_library().efx_sbc_enc_state_bytes())
+
+
+def import_pcm_out_samples(in_rate: int, out_rate: int, first_in: int, n_in: int) -> int:
+    """Samples per stream an import_pcm call writes: ceil((first_in + n_in) o / r) - ceil(first_in o / r)
+    (efx_import_pcm_out_samples; -1 for invalid arguments)."""
+    return int(load_library().efx_import_pcm_out_samples(in_rate, out_rate, first_in, n_in))
+
+
+def import_pcm_delay(in_rate: int, out_rate: int) -> int:
+    """The resampler's delay W in input frames, 0 for equal rates (efx_import_pcm_delay; -1 for invalid rates)."""
+    return int(load_library().efx_import_pcm_delay(in_rate, out_rate))
+
+
+def import_pcm_state_bytes() -> int:
+    return int(load_library().efx_import_pcm_state_bytes())
+
+
+def import_pcm_filter() -> np.ndarray:
+    """The resampler's prototype table T (efx_import_pcm_filter): int32, 16 P + 1 entries."""
+    lib = load_library()
+    t = np.empty(lib.efx_import_pcm_filter(None, 0), dtype=np.int32)
+    lib.efx_import_pcm_filter(t.ctypes.data, t.size)
+    return t
 
 
 def mux_bound(video_bytes: int, n_frames: int, frame_bytes: int, frames_per_pes: int) -> int:
@@ -931,6 +968,87 @@ class Decoder:
         _check(self._ctx, self._lib.efx_sbc_decode(self._ctx, n_streams, g(frames), stream_stride, frame_bytes, n_frames,
                                                    g(state), g(pcm), pcm_stride, g(ret), g(pcm_count), 1 if probe_first else 0))
 
+    # -- sound in (efx_import_pcm) -----------------------------------------------------------
+    def import_pcm_to(self, src: DeviceBuffer | int, state: DeviceBuffer | int | None, dst: DeviceBuffer | int, *, n_streams: int,
+                      n_in: int, in_rate: int, out_rate: int = 48000, channels: int = 1, layout: int = PCM_INTERLEAVED, weights=None,
+                      first_in: int = 0, src_stride: int = 0, dst_stride: int = 0) -> int:
+        """efx_import_pcm on raw device memory (DeviceBuffers or pointers), asynchronous on the library's stream: stream i's
+        n_in frames of `channels` int16 samples at src + i x src_stride elements (0 = n_in x channels rounded up to 8), its
+        mono samples at out_rate at dst + i x dst_stride elements (0 = the call's output count rounded up to 8), the
+        streams' states (import_pcm_state_bytes() each, zeros = fresh; None only for equal rates) updated in place.
+        weights: up to 8 Q15 downmix weights (None: 32768 // channels each).  Returns the call's output count."""
+        g = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else b)
+        w = [int(v) for v in (weights if weights is not None else ())]
+        if len(w) > 8:
+            raise ValueError("at most 8 downmix weights")
+        n_out = import_pcm_out_samples(in_rate, out_rate, first_in, n_in) if n_in >= 0 else -1
+        r8 = lambda v: (v + 7) // 8 * 8
+        o = _ImportPcmOpts(n_streams, n_in, in_rate, out_rate, channels, layout, (C.c_int * 8)(*(w + [0] * (8 - len(w)))), first_in,
+                           src_stride or r8(max(0, n_in * channels)), dst_stride or r8(max(0, n_out)))
+        _check(self._ctx, self._lib.efx_import_pcm(self._ctx, C.byref(o), g(src), g(state), g(dst)))
+        return n_out
+
+    def import_pcm(self, pcm, *, rate: int, out_rate: int = 48000, layout: str = "interleaved", weights=None, cont: bool = False,
+                   flush: bool = False):
+        """int16 PCM of any rate (8 .. 192 kHz, at most 4 x out_rate) and 1 .. 8 channels as mono at out_rate (16000, 32000,
+        44100 or 48000), the input of sbc_encode(), downmixed and resampled on the device (efx_import_pcm; the arithmetic:
+        include/efx.h).  pcm: a NumPy array, or an int16 torch tensor on the decoder's device, of shape [n, frames] (mono)
+        or [n, frames, channels] (layout="interleaved") or [n, channels, frames] (layout="planar").  weights: Q15 downmix
+        weights, one per channel (None: 32768 // channels each).  Returns an int16 torch tensor [n, n_out] on the device,
+        n_out = ceil(frames x out_rate / rate) for a fresh stream.
+
+        cont=True continues the streams of this object's previous import_pcm (the filter's history and the position are
+        kept); otherwise the streams start afresh.  flush=True appends the filter's delay W = import_pcm_delay(rate,
+        out_rate) of zero frames, so that the tail of the input comes out.  Synchronises torch's current stream before and
+        the library's after."""
+        import torch
+        device = torch.device("cuda", self.device)
+        if layout not in _PCM_LAYOUTS:
+            raise ValueError(f"unknown layout {layout!r}: 'interleaved' or 'planar'")
+        if isinstance(pcm, np.ndarray):
+            pcm = torch.from_numpy(np.ascontiguousarray(pcm, dtype=np.int16)).to(device)
+        if not isinstance(pcm, torch.Tensor) or pcm.dtype != torch.int16 or pcm.device != device or pcm.dim() not in (2, 3):
+            raise ValueError(f"pcm must be int16 [n, frames] or [n, frames, channels] on {device} (or a NumPy array)")
+        if pcm.dim() == 2:
+            pcm = pcm.unsqueeze(2 if layout == "interleaved" else 1)
+        n = int(pcm.shape[0])
+        frames, channels = (int(pcm.shape[1]), int(pcm.shape[2])) if layout == "interleaved" else (int(pcm.shape[2]), int(pcm.shape[1]))
+        W = import_pcm_delay(rate, out_rate)
+        if W < 0 or not 1 <= channels <= 8 or n < 1:
+            raise ValueError("rate, out_rate or the channel count out of range")
+        if flush and W:
+            pcm = torch.cat([pcm, torch.zeros((n, W, channels) if layout == "interleaved" else (n, channels, W), dtype=torch.int16,
+                                              device=device)], dim=1 if layout == "interleaved" else 2)
+            frames += W
+        if frames < 1:
+            raise ValueError("no input frames")
+        key = (n, rate, out_rate, channels)
+        st = getattr(self, "_import_pcm_state", None)
+        if not cont or st is None or st[0] != key:
+            if cont:
+                raise EfxError(-5, "import_pcm: cont without a previous import_pcm of as many streams, channels and the same rates")
+            st = (key, torch.zeros((n, import_pcm_state_bytes()), dtype=torch.uint8, device=device), 0)
+        _, state, first_in = st
+        r8 = lambda v: (v + 7) // 8 * 8
+        src_stride = r8(frames * channels)
+        src = pcm.contiguous().view(n, frames * channels)
+        if src_stride != frames * channels or src.data_ptr() % 16:
+            padded = torch.zeros((n, src_stride), dtype=torch.int16, device=device)
+            padded[:, :frames * channels] = src
+            src = padded
+        n_out = import_pcm_out_samples(rate, out_rate, first_in, frames)
+        if n_out < 0:
+            raise ValueError("too many frames for one call")
+        dst_stride = r8(max(n_out, 1))
+        out = torch.zeros((n, dst_stride), dtype=torch.int16, device=device)
+        torch.cuda.current_stream(device).synchronize()
+        self.import_pcm_to(src.data_ptr(), state.data_ptr(), out.data_ptr(), n_streams=n, n_in=frames, in_rate=rate,
+                           out_rate=out_rate, channels=channels, layout=_PCM_LAYOUTS[layout], weights=weights, first_in=first_in,
+                           src_stride=src_stride, dst_stride=dst_stride)
+        self.sync()
+        self._import_pcm_state = (key, state, first_in + frames)
+        return out[:, :n_out]
+
     # -- SBC encode (efx_sbc_encode) and A/V multiplexing (efx_mux_av) ------------------------------
     def sbc_encode_to(self, pcm: DeviceBuffer | int, state: DeviceBuffer | int, frames: DeviceBuffer | int, *, n_streams: int,
                       n_frames: int, blocks: int = 16, mode: int = 0, allocation: int = 0, bitpool: int = 28, frequency: int = 3,
@@ -1053,18 +1171,44 @@ class Decoder:
 
     def encode_av(self, pictures, pcm, *, qscale: int = 8, gop: int = 12, search: int = 7, first_pts: int = 0, blocks: int = 16,
                   allocation: int = 0, bitpool: int = 28, frequency: int = 3, sample_rate: int = 48000, frames_per_pes: int = 8,
-                  audio_pid: int = 0x101, bitrate: int | None = None, vbv_bits: int = 250_000, qmin: int = 3, qmax: int = 31):
+                  audio_pid: int = 0x101, bitrate: int | None = None, vbv_bits: int = 250_000, qmin: int = 3, qmax: int = 31,
+                  pcm_rate: int | None = None, pcm_layout: str = "interleaved"):
         """Pictures + PCM -> complete titles: encode (transport streams) -> sbc_encode (mono) -> mux, queued back to back on
         the library's stream with nothing synchronised in between.  pictures: (n, P, 101376) I420 as for encode(); pcm: int16
         [n, samples], a whole number of frames of blocks x 8 samples; the audio starts at the first picture's PTS.  Every
         stream starts afresh.  Returns (titles: list of bytes, status: uint32 array of ENCODE_* | MUX_* bits).
 
         bitrate: rate control of the video leg only, as for encode(): the rate and the buffer model cover the video PID's
-        packets; the audio packets the multiplexer adds are outside the model."""
+        packets; the audio packets the multiplexer adds are outside the model.
+
+        pcm_rate: the PCM is source audio at this rate, [n, frames] or [n, frames, channels] ([n, channels, frames] with
+        pcm_layout="planar"): it goes through import_pcm_to (equal downmix weights) into a device buffer zero-padded to whole
+        SBC frames, queued in front of sbc_encode_to with nothing synchronised in between.  The output rate is sample_rate
+        (16000, 32000, 44100 or 48000) and `frequency` follows it.  The resampler's delay (16 output samples, 0.33 ms at
+        48 kHz) is not compensated."""
         import torch
         device = torch.device("cuda", self.device)
         to_dev = lambda t, dt: torch.from_numpy(np.ascontiguousarray(t)).to(device) if isinstance(t, np.ndarray) else t
         pictures, pcm = to_dev(pictures, np.uint8), to_dev(pcm, np.int16)
+        imp = None
+        if pcm_rate is not None:
+            if pcm_layout not in _PCM_LAYOUTS or sample_rate not in _SBC_FREQUENCY or import_pcm_delay(pcm_rate, sample_rate) < 0:
+                raise ValueError("pcm_layout, pcm_rate or sample_rate out of range (efx_import_pcm)")
+            if pcm.dtype != torch.int16 or pcm.dim() not in (2, 3) or pcm.device != device:
+                raise ValueError(f"pcm must be int16 [n, frames] or [n, frames, channels] on {device}")
+            if pcm.dim() == 2:
+                pcm = pcm.unsqueeze(2 if pcm_layout == "interleaved" else 1)
+            in_frames, in_ch = (int(pcm.shape[1]), int(pcm.shape[2])) if pcm_layout == "interleaved" else (int(pcm.shape[2]), int(pcm.shape[1]))
+            n_out = import_pcm_out_samples(pcm_rate, sample_rate, 0, in_frames)
+            if in_frames < 1 or not 1 <= in_ch <= 8 or n_out < 0:
+                raise ValueError("pcm: no frames, too many frames or more than 8 channels")
+            src_stride = (in_frames * in_ch + 7) // 8 * 8
+            src = torch.zeros((int(pcm.shape[0]), src_stride), dtype=torch.int16, device=device)
+            src[:, :in_frames * in_ch] = pcm.contiguous().view(int(pcm.shape[0]), -1)
+            frequency = _SBC_FREQUENCY[sample_rate]
+            # the resampled stream, zero-padded to whole frames: what sbc_encode_to reads
+            pcm = torch.zeros((int(pcm.shape[0]), -(-n_out // (blocks * 8)) * blocks * 8), dtype=torch.int16, device=device)
+            imp = (src, in_frames, in_ch, src_stride)
         if pictures.dtype != torch.uint8 or pictures.dim() != 3 or pictures.shape[-1] != FRAME_BYTES or pictures.device != device:
             raise ValueError(f"pictures must be uint8 (n, P, {FRAME_BYTES}) on {device}")
         n, P = int(pictures.shape[0]), int(pictures.shape[1])
@@ -1083,11 +1227,19 @@ class Decoder:
             d_meta, d_state = DeviceBuffer(self, 4 * r16(4 * n)), DeviceBuffer(self, n * sbc_enc_state_bytes())
             bufs += [d_v, d_a, d_dst, d_meta, d_state]
             d_state.upload(np.zeros(n * sbc_enc_state_bytes(), dtype=np.uint8))
+            if imp is not None:
+                d_istate = DeviceBuffer(self, n * import_pcm_state_bytes())
+                bufs.append(d_istate)
+                d_istate.upload(np.zeros(n * import_pcm_state_bytes(), dtype=np.uint8))
             p_vlen, p_vst, p_len, p_st = (d_meta.ptr + k * r16(4 * n) for k in range(4))
             torch.cuda.current_stream(device).synchronize()
             self.encode_to(pictures.data_ptr(), d_v, p_vlen, p_vst, n_streams=n, n_pictures=P, qscale=qscale, gop=gop, search=search,
                            fmt=FORMAT_TS, first_pts=first_pts, dst_stride=v_stride, bitrate=bitrate, vbv_bits=vbv_bits, qmin=qmin,
                            qmax=qmax)
+            if imp is not None:
+                self.import_pcm_to(imp[0].data_ptr(), d_istate, pcm.data_ptr(), n_streams=n, n_in=imp[1], in_rate=pcm_rate,
+                                   out_rate=sample_rate, channels=imp[2], layout=_PCM_LAYOUTS[pcm_layout], src_stride=imp[3],
+                                   dst_stride=int(pcm.shape[1]))
             if n_frames:
                 self.sbc_encode_to(pcm.data_ptr(), d_state, d_a, n_streams=n, n_frames=n_frames, blocks=blocks, mode=0,
                                    allocation=allocation, bitpool=bitpool, frequency=frequency, pcm_stride=int(pcm.shape[1]),

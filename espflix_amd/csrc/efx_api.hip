@@ -56,6 +56,8 @@ template <int FMT, int CHROMA>
 __global__ void k_export(const uint8_t*, int, ExportArgs);  // (k_export.hip: the five (format, chroma) instances)
 __global__ void k_import_taps(ImportTap*, ImportArgs);  // (k_import.hip)
 __global__ void k_import(const uint8_t*, uint8_t*, const ImportTap*, ImportArgs);
+__global__ void k_import_pcm(ImportPcmArgs);  // (k_import_pcm.hip)
+__global__ void k_import_pcm_state(ImportPcmArgs);
 __global__ void k_enc_begin(EncArgs);
 __global__ void k_enc_act(EncArgs);
 __global__ void k_enc_rows(EncArgs);
@@ -235,6 +237,7 @@ struct efx_ctx {
     uint32_t* d_mux_before = nullptr;            // efx_mux_av's scratch: per (stream, audio PES) the video packets in front of it
     size_t mux_before_cap = 0;
     ImportTap* d_import_taps = nullptr;          // efx_import_frames' tap table: written and read on the device, in stream order
+    int32_t* d_import_pcm_table = nullptr;       // efx_import_pcm's prototype filter (import_pcm.h, efx_tables.cpp)
     int parse_wg_cap = 0;  // k_parse workgroups resident per parse kernel while reconstruction launches are queued (0: no cap); EFX_PARSE_WG_CAP
     // launch structure (efx_set_option; the environment variables of the same names, upper case with EFX_, set the defaults)
     int opt_groups = 0;        // reconstruction groups per call: 0 = one group behind a busy reconstruction stream, groups of
@@ -626,6 +629,7 @@ int efx_create(const efx_config* cfg, efx_ctx** out)
     A(dalloc(&ctx->d_sbc_tables, 1));
     A(dalloc(&ctx->d_sbc_enc_tables, 1));
     A(dalloc(&ctx->d_import_taps, kImportTapRows));
+    A(dalloc(&ctx->d_import_pcm_table, ipcm::kTableLen));
     if (e != hipSuccess) {
         fprintf(stderr, "efx_create: %s\n", hipGetErrorString(e));
         return bail(EFX_ERR_DEVICE);
@@ -684,6 +688,11 @@ int efx_create(const efx_config* cfg, efx_ctx** out)
         sbcenc::build_tables(&et);
         A(hipMemcpy(ctx->d_sbc_enc_tables, &et, sizeof(et), hipMemcpyHostToDevice));
     }
+    {
+        std::vector<int32_t> pt(ipcm::kTableLen);
+        build_import_pcm_table(pt.data());
+        A(hipMemcpy(ctx->d_import_pcm_table, pt.data(), pt.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
     A(hipMemset(ctx->d_frames, 0, n * D * kFrameBytes));
     for (auto& sl : ctx->slot) {
         A(hipMemset(sl.d_mbrecs, 0, n * P * kMbCount * sizeof(MbRec)));
@@ -723,7 +732,7 @@ void efx_destroy(efx_ctx* ctx)
     void* bufs[] = {ctx->d_tables, ctx->d_tm_tables, ctx->d_sbc_flags, ctx->d_sbc_next, ctx->d_sbc_info, ctx->d_sbc_plan, ctx->d_sbc_extra, ctx->d_sbc_cover, ctx->d_state, ctx->d_frames, ctx->d_video[0],  ctx->d_video[1], ctx->d_video_lines[0],
                     ctx->d_video_lines[1], ctx->d_hash, ctx->d_ts, ctx->d_demux_chunks, ctx->d_sbc_tables, ctx->d_idx_info, ctx->d_ts_off, ctx->d_idx_len,
                     ctx->d_idx_base, ctx->d_idx_seq, ctx->d_enc_state, ctx->d_enc_pics, ctx->d_enc_slices, ctx->d_enc_slice_len,
-                    ctx->d_enc_act, ctx->d_enc_tables, ctx->d_sbc_enc_tables, ctx->d_mux_before, ctx->d_import_taps};
+                    ctx->d_enc_act, ctx->d_enc_tables, ctx->d_sbc_enc_tables, ctx->d_mux_before, ctx->d_import_taps, ctx->d_import_pcm_table};
     if (ctx->h_enc_full)
         (void)hipHostFree(ctx->h_enc_full);
     for (auto& te : ctx->timing_ring)
@@ -2407,6 +2416,93 @@ int efx_sbc_encode(efx_ctx* ctx, const efx_sbc_encode_opts* o, const int16_t* pc
     const dim3 grid((unsigned)std::min(a.n_groups, 1 << 20), (unsigned)std::min(a.n_streams, 65535));
     hipLaunchKernelGGL(k_sbc_enc, grid, dim3(256), 0, ctx->stream, a);
     hipLaunchKernelGGL(k_sbc_enc_state, dim3((unsigned)a.n_streams), dim3(192), 0, ctx->stream, a);
+    EFX_HIP(hipGetLastError());
+    return EFX_OK;
+}
+
+// ---- sound in (k_import_pcm.hip) ------------------------------------------------------------------------------------------------
+static bool import_pcm_rates_ok(int in_rate, int out_rate)
+{
+    if (out_rate != 16000 && out_rate != 32000 && out_rate != 44100 && out_rate != 48000)
+        return false;
+    return in_rate >= ipcm::kMinRate && in_rate <= ipcm::kMaxRate && in_rate <= ipcm::kMaxRatio * out_rate;
+}
+
+int efx_import_pcm_out_samples(int in_rate, int out_rate, int64_t first_in, int n_in)
+{
+    if (!import_pcm_rates_ok(in_rate, out_rate) || first_in < 0 || first_in >= ipcm::kMaxFirstIn || n_in < 0)
+        return -1;
+    const int64_t n = ipcm::out_samples(in_rate, out_rate, first_in, n_in);
+    return n > 0x7FFFFFFF ? -1 : (int)n;
+}
+
+int efx_import_pcm_delay(int in_rate, int out_rate)
+{
+    return import_pcm_rates_ok(in_rate, out_rate) ? ipcm::delay(in_rate, out_rate) : -1;
+}
+
+size_t efx_import_pcm_state_bytes(void) { return ipcm::kStateBytes; }
+
+int efx_import_pcm_filter(int32_t* out, int cap)
+{
+    if (out && cap > 0) {
+        std::vector<int32_t> t(ipcm::kTableLen);
+        build_import_pcm_table(t.data());
+        std::copy(t.begin(), t.begin() + std::min(cap, ipcm::kTableLen), out);
+    }
+    return ipcm::kTableLen;
+}
+
+int efx_import_pcm(efx_ctx* ctx, const efx_import_pcm_opts* o, const int16_t* src_device, void* state_device, int16_t* dst_device)
+{
+    bind_device(ctx);
+    if (!ctx || !o)
+        return EFX_ERR_ARG;
+    auto misaligned = [](const void* p) { return !p || ((uintptr_t)p & 15); };
+    if (o->n_streams < 1 || o->n_streams > ctx->cfg.max_streams)
+        return fail(ctx, EFX_ERR_ARG, "efx_import_pcm: n_streams outside 1 .. max_streams");
+    if (!import_pcm_rates_ok(o->in_rate, o->out_rate))
+        return fail(ctx, EFX_ERR_ARG, "efx_import_pcm: out_rate must be 16000, 32000, 44100 or 48000, in_rate 8000 .. 192000 and at most 4 x out_rate");
+    if (o->channels < 1 || o->channels > ipcm::kMaxChannels)
+        return fail(ctx, EFX_ERR_ARG, "efx_import_pcm: channels outside 1 .. 8");
+    if (o->n_in < 1 || (long long)o->n_in * o->channels >= (1ll << 31))
+        return fail(ctx, EFX_ERR_ARG, "efx_import_pcm: n_in must be >= 1 and n_in x channels below 2^31");
+    if (o->layout != EFX_PCM_INTERLEAVED && o->layout != EFX_PCM_PLANAR)
+        return fail(ctx, EFX_ERR_ARG, "efx_import_pcm: layout must be EFX_PCM_INTERLEAVED or EFX_PCM_PLANAR");
+    long long wsum = 0;
+    for (int c = 0; c < o->channels; c++)
+        wsum += std::llabs((long long)o->mix_q15[c]);
+    if (wsum > 32768)
+        return fail(ctx, EFX_ERR_ARG, "efx_import_pcm: the downmix weights' absolute values sum to more than 32768");
+    if (o->first_in < 0 || o->first_in >= ipcm::kMaxFirstIn)
+        return fail(ctx, EFX_ERR_ARG, "efx_import_pcm: first_in outside 0 .. 2^40 - 1");
+    const int64_t n_out = ipcm::out_samples(o->in_rate, o->out_rate, o->first_in, o->n_in);
+    if (n_out > 0x7FFFFFFF)
+        return fail(ctx, EFX_ERR_ARG, "efx_import_pcm: more than 2^31 - 1 output samples in one call");
+    if (o->src_stride < (size_t)o->n_in * o->channels || (o->src_stride & 7))
+        return fail(ctx, EFX_ERR_ARG, "efx_import_pcm: src_stride must be a multiple of 8 and hold n_in x channels elements");
+    if (o->dst_stride < (size_t)n_out || (o->dst_stride & 7))
+        return fail(ctx, EFX_ERR_ARG, "efx_import_pcm: dst_stride must be a multiple of 8 and hold the call's output samples");
+    const bool equal = o->in_rate == o->out_rate;
+    if (misaligned(src_device) || misaligned(dst_device) || (equal ? ((uintptr_t)state_device & 15) != 0 : misaligned(state_device)))
+        return fail(ctx, EFX_ERR_ARG, "efx_import_pcm: src, state and dst must be 16-byte aligned device pointers");
+    ImportPcmArgs a{};
+    a.src = src_device;
+    a.state = equal ? nullptr : static_cast<int16_t*>(state_device);
+    a.dst = dst_device;
+    a.table = ctx->d_import_pcm_table;
+    a.src_stride = o->src_stride;
+    a.dst_stride = o->dst_stride;
+    a.plan = ipcm::plan(o->in_rate, o->out_rate, o->channels, o->layout, o->mix_q15, o->first_in, o->n_in);
+    if (n_out > 0) {
+        // a stream's tiles go round robin over grid.y workgroups, which copy the table into LDS once each: enough
+        // workgroups to fill the device, no more than there are tiles
+        const int tiles = (int)((n_out + ipcm::kTile - 1) / ipcm::kTile);
+        const int per_stream = std::max(1, std::min(tiles, (8 * ctx->n_cus + o->n_streams - 1) / o->n_streams));
+        hipLaunchKernelGGL(k_import_pcm, dim3((unsigned)o->n_streams, (unsigned)per_stream), dim3(256), 0, ctx->stream, a);
+    }
+    if (!equal)
+        hipLaunchKernelGGL(k_import_pcm_state, dim3((unsigned)o->n_streams), dim3(128), 0, ctx->stream, a);
     EFX_HIP(hipGetLastError());
     return EFX_OK;
 }

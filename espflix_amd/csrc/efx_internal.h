@@ -15,6 +15,7 @@
 #include <cstdint>
 
 #include "enc_rate.h"
+#include "import_pcm.h"
 
 namespace efx {
 
@@ -173,6 +174,16 @@ struct ImportArgs {
     int dst_x, dst_y, dst_w, dst_h;      // destination rectangle
     int full_range;
     size_t src_stride, dst_stride;
+};
+
+// k_import_pcm / k_import_pcm_state launch arguments (by value): efx_import_pcm_opts, checked, as import_pcm.h's plan
+struct ImportPcmArgs {
+    const int16_t* src;    // stream i at src + i * src_stride
+    int16_t* state;        // stream i: 128 int16 at state + i * 128 (k_import_pcm reads, k_import_pcm_state writes); null when the rates are equal
+    int16_t* dst;          // stream i's plan.n_out samples at dst + i * dst_stride
+    const int32_t* table;  // the prototype, ipcm::kTableLen entries
+    size_t src_stride, dst_stride;
+    ipcm::Plan plan;
 };
 
 // per-stream result of k_ts_sequences
@@ -344,6 +355,7 @@ struct MuxArgs {
 };
 
 void build_sbc_tables(SbcTables* t);
+void build_import_pcm_table(int32_t* T);  // ipcm::kTableLen entries
 void build_parse_tables(ParseTables* t);
 void build_video_tables(int ntsc, VideoTables* t);
 

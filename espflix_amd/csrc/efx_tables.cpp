@@ -9,10 +9,13 @@
 //    (video_init/pal_init/usec, video.cpp:554-630; LUT derivation gen_palettes,
 //    espflix.cpp:1091-1161).  tests/test_abi.py and tests/test_oracle_golden.py pin the values
 //    against the reference-derived goldens (geometry, colour LUT, zig-zag, pre-multipliers).
+//  * the resampler's prototype of efx_import_pcm (build_import_pcm_table, at the end): a Kaiser-windowed sinc in double,
+//    pinned by tests/golden/import_pcm_table.npy.
 #include <cmath>
 #include <cstring>
 
 #include "efx_internal.h"
+#include "import_pcm.h"
 #include "mpeg1_codebook.h"
 #include "sbc_proto.h"
 
@@ -408,6 +411,33 @@ void build_tm_tables(TmTables* t)
     t->e[kTbEscP + 1] = TmBuilder::make(1, 7, 128, 0, coef | kTmAdd, none, kWDct);
     t->e[kTbEscN + 0] = TmBuilder::make(1, 7, -256, 0, coef | kTmAdd, none, kWDct);
     t->e[kTbEscN + 1] = TmBuilder::make(1, 7, -128, 0, coef | kTmAdd, none, kWDct);
+}
+
+// efx_import_pcm's prototype filter (include/efx.h): T[i] = round(2^Q p(i / P)), i = 0 .. 16 P, with
+// p(u) = 0.97 sinc(0.97 u) I0(9 sqrt(1 - (u / 16)^2)) / I0(9) for |u| < 16 and p(16) = 0.  I0 by its power series
+// sum ((x / 2)^2k / (k!)^2) -- the terms fall below 2^-60 of the sum long before k = 64 for x <= 9 --, so sin() is the only
+// library function the table depends on.
+static double bessel_i0(double x)
+{
+    const double y = x * x / 4;
+    double term = 1, sum = 1;
+    for (int k = 1; k < 64; k++) {
+        term *= y / ((double)k * k);
+        sum += term;
+    }
+    return sum;
+}
+
+void build_import_pcm_table(int32_t* T)
+{
+    const double cutoff = 0.97, beta = 9.0, i0b = bessel_i0(beta);
+    for (int i = 0; i < ipcm::kTableLen - 1; i++) {
+        const double u = (double)i / ipcm::kP, x = M_PI * cutoff * u;
+        const double sinc = i == 0 ? 1.0 : std::sin(x) / x;
+        const double w = bessel_i0(beta * std::sqrt(1.0 - (u / ipcm::kHalf) * (u / ipcm::kHalf))) / i0b;
+        T[i] = (int32_t)std::floor((double)(1 << ipcm::kQ) * cutoff * sinc * w + 0.5);
+    }
+    T[ipcm::kTableLen - 1] = 0;
 }
 
 }  // namespace efx

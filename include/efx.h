@@ -568,6 +568,77 @@ size_t efx_sbc_enc_state_bytes(void);
 int efx_sbc_encode(efx_ctx* ctx, const efx_sbc_encode_opts* opts, const int16_t* pcm_device, void* state_device,
                    uint8_t* frames_device);
 
+/* -- sound in: PCM of any rate and channel count to the SBC rates, mono (k_import_pcm) ------ */
+/* efx_sbc_encode and the player want 48 kHz mono int16 (src/video.cpp:953-987); source audio is 44.1 kHz stereo, 48 kHz
+ * 5.1 or 96 kHz.  efx_import_pcm is the `-ar 48000 -ac 1` of the reference indexer's ffmpeg line
+ * (indexer/indexer.cpp:307) on the device: it downmixes 1 .. 8 channels to one and resamples 8 .. 192 kHz to one of the
+ * SBC header's four rates, for n_streams streams at once, in pieces of any length.
+ *
+ * Meaning.  With r = in_rate and o = out_rate a stream that has taken N input frames in total has produced
+ * ceil(N o / r) output samples, so a call writes ceil((first_in + n_in) o / r) - ceil(first_in o / r) samples per stream
+ * (efx_import_pcm_out_samples; possibly 0), at dst + i * dst_stride.  Calls with first_in carried on (first_in += n_in,
+ * the same state) give the samples of one long call.  Output n sits at input time n r / o - W, W = efx_import_pcm_delay
+ * input frames (16 / out_rate seconds when r <= o: 0.33 ms at 48 kHz): the filter is causal, the tail comes out when the
+ * caller feeds W zero frames.  Nothing compensates the delay.
+ *
+ * The arithmetic (espflix_amd/csrc/import_pcm.h) is an integer function of the source bytes, bit-reproducible anywhere;
+ * >> is arithmetic, div and mod are those of non-negative operands, clamp16 clamps to -32768 .. 32767.
+ *   Downmix.  m[j] = clamp16((sum over c of w[c] x[j][c] + 16384) >> 15), w = mix_q15, or floor(32768 / channels) each
+ *   when all eight are zero.  sum |w| <= 32768, so the sum fits 32 bits.
+ *   r == o.  y[n] = m[n]: no filter, no delay, the state is neither read nor written.
+ *   Otherwise the prototype is the default design of ffmpeg's resampler, which is what the indexer's line runs: 32 taps
+ *   at ratios >= 1, a Kaiser window of beta 9, cutoff 0.97:
+ *     p(u) = 0.97 sinc(0.97 u) I0(9 sqrt(1 - (u / 16)^2)) / I0(9) for |u| < 16, 0 from there on   (sinc(x) = sin(pi x) / (pi x))
+ *   tabulated as T[i] = round(2^Q p(i / P)), i = 0 .. 16 P (T[16 P] = 0), with P = 512 and Q = 22 (efx_import_pcm_filter).
+ *   M = max(r, o), W = ceil(16 M / o) (<= 64 because r <= 4 o).  For output n: a = n r, fl = a div o, and the taps are
+ *   j = fl - 2W + 1 .. fl; m[j] of a fresh stream is 0 for j < 0.  For each tap
+ *     e = |j o - a + W o|,  q = (e P) div M,  rho = (e P) mod M;   k = 0 when q >= 16 P, else
+ *     f = (rho 4096) div M,  k = T[q] + (((T[q + 1] - T[q]) f) >> 12)
+ *   acc = sum of k m[j] in 64 bits; when r > o the filter is M / o times as wide and acc = floor(acc o / r);
+ *     y[n] = clamp16((acc + 2^(Q - 1)) >> Q)
+ *   (the largest sum of |k| over the phases is 2.28 x 2^Q: hence the clamp).  e grows by o from tap to tap, so
+ *   (e P 4096) div M = 4096 q + f steps with a carry: no division per tap.
+ *
+ * State.  efx_import_pcm_state_bytes() = 256 bytes per stream, 16-byte aligned: the 127 newest mixed samples m[first_in -
+ * 127 .. first_in - 1] as int16 and one zero; 2W - 1 <= 127 of them are the history the next call's taps reach.  All zero
+ * = a fresh stream.
+ *
+ * Memory contract.  For stream i the kernels read only the n_in x channels int16 elements from src + i * src_stride, in
+ * 16-byte pieces aligned down inside that interval (a last piece that would end behind it is read element by element),
+ * and write only the call's output samples of stream i.  src_device, state_device and dst_device are 16-byte aligned, the
+ * strides are multiples of 8 elements. */
+#define EFX_PCM_PLANAR 2  /* efx_import_pcm: channel c of a call's n_in frames at + c * n_in elements */
+typedef struct efx_import_pcm_opts {
+    int n_streams;        /* 1 .. max_streams */
+    int n_in;             /* input sample frames per stream in this call, >= 1; n_in x channels < 2^31 */
+    int in_rate;          /* Hz, 8000 .. 192000, and in_rate <= 4 * out_rate */
+    int out_rate;         /* 16000, 32000, 44100 or 48000 (the SBC header's four) */
+    int channels;         /* 1 .. 8 */
+    int layout;           /* EFX_PCM_INTERLEAVED: frames of `channels` samples; EFX_PCM_PLANAR: channel c at + c * n_in elements */
+    int mix_q15[8];       /* downmix weights; all zero = floor(32768 / channels) each; sum of |w| over the channels <= 32768 */
+    int64_t first_in;     /* index in the stream of this call's first input frame (0 on a fresh stream), 0 .. 2^40 - 1 */
+    size_t src_stride;    /* int16 elements between streams, >= n_in * channels, multiple of 8 */
+    size_t dst_stride;    /* int16 elements between streams, >= the call's output count, multiple of 8 */
+} efx_import_pcm_opts;
+/* Asynchronous on the context's stream: no host synchronisation, at most two launches whatever the counts (the outputs;
+ * the hand-over of the history, a launch of its own because the last tile must not overwrite what the first still reads;
+ * none for a call without output samples, one when the rates are equal), so calls with different rates may be queued
+ * back to back.  No decoder, encoder or SBC state is touched.  state_device may be NULL when the rates are equal.
+ * EFX_ERR_ARG: a field out of range, n_in x channels >= 2^31, in_rate > 4 out_rate, an out_rate that is not one of the
+ * four, an unknown layout, sum |w| > 32768, first_in negative or >= 2^40, a NULL or misaligned (16 bytes) pointer, a stride
+ * that is too small or not a multiple of 8. */
+int efx_import_pcm(efx_ctx* ctx, const efx_import_pcm_opts* opts, const int16_t* src_device, void* state_device,
+                   int16_t* dst_device);
+/* ceil((first_in + n_in) o / r) - ceil(first_in o / r); -1 for rates, a first_in or an n_in (< 0) that efx_import_pcm
+ * rejects or a count above 2^31 - 1.  Host only. */
+int efx_import_pcm_out_samples(int in_rate, int out_rate, int64_t first_in, int n_in);
+/* W, in input frames; 0 when the rates are equal; -1 for rates efx_import_pcm rejects.  Host only. */
+int efx_import_pcm_delay(int in_rate, int out_rate);
+/* 256.  Host only. */
+size_t efx_import_pcm_state_bytes(void);
+/* The table T: copies min(cap, length) entries to out (may be NULL with cap 0) and returns the length, 16 P + 1.  Host only. */
+int efx_import_pcm_filter(int32_t* out, int cap);
+
 /* -- A/V multiplexer: video transport stream + SBC frames -> a title (espflix_amd/csrc/k_mux.hip) -- */
 /* The reference player takes its audio from PES packets on PID 0x101 / 0x102 of the transport stream that carries the
  * video on PID 0x100 (MpegDecoder::demux, src/player.cpp:421-433).  Output, byte for byte (tests/mux_model.py restates it):
