@@ -93,6 +93,12 @@ class _ImportOpts(C.Structure):
                [("src_stride", C.c_size_t), ("dst_stride", C.c_size_t)]
 
 
+class _CropOpts(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("n_streams", "images_per_stream", "format", "width", "height", "full_range", "limit",
+                                       "round")] + \
+               [("src_stride", C.c_size_t), ("sums_stride", C.c_size_t)]
+
+
 class _EncodeOpts(C.Structure):
     _fields_ = [("n_streams", C.c_int), ("n_pictures", C.c_int), ("format", C.c_int), ("qscale", C.c_int), ("gop", C.c_int),
                 ("search", C.c_int), ("cont", C.c_int), ("first_pts", C.c_int64), ("src_stride", C.c_size_t),
@@ -184,6 +190,7 @@ _SYMBOLS = {
     "efx_export_frames": (C.c_int, [_P, C.POINTER(_ExportOpts), _P]),
     "efx_import_src_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "efx_import_frames": (C.c_int, [_P, C.POINTER(_ImportOpts), _P, _P]),
+    "efx_detect_crop": (C.c_int, [_P, C.POINTER(_CropOpts), _P, _P, _P]),
     "efx_encode": (C.c_int, [_P, C.POINTER(_EncodeOpts), _P, _P, _P, _P, _P]),
     "efx_encode_rc": (C.c_int, [_P, C.POINTER(_EncodeOpts), C.POINTER(_EncodeRate), _P, _P, _P, _P, _P, _P]),
     "efx_encode_bound": (C.c_size_t, [C.c_int, C.c_int]),
@@ -321,6 +328,24 @@ def letterbox_rect(width: int, height: int):
     else:
         w, h = max(16, (FRAME_HEIGHT * width // height) & ~1), FRAME_HEIGHT
     return ((FRAME_WIDTH - w) // 2) & ~1, ((FRAME_HEIGHT - h) // 2) & ~1, w, h
+
+
+def cover_crop(width: int, height: int, region=None):
+    """The crop (x, y, w, h) of fit="cover": the largest centred rectangle of the frame's 11 : 6 shape inside region =
+    (x, y, w, h) of a width x height picture (None: the whole picture).  Integer rule: where w * 192 >= h * 352 the
+    height stays and w' = floor(h * 352 / 192) rounded down to even, otherwise the width stays and h' =
+    floor(w * 192 / 352) rounded down to even; x' = x + (((w - w') >> 1) & ~1), and y' likewise: an even step from the
+    region's corner, centred to within one.  cover_crop(1280, 546) == (140, 0, 1000, 546).  Host only."""
+    x, y, w, h = region or (0, 0, width, height)
+    if w < 1 or h < 1 or x < 0 or y < 0 or x + w > width or y + h > height:
+        raise ValueError(f"region {(x, y, w, h)} is not a rectangle of a {width} x {height} picture")
+    if w * FRAME_HEIGHT >= h * FRAME_WIDTH:
+        cw, ch = (h * FRAME_WIDTH // FRAME_HEIGHT) & ~1, h
+    else:
+        cw, ch = w, (w * FRAME_HEIGHT // FRAME_WIDTH) & ~1
+    if cw < 1 or ch < 1:
+        raise ValueError(f"region {(x, y, w, h)} is too thin for a rectangle of the frame's shape")
+    return x + (((w - cw) >> 1) & ~1), y + (((h - ch) >> 1) & ~1), cw, ch
 
 
 def _import_geometry(shape, fmt, width, height):
@@ -727,16 +752,105 @@ class Decoder:
                         1 if full_range else 0, src_stride, dst_stride)
         _check(self._ctx, self._lib.efx_import_frames(self._ctx, C.byref(o), g(src), g(dst)))
 
+    def _stage_pictures(self, src, n: int, image: int, stride: int, bufs: list, keep: list):
+        """The source of import_pictures / detect_crop in device memory, image i at + i * stride: (pointer, array input?,
+        must the caller synchronise before it returns?).  An array is uploaded into a DeviceBuffer appended to bufs (the
+        caller frees it after a sync); a tensor is used in place when it is packed and aligned, else copied; it is
+        appended to keep, and torch's current stream is synchronised first unless it is the decoder's."""
+        if isinstance(src, np.ndarray):
+            host = np.zeros((n, stride), dtype=np.uint8)
+            host[:, :image] = np.ascontiguousarray(src, dtype=np.uint8).reshape(n, image)
+            sbuf = DeviceBuffer(self, n * stride)
+            bufs.append(sbuf)
+            sbuf.upload(host)
+            return sbuf.ptr, True, False
+        import torch
+        device = torch.device("cuda", self.device)
+        if not isinstance(src, torch.Tensor) or src.dtype != torch.uint8 or src.device != device:
+            raise ValueError(f"src must be a uint8 tensor on {device} (or a NumPy array)")
+        flat = src.contiguous()
+        if stride != image or flat.data_ptr() % 16:
+            padded = torch.zeros((n, stride), dtype=torch.uint8, device=device)
+            padded[:, :image] = flat.view(n, image)
+            flat = padded
+        keep.append(flat)
+        must_sync = False
+        cur = torch.cuda.current_stream(device)
+        if not self.hip_stream or cur.cuda_stream != self.hip_stream:
+            cur.synchronize()
+            must_sync = flat is not src  # (torch may hand a staging copy's memory out again on its own stream)
+        return flat.data_ptr(), False, must_sync
+
+    # -- black borders (efx_detect_crop) ----------------------------------------------------
+    def detect_crop_to(self, src: DeviceBuffer | int, rects: DeviceBuffer | int, *, n_streams: int, images_per_stream: int,
+                       fmt: str, width: int, height: int, limit: int = 24, round: int = 16, full_range: bool = False,
+                       src_stride: int = 0, sums: DeviceBuffer | int | None = None, sums_stride: int = 0):
+        """efx_detect_crop on raw device memory (DeviceBuffers or pointers), asynchronous on the library's stream: source
+        image k (fmt "i420", "rgb24" or "rgbp", width x height) at src + k * src_stride (0 = import_src_bytes() rounded
+        up to 16) belongs to stream k // images_per_stream; stream i's record of eight int32 (x, y, w, h, x1, y1, x2,
+        y2; the definition: include/efx.h) goes to rects + 32 i.  sums: when given, receives per image the height row
+        sums and the width column sums (uint32), image k at + 4 * k * sums_stride bytes (0 = height + width rounded up
+        to 4)."""
+        if fmt not in _PIX_FORMATS:
+            raise ValueError(f"unknown format {fmt!r}: one of {sorted(_PIX_FORMATS)}")
+        g = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
+        o = _CropOpts(n_streams, images_per_stream, _PIX_FORMATS[fmt], width, height, 1 if full_range else 0, limit, round,
+                      src_stride, sums_stride)
+        _check(self._ctx, self._lib.efx_detect_crop(self._ctx, C.byref(o), g(src), g(rects), g(sums)))
+
+    def detect_crop(self, src, *, fmt: str | None = None, width: int | None = None, height: int | None = None,
+                    images_per_stream: int | None = None, limit: int = 24, round: int = 16,
+                    full_range: bool = False) -> np.ndarray:
+        """The black borders of source pictures, found on the device (efx_detect_crop): an int32 array of shape
+        (n_streams, 8) with x, y, w, h -- the crop for import_pictures(crop=...) -- and the bounds x1, y1, x2, y2 of the
+        detected picture (inclusive; x2 < x1: every image was black, the crop is the whole picture).  src as
+        import_pictures takes it (arrays and tensors, fmt / width / height likewise).  Every images_per_stream
+        consecutive images form a stream with one rectangle, the union of its images; None: all images are one stream.
+        A row or column is picture when its mean luma exceeds limit (for RGB sources the luma import_pictures would
+        write with this full_range); the rectangle's sides are multiples of round where there is room, even otherwise.
+        Waits for the result."""
+        fmt, n, width, height = _import_geometry(src.shape, fmt, width, height)
+        image = import_src_bytes(fmt, width, height)
+        if not image or n < 1:
+            raise ValueError(f"{fmt} pictures of {width} x {height} cannot be read (2 .. 4096, i420: even; n >= 1)")
+        per = n if images_per_stream is None else images_per_stream
+        if per < 1 or n % per:
+            raise ValueError(f"images_per_stream={images_per_stream} does not divide the {n} images")
+        stride = (image + 15) // 16 * 16
+        bufs, keep = [], []
+        try:
+            src_ptr, _, _ = self._stage_pictures(src, n, image, stride, bufs, keep)
+            return self._detect_rects(src_ptr, n // per, per, fmt, width, height, limit, round, full_range, stride)
+        finally:
+            for b in bufs:
+                b.free()
+
+    def _detect_rects(self, src_ptr, n_streams, per, fmt, width, height, limit, round, full_range, stride) -> np.ndarray:
+        rbuf = DeviceBuffer(self, 32 * n_streams)
+        try:
+            self.detect_crop_to(src_ptr, rbuf, n_streams=n_streams, images_per_stream=per, fmt=fmt, width=width, height=height,
+                                limit=limit, round=round, full_range=full_range, src_stride=stride)
+            self.sync()
+            return rbuf.download(np.int32, 8 * n_streams).reshape(n_streams, 8)
+        finally:
+            rbuf.free()
+
     def import_pictures(self, src, *, fmt: str | None = None, width: int | None = None, height: int | None = None, crop=None,
-                        fit: str = "stretch", full_range: bool = False, out=None, sync: bool = True):
+                        fit: str = "stretch", full_range: bool = False, out=None, sync: bool = True, crop_limit: int = 24,
+                        crop_round: int = 16):
         """Pictures of any size as (n, 101376) I420 pictures of 352 x 192, the layout encode() takes, cropped, scaled and
         converted on the device (efx_import_frames; the arithmetic: include/efx.h).  src: a NumPy array, or a uint8
         torch tensor on the decoder's device, of shape (n, H, W, 3) for "rgb24", (n, 3, H, W) for "rgbp", or
         (n, H * W * 3 // 2) for "i420" together with width= and height=; fmt=None infers the format from the shape (four
-        axes: rgb24 when the last one is 3, else rgbp; two axes: i420).  crop = (x, y, w, h) of the source.
-        fit="stretch" fills the frame; fit="letterbox" keeps the aspect ratio of the source (of the crop): the picture
-        goes into letterbox_rect(w, h), the largest centred rectangle of that ratio with even sides, and the rest of
-        the frame is black.  full_range: RGB sources only, False = BT.601 studio swing (what MPEG-1 carries).
+        axes: rgb24 when the last one is 3, else rgbp; two axes: i420).  crop = (x, y, w, h) of the source, or "auto":
+        the black borders of the call's images, taken as one stream, are found on the device (detect_crop with
+        limit=crop_limit, round=crop_round) and cut off; the 32-byte record is read back, which is one synchronisation
+        of the library's stream in front of the import.
+        fit="stretch" fills the frame; fit="letterbox" keeps the aspect ratio of the source (of the crop, given or
+        detected): the picture goes into letterbox_rect(w, h), the largest centred rectangle of that ratio with even
+        sides, and the rest of the frame is black; fit="cover" narrows the crop (given, detected or the whole picture)
+        to cover_crop(), the largest centred rectangle of the frame's shape inside it, and fills the frame with that.
+        full_range: RGB sources only, False = BT.601 studio swing (what MPEG-1 carries).
 
         Returns a tensor for tensor input and an array for array input.  out: a preallocated contiguous uint8 tensor
         of n * 101376 elements on this device, or a DeviceBuffer (then returned as is); with out given, array input
@@ -746,43 +860,28 @@ class Decoder:
         it is the decoder's stream (hip_stream=).  sync=True (default) waits for the import.  sync=False is only safe
         under the conditions export() names: the decoder lives on torch's current stream, or the caller calls sync()
         before using the result."""
-        if fit not in ("stretch", "letterbox"):
-            raise ValueError(f"unknown fit {fit!r}: 'stretch' or 'letterbox'")
+        if fit not in ("stretch", "letterbox", "cover"):
+            raise ValueError(f"unknown fit {fit!r}: 'stretch', 'letterbox' or 'cover'")
+        if isinstance(crop, str) and crop != "auto":
+            raise ValueError(f"unknown crop {crop!r}: a rectangle (x, y, w, h), None or 'auto'")
         fmt, n, width, height = _import_geometry(src.shape, fmt, width, height)
         image = import_src_bytes(fmt, width, height)
         if not image or n < 1:
             raise ValueError(f"{fmt} pictures of {width} x {height} cannot be imported (2 .. 4096, i420: even; n >= 1)")
         stride = (image + 15) // 16 * 16
-        rect = None
-        if fit == "letterbox":
-            rect = letterbox_rect(*(crop[2:] if crop else (width, height)))
         nbytes = n * FRAME_BYTES
         bufs, keep = [], []
         try:
-            is_array = isinstance(src, np.ndarray)
-            if is_array:
-                host = np.zeros((n, stride), dtype=np.uint8)
-                host[:, :image] = np.ascontiguousarray(src, dtype=np.uint8).reshape(n, image)
-                sbuf = DeviceBuffer(self, n * stride)
-                bufs.append(sbuf)
-                sbuf.upload(host)
-                src_ptr = sbuf.ptr
-            else:
-                import torch
-                device = torch.device("cuda", self.device)
-                if not isinstance(src, torch.Tensor) or src.dtype != torch.uint8 or src.device != device:
-                    raise ValueError(f"src must be a uint8 tensor on {device} (or a NumPy array)")
-                flat = src.contiguous()
-                if stride != image or flat.data_ptr() % 16:
-                    padded = torch.zeros((n, stride), dtype=torch.uint8, device=device)
-                    padded[:, :image] = flat.view(n, image)
-                    flat = padded
-                keep.append(flat)
-                cur = torch.cuda.current_stream(device)
-                if not self.hip_stream or cur.cuda_stream != self.hip_stream:
-                    cur.synchronize()
-                    sync = sync or flat is not src  # (torch may hand a staging copy's memory out again on its own stream)
-                src_ptr = flat.data_ptr()
+            src_ptr, is_array, must_sync = self._stage_pictures(src, n, image, stride, bufs, keep)
+            sync = sync or must_sync
+            if isinstance(crop, str):
+                rec = self._detect_rects(src_ptr, 1, n, fmt, width, height, crop_limit, crop_round, full_range, stride)
+                crop = tuple(int(v) for v in rec[0, :4])
+            if fit == "cover":
+                crop = cover_crop(width, height, crop)
+            rect = None
+            if fit == "letterbox":
+                rect = letterbox_rect(*(crop[2:] if crop else (width, height)))
             obuf = None
             if isinstance(out, DeviceBuffer):
                 if out.nbytes < nbytes:

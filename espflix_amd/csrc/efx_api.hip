@@ -20,6 +20,7 @@
 #include "efx_internal.h"
 #include "enc_core.h"
 #include "import_px.h"
+#include "crop_px.h"
 #include "parse_tm.h"
 #include "sbc_enc_core.h"
 
@@ -56,6 +57,11 @@ template <int FMT, int CHROMA>
 __global__ void k_export(const uint8_t*, int, ExportArgs);  // (k_export.hip: the five (format, chroma) instances)
 __global__ void k_import_taps(ImportTap*, ImportArgs);  // (k_import.hip)
 __global__ void k_import(const uint8_t*, uint8_t*, const ImportTap*, ImportArgs);
+__global__ void k_crop_zero(CropArgs);  // (k_cropdetect.hip)
+__global__ void k_crop_sums_i420(CropArgs);
+__global__ void k_crop_sums_rgb24(CropArgs);
+__global__ void k_crop_sums_rgbp(CropArgs);
+__global__ void k_crop_rects(CropArgs);
 __global__ void k_import_pcm(ImportPcmArgs);  // (k_import_pcm.hip)
 __global__ void k_import_pcm_state(ImportPcmArgs);
 __global__ void k_enc_begin(EncArgs);
@@ -238,6 +244,8 @@ struct efx_ctx {
     size_t mux_before_cap = 0;
     ImportTap* d_import_taps = nullptr;          // efx_import_frames' tap table: written and read on the device, in stream order
     int32_t* d_import_pcm_table = nullptr;       // efx_import_pcm's prototype filter (import_pcm.h, efx_tables.cpp)
+    uint32_t* d_crop_sums = nullptr;             // efx_detect_crop's row and column sums when the caller gives no buffer:
+    size_t crop_sums_cap = 0;                    // allocated at the first such call, regrown when a call needs more (elements)
     int parse_wg_cap = 0;  // k_parse workgroups resident per parse kernel while reconstruction launches are queued (0: no cap); EFX_PARSE_WG_CAP
     // launch structure (efx_set_option; the environment variables of the same names, upper case with EFX_, set the defaults)
     int opt_groups = 0;        // reconstruction groups per call: 0 = one group behind a busy reconstruction stream, groups of
@@ -732,7 +740,8 @@ void efx_destroy(efx_ctx* ctx)
     void* bufs[] = {ctx->d_tables, ctx->d_tm_tables, ctx->d_sbc_flags, ctx->d_sbc_next, ctx->d_sbc_info, ctx->d_sbc_plan, ctx->d_sbc_extra, ctx->d_sbc_cover, ctx->d_state, ctx->d_frames, ctx->d_video[0],  ctx->d_video[1], ctx->d_video_lines[0],
                     ctx->d_video_lines[1], ctx->d_hash, ctx->d_ts, ctx->d_demux_chunks, ctx->d_sbc_tables, ctx->d_idx_info, ctx->d_ts_off, ctx->d_idx_len,
                     ctx->d_idx_base, ctx->d_idx_seq, ctx->d_enc_state, ctx->d_enc_pics, ctx->d_enc_slices, ctx->d_enc_slice_len,
-                    ctx->d_enc_act, ctx->d_enc_tables, ctx->d_sbc_enc_tables, ctx->d_mux_before, ctx->d_import_taps, ctx->d_import_pcm_table};
+                    ctx->d_enc_act, ctx->d_enc_tables, ctx->d_sbc_enc_tables, ctx->d_mux_before, ctx->d_import_taps, ctx->d_import_pcm_table,
+                    ctx->d_crop_sums};
     if (ctx->h_enc_full)
         (void)hipHostFree(ctx->h_enc_full);
     for (auto& te : ctx->timing_ring)
@@ -1852,6 +1861,66 @@ int efx_import_frames(efx_ctx* ctx, const efx_import_opts* o, const void* src_de
     hipLaunchKernelGGL(k_import_taps, dim3((kImportTapRows + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_import_taps, a);
     hipLaunchKernelGGL(k_import, dim3((unsigned)o->n_images * kImportBands), dim3(256), 0, ctx->stream,
                        static_cast<const uint8_t*>(src_device), dst_device, ctx->d_import_taps, a);
+    EFX_HIP(hipGetLastError());
+    return EFX_OK;
+}
+
+// ---- black borders (k_cropdetect.hip) -------------------------------------------------------------------------------------------
+int efx_detect_crop(efx_ctx* ctx, const efx_crop_opts* o, const void* src_device, efx_crop_rect* rects_device, uint32_t* sums_device)
+{
+    bind_device(ctx);
+    if (!ctx || !o)
+        return EFX_ERR_ARG;
+    if (!src_device || ((uintptr_t)src_device & 15) || !rects_device || ((uintptr_t)rects_device & 15) || ((uintptr_t)sums_device & 15))
+        return fail(ctx, EFX_ERR_ARG, "efx_detect_crop: src_device, rects_device and sums_device (when given) must be 16-byte aligned device pointers");
+    const size_t image = efx_import_src_bytes(o->format, o->width, o->height);
+    if (!image)
+        return fail(ctx, EFX_ERR_ARG, "efx_detect_crop: unknown format, or width / height outside 2 .. 4096 (I420: even)");
+    if (o->n_streams < 1 || o->images_per_stream < 1 || (int64_t)o->n_streams * o->images_per_stream > INT32_MAX)
+        return fail(ctx, EFX_ERR_ARG, "efx_detect_crop: n_streams and images_per_stream must be >= 1, their product below 2^31");
+    if (o->limit < 0 || o->limit > 255)
+        return fail(ctx, EFX_ERR_ARG, "efx_detect_crop: limit outside 0 .. 255");
+    if (o->round < 2 || o->round > 64 || (o->round & 1))
+        return fail(ctx, EFX_ERR_ARG, "efx_detect_crop: round must be even, 2 .. 64");
+    CropArgs a{};
+    a.src = static_cast<const uint8_t*>(src_device);
+    a.rects = reinterpret_cast<int32_t*>(rects_device);
+    a.n_streams = o->n_streams;
+    a.images_per_stream = o->images_per_stream;
+    a.n_images = o->n_streams * o->images_per_stream;
+    a.format = o->format, a.width = o->width, a.height = o->height;
+    a.full_range = o->full_range ? 1 : 0;
+    a.limit = o->limit, a.round = o->round;
+    a.src_stride = o->src_stride ? o->src_stride : (image + 15) / 16 * 16;
+    a.sums_stride = o->sums_stride ? o->sums_stride : ((size_t)o->height + o->width + 3) / 4 * 4;
+    if (a.src_stride < image || (a.src_stride & 15))
+        return fail(ctx, EFX_ERR_ARG, "efx_detect_crop: src_stride must be a multiple of 16 and hold an image");
+    if (a.sums_stride < (size_t)o->height + o->width || (a.sums_stride & 3))
+        return fail(ctx, EFX_ERR_ARG, "efx_detect_crop: sums_stride must be a multiple of 4 and hold height + width sums");
+    if (sums_device) {
+        a.sums = sums_device;
+    } else {
+        const size_t need = (size_t)a.n_images * a.sums_stride;
+        if (need > ctx->crop_sums_cap) {
+            // (queued calls may still use the old block: this call waits for them)
+            EFX_HIP(hipStreamSynchronize(ctx->stream));
+            if (ctx->d_crop_sums)
+                (void)dev_free(ctx->d_crop_sums);
+            ctx->d_crop_sums = nullptr;
+            ctx->crop_sums_cap = 0;
+            EFX_HIP(dalloc(&ctx->d_crop_sums, need));
+            ctx->crop_sums_cap = need;
+        }
+        a.sums = ctx->d_crop_sums;
+    }
+    // three launches whatever the counts are (a workgroup takes further items when there are more than the grid's)
+    const size_t cap = (size_t)1 << 20;
+    const size_t zero_wgs = ((size_t)a.n_images * a.width + 255) / 256;
+    const size_t sum_wgs = (size_t)a.n_images * ((a.height + cpx::kBandRows - 1) / cpx::kBandRows);
+    hipLaunchKernelGGL(k_crop_zero, dim3((unsigned)std::min(zero_wgs, cap)), dim3(256), 0, ctx->stream, a);
+    auto* const k_sums = a.format == EFX_PIX_I420 ? k_crop_sums_i420 : a.format == EFX_PIX_RGB24 ? k_crop_sums_rgb24 : k_crop_sums_rgbp;
+    hipLaunchKernelGGL(k_sums, dim3((unsigned)std::min(sum_wgs, cap)), dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL(k_crop_rects, dim3((unsigned)std::min((size_t)a.n_streams, cap)), dim3(256), 0, ctx->stream, a);
     EFX_HIP(hipGetLastError());
     return EFX_OK;
 }

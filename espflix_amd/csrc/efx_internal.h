@@ -176,6 +176,16 @@ struct ImportArgs {
     size_t src_stride, dst_stride;
 };
 
+// k_crop_zero / k_crop_sums / k_crop_rects launch arguments (by value): efx_crop_opts, checked (k_cropdetect.hip)
+struct CropArgs {
+    const uint8_t* src;  // image k at src + k * src_stride
+    uint32_t* sums;      // image k: R[0 .. height), C[0 .. width) at sums + k * sums_stride (the caller's, or the context's scratch)
+    int32_t* rects;      // stream i: 8 int32 at rects + 8 i
+    size_t src_stride, sums_stride;
+    int n_streams, images_per_stream, n_images;
+    int format, width, height, full_range, limit, round;
+};
+
 // k_import_pcm / k_import_pcm_state launch arguments (by value): efx_import_pcm_opts, checked, as import_pcm.h's plan
 struct ImportPcmArgs {
     const int16_t* src;    // stream i at src + i * src_stride

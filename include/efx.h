@@ -313,6 +313,64 @@ size_t efx_import_src_bytes(int format, int width, int height);
  * crop to half the rectangle). */
 int efx_import_frames(efx_ctx* ctx, const efx_import_opts* opts, const void* src_device, uint8_t* dst_device);
 
+/* -- black borders: where the crop rectangle comes from (k_cropdetect) --------------------- */
+/* Source films arrive letterboxed or pillarboxed, and efx_import_frames takes its crop from the caller.  The reference
+ * indexer finds it with a second ffmpeg run (indexer/indexer.cpp:298-300: `-vf cropdetect=24:16:0`, next to the
+ * `crop=992:546:144:0 ... -s 352x192` line it feeds).  efx_detect_crop is that step on the device, for a batch: it reads
+ * the luma of n_streams x images_per_stream source pictures (the formats, sizes and layout of efx_import_frames) and
+ * leaves one rectangle per stream.  The definition is this library's own -- the idea of cropdetect=limit:round:0, stated
+ * exactly -- and an integer function of the source bytes (espflix_amd/csrc/crop_px.h), bit-reproducible anywhere.
+ *
+ *   Luma.  L(x, y) of a W x H image: the Y plane of an I420 source (its chroma planes are never read); for RGB24 / RGBP
+ *   the Y that efx_import_frames would write, Y of the matrix above for full_range (studio swing: black is 16, so ffmpeg's
+ *   default limit 24 means what it means there).
+ *   Sums.  R[y] = sum over x of L(x, y), C[x] = sum over y of L(x, y), exact in uint32 (at most 4096 x 255).
+ *   Classification.  Row y is picture when R[y] > limit x W, column x when C[x] > limit x H; equality is black.
+ *   Per image.  An image with at least one picture row and one picture column contributes top / bottom, its first and
+ *   last picture row, and left / right, its first and last picture column.  Any other image (all black: a fade inside a
+ *   title) contributes nothing -- it neither widens nor resets anything.
+ *   Per stream.  A stream is images_per_stream consecutive images (image k belongs to stream k / images_per_stream).
+ *   Over its contributing images x1 = min left, x2 = max right, y1 = min top, y2 = max bottom, all inclusive.
+ *   Rounding, per axis, bounds a .. b inclusive, r = round:  a' = a + (a & 1);  avail = b + 1 - a';  avail < 2: the axis
+ *   fails;  len = avail - avail mod r when avail >= r, else avail & ~1;  pos = a' + (((avail - len) >> 1) & ~1).
+ *   pos and len are even, pos >= a, pos + len <= b + 1: the rectangle lies inside the detected picture, centred to within
+ *   one even step.
+ *   Record.  Eight int32 per stream: x, y, w, h, x1, y1, x2, y2.  No image contributed: x1 = W, y1 = H, x2 = y2 = -1.
+ *   No image contributed or an axis failed: x, y, w, h = 0, 0, W, H, the whole picture, which efx_import_frames accepts
+ *   as a crop for every format.
+ *
+ * Memory contract (efx_import_frames').  For image k the kernels read only bytes in [src + k * src_stride, src + k *
+ * src_stride + efx_import_src_bytes() rounded up to 16), for I420 only the first W x H of them rounded up to 16, in
+ * 16-byte pieces aligned down inside that interval, each luma byte (RGB: each component) once.  They write the n_streams
+ * records and, when sums_device is given, for image k R[0 .. H) followed by C[0 .. W) at sums_device + k * sums_stride;
+ * the elements between images are not written.  With sums_device NULL the sums live in scratch of the context, allocated
+ * at the first such call, regrown when a later call needs more (such a call may wait for the stream) and freed by
+ * efx_destroy.
+ *
+ * Out of scope: handing the rectangle to efx_import_frames on the device (its geometry is a host argument: read the
+ * 32-byte record back), ffmpeg's reset window and its motion-vector mode, and byte compatibility with ffmpeg's rounding
+ * (which does not promise even offsets). */
+typedef struct efx_crop_opts {
+    int n_streams;          /* >= 1; not tied to max_streams (like efx_import_frames' n_images) */
+    int images_per_stream;  /* >= 1; image k belongs to stream k / images_per_stream; n_streams x images_per_stream < 2^31 */
+    int format;             /* efx_pixel_format of the source */
+    int width, height;      /* as efx_import_frames: 2 .. 4096, I420 even */
+    int full_range;         /* RGB sources: which luma (see above); ignored for I420 */
+    int limit;              /* 0 .. 255; ffmpeg's default: 24 */
+    int round;              /* even, 2 .. 64; ffmpeg's default: 16 */
+    size_t src_stride;      /* bytes between images; 0 = efx_import_src_bytes() rounded up to 16; multiple of 16 */
+    size_t sums_stride;     /* uint32 elements between images in sums_device; 0 = (height + width) rounded up to 4 */
+} efx_crop_opts;
+typedef struct efx_crop_rect { int32_t x, y, w, h, x1, y1, x2, y2; } efx_crop_rect;
+/* Asynchronous on the context's stream: no host synchronisation, three launches whatever the counts are (the column
+ * sums to zero, the sums, the rectangles), and no decoder, encoder, SBC or import state is touched.
+ * EFX_ERR_ARG: a NULL or misaligned (16 bytes) src_device or rects_device, a misaligned sums_device, n_streams or
+ * images_per_stream < 1 or their product above 2^31 - 1, an unknown format, width or height out of range (I420: odd),
+ * limit outside 0 .. 255, round odd or outside 2 .. 64, a src_stride that is too small or not a multiple of 16, a
+ * sums_stride below width + height or not a multiple of 4. */
+int efx_detect_crop(efx_ctx* ctx, const efx_crop_opts* opts, const void* src_device, efx_crop_rect* rects_device,
+                    uint32_t* sums_device /* may be NULL */);
+
 /* -- MPEG-1 encode on the device (k_encode) ---------------------------------------------- */
 /* The reference plays titles that were "encoded with ffmpeg at around 1.5MBits" (README.md:87) ahead of time; nothing in it
  * writes a stream.  efx_encode turns I420 pictures in device memory (the layout efx_export_frames writes: Y 192 x 352, then
