@@ -47,6 +47,7 @@ MUX_FULL = 1024           # efx_mux_av: the stream's output region is too small,
 MUX_BAD_VIDEO = 2048      # efx_mux_av: the video input is not a transport stream of PID 0x100 that starts with a PES (efx.h)
 PCM_FRAME_PLANAR, PCM_INTERLEAVED = 0, 1   # efx_sbc_encode_opts.pcm_layout
 PCM_PLANAR = 2                             # efx_import_pcm_opts.layout (or PCM_INTERLEAVED)
+TRICK_FROM_I420, TRICK_FROM_RING = 0, 1    # efx_trick_opts.source
 _PCM_LAYOUTS = {"interleaved": PCM_INTERLEAVED, "planar": PCM_PLANAR}
 _SBC_FREQUENCY = {16000: 0, 32000: 1, 44100: 2, 48000: 3}  # the SBC header's code of efx_import_pcm's output rates
 
@@ -97,6 +98,12 @@ class _CropOpts(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("n_streams", "images_per_stream", "format", "width", "height", "full_range", "limit",
                                        "round")] + \
                [("src_stride", C.c_size_t), ("sums_stride", C.c_size_t)]
+
+
+class _TrickOpts(C.Structure):
+    _fields_ = [("n_streams", C.c_int), ("n_pictures", C.c_int), ("speed", C.c_int), ("source", C.c_int), ("first_stream", C.c_int),
+                ("first_picture", C.c_int64), ("total_pictures", C.c_int64), ("src_stride", C.c_size_t),
+                ("fwd_stride", C.c_size_t), ("rwd_stride", C.c_size_t)]
 
 
 class _EncodeOpts(C.Structure):
@@ -191,6 +198,8 @@ _SYMBOLS = {
     "efx_import_src_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "efx_import_frames": (C.c_int, [_P, C.POINTER(_ImportOpts), _P, _P]),
     "efx_detect_crop": (C.c_int, [_P, C.POINTER(_CropOpts), _P, _P, _P]),
+    "efx_trick_pick": (C.c_int, [_P, C.POINTER(_TrickOpts), _P, _P, _P]),
+    "efx_trick_count": (C.c_int64, [C.c_int64, C.c_int64, C.c_int]),
     "efx_encode": (C.c_int, [_P, C.POINTER(_EncodeOpts), _P, _P, _P, _P, _P]),
     "efx_encode_rc": (C.c_int, [_P, C.POINTER(_EncodeOpts), C.POINTER(_EncodeRate), _P, _P, _P, _P, _P, _P]),
     "efx_encode_bound": (C.c_size_t, [C.c_int, C.c_int]),
@@ -379,6 +388,13 @@ def encode_bound(fmt: int, n_pictures: int) -> int:
     return int(load_library().efx_encode_bound(fmt, n_pictures))
 
 
+def trick_count(first_picture: int, n_pictures: int, speed: int) -> int:
+    """Picks among the pictures first_picture .. first_picture + n_pictures - 1 of a title at `speed` (every speed-th picture
+    of the title, counted from picture 0): ceil((first_picture + n_pictures) / speed) - ceil(first_picture / speed)
+    (efx_trick_count; -1 for invalid arguments)."""
+    return int(load_library().efx_trick_count(first_picture, n_pictures, speed))
+
+
 def sbc_state_bytes() -> int:
     return int(load_library().efx_sbc_state_bytes())
 
@@ -423,6 +439,14 @@ def mux_bound(video_bytes: int, n_frames: int, frame_bytes: int, frames_per_pes:
 def mux_audio_packets(n_frames: int, frame_bytes: int, frames_per_pes: int) -> int:
     """Audio packets efx_mux_av writes per stream: add to audio_cc (mod 16) for the next call."""
     return int(load_library().efx_mux_audio_packets(n_frames, frame_bytes, frames_per_pes))
+
+
+def _count_pictures(es: bytes) -> int:
+    """picture_start_codes (00 00 01 00) of an elementary stream."""
+    a = np.frombuffer(es, dtype=np.uint8)
+    if a.size < 4:
+        return 0
+    return int(np.count_nonzero((a[:-3] == 0) & (a[1:-2] == 0) & (a[2:-1] == 1) & (a[3:] == 0)))
 
 
 def _check(ctx, status: int):
@@ -1354,6 +1378,176 @@ class Decoder:
         finally:
             for b in bufs:
                 b.free()
+
+    # -- fast-forward and rewind streams (efx_trick_pick) --------------------------------------------
+    def trick_pick_to(self, src: DeviceBuffer | int | None, fwd: DeviceBuffer | int | None, rwd: DeviceBuffer | int | None, *,
+                      n_streams: int, n_pictures: int, speed: int = 15, first_picture: int = 0, total_pictures: int = 0,
+                      source: int = TRICK_FROM_I420, first_stream: int = 0, src_stride: int = 0, fwd_stride: int = 0,
+                      rwd_stride: int = 0) -> int:
+        """efx_trick_pick on raw device memory (DeviceBuffers or pointers), asynchronous on the library's stream: of the
+        pictures first_picture .. first_picture + n_pictures - 1 of a title, every one whose title index is a multiple of
+        speed goes, as a 101376-byte I420 image, to fwd (may be None) in playing order from image 0 of the call, and to rwd
+        (may be None) at image K - 1 - k of the title's K = ceil(total_pictures / speed) picks (the rule: include/efx.h).
+        source TRICK_FROM_I420: stream i's pictures at src + i * src_stride (0 = packed); TRICK_FROM_RING: src is None,
+        picture j is picture j of the most recent decode of stream first_stream + i.  fwd_stride / rwd_stride 0 = packed
+        (the call's picks / K images).  Returns the call's picks (trick_count)."""
+        g = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else b)
+        picks = trick_count(first_picture, n_pictures, speed)
+        K = trick_count(0, max(0, total_pictures), speed)
+        o = _TrickOpts(n_streams, n_pictures, speed, source, first_stream, first_picture, total_pictures,
+                       src_stride or max(0, n_pictures) * FRAME_BYTES, fwd_stride or max(0, picks) * FRAME_BYTES,
+                       rwd_stride or max(0, K) * FRAME_BYTES)
+        _check(self._ctx, self._lib.efx_trick_pick(self._ctx, C.byref(o), g(src), g(fwd), g(rwd)))
+        return picks
+
+    def trick_streams(self, pictures=None, *, title=None, speed: int = 15, gop: int = 3, qscale: int = 8, search: int = 7,
+                      bitrate: int | None = None, vbv_bits: int = 250_000, qmin: int = 3, qmax: int = 31, first_pts: int = 0,
+                      piece: int | None = None):
+        """The fast-forward and the rewind stream of n titles (the reference indexer's `-g 3 ... setpts=PTS/15` and
+        `-vf reverse` runs, indexer/indexer.cpp:308-309): every speed-th picture of a title, encoded in playing order and in
+        reverse order as transport streams with GOPs of `gop` pictures.  Returns (fwd: list of bytes, rwd: list of bytes,
+        status: uint32 [2, n] of ENCODE_* bits, row 0 fwd, row 1 rwd).
+
+        pictures: (n, P, 101376) I420 as for encode() (a uint8 tensor on the decoder's device or a NumPy array): the picks
+        are taken from them in pieces of `piece` pictures (None: all at once).
+        title: instead, a list of n transport streams (as encode_av / encode return them): they are uploaded once and
+        decoded in pieces of `piece` pictures (None, and at most: min(max_pictures, ring_depth - 1)), and after each piece
+        the picks are taken straight from the frame rings.  The titles must hold the same number of pictures (ValueError)
+        and decode with status 0 (EfxError); the decoder's state is that of the title's last piece afterwards.  The rewind
+        placement needs the picture count before the first pick: it is taken on the host, from each title's demultiplexed
+        elementary stream (es(): one device-to-host copy of every title's video bytes, scanned for picture start codes),
+        because the decoder's own count covers one call's pictures only.
+
+        Either way each piece's picks are encoded as they come, continuing the fast-forward stream (encode_to, cont), with
+        nothing synchronised between the pick and the encode of a piece; the rewind stream is encoded after the last piece
+        (the encoder keeps one set of streams per context, and a reversed stream cannot start before the title has ended).
+        Both streams start at first_pts; trick picture k carries first_pts + 3003 k.  qscale, search and bitrate ... qmax as
+        for encode().  Synchronises: torch's current stream before (tensor input), the library's after."""
+        if (pictures is None) == (title is None):
+            raise ValueError("give pictures or title=, not both")
+        if not 1 <= speed <= 255:
+            raise ValueError("speed must be 1 .. 255")
+        bufs, keep = [], []
+        try:
+            if pictures is not None:
+                if len(pictures.shape) != 3 or pictures.shape[-1] != FRAME_BYTES or pictures.shape[1] < 1 or pictures.shape[0] < 1:
+                    raise ValueError(f"pictures must have shape (n, P, {FRAME_BYTES}), got {tuple(pictures.shape)}")
+                n, P = int(pictures.shape[0]), int(pictures.shape[1])
+                if isinstance(pictures, np.ndarray):
+                    sbuf = DeviceBuffer(self, pictures.size)
+                    bufs.append(sbuf)
+                    sbuf.upload(np.ascontiguousarray(pictures, dtype=np.uint8))
+                    src_ptr = sbuf.ptr
+                else:
+                    import torch
+                    device = torch.device("cuda", self.device)
+                    if not isinstance(pictures, torch.Tensor) or pictures.dtype != torch.uint8 or pictures.device != device:
+                        raise ValueError(f"pictures must be a uint8 tensor on {device} (or a NumPy array)")
+                    pictures = pictures.contiguous()
+                    if pictures.data_ptr() % 16:
+                        pictures = pictures.clone()
+                    keep.append(pictures)
+                    torch.cuda.current_stream(device).synchronize()
+                    src_ptr = pictures.data_ptr()
+                step = P if piece is None else piece
+                if step < 1:
+                    raise ValueError("piece must be >= 1")
+            else:
+                n = len(title)
+                self.upload(title, FORMAT_TS)
+                counts = [_count_pictures(self.es(i)) for i in range(n)]
+                P = counts[0]
+                if P < 1 or any(c != P for c in counts):
+                    raise ValueError(f"the titles of a batch must hold the same number of pictures (at least 1), got {counts}")
+                limit = min(self.max_pictures, self.ring_depth - 1)
+                step = limit if piece is None else piece
+                if not 1 <= step <= limit:
+                    raise ValueError(f"piece must be 1 .. min(max_pictures, ring_depth - 1) = {limit}")
+            K = trick_count(0, P, speed)
+            pieces = [(first, min(step, P - first)) for first in range(0, P, step)]
+            picks = [trick_count(first, cnt, speed) for first, cnt in pieces]
+            fwd_cap = max(picks)
+            d_fwd, d_rwd = DeviceBuffer(self, n * fwd_cap * FRAME_BYTES), DeviceBuffer(self, n * K * FRAME_BYTES)
+            bufs += [d_fwd, d_rwd]
+            # every encode call (at most 255 pictures) writes a region of its own; the bytes are put together at the end
+            split = lambda c: [(a, min(255, c - a)) for a in range(0, c, 255)]
+            calls = [[sub for c in picks for sub in split(c)], split(K)]
+            r16 = lambda v: (v + 15) // 16 * 16
+            total = sum(n * encode_bound(FORMAT_TS, c) for side in calls for _, c in side)
+            d_dst, d_meta = DeviceBuffer(self, total), DeviceBuffer(self, 2 * r16(4 * n) * sum(len(side) for side in calls))
+            bufs += [d_dst, d_meta]
+            done = []  # (side, offset of the region in d_dst, its stride, offset of the byte counts in d_meta)
+            state = {"dst": 0, "meta": 0}
+
+            def encode_call(side, src, src_stride, count, cont):
+                stride = self.encode_to(src, d_dst.ptr + state["dst"], d_meta.ptr + state["meta"],
+                                        d_meta.ptr + state["meta"] + r16(4 * n), n_streams=n, n_pictures=count, qscale=qscale,
+                                        gop=gop, search=search, fmt=FORMAT_TS, cont=cont, first_pts=first_pts,
+                                        src_stride=src_stride, bitrate=bitrate, vbv_bits=vbv_bits, qmin=qmin, qmax=qmax)
+                done.append((side, state["dst"], stride, state["meta"]))
+                state["dst"] += n * stride
+                state["meta"] += 2 * r16(4 * n)
+
+            started = False
+            for (first, cnt), c in zip(pieces, picks):
+                if title is not None:
+                    self.decode(sync=False, first_picture=first, n_pictures=cnt)
+                    self.trick_pick_to(None, d_fwd, d_rwd, n_streams=n, n_pictures=cnt, speed=speed, first_picture=first,
+                                       total_pictures=P, source=TRICK_FROM_RING, fwd_stride=fwd_cap * FRAME_BYTES)
+                else:
+                    self.trick_pick_to(src_ptr + first * FRAME_BYTES, d_fwd, d_rwd, n_streams=n, n_pictures=cnt, speed=speed,
+                                       first_picture=first, total_pictures=P, src_stride=P * FRAME_BYTES,
+                                       fwd_stride=fwd_cap * FRAME_BYTES)
+                for a, sub in split(c):
+                    encode_call(0, d_fwd.ptr + a * FRAME_BYTES, fwd_cap * FRAME_BYTES, sub, started)
+                    started = True
+                if title is not None:
+                    for i in range(n):  # (synchronises: behind the piece's encode)
+                        bits = self.stream_status(i) & ~STREAM_TRUNCATED
+                        if bits or self.picture_count(i) != cnt:
+                            raise EfxError(-5, f"trick_streams: title {i} decodes with status {bits:#x}, {self.picture_count(i)} of "
+                                               f"{cnt} pictures from picture {first}")
+            for a, sub in split(K):
+                encode_call(1, d_rwd.ptr + a * FRAME_BYTES, K * FRAME_BYTES, sub, a > 0)
+            self.sync()
+            out, status = ([b""] * n, [b""] * n), np.zeros((2, n), dtype=np.uint32)
+            for side, off, stride, meta in done:
+                part, st = self._download_streams(d_dst.ptr + off, stride, d_meta.ptr + meta, d_meta.ptr + meta + r16(4 * n), n)
+                out[side][:] = [x + y for x, y in zip(out[side], part)]
+                status[side] |= st
+            return out[0], out[1], status
+        finally:
+            try:
+                self.sync()  # (after an error: queued calls may still use the buffers)
+            except EfxError:
+                pass
+            for b in bufs:
+                b.free()
+
+    def make_title(self, pictures, pcm, *, speed: int = 15, trick_gop: int = 3, **encode_av):
+        """A complete title directory per stream, as the reference's indexer leaves it (indexer/indexer.cpp:292-321) and its
+        player opens it (src/espflix.cpp:647,787-792): returns (list of n dicts {"video.ts", "video_fwd.ts", "video_rwd.ts",
+        "video.idx"} of bytes, status: uint32 [3, n], rows video.ts (ENCODE_* | MUX_* bits), video_fwd.ts, video_rwd.ts).
+
+        video.ts is encode_av(pictures, pcm, **encode_av).  The trick streams are trick_streams(pictures, speed=speed,
+        gop=trick_gop) with the same qscale, search, first_pts and rate-control keywords, without audio.  They are made
+        from the SOURCE pictures, one generation better than the reference, whose ffmpeg runs recode the finished
+        video.ts.  video.idx is idx_build over index_streams([main, fwd, rwd], trick_speed=[1, speed, speed]), one call per
+        title -- max_stream_bytes must hold the three streams of a title -- or, on a context with max_streams below 3, one
+        call per stream (the same records: a stream's record does not depend on the others)."""
+        titles, st = self.encode_av(pictures, pcm, **encode_av)
+        keys = ("qscale", "search", "first_pts", "bitrate", "vbv_bits", "qmin", "qmax")
+        fwd, rwd, tst = self.trick_streams(pictures, speed=speed, gop=trick_gop, **{k: encode_av[k] for k in keys if k in encode_av})
+        out = []
+        for main, f, r in zip(titles, fwd, rwd):
+            three, speeds = [main, f, r], [1, speed, speed]
+            if self.max_streams >= 3:
+                res = self.index_streams(three, trick_speed=speeds)
+            else:  # (efx_index_streams takes at most max_streams streams: a stream's record does not depend on the others)
+                res = [self.index_streams([s], trick_speed=[sp])[0] for s, sp in zip(three, speeds)]
+            out.append({"video.ts": main, "video_fwd.ts": f, "video_rwd.ts": r,
+                        "video.idx": idx_build([rec for rec, _ in res], [smp for _, smp in res])})
+        return out, np.vstack([st[None], tst])
 
     def pdm(self, n_streams: int, pcm: DeviceBuffer | int, n_samples: int, state: DeviceBuffer | int,
             dst: DeviceBuffer | int):

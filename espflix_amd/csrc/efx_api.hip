@@ -23,6 +23,7 @@
 #include "crop_px.h"
 #include "parse_tm.h"
 #include "sbc_enc_core.h"
+#include "trick_sel.h"
 
 namespace efx {
 // kernels (k_demux.hip, k_index.hip, k_parse.hip, k_recon.hip, k_video.hip)
@@ -62,6 +63,8 @@ __global__ void k_crop_sums_i420(CropArgs);
 __global__ void k_crop_sums_rgb24(CropArgs);
 __global__ void k_crop_sums_rgbp(CropArgs);
 __global__ void k_crop_rects(CropArgs);
+template <int SOURCE>
+__global__ void k_trick(TrickArgs);  // (k_trick.hip: the I420 and the ring instance)
 __global__ void k_import_pcm(ImportPcmArgs);  // (k_import_pcm.hip)
 __global__ void k_import_pcm_state(ImportPcmArgs);
 __global__ void k_enc_begin(EncArgs);
@@ -1922,6 +1925,98 @@ int efx_detect_crop(efx_ctx* ctx, const efx_crop_opts* o, const void* src_device
     hipLaunchKernelGGL(k_sums, dim3((unsigned)std::min(sum_wgs, cap)), dim3(256), 0, ctx->stream, a);
     hipLaunchKernelGGL(k_crop_rects, dim3((unsigned)std::min((size_t)a.n_streams, cap)), dim3(256), 0, ctx->stream, a);
     EFX_HIP(hipGetLastError());
+    return EFX_OK;
+}
+
+// ---- fast-forward and rewind picks (k_trick.hip) ----------------------------------------------------------------------------------
+int64_t efx_trick_count(int64_t first_picture, int64_t n_pictures, int speed) { return tsel::count(first_picture, n_pictures, speed); }
+
+int efx_trick_pick(efx_ctx* ctx, const efx_trick_opts* o, const uint8_t* src_device, uint8_t* fwd_device, uint8_t* rwd_device)
+{
+    bind_device(ctx);
+    if (!ctx || !o)
+        return EFX_ERR_ARG;
+    const bool ring = o->source == EFX_TRICK_FROM_RING;
+    if (o->source != EFX_TRICK_FROM_I420 && !ring)
+        return fail(ctx, EFX_ERR_ARG, "efx_trick_pick: unknown source");
+    if (o->n_streams < 1 || o->n_pictures < 1)
+        return fail(ctx, EFX_ERR_ARG, "efx_trick_pick: n_streams and n_pictures must be >= 1");
+    const int64_t picks = tsel::count(o->first_picture, o->n_pictures, o->speed);
+    if (picks < 0)
+        return fail(ctx, EFX_ERR_ARG, "efx_trick_pick: speed outside 1 .. 255 or first_picture outside 0 .. 2^40 - 1");
+    if ((uint64_t)o->n_streams * (uint64_t)picks > ((uint64_t)1 << 40))
+        return fail(ctx, EFX_ERR_ARG, "efx_trick_pick: more than 2^40 picked pictures in one call");
+    if (!fwd_device && !rwd_device)
+        return fail(ctx, EFX_ERR_ARG, "efx_trick_pick: fwd_device and rwd_device are both NULL");
+    if (ring ? src_device != nullptr : src_device == nullptr)
+        return fail(ctx, EFX_ERR_ARG, "efx_trick_pick: src_device must be given with the I420 source and NULL with the ring source");
+    if (((uintptr_t)src_device | (uintptr_t)fwd_device | (uintptr_t)rwd_device) & 15)
+        return fail(ctx, EFX_ERR_ARG, "efx_trick_pick: src_device, fwd_device and rwd_device must be 16-byte aligned");
+    if (!ring && (o->src_stride < (size_t)o->n_pictures * kFrameBytes || (o->src_stride & 15)))
+        return fail(ctx, EFX_ERR_ARG, "efx_trick_pick: src_stride must be a multiple of 16 and hold n_pictures pictures");
+    if (fwd_device && (o->fwd_stride < (size_t)picks * kFrameBytes || (o->fwd_stride & 15)))
+        return fail(ctx, EFX_ERR_ARG, "efx_trick_pick: fwd_stride must be a multiple of 16 and hold the call's picks");
+    int64_t K = 0;
+    if (rwd_device) {
+        if (o->total_pictures < o->first_picture + o->n_pictures)
+            return fail(ctx, EFX_ERR_ARG, "efx_trick_pick: total_pictures below first_picture + n_pictures");
+        K = tsel::total_picks(o->total_pictures, o->speed);
+        if (o->rwd_stride / kFrameBytes < (uint64_t)K || (o->rwd_stride & 15))
+            return fail(ctx, EFX_ERR_ARG, "efx_trick_pick: rwd_stride must be a multiple of 16 and hold the title's K picks");
+    }
+    TrickArgs a{};
+    a.src = src_device;
+    a.fwd = fwd_device;
+    a.rwd = rwd_device;
+    a.src_stride = o->src_stride;
+    a.fwd_stride = o->fwd_stride;
+    a.rwd_stride = o->rwd_stride;
+    a.first_picture = o->first_picture;
+    a.k0 = tsel::first_pick(o->first_picture, o->speed);
+    a.K = K;
+    a.n_streams = o->n_streams;
+    a.n_picks = (int)picks;
+    a.speed = o->speed;
+    if (ring) {
+        if (o->first_stream < 0 || o->n_pictures > ctx->cfg.max_pictures)
+            return fail(ctx, EFX_ERR_ARG, "efx_trick_pick: first_stream below 0 or n_pictures above max_pictures");
+        if (!ctx->decoded || ctx->n_groups < 1)
+            return fail(ctx, EFX_ERR_STATE, "efx_trick_pick: ring source before any decode");
+        if (o->first_stream > ctx->last_n_streams - o->n_streams)
+            return fail(ctx, EFX_ERR_STATE, "efx_trick_pick: stream range beyond the most recent decode's streams");
+        if (o->n_pictures >= ctx->cfg.ring_depth)
+            return fail(ctx, EFX_ERR_STATE, "efx_trick_pick: n_pictures >= ring_depth: a picture of the call is already overwritten");
+        a.src = ctx->d_frames;
+        a.first_stream = o->first_stream;
+        a.ring_depth = ctx->cfg.ring_depth;
+        a.n_groups = ctx->n_groups;
+        for (int g = 0; g < ctx->n_groups; g++) {
+            a.group_first[g] = ctx->groups[g].first;
+            a.call_pos[g] = ctx->slot[ctx->groups[g].slot].d_call_pos;
+        }
+    }
+    if (picks == 0)
+        return EFX_OK;  // nothing to move: no launch
+    // one launch whatever the counts are (a workgroup takes further runs of items when there are more than the grid's)
+    // (at most 2^40 picked pictures, checked above: fewer than 2^53 items)
+    const uint64_t items = (uint64_t)o->n_streams * (uint64_t)picks * tsel::kPiecesPerPicture;
+    const uint64_t runs = (items + kTrickItemsPerBlock - 1) / kTrickItemsPerBlock;
+    const unsigned blocks = (unsigned)std::min<uint64_t>(runs, kTrickMaxBlocks);
+    if (ring)
+        hipLaunchKernelGGL((k_trick<EFX_TRICK_FROM_RING>), dim3(blocks), dim3(256), 0, ctx->stream, a);
+    else
+        hipLaunchKernelGGL((k_trick<EFX_TRICK_FROM_I420>), dim3(blocks), dim3(256), 0, ctx->stream, a);
+    EFX_HIP(hipGetLastError());
+    if (ring) {
+        // as efx_export_frames' picture mode: the hand-over slots whose call records the kernel reads are recycled only
+        // behind it
+        for (int g = 0; g < ctx->n_groups; g++) {
+            const efx_ctx::Group& gr = ctx->groups[g];
+            if (gr.count > 0 && gr.first < o->first_stream + o->n_streams && gr.first + gr.count > o->first_stream)
+                EFX_HIP(hipEventRecord(ctx->slot[gr.slot].recon_done, ctx->stream));
+        }
+        ctx->last_recon_done = ctx->slot[ctx->groups[ctx->n_groups - 1].slot].recon_done;
+    }
     return EFX_OK;
 }
 

@@ -153,6 +153,26 @@ struct ExportArgs {
     size_t dst_stride;
 };
 
+// k_trick (k_trick.hip): one item = 16 bytes of one picked picture of one stream; a workgroup moves kTrickItemsPerBlock
+// consecutive items (4 passes of 256 threads), and takes further such runs when there are more than the grid's
+constexpr int kTrickItemsPerBlock = 1024;
+constexpr unsigned kTrickMaxBlocks = 1u << 20;
+
+// k_trick launch arguments (by value): efx_trick_opts, checked
+struct TrickArgs {
+    const uint8_t* src;  // I420 source: stream i, picture j at src + i * src_stride + j * 101376; ring source: the frame rings
+    uint8_t* fwd;        // may be null: stream i, pick k at fwd + i * fwd_stride + (k - k0) * 101376
+    uint8_t* rwd;        // may be null: stream i, pick k at rwd + i * rwd_stride + (K - 1 - k) * 101376
+    size_t src_stride, fwd_stride, rwd_stride;
+    int64_t first_picture;  // title index of the call's picture 0
+    int64_t k0, K;          // the call's first pick, the picks of the whole title (trick_sel.h)
+    int n_streams, n_picks, speed;
+    // ring source (k_export's picture mode: ring_px.h)
+    int first_stream, ring_depth, n_groups;
+    int group_first[kExportMaxGroups];
+    const int32_t* call_pos[kExportMaxGroups];
+};
+
 // k_import (k_import.hip): the taps of one destination index of one axis, written by k_import_taps (import_px.h: taps())
 constexpr int kImportTapSlots = 132;  // ipx::kMaxTaps rounded up so that a record is a multiple of 16 bytes
 struct ImportTap {

@@ -18,6 +18,7 @@
 #include "efx.h"
 #include "efx_internal.h"
 #include "export_px.h"
+#include "ring_px.h"
 
 namespace efx {
 
@@ -26,12 +27,8 @@ namespace {
 constexpr int kYBytes = EFX_FRAME_WIDTH * EFX_FRAME_HEIGHT;  // I420 / RGBP plane offsets
 constexpr int kCBytes = kYBytes / 4;
 
-__device__ inline int luma_row_off(int y) { return (y >> 4) * kStripBytes + (y & 15) * kStride; }
-// plane 1 = Cb (U): strip rows 0-7; plane 2 = Cr (V): strip rows 8-15 (k_video.hip's accessor)
-__device__ inline int chroma_row_off(int plane, int c)
-{
-    return (c >> 3) * kStripBytes + ((c & 7) + (plane == 2 ? 8 : 0)) * kStride + EFX_FRAME_WIDTH;
-}
+using ring::chroma_row_off;  // (ring_px.h: shared with k_trick.hip)
+using ring::luma_row_off;
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
@@ -124,17 +121,9 @@ __global__ __launch_bounds__(256) void k_export(const uint8_t* __restrict__ fram
         const int stream = a.first_stream + s;
 
         int slot = a.slot;
-        if (slot < 0) {
+        if (slot < 0)
             // picture mode: the ring position k_advance recorded for this stream's group (efx_stream_picture_slot)
-            const int32_t* cp = a.call_pos[0];
-#pragma unroll
-            for (int i = 1; i < kExportMaxGroups; i++)
-                if (i < a.n_groups && stream >= a.group_first[i])
-                    cp = a.call_pos[i];
-            const int pos0 = cp[2 * stream], f = cp[2 * stream + 1];
-            const uint32_t q = (uint32_t)pos0 + (uint32_t)(f < 0 ? a.picture + 1 : max(0, a.picture - f));
-            slot = (int)(q % (uint32_t)a.ring_depth);
-        }
+            slot = ring::picture_slot(a, stream, a.picture);
         const uint8_t* fr = frames + ((size_t)stream * a.ring_depth + slot) * kFrameBytes;
         uint8_t* dst = a.dst + (size_t)s * a.dst_stride;
         const int y0 = 2 * cy;

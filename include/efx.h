@@ -477,6 +477,66 @@ int efx_encode_rc(efx_ctx* ctx, const efx_encode_opts* opts, const efx_encode_ra
                   uint8_t* dst_device, uint32_t* len_device, uint32_t* status_device, uint8_t* recon_device,
                   uint8_t* qscale_out_device);
 
+/* -- fast-forward and rewind streams: which pictures make them (k_trick) ------------------- */
+/* A title of the reference is four files: the player opens video_rwd.ts, video.ts and video_fwd.ts by name
+ * (src/espflix.cpp:647,787-792) and maps between them with the three records of video.idx (589-628).  The indexer makes
+ * the two trick streams with two more ffmpeg runs (indexer/indexer.cpp:308-309): `-g 3 ... -an -filter:v "setpts=PTS/15"`
+ * keeps every fifteenth picture in GOPs of 3 without audio, `-vf reverse` turns that stream round.  efx_trick_pick is the
+ * selection of both runs on the device, for a batch: it gathers the picked pictures as I420 images, in playing order for
+ * the fast-forward encoder and in reverse order for the rewind encoder; efx_encode (gop 3) makes the streams.
+ *
+ * The rule (espflix_amd/csrc/trick_sel.h).  A title is the pictures t = 0 .. total-1; speed is 1 .. 255 (the reference: 15).
+ *   Picture t is picked iff t mod speed == 0; it is pick k = t / speed of the K = ceil(total / speed) picks of the title.
+ *   A call offers the pictures t = first_picture + j, j = 0 .. n_pictures-1.  With k0 = ceil(first_picture / speed) it
+ *   holds the picks k0 .. k0 + c - 1, c = ceil((first_picture + n_pictures) / speed) - k0, which may be 0.
+ *   fwd placement is call-relative: pick k goes to image k - k0 of the fwd region, so the fast-forward stream can be
+ *   encoded piece by piece (efx_encode with cont = 1).
+ *   rwd placement is title-absolute: pick k goes to image K - 1 - k of the rwd region, because a reversed stream cannot
+ *   start before the title has ended; the region holds K images and is complete after the call that offers the last picture.
+ *
+ * Sources.  EFX_TRICK_FROM_I420: pictures in the layout efx_encode reads, stream i, picture j at src_device + i *
+ * src_stride + j * 101376.  EFX_TRICK_FROM_RING: the frame rings; picture j of stream first_stream + i is picture j of the
+ * most recent efx_decode* of that stream, and a picked picture is written as the 101376 bytes efx_export_frames with
+ * EFX_PIX_I420, slot = -1, picture = j writes for that stream: the same slot arithmetic, read on the device from the record
+ * the decode left -- also where export's result is whatever the slot holds (a picture ahead of the first PTS).
+ *
+ * Stream i's images go to fwd_device + i * fwd_stride and rwd_device + i * rwd_stride, image m at + m * 101376.
+ *
+ * Memory contract.  Unpicked pictures are never read; a picked picture is read once, also when both destinations are
+ * given.  The call writes only the 101376 bytes of every picked image in each region given: the bytes between images,
+ * between streams, and the images of picks that belong to other calls are left alone.  The regions must not overlap the
+ * source or each other; the call cannot check that.
+ *
+ * Asynchronous on the context's stream, no host synchronisation: one launch whatever the counts are, none for a call
+ * without picks (which returns EFX_OK), and no decoder, encoder, SBC or import state is touched.
+ * EFX_ERR_ARG: a field out of range; more than 2^40 picked pictures (n_streams x the call's picks); both destinations
+ * NULL; src_device NULL with the I420 source or not NULL with the ring source; a pointer that is not 16-byte aligned; a stride (of a region that is given; src_stride with the I420
+ * source) that is too small or not a multiple of 16; total_pictures below first_picture + n_pictures when rwd_device is
+ * given.  EFX_ERR_STATE (ring source): no decode yet; the stream range beyond the stream count of the most recent
+ * decode; n_pictures >= ring_depth (a picture of the call would already be overwritten).
+ *
+ * Out of scope: blending or any filtering of the picks (ffmpeg's setpts only drops pictures as well), ffmpeg's frame-rate
+ * conform, a rewind stream made piecewise, and the multi-device entry points. */
+#define EFX_TRICK_FROM_I420 0   /* src_device: pictures in the layout efx_encode reads, stream i at src + i * src_stride */
+#define EFX_TRICK_FROM_RING 1   /* the frame rings: picture j of the most recent efx_decode* of streams first_stream + i */
+typedef struct efx_trick_opts {
+    int n_streams;            /* >= 1 (ring: first_stream + n_streams within the most recent decode's stream count) */
+    int n_pictures;           /* pictures per stream offered by this call, >= 1 (ring: <= max_pictures and < ring_depth) */
+    int speed;                /* 1 .. 255 */
+    int source;               /* EFX_TRICK_FROM_* */
+    int first_stream;         /* ring source only, >= 0 */
+    int64_t first_picture;    /* title index of the call's picture 0, 0 .. 2^40 - 1 */
+    int64_t total_pictures;   /* of the title; read only when rwd_device != NULL; >= first_picture + n_pictures */
+    size_t src_stride;        /* I420 source: >= n_pictures x 101376, multiple of 16 */
+    size_t fwd_stride;        /* >= the call's picks x 101376, multiple of 16 */
+    size_t rwd_stride;        /* >= K x 101376, multiple of 16 */
+} efx_trick_opts;
+int efx_trick_pick(efx_ctx* ctx, const efx_trick_opts* opts, const uint8_t* src_device /* NULL for the ring */,
+                   uint8_t* fwd_device /* may be NULL */, uint8_t* rwd_device /* may be NULL */);
+/* The picks a call holds: ceil((first_picture + n_pictures) / speed) - ceil(first_picture / speed).  Host only; -1 for
+ * invalid arguments (first_picture outside 0 .. 2^40 - 1, n_pictures outside 0 .. 2^31 - 1, speed outside 1 .. 255). */
+int64_t efx_trick_count(int64_t first_picture, int64_t n_pictures, int speed);
+
 /* -- composite video out (video_init / video_isr, src/video.cpp:572-630,1122-1198) -------- */
 typedef struct efx_video_params {
     int line_width, line_count;        /* samples per line, lines per field */
