@@ -12,6 +12,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 from dataclasses import dataclass
+from fractions import Fraction
 
 import numpy as np
 
@@ -104,6 +105,11 @@ class _TrickOpts(C.Structure):
     _fields_ = [("n_streams", C.c_int), ("n_pictures", C.c_int), ("speed", C.c_int), ("source", C.c_int), ("first_stream", C.c_int),
                 ("first_picture", C.c_int64), ("total_pictures", C.c_int64), ("src_stride", C.c_size_t),
                 ("fwd_stride", C.c_size_t), ("rwd_stride", C.c_size_t)]
+
+
+class _ConformOpts(C.Structure):
+    _fields_ = [("n_streams", C.c_int), ("n_pictures", C.c_int), ("in_num", C.c_int32), ("in_den", C.c_int32), ("out_code", C.c_int),
+                ("first_picture", C.c_int64), ("src_stride", C.c_size_t), ("dst_stride", C.c_size_t)]
 
 
 class _EncodeOpts(C.Structure):
@@ -203,6 +209,12 @@ _SYMBOLS = {
     "efx_encode": (C.c_int, [_P, C.POINTER(_EncodeOpts), _P, _P, _P, _P, _P]),
     "efx_encode_rc": (C.c_int, [_P, C.POINTER(_EncodeOpts), C.POINTER(_EncodeRate), _P, _P, _P, _P, _P, _P]),
     "efx_encode_bound": (C.c_size_t, [C.c_int, C.c_int]),
+    "efx_encode_set_picture_rate": (C.c_int, [_P, C.c_int]),
+    "efx_picture_pts_offset": (C.c_int64, [C.c_int, C.c_int64]),
+    "efx_picture_rate_code": (C.c_int, [C.c_int64, C.c_int64]),
+    "efx_conform_rate": (C.c_int, [_P, C.POINTER(_ConformOpts), _P, _P]),
+    "efx_conform_count": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64]),
+    "efx_conform_source": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int64]),
     "efx_composite_fields": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "efx_composite_fields_ex": (C.c_int, [_P, C.POINTER(_FieldOpts), _P]),
     "efx_demux_audio": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(C.c_size_t), _P, C.c_size_t, _P]),
@@ -395,6 +407,59 @@ def trick_count(first_picture: int, n_pictures: int, speed: int) -> int:
     return int(load_library().efx_trick_count(first_picture, n_pictures, speed))
 
 
+# the picture rates MPEG-1 codes (picture_rate 1 .. 8; include/efx.h)
+PICTURE_RATES = {1: Fraction(24000, 1001), 2: Fraction(24), 3: Fraction(25), 4: Fraction(30000, 1001), 5: Fraction(30),
+                 6: Fraction(50), 7: Fraction(60000, 1001), 8: Fraction(60)}
+_FLOAT_RATES = {23.976: PICTURE_RATES[1], 29.97: PICTURE_RATES[4], 59.94: PICTURE_RATES[7]}
+
+
+def _rate(fps) -> Fraction:
+    """A picture rate given as Fraction, "num/den", int or float (23.976, 29.97 and 59.94 mean the x/1001 rates)."""
+    if isinstance(fps, bool) or fps is None:
+        raise ValueError(f"not a picture rate: {fps!r}")
+    if isinstance(fps, float):
+        f = _FLOAT_RATES[fps] if fps in _FLOAT_RATES else Fraction(repr(fps))
+    else:
+        f = Fraction(fps)
+    if f <= 0:
+        raise ValueError(f"not a picture rate: {fps!r}")
+    return f
+
+
+def picture_rate_code(fps) -> int:
+    """The MPEG-1 picture_rate code (1 .. 8) whose rate is exactly fps, or 0 (efx_picture_rate_code)."""
+    f = _rate(fps)
+    if f.numerator >= 1 << 63 or f.denominator >= 1 << 63:
+        return 0
+    return int(load_library().efx_picture_rate_code(f.numerator, f.denominator))
+
+
+def _fps_code(fps) -> int:
+    """fps= of the encode calls as a code: None = 30000/1001; a rate MPEG-1 does not code is a ValueError."""
+    if fps is None:
+        return 4
+    code = picture_rate_code(fps)
+    if not code:
+        raise ValueError(f"fps={fps!r} is not a rate MPEG-1 codes: one of {', '.join(str(r) for r in PICTURE_RATES.values())} "
+                         "(conform other rates first: fps_out=, Decoder.conform)")
+    return code
+
+
+def picture_pts_offset(fps, k: int) -> int:
+    """90 kHz ticks from picture 0 to picture k of a stream encoded at fps: floor(k x 90000 / fps)
+    (efx_picture_pts_offset; -1 for k outside 0 .. 2^32)."""
+    return int(load_library().efx_picture_pts_offset(_fps_code(fps), k))
+
+
+def conform_count(fps_in, fps_out, first_picture: int, n_pictures: int) -> int:
+    """Output pictures of a conform call that offers the source pictures first_picture .. first_picture + n_pictures - 1 of
+    a title at fps_in for an output at fps_out, a coded rate (efx_conform_count; -1 for arguments the call rejects)."""
+    f = _rate(fps_in)
+    if f.numerator >= 1 << 31 or f.denominator >= 1 << 31:
+        return -1
+    return int(load_library().efx_conform_count(f.numerator, f.denominator, _fps_code(fps_out), first_picture, n_pictures))
+
+
 def sbc_state_bytes() -> int:
     return int(load_library().efx_sbc_state_bytes())
 
@@ -523,6 +588,7 @@ class Decoder:
         self.device = device
         self.hip_stream = hip_stream
         self.n_streams = 0
+        self._enc_rate_code = 4  # picture_rate of the streams cont=True continues
 
     def close(self):
         if self._ctx:
@@ -941,15 +1007,25 @@ class Decoder:
                   status: DeviceBuffer | int, *, n_streams: int, n_pictures: int, qscale: int = 8, gop: int = 12,
                   search: int = 7, fmt: int = FORMAT_TS, cont: bool = False, first_pts: int = 0, src_stride: int = 0,
                   dst_stride: int = 0, recon: DeviceBuffer | int | None = None, bitrate: int | None = None,
-                  vbv_bits: int = 250_000, qmin: int = 3, qmax: int = 31, qscale_out: DeviceBuffer | int | None = None):
+                  vbv_bits: int = 250_000, qmin: int = 3, qmax: int = 31, qscale_out: DeviceBuffer | int | None = None, fps=None):
         """efx_encode on raw device memory (DeviceBuffers or pointers), asynchronous on the library's stream: stream i's
         pictures at src + i * src_stride (0 = packed), its bytes appended to dst + i * dst_stride (0 = efx_encode_bound),
         uint32 byte counts and status bits to length / status, the reconstruction to recon (optional).
 
         bitrate (bit/s): efx_encode_rc instead -- every picture's quantiser chosen on the device under the buffer model
         of efx.h (vbv_bits, qmin, qmax; qscale is the first picture's), the n_streams x n_pictures quantisers to
-        qscale_out (optional).  The defaults are the profile of the reference's indexer."""
+        qscale_out (optional).  The defaults are the profile of the reference's indexer.
+
+        fps: the picture rate of fresh streams, one of PICTURE_RATES as Fraction, "24000/1001", int or 23.976 / 29.97 /
+        59.94; None = 30000/1001 (efx_encode_set_picture_rate in front of every cont=False call, so a rate never stays in
+        force from an earlier call).  With cont=True the streams keep their rate: fps must be None or that rate."""
         g = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else b)
+        if cont:
+            if fps is not None and _fps_code(fps) != self._enc_rate_code:
+                raise ValueError(f"fps={fps!r} with cont=True: the streams run at {PICTURE_RATES[self._enc_rate_code]}")
+        else:
+            code = _fps_code(fps)
+            _check(self._ctx, self._lib.efx_encode_set_picture_rate(self._ctx, code))
         o = _EncodeOpts(n_streams, n_pictures, fmt, qscale, gop, search, 1 if cont else 0, first_pts,
                         src_stride or n_pictures * FRAME_BYTES, dst_stride or encode_bound(fmt, n_pictures))
         if bitrate is None:
@@ -958,11 +1034,13 @@ class Decoder:
             r = _EncodeRate(bitrate, vbv_bits, qmin, qmax)
             _check(self._ctx, self._lib.efx_encode_rc(self._ctx, C.byref(o), C.byref(r), g(src), g(dst), g(length), g(status),
                                                       g(recon), g(qscale_out)))
+        if not cont:
+            self._enc_rate_code = code
         return o.dst_stride
 
     def encode(self, pictures, *, qscale: int = 8, gop: int = 12, search: int = 7, fmt: int = FORMAT_TS, cont: bool = False,
                first_pts: int = 0, recon: bool = False, dst_stride: int = 0, bitrate: int | None = None,
-               vbv_bits: int = 250_000, qmin: int = 3, qmax: int = 31) -> EncodeResult:
+               vbv_bits: int = 250_000, qmin: int = 3, qmax: int = 31, fps=None) -> EncodeResult:
         """Encode (n, P, 101376) I420 pictures (the layout export("i420") writes) into n MPEG-1 streams of P pictures: a uint8
         torch tensor on the decoder's device or a NumPy array.  Stream i takes the pictures of row i (the order export()
         gives streams).  Returns each stream's bytes, its status bits and, with recon=True, what a decoder reconstructs
@@ -977,7 +1055,10 @@ class Decoder:
 
         bitrate (bit/s of the bytes in fmt): rate control (efx_encode_rc) under a buffer of vbv_bits bits, quantisers
         qmin..qmax, qscale for the first picture of a fresh stream; the result's qscales holds every picture's quantiser
-        and status may carry ENCODE_VBV.  cont=True must keep bitrate and vbv_bits."""
+        and status may carry ENCODE_VBV.  cont=True must keep bitrate and vbv_bits.
+
+        fps: the streams' picture rate as for encode_to (None = 30000/1001): picture k carries first_pts +
+        picture_pts_offset(fps, k)."""
         lead = tuple(pictures.shape[:-1])
         if len(lead) != 2 or pictures.shape[-1] != FRAME_BYTES:
             raise ValueError(f"pictures must have shape (n, P, {FRAME_BYTES}), got {tuple(pictures.shape)}")
@@ -1017,7 +1098,7 @@ class Decoder:
             status_off = (4 * n + 15) // 16 * 16
             self.encode_to(src_ptr, dst, meta.ptr, meta.ptr + status_off, n_streams=n, n_pictures=P, qscale=qscale, gop=gop,
                            search=search, fmt=fmt, cont=cont, first_pts=first_pts, dst_stride=stride, recon=rec_ptr,
-                           bitrate=bitrate, vbv_bits=vbv_bits, qmin=qmin, qmax=qmax, qscale_out=q_buf)
+                           bitrate=bitrate, vbv_bits=vbv_bits, qmin=qmin, qmax=qmax, qscale_out=q_buf, fps=fps)
             self.sync()
             lens = meta.download(np.uint32, n)
             st = np.empty(n, dtype=np.uint32)
@@ -1295,7 +1376,7 @@ class Decoder:
     def encode_av(self, pictures, pcm, *, qscale: int = 8, gop: int = 12, search: int = 7, first_pts: int = 0, blocks: int = 16,
                   allocation: int = 0, bitpool: int = 28, frequency: int = 3, sample_rate: int = 48000, frames_per_pes: int = 8,
                   audio_pid: int = 0x101, bitrate: int | None = None, vbv_bits: int = 250_000, qmin: int = 3, qmax: int = 31,
-                  pcm_rate: int | None = None, pcm_layout: str = "interleaved"):
+                  pcm_rate: int | None = None, pcm_layout: str = "interleaved", fps=None):
         """Pictures + PCM -> complete titles: encode (transport streams) -> sbc_encode (mono) -> mux, queued back to back on
         the library's stream with nothing synchronised in between.  pictures: (n, P, 101376) I420 as for encode(); pcm: int16
         [n, samples], a whole number of frames of blocks x 8 samples; the audio starts at the first picture's PTS.  Every
@@ -1308,7 +1389,10 @@ class Decoder:
         pcm_layout="planar"): it goes through import_pcm_to (equal downmix weights) into a device buffer zero-padded to whole
         SBC frames, queued in front of sbc_encode_to with nothing synchronised in between.  The output rate is sample_rate
         (16000, 32000, 44100 or 48000) and `frequency` follows it.  The resampler's delay (16 output samples, 0.33 ms at
-        48 kHz) is not compensated."""
+        48 kHz) is not compensated.
+
+        fps: the video's picture rate as for encode() (None = 30000/1001).  The audio's PTS come from the sample count
+        and do not depend on it."""
         import torch
         device = torch.device("cuda", self.device)
         to_dev = lambda t, dt: torch.from_numpy(np.ascontiguousarray(t)).to(device) if isinstance(t, np.ndarray) else t
@@ -1358,7 +1442,7 @@ class Decoder:
             torch.cuda.current_stream(device).synchronize()
             self.encode_to(pictures.data_ptr(), d_v, p_vlen, p_vst, n_streams=n, n_pictures=P, qscale=qscale, gop=gop, search=search,
                            fmt=FORMAT_TS, first_pts=first_pts, dst_stride=v_stride, bitrate=bitrate, vbv_bits=vbv_bits, qmin=qmin,
-                           qmax=qmax)
+                           qmax=qmax, fps=fps)
             if imp is not None:
                 self.import_pcm_to(imp[0].data_ptr(), d_istate, pcm.data_ptr(), n_streams=n, n_in=imp[1], in_rate=pcm_rate,
                                    out_rate=sample_rate, channels=imp[2], layout=_PCM_LAYOUTS[pcm_layout], src_stride=imp[3],
@@ -1378,6 +1462,78 @@ class Decoder:
         finally:
             for b in bufs:
                 b.free()
+
+    # -- picture rates (efx_conform_rate) ----------------------------------------------------------------
+    def conform_to(self, src: DeviceBuffer | int, dst: DeviceBuffer | int, *, n_streams: int, n_pictures: int, fps_in, fps_out,
+                   first_picture: int = 0, src_stride: int = 0, dst_stride: int = 0) -> int:
+        """efx_conform_rate on raw device memory (DeviceBuffers or pointers), asynchronous on the library's stream: the
+        source pictures first_picture .. first_picture + n_pictures - 1 of a title at fps_in (any constant rate: Fraction,
+        "num/den", int or float), stream i's at src + i * src_stride (0 = packed), become the output pictures at fps_out
+        (a coded rate) that show them, by dropping and repeating pictures (the rule: include/efx.h), stream i's at dst + i *
+        dst_stride (0 = packed: the call's outputs).  Returns the call's outputs (conform_count)."""
+        g = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
+        f, code = _rate(fps_in), _fps_code(fps_out)
+        n_out = conform_count(f, fps_out, first_picture, n_pictures)
+        if n_out < 0:
+            raise ValueError(f"conform {f} -> {PICTURE_RATES[code]}: the rates, first_picture={first_picture} or "
+                             f"n_pictures={n_pictures} are out of range (efx_conform_rate)")
+        o = _ConformOpts(n_streams, n_pictures, f.numerator, f.denominator, code, first_picture,
+                         src_stride or n_pictures * FRAME_BYTES, dst_stride or n_out * FRAME_BYTES)
+        _check(self._ctx, self._lib.efx_conform_rate(self._ctx, C.byref(o), g(src), g(dst)))
+        return n_out
+
+    def conform(self, pictures, fps_in, fps_out, *, first_picture: int = 0):
+        """(n, P, 101376) I420 pictures at fps_in as (n, P', 101376) pictures at fps_out, a rate MPEG-1 codes, conformed on
+        the device (conform_to): a uint8 tensor on the decoder's device (a tensor is returned) or a NumPy array (an array
+        is returned).  P' = conform_count(fps_in, fps_out, first_picture, P), which may be 0.  Synchronises: torch's
+        current stream before (tensor input), the library's after."""
+        if len(pictures.shape) != 3 or pictures.shape[-1] != FRAME_BYTES or pictures.shape[0] < 1 or pictures.shape[1] < 1:
+            raise ValueError(f"pictures must have shape (n, P, {FRAME_BYTES}), got {tuple(pictures.shape)}")
+        n, P = int(pictures.shape[0]), int(pictures.shape[1])
+        n_out = conform_count(fps_in, fps_out, first_picture, P)
+        if n_out < 0:
+            raise ValueError(f"conform {fps_in!r} -> {fps_out!r}: out of range (efx_conform_rate)")
+        bufs = []
+        try:
+            if isinstance(pictures, np.ndarray):
+                sbuf, dbuf = DeviceBuffer(self, pictures.size), DeviceBuffer(self, max(1, n * n_out * FRAME_BYTES))
+                bufs += [sbuf, dbuf]
+                sbuf.upload(np.ascontiguousarray(pictures, dtype=np.uint8))
+                self.conform_to(sbuf, dbuf, n_streams=n, n_pictures=P, fps_in=fps_in, fps_out=fps_out, first_picture=first_picture)
+                self.sync()
+                return dbuf.download(np.uint8, n * n_out * FRAME_BYTES).reshape(n, n_out, FRAME_BYTES)
+            import torch
+            device = torch.device("cuda", self.device)
+            if not isinstance(pictures, torch.Tensor) or pictures.dtype != torch.uint8 or pictures.device != device:
+                raise ValueError(f"pictures must be a uint8 tensor on {device} (or a NumPy array)")
+            src = pictures.contiguous()
+            if src.data_ptr() % 16:
+                src = src.clone()
+            out = torch.empty((n, n_out, FRAME_BYTES), dtype=torch.uint8, device=device)
+            torch.cuda.current_stream(device).synchronize()
+            if n_out:
+                self.conform_to(src.data_ptr(), out.data_ptr(), n_streams=n, n_pictures=P, fps_in=fps_in, fps_out=fps_out,
+                                first_picture=first_picture)
+            self.sync()
+            return out
+        finally:
+            for b in bufs:
+                b.free()
+
+    def make_poster(self, image, *, qscale: int = 2, fps=24, **import_kw) -> bytes:
+        """poster.ts of a title, which the reference's player opens for every title it browses (src/espflix.cpp:1060-1068)
+        and its indexer makes with `-filter:v fps=fps=24 -q 2` (indexer/indexer.cpp:306): the image -- one picture as
+        import_pictures takes it, (H, W, 3), (3, H, W) or with a leading axis of 1 -- imported (import_kw: fmt, fit, crop
+        ...), then one I picture at qscale and fps as a transport stream."""
+        if len(image.shape) == 3:
+            image = image[None]
+        if image.shape[0] != 1:
+            raise ValueError("make_poster takes one image")
+        pic = self.import_pictures(image, **import_kw)
+        res = self.encode(pic.reshape(1, 1, FRAME_BYTES), qscale=qscale, gop=1, fmt=FORMAT_TS, fps=fps)
+        if int(res.status[0]):
+            raise EfxError(-5, f"make_poster: the encoder's status is {int(res.status[0]):#x}")
+        return res.streams[0]
 
     # -- fast-forward and rewind streams (efx_trick_pick) --------------------------------------------
     def trick_pick_to(self, src: DeviceBuffer | int | None, fwd: DeviceBuffer | int | None, rwd: DeviceBuffer | int | None, *,
@@ -1402,7 +1558,7 @@ class Decoder:
 
     def trick_streams(self, pictures=None, *, title=None, speed: int = 15, gop: int = 3, qscale: int = 8, search: int = 7,
                       bitrate: int | None = None, vbv_bits: int = 250_000, qmin: int = 3, qmax: int = 31, first_pts: int = 0,
-                      piece: int | None = None):
+                      piece: int | None = None, fps=None):
         """The fast-forward and the rewind stream of n titles (the reference indexer's `-g 3 ... setpts=PTS/15` and
         `-vf reverse` runs, indexer/indexer.cpp:308-309): every speed-th picture of a title, encoded in playing order and in
         reverse order as transport streams with GOPs of `gop` pictures.  Returns (fwd: list of bytes, rwd: list of bytes,
@@ -1421,12 +1577,13 @@ class Decoder:
         Either way each piece's picks are encoded as they come, continuing the fast-forward stream (encode_to, cont), with
         nothing synchronised between the pick and the encode of a piece; the rewind stream is encoded after the last piece
         (the encoder keeps one set of streams per context, and a reversed stream cannot start before the title has ended).
-        Both streams start at first_pts; trick picture k carries first_pts + 3003 k.  qscale, search and bitrate ... qmax as
-        for encode().  Synchronises: torch's current stream before (tensor input), the library's after."""
+        Both streams start at first_pts; trick picture k carries first_pts + picture_pts_offset(fps, k) (fps as for
+        encode(): None = 30000/1001, first_pts + 3003 k).  qscale, search and bitrate ... qmax as for encode().  Synchronises: torch's current stream before (tensor input), the library's after."""
         if (pictures is None) == (title is None):
             raise ValueError("give pictures or title=, not both")
         if not 1 <= speed <= 255:
             raise ValueError("speed must be 1 .. 255")
+        _fps_code(fps)
         bufs, keep = [], []
         try:
             if pictures is not None:
@@ -1483,7 +1640,8 @@ class Decoder:
                 stride = self.encode_to(src, d_dst.ptr + state["dst"], d_meta.ptr + state["meta"],
                                         d_meta.ptr + state["meta"] + r16(4 * n), n_streams=n, n_pictures=count, qscale=qscale,
                                         gop=gop, search=search, fmt=FORMAT_TS, cont=cont, first_pts=first_pts,
-                                        src_stride=src_stride, bitrate=bitrate, vbv_bits=vbv_bits, qmin=qmin, qmax=qmax)
+                                        src_stride=src_stride, bitrate=bitrate, vbv_bits=vbv_bits, qmin=qmin, qmax=qmax,
+                                        fps=fps)
                 done.append((side, state["dst"], stride, state["meta"]))
                 state["dst"] += n * stride
                 state["meta"] += 2 * r16(4 * n)
@@ -1524,7 +1682,7 @@ class Decoder:
             for b in bufs:
                 b.free()
 
-    def make_title(self, pictures, pcm, *, speed: int = 15, trick_gop: int = 3, **encode_av):
+    def make_title(self, pictures, pcm, *, speed: int = 15, trick_gop: int = 3, fps=None, fps_out=None, poster=None, **encode_av):
         """A complete title directory per stream, as the reference's indexer leaves it (indexer/indexer.cpp:292-321) and its
         player opens it (src/espflix.cpp:647,787-792): returns (list of n dicts {"video.ts", "video_fwd.ts", "video_rwd.ts",
         "video.idx"} of bytes, status: uint32 [3, n], rows video.ts (ENCODE_* | MUX_* bits), video_fwd.ts, video_rwd.ts).
@@ -1534,10 +1692,31 @@ class Decoder:
         from the SOURCE pictures, one generation better than the reference, whose ffmpeg runs recode the finished
         video.ts.  video.idx is idx_build over index_streams([main, fwd, rwd], trick_speed=[1, speed, speed]), one call per
         title -- max_stream_bytes must hold the three streams of a title -- or, on a context with max_streams below 3, one
-        call per stream (the same records: a stream's record does not depend on the others)."""
-        titles, st = self.encode_av(pictures, pcm, **encode_av)
+        call per stream (the same records: a stream's record does not depend on the others).
+
+        fps: the pictures' rate (None = 30000/1001).  A rate MPEG-1 codes is encoded as it is: video.ts and both trick
+        streams carry its code, and trick picture k is at first_pts + picture_pts_offset(fps, k).  Any other rate needs
+        fps_out, a coded rate (ValueError otherwise: nothing is guessed): the pictures are conformed on the device
+        (conform) before encode_av and trick_streams see them.  The PCM is not touched: the audio's PTS come from its
+        sample count.  poster: an image as make_poster takes it; the dictionaries then hold "poster.ts" as well."""
+        if fps is not None and fps_out is None and not picture_rate_code(fps):
+            raise ValueError(f"fps={fps!r} is not a rate MPEG-1 codes; give fps_out=, one of "
+                             f"{', '.join(str(r) for r in PICTURE_RATES.values())}")
+        if fps_out is not None:
+            _fps_code(fps_out)
+            if fps is None:
+                raise ValueError("fps_out= needs fps=, the rate of the pictures")
+            if _rate(fps) != _rate(fps_out):
+                if isinstance(pictures, np.ndarray):
+                    import torch
+                    pictures = torch.from_numpy(np.ascontiguousarray(pictures)).to(torch.device("cuda", self.device))
+                pictures = self.conform(pictures, fps, fps_out)
+            fps = fps_out
+        titles, st = self.encode_av(pictures, pcm, fps=fps, **encode_av)
         keys = ("qscale", "search", "first_pts", "bitrate", "vbv_bits", "qmin", "qmax")
-        fwd, rwd, tst = self.trick_streams(pictures, speed=speed, gop=trick_gop, **{k: encode_av[k] for k in keys if k in encode_av})
+        fwd, rwd, tst = self.trick_streams(pictures, speed=speed, gop=trick_gop, fps=fps,
+                                           **{k: encode_av[k] for k in keys if k in encode_av})
+        poster_ts = None if poster is None else self.make_poster(poster)
         out = []
         for main, f, r in zip(titles, fwd, rwd):
             three, speeds = [main, f, r], [1, speed, speed]
@@ -1547,6 +1726,8 @@ class Decoder:
                 res = [self.index_streams([s], trick_speed=[sp])[0] for s, sp in zip(three, speeds)]
             out.append({"video.ts": main, "video_fwd.ts": f, "video_rwd.ts": r,
                         "video.idx": idx_build([rec for rec, _ in res], [smp for _, smp in res])})
+            if poster_ts is not None:
+                out[-1]["poster.ts"] = poster_ts
         return out, np.vstack([st[None], tst])
 
     def pdm(self, n_streams: int, pcm: DeviceBuffer | int, n_samples: int, state: DeviceBuffer | int,

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "efx.h"
+#include "conform_sel.h"
 #include "efx_internal.h"
 #include "enc_core.h"
 #include "import_px.h"
@@ -65,6 +66,7 @@ __global__ void k_crop_sums_rgbp(CropArgs);
 __global__ void k_crop_rects(CropArgs);
 template <int SOURCE>
 __global__ void k_trick(TrickArgs);  // (k_trick.hip: the I420 and the ring instance)
+__global__ void k_conform(ConformArgs);  // (k_conform.hip)
 __global__ void k_import_pcm(ImportPcmArgs);  // (k_import_pcm.hip)
 __global__ void k_import_pcm_state(ImportPcmArgs);
 __global__ void k_enc_begin(EncArgs);
@@ -289,6 +291,8 @@ struct efx_ctx {
     bool enc_started = false;            // streams exist that cont = 1 may continue
     uint32_t enc_generation = 0;         // fresh efx_encode calls so far: the value a call writes to *h_enc_full when a stream fills up
     int enc_n_streams = 0, enc_format = 0, enc_gop = 0;  // of the call that started them
+    int enc_rate_code = enc::kRateDefault;  // ... and their picture_rate
+    int enc_next_rate_code = enc::kRateDefault;  // efx_encode_set_picture_rate: the picture_rate of the streams a cont = 0 call starts
     bool enc_rc = false;                 // ... which was efx_encode_rc, at enc_bitrate / enc_vbv_bits
     int enc_bitrate = 0, enc_vbv_bits = 0;
 
@@ -2020,6 +2024,76 @@ int efx_trick_pick(efx_ctx* ctx, const efx_trick_opts* o, const uint8_t* src_dev
     return EFX_OK;
 }
 
+// ---- picture rates conformed (k_conform.hip) -------------------------------------------------------------------------------------
+int64_t efx_conform_count(int in_num, int in_den, int out_code, int64_t first_picture, int64_t n_pictures)
+{
+    return csel::count(in_num, in_den, out_code, first_picture, n_pictures);
+}
+
+int64_t efx_conform_source(int in_num, int in_den, int out_code, int64_t n) { return csel::source_of(in_num, in_den, out_code, n); }
+
+int efx_conform_rate(efx_ctx* ctx, const efx_conform_opts* o, const uint8_t* src_device, uint8_t* dst_device)
+{
+    bind_device(ctx);
+    if (!ctx || !o)
+        return EFX_ERR_ARG;
+    if (o->n_streams < 1 || o->n_pictures < 1)
+        return fail(ctx, EFX_ERR_ARG, "efx_conform_rate: n_streams and n_pictures must be >= 1");
+    csel::Ratio r;
+    if (!csel::ratio(o->in_num, o->in_den, o->out_code, &r))
+        return fail(ctx, EFX_ERR_ARG, "efx_conform_rate: in_num / in_den below 1, out_code outside 1 .. 8, a reduced term of the ratio of 2^31 or "
+                                      "more, or rates more than 64 : 1 apart");
+    if (!csel::span_ok(r, o->first_picture, o->n_pictures))
+        return fail(ctx, EFX_ERR_ARG, "efx_conform_rate: first_picture + n_pictures or the last output's index above 2^31 - 1");
+    const int64_t n0 = csel::outputs(r, o->first_picture), n_out = csel::outputs(r, o->first_picture + o->n_pictures) - n0;
+    if (n_out > INT32_MAX || (uint64_t)o->n_streams * (uint64_t)n_out > ((uint64_t)1 << 40))
+        return fail(ctx, EFX_ERR_ARG, "efx_conform_rate: more than 2^40 output pictures in one call");
+    if (!src_device || !dst_device || (((uintptr_t)src_device | (uintptr_t)dst_device) & 15))
+        return fail(ctx, EFX_ERR_ARG, "efx_conform_rate: src_device and dst_device must be 16-byte aligned device pointers");
+    if (o->src_stride < (size_t)o->n_pictures * kFrameBytes || (o->src_stride & 15))
+        return fail(ctx, EFX_ERR_ARG, "efx_conform_rate: src_stride must be a multiple of 16 and hold n_pictures pictures");
+    if (o->dst_stride / kFrameBytes < (uint64_t)n_out || (o->dst_stride & 15))
+        return fail(ctx, EFX_ERR_ARG, "efx_conform_rate: dst_stride must be a multiple of 16 and hold the call's outputs");
+    if (n_out == 0)
+        return EFX_OK;  // nothing to move: no launch
+    ConformArgs a{};
+    a.src = src_device;
+    a.dst = dst_device;
+    a.src_stride = o->src_stride;
+    a.dst_stride = o->dst_stride;
+    a.A = r.A;
+    a.B = r.B;
+    a.first_picture = o->first_picture;
+    a.n0 = n0;
+    a.n_streams = o->n_streams;
+    a.n_out = (int)n_out;
+    // one launch whatever the counts are (a workgroup takes further runs of items when there are more than the grid's)
+    const uint64_t runs = tsel::run_count((uint64_t)o->n_streams * (uint64_t)n_out);
+    hipLaunchKernelGGL(k_conform, dim3((unsigned)std::min<uint64_t>(runs, kTrickMaxBlocks)), dim3(256), 0, ctx->stream, a);
+    EFX_HIP(hipGetLastError());
+    return EFX_OK;
+}
+
+// ---- the encoder's picture rate -----------------------------------------------------------------------------------------------------
+int64_t efx_picture_pts_offset(int code, int64_t k)
+{
+    if (!enc::rate_code_ok(code) || k < 0 || k > ((int64_t)1 << 32))
+        return -1;
+    return enc::rate_pts_offset(code, k);
+}
+
+int efx_picture_rate_code(int64_t num, int64_t den) { return csel::rate_code(num, den); }
+
+int efx_encode_set_picture_rate(efx_ctx* ctx, int code)
+{
+    if (!ctx)
+        return EFX_ERR_ARG;
+    if (!enc::rate_code_ok(code))
+        return fail(ctx, EFX_ERR_ARG, "efx_encode_set_picture_rate: code outside 1 .. 8");
+    ctx->enc_next_rate_code = code;
+    return EFX_OK;
+}
+
 size_t efx_encode_bound(int format, int n_pictures)
 {
     if ((format != EFX_FORMAT_ES && format != EFX_FORMAT_TS) || n_pictures < 1 || n_pictures > 255)
@@ -2131,10 +2205,12 @@ static int encode_impl(efx_ctx* ctx, const efx_encode_opts* o, const efx_encode_
     a.format = o->format;
     a.f_code = o->search <= 7 ? 1 : 2;
     a.cont = o->cont;
+    a.rate_code = o->cont ? ctx->enc_rate_code : ctx->enc_next_rate_code;
     if (rate) {
         a.rc = 1;
         a.rate.cap = (int64_t)rate->vbv_bits * 90000;
         a.rate.gain = (int64_t)rate->bitrate * enc::kRcTick;
+        a.bitrate = rate->bitrate;
         a.rate.qmin = rate->qmin;
         a.rate.qmax = rate->qmax;
         a.rate.q0 = o->qscale < rate->qmin ? rate->qmin : (o->qscale > rate->qmax ? rate->qmax : o->qscale);
@@ -2155,6 +2231,7 @@ static int encode_impl(efx_ctx* ctx, const efx_encode_opts* o, const efx_encode_
         ctx->enc_n_streams = o->n_streams;
         ctx->enc_format = o->format;
         ctx->enc_gop = o->gop;
+        ctx->enc_rate_code = a.rate_code;
         ctx->enc_rc = rate != nullptr;
         ctx->enc_bitrate = rate ? rate->bitrate : 0;
         ctx->enc_vbv_bits = rate ? rate->vbv_bits : 0;

@@ -347,11 +347,24 @@ struct EncArgs {
     uint32_t generation;      // of the streams: counts the fresh efx_encode calls of the context
     int64_t first_pts;
     int n_streams, n_pictures, picture, qscale, gop, search, format, f_code, cont;
+    int rate_code;            // picture_rate of the streams, 1 .. 8 (efx_encode_set_picture_rate; enc_core.h)
     // efx_encode_rc (rc = 1): the quantiser of every picture comes from enc::rate_decide, not from qscale
     int rc;
-    enc::RateParams rate;
+    enc::RateParams rate;     // (gain: of the default picture rate; the kernels put every picture's own in its place)
+    int64_t bitrate;
     uint32_t* act;            // per (stream, row): the row's summed dev and summed min(dev, zero-vector SAD) (k_enc_act)
     uint8_t* qscale_out;      // may be null: the quantiser of (stream i, picture p) at qscale_out + i * n_pictures + p, 0 = not written
+};
+
+// k_conform (k_conform.hip) launch arguments (by value): efx_conform_opts, checked.  Items and runs are k_trick's.
+struct ConformArgs {
+    const uint8_t* src;  // stream i, picture j of the call at src + i * src_stride + j * 101376
+    uint8_t* dst;        // stream i, output n0 + m at dst + i * dst_stride + m * 101376
+    size_t src_stride, dst_stride;
+    int64_t A, B;           // the reduced ratio of conform_sel.h
+    int64_t first_picture;  // title index of the call's picture 0
+    int64_t n0;             // the call's first output
+    int n_streams, n_out;
 };
 
 // k_sbc_enc launch arguments (by value): efx_sbc_encode_opts, checked, with the context's tables

@@ -308,18 +308,41 @@ struct Bits {
     }
 };
 
-// Sequence header (352 x 192, square pels, 29.97 Hz, default matrices) + GOP header (closed) when `seq`, then the picture
-// header: temporal_reference, type (1 = I, 2 = P), vbv_delay 0xFFFF, full_pel_forward_vector 0 and forward_f_code for P.
-// Returns the bytes written (at most kHdrCap).
-EFX_ENC_HD inline uint32_t write_headers(uint8_t* out, bool seq, uint32_t picture_number, int tref, int type, int f_code)
+// The eight picture rates MPEG-1 codes (picture_rate 1 .. 8): one picture period is kRateTickNum / 2^kRateTickShift ticks
+// of 90 kHz (24000/1001 Hz: 15015/4; 60000/1001 Hz: 3003/2), and the GOP time code counts kRateNominal pictures a second
+constexpr int kRateDefault = 4;  // 30000/1001 Hz
+EFX_ENC_HD inline bool rate_code_ok(int code) { return code >= 1 && code <= 8; }
+EFX_ENC_HD inline int64_t rate_tick_num(int code)
+{
+    const int16_t num[9] = {0, 15015, 3750, 3600, 3003, 3000, 1800, 3003, 1500};
+    return num[code];
+}
+EFX_ENC_HD inline int rate_tick_shift(int code) { return code == 1 ? 2 : (code == 7 ? 1 : 0); }
+EFX_ENC_HD inline uint32_t rate_nominal(int code)
+{
+    const uint8_t f[9] = {0, 24, 24, 25, 30, 30, 50, 60, 60};
+    return f[code];
+}
+// 90 kHz ticks from picture 0 to picture k: floor(k x period), no accumulated rounding (k <= 2^32)
+EFX_ENC_HD inline int64_t rate_pts_offset(int code, int64_t k) { return (k * rate_tick_num(code)) >> rate_tick_shift(code); }
+// ... and from picture k to picture k + 1: the period, or one of the two steps around it (codes 1 and 7)
+EFX_ENC_HD inline int64_t rate_pts_step(int code, int64_t k) { return rate_pts_offset(code, k + 1) - rate_pts_offset(code, k); }
+
+// Sequence header (352 x 192, square pels, picture_rate `rate_code`, default matrices) + GOP header (closed, time code of
+// picture_number at the code's nominal rate, drop_frame 0) when `seq`, then the picture header: temporal_reference, type
+// (1 = I, 2 = P), vbv_delay 0xFFFF, full_pel_forward_vector 0 and forward_f_code for P.  Returns the bytes written (at
+// most kHdrCap).
+EFX_ENC_HD inline uint32_t write_headers(uint8_t* out, bool seq, uint32_t picture_number, int tref, int type, int f_code,
+                                         int rate_code = kRateDefault)
 {
     Bits bw{out, 0, 0, 0};
     if (seq) {
+        const uint32_t F = rate_nominal(rate_code);
         bw.start_code(0xB3);
         bw.put(kW, 12);
         bw.put(kH, 12);
         bw.put(1, 4);
-        bw.put(4, 4);
+        bw.put((uint32_t)rate_code, 4);
         bw.put(3750, 18);
         bw.put(1, 1);
         bw.put(20, 10);
@@ -327,8 +350,8 @@ EFX_ENC_HD inline uint32_t write_headers(uint8_t* out, bool seq, uint32_t pictur
         bw.put(0, 1);
         bw.put(0, 1);
         bw.start_code(0xB8);
-        const uint32_t pictures = picture_number % 30, seconds = (picture_number / 30) % 60, minutes = (picture_number / 1800) % 60,
-                       hours = (picture_number / 108000) % 24;
+        const uint32_t pictures = picture_number % F, seconds = (picture_number / F) % 60, minutes = (picture_number / (60 * F)) % 60,
+                       hours = (picture_number / (3600 * F)) % 24;
         bw.put((hours << 19) | (minutes << 13) | (1u << 12) | (seconds << 6) | pictures, 25);
         bw.put(1, 1);  // closed_gop
         bw.put(0, 1);  // broken_link

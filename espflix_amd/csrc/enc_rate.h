@@ -19,7 +19,7 @@
 namespace efx {
 namespace enc {
 
-constexpr int64_t kRcTick = 3003;          // the encoder's fixed PTS step: one picture period in 90 kHz ticks
+constexpr int64_t kRcTick = 3003;          // one picture period in 90 kHz ticks at the default picture rate (30000/1001 Hz)
 constexpr int64_t kRcByte = 8 * 90000;     // one byte in buffer units (1 / 90000 bit)
 constexpr int kRcActBias = 16384;          // activity that stands for what a picture costs before any coefficient
 constexpr int kRcHorizonMax = 48;          // pictures the controller looks ahead, at most
@@ -30,7 +30,7 @@ constexpr int64_t kRcCpaMax = 0xFFFFF;     // bound of the history figure: keeps
 // What a call fixes for every stream (efx_encode_rate, checked)
 struct RateParams {
     int64_t cap;   // C = vbv_bits x 90000
-    int64_t gain;  // G = bitrate x 3003
+    int64_t gain;  // G = bitrate x the ticks the picture lasts (enc_core.h: rate_pts_step; 3003 at the default rate)
     int qmin, qmax, q0;  // q0 = clamp(opts->qscale, qmin, qmax): the first picture of a fresh stream
 };
 

@@ -16,7 +16,8 @@
 //
 // efx_encode_rc: every wave of k_enc_rows adds the twelve row sums of its stream in row order and evaluates
 // enc::rate_decide (enc_rate.h), a pure function of the stream's state and those sums, so all twelve arrive at the same
-// quantiser; k_enc_pack evaluates it once more, then applies the buffer model to the bytes it wrote.
+// quantiser; k_enc_pack evaluates it once more, then applies the buffer model to the bytes it wrote.  The model's gain is
+// the picture's own: bitrate x the ticks from its PTS to the next picture's (rate_params).
 //
 // Every store is a vector store (global / LDS); the only serial part is the bit writer of a slice.
 #include <hip/hip_runtime.h>
@@ -116,6 +117,15 @@ __global__ __launch_bounds__(64) void k_enc_act(EncArgs a)
     }
 }
 
+// The call's rate parameters with the gain of the stream's picture about to be coded: G_k = bitrate x (offset(k + 1) -
+// offset(k)) of the streams' picture rate, used for every picture of the look-ahead's horizon too
+__device__ inline enc::RateParams rate_params(const EncArgs& a, const EncState& S)
+{
+    enc::RateParams p = a.rate;
+    p.gain = a.bitrate * enc::rate_pts_step(a.rate_code, (int64_t)S.pictures);
+    return p;
+}
+
 // The picture's quantiser under rate control: the stream's row sums added in row order, then the controller.  Every wave
 // of a stream (and k_enc_pack) gets the same value.
 __device__ inline int rate_q(const EncArgs& a, const EncState& S, int s, uint32_t* act_i, uint32_t* act_p)
@@ -128,7 +138,7 @@ __device__ inline int rate_q(const EncArgs& a, const EncState& S, int s, uint32_
     }
     *act_i = ai;
     *act_p = ap;
-    return enc::rate_decide(S.rate, a.rate, S.pictures, (int)(S.pictures % (uint32_t)a.gop), a.gop, ai, ap);
+    return enc::rate_decide(S.rate, rate_params(a, S), S.pictures, (int)(S.pictures % (uint32_t)a.gop), a.gop, ai, ap);
 }
 
 __global__ __launch_bounds__(64) void k_enc_rows(EncArgs a)
@@ -278,7 +288,7 @@ __global__ __launch_bounds__(256) void k_enc_pack(EncArgs a)
     const bool ts = a.format == EFX_FORMAT_TS;
     if (tid == 0) {
         seg[0] = 0;
-        seg[1] = write_headers(hdr, phase == 0, S.pictures, (int)phase, type, a.f_code);
+        seg[1] = write_headers(hdr, phase == 0, S.pictures, (int)phase, type, a.f_code, a.rate_code);
         for (int k = 0; k < kMbRows; k++)
             seg[k + 2] = seg[k + 1] + a.slice_len[(size_t)s * kMbRows + k];
         const uint32_t es = seg[kMbRows + 1];
@@ -288,7 +298,7 @@ __global__ __launch_bounds__(256) void k_enc_pack(EncArgs a)
     }
     __syncthreads();
     const uint32_t bytes = sh_bytes, es_len = seg[kMbRows + 1];
-    const int64_t pts = (S.first_pts + 3003 * (int64_t)S.pictures) & ((1ll << 33) - 1);
+    const int64_t pts = (S.first_pts + rate_pts_offset(a.rate_code, (int64_t)S.pictures)) & ((1ll << 33) - 1);
     if (sh_ok) {
         uint8_t* out = a.dst + (size_t)s * a.dst_stride + S.out_len;
         const uint8_t* sl = a.slices + (size_t)s * kMbRows * kSliceCap;
@@ -322,7 +332,7 @@ __global__ __launch_bounds__(256) void k_enc_pack(EncArgs a)
             // a picture that was not written changes nothing of the buffer or the history
             uint32_t act_i, act_p;
             const int q = rate_q(a, S, s, &act_i, &act_p);
-            if (sh_ok && rate_update(&S.rate, a.rate, (int)phase, q, bytes, act_i, act_p))
+            if (sh_ok && rate_update(&S.rate, rate_params(a, S), (int)phase, q, bytes, act_i, act_p))
                 S.status |= EFX_ENCODE_VBV;
             if (a.qscale_out)
                 a.qscale_out[(size_t)s * a.n_pictures + a.picture] = (uint8_t)(sh_ok ? q : 0);

@@ -420,7 +420,8 @@ typedef struct efx_encode_opts {
     int gop;            /* an I picture every `gop` pictures of a stream, 1 .. 255 (1 = I pictures only) */
     int search;         /* full-pel motion search radius 0 .. 15; 0 = the zero vector only */
     int cont;           /* 0: every stream starts afresh; 1: continue the streams of the previous efx_encode */
-    int64_t first_pts;  /* TS, fresh streams: PTS of picture 0 (90 kHz, 0 .. 2^33-1); picture k carries first_pts + 3003 k */
+    int64_t first_pts;  /* TS, fresh streams: PTS of picture 0 (90 kHz, 0 .. 2^33-1); picture k carries first_pts + 3003 k at the
+                           default picture rate (efx_encode_set_picture_rate below) */
     size_t src_stride;  /* bytes from one stream's pictures to the next (>= n_pictures * 101376, multiple of 16) */
     size_t dst_stride;  /* bytes of output region per stream (multiple of 16) */
 } efx_encode_opts;
@@ -428,6 +429,30 @@ int efx_encode(efx_ctx* ctx, const efx_encode_opts* opts, const uint8_t* src_dev
                uint32_t* status_device, uint8_t* recon_device);
 /* Worst-case bytes of one stream of n_pictures pictures in `format` (0 for invalid arguments).  Host only. */
 size_t efx_encode_bound(int format, int n_pictures);
+
+/* -- the encoder's picture rate -- */
+/* MPEG-1 codes eight picture rates.  P = 90 kHz ticks per picture, F = the nominal rate the GOP time code counts with:
+ *   code   rate         P         F          code   rate         P        F
+ *   1      24000/1001   15015/4   24         5      30           3000     30
+ *   2      24           3750      24         6      50           1800     50
+ *   3      25           3600      25         7      60000/1001   3003/2   60
+ *   4      30000/1001   3003      30         8      60           1500     60
+ * efx_encode_set_picture_rate sets the rate of the streams that later cont = 0 calls of efx_encode / efx_encode_rc start;
+ * a fresh context has code 4.  Streams continued with cont = 1 keep the rate they started with, whatever was set in
+ * between.  EFX_ERR_ARG: code outside 1 .. 8 (the rate set before stays).
+ *
+ * What the rate changes, and nothing else: the sequence header's picture_rate is the code; picture k of a stream carries
+ * the PTS (first_pts + floor(k x P)) mod 2^33 -- computed from k, so no rounding accumulates; codes 1 and 7 alternate
+ * between two steps (3753 / 3754, 1501 / 1502) --; the GOP header's time code of picture n is n % F pictures, (n / F) % 60
+ * seconds and so on, drop_frame 0; and efx_encode_rc's gain per picture (below).  The slices of a picture do not depend on
+ * the rate.  The reference decoder reads picture_rate for its drop-frame flag only (src/player.cpp:663,683) and its player
+ * paces video by PTS alone (src/video.cpp:1024-1057), so a title plays at the speed its PTS say.
+ *
+ * efx_picture_pts_offset(code, k) = floor(k x P), host only; -1 for a code outside 1 .. 8 or k outside 0 .. 2^32.
+ * efx_picture_rate_code(num, den) = the code whose rate is num / den exactly (any representation: 48/2 is code 2), or 0. */
+int efx_encode_set_picture_rate(efx_ctx* ctx, int code);
+int64_t efx_picture_pts_offset(int code, int64_t k);
+int efx_picture_rate_code(int64_t num, int64_t den);
 
 /* -- encode to a bit rate: one quantiser_scale per picture under a buffer model (k_encode, enc_rate.h) -- */
 /* The reference's indexer prepares every title with `-b:v 1500k -maxrate 1500k -bufsize 0.25M -qmin 3`
@@ -438,20 +463,23 @@ size_t efx_encode_bound(int format, int n_pictures);
  *
  * The buffer model.  Units are u = 1/90000 bit, in signed 64-bit integers.
  *   capacity            C = vbv_bits x 90000
- *   gain per picture    G = bitrate x 3003          (3003 ticks of 90 kHz: the encoder's fixed PTS step)
+ *   gain of picture k   G_k = bitrate x (offset(k + 1) - offset(k))   the 90 kHz ticks from picture k's PTS to the next one's
+ *                                                   (efx_picture_pts_offset at the streams' picture rate): bitrate x 3003 at the
+ *                                                   default rate, two alternating values at codes 1 and 7
  *   cost of a picture   8 x 90000 x bytes           bytes = what the picture appends to the output in `format`: headers plus
  *                                                   slices (ES), its whole 188-byte packets (TS)
  * A fresh stream starts with F = C.  For each picture written:
  *   1. F -= cost
  *   2. if F < 0 the stream gets the status bit EFX_ENCODE_VBV, which stays set for the rest of the call (like
  *      EFX_ENCODE_FULL, it is reported per call)
- *   3. F = min(C, F + G): a full buffer stops filling (what -maxrate means for a client that pulls); debt is carried,
+ *   3. F = min(C, F + G_k): a full buffer stops filling (what -maxrate means for a client that pulls); debt is carried,
  *      not forgiven
  * A picture that is not written because of EFX_ENCODE_FULL changes nothing.  F is carried across cont = 1 calls.
  *
  * The controller (espflix_amd/csrc/enc_rate.h, DESIGN.md "Rate control") decides from F, from what the stream's previous I
  * and P pictures cost per unit of activity, and from the measured activity of the picture about to be coded, so the first
- * P picture after a scene cut is not coded at the quantiser of the easy pictures before it.  Fixed rules:
+ * P picture after a scene cut is not coded at the quantiser of the easy pictures before it.  Its look-ahead for picture k
+ * uses G_k for every picture of its horizon.  Fixed rules:
  *   - the first picture of a fresh stream is coded at clamp(opts->qscale, qmin, qmax);
  *   - a picture that starts with F <= 0 is coded at qmax;
  *   - with qmin == qmax every picture is coded at that value (the bytes are efx_encode's at that qscale).
@@ -515,8 +543,8 @@ int efx_encode_rc(efx_ctx* ctx, const efx_encode_opts* opts, const efx_encode_ra
  * given.  EFX_ERR_STATE (ring source): no decode yet; the stream range beyond the stream count of the most recent
  * decode; n_pictures >= ring_depth (a picture of the call would already be overwritten).
  *
- * Out of scope: blending or any filtering of the picks (ffmpeg's setpts only drops pictures as well), ffmpeg's frame-rate
- * conform, a rewind stream made piecewise, and the multi-device entry points. */
+ * Out of scope: blending or any filtering of the picks (ffmpeg's setpts only drops pictures as well), a rewind stream made
+ * piecewise, and the multi-device entry points.  (ffmpeg's frame-rate conform is efx_conform_rate, below.) */
 #define EFX_TRICK_FROM_I420 0   /* src_device: pictures in the layout efx_encode reads, stream i at src + i * src_stride */
 #define EFX_TRICK_FROM_RING 1   /* the frame rings: picture j of the most recent efx_decode* of streams first_stream + i */
 typedef struct efx_trick_opts {
@@ -536,6 +564,54 @@ int efx_trick_pick(efx_ctx* ctx, const efx_trick_opts* opts, const uint8_t* src_
 /* The picks a call holds: ceil((first_picture + n_pictures) / speed) - ceil(first_picture / speed).  Host only; -1 for
  * invalid arguments (first_picture outside 0 .. 2^40 - 1, n_pictures outside 0 .. 2^31 - 1, speed outside 1 .. 255). */
 int64_t efx_trick_count(int64_t first_picture, int64_t n_pictures, int speed);
+
+/* -- any constant picture rate conformed to a coded one (k_conform) -------------------------- */
+/* The encoder keeps the source's picture rate where MPEG-1 can code it (efx_encode_set_picture_rate).  Sources at other
+ * rates -- 15, 12.5, 48 or 120 Hz, container rates such as 1000000/41667 -- are conformed first, by dropping and repeating
+ * pictures: ffmpeg's `fps` filter with round=near, stated here as this library's own definition.
+ *
+ * The rule (espflix_amd/csrc/conform_sel.h).  The source runs at r = in_num / in_den Hz, the output at the rate o of
+ * out_code (the table above).  Source picture i, shown at time i / r, belongs to output slot floor(i o / r + 1/2); output
+ * picture n shows the last source picture whose slot is <= n.  With A : B = in_num x out_den : 2 x out_num x in_den,
+ * reduced by their greatest common divisor:
+ *   src(n)  = floor(((2 n + 1) A - 1) / B)
+ *   Nout(N) = max(0, ceil((N B + 1 - A) / (2 A)))    outputs the stream holds after its first N source pictures
+ * Equal rates copy; 50 -> 25 shows 2 n; 15 -> 30 shows floor(n / 2).
+ *   A call offers the source pictures first_picture + j, j = 0 .. n_pictures-1, and writes the outputs Nout(first_picture)
+ *   .. Nout(first_picture + n_pictures) - 1, which may be none.  The placement is call-relative: output Nout(first_picture)
+ *   + m goes to image m.  Every output's source lies inside the call, so pieces need no state, and the outputs of the
+ *   pieces of a title, concatenated, are those of one long call.
+ *
+ * Stream i's pictures at src_device + i * src_stride + j * 101376 (I420, the layout efx_encode reads), its images at
+ * dst_device + i * dst_stride + m * 101376.
+ *
+ * Memory contract.  A dropped source picture is never read, a repeated one is read once per output.  The call writes
+ * only the 101376 bytes of every output image: the bytes between images and between streams are left alone.  The regions
+ * must not overlap; the call cannot check that.
+ *
+ * Asynchronous on the context's stream, no host synchronisation: one launch whatever the counts are, none for a call
+ * without outputs (which returns EFX_OK), and no decoder, encoder, SBC or import state is touched.
+ * EFX_ERR_ARG: a field out of range; a reduced A or B of 2^31 or more; first_picture + n_pictures or an output's index
+ * above 2^31 - 1; rates more than 64 : 1 apart, either way; more than 2^40 output pictures (n_streams x the call's
+ * outputs); a NULL or misaligned (16 bytes) pointer; a stride that is too small or not a multiple of 16.
+ *
+ * Out of scope: blending or motion interpolation; a flush of the last partial output period (when the output rate is the
+ * lower one, up to one output picture at the end of a title is not produced); the frame rings as source; input whose rate
+ * varies; and the multi-device entry points. */
+typedef struct efx_conform_opts {
+    int n_streams;          /* >= 1 */
+    int n_pictures;         /* source pictures per stream offered by this call, >= 1 */
+    int32_t in_num, in_den; /* the source's rate in Hz as a fraction, both >= 1 */
+    int out_code;           /* the output's rate: picture_rate code 1 .. 8 */
+    int64_t first_picture;  /* title index of the call's source picture 0, >= 0 */
+    size_t src_stride;      /* >= n_pictures x 101376, multiple of 16 */
+    size_t dst_stride;      /* >= the call's outputs x 101376, multiple of 16 */
+} efx_conform_opts;
+int efx_conform_rate(efx_ctx* ctx, const efx_conform_opts* opts, const uint8_t* src_device, uint8_t* dst_device);
+/* The outputs a call holds, Nout(first_picture + n_pictures) - Nout(first_picture) (n_pictures may be 0), and the title
+ * index src(n) of the source picture of output n.  Host only; -1 for arguments the call rejects. */
+int64_t efx_conform_count(int in_num, int in_den, int out_code, int64_t first_picture, int64_t n_pictures);
+int64_t efx_conform_source(int in_num, int in_den, int out_code, int64_t n);
 
 /* -- composite video out (video_init / video_isr, src/video.cpp:572-630,1122-1198) -------- */
 typedef struct efx_video_params {
