@@ -44,6 +44,8 @@ STREAM_INTERNAL = 256     # never expected: a lost hand-over inside the reconstr
 STREAM_SLICE_ORDER = 128  # slice start codes of a picture not strictly rising in bitstream order: see efx.h
 ENCODE_FULL = 512         # efx_encode: the stream's output region filled up (efx.h)
 ENCODE_VBV = 4096         # efx_encode_rc: the buffer model's level went below zero during the call (efx.h)
+SCENE_CUT_DEFAULT = 144   # scene_cut=True: the threshold that separates the cuts of the test clips (profiles/scene_cut.md)
+PICTURE_I, PICTURE_P, PICTURE_CUT_I = 1, 2, 5   # efx_enc_picture_info.type
 MUX_FULL = 1024           # efx_mux_av: the stream's output region is too small, nothing written (efx.h)
 MUX_BAD_VIDEO = 2048      # efx_mux_av: the video input is not a transport stream of PID 0x100 that starts with a PES (efx.h)
 PCM_FRAME_PLANAR, PCM_INTERLEAVED = 0, 1   # efx_sbc_encode_opts.pcm_layout
@@ -122,6 +124,14 @@ class _EncodeRate(C.Structure):
     _fields_ = [("bitrate", C.c_int), ("vbv_bits", C.c_int), ("qmin", C.c_int), ("qmax", C.c_int)]
 
 
+class _SceneCut(C.Structure):
+    _fields_ = [("threshold", C.c_int), ("min_gop", C.c_int)]
+
+
+class _EncPictureInfo(C.Structure):
+    _fields_ = [("cut_i", C.c_uint32), ("cut_p", C.c_uint32), ("type", C.c_uint8), ("pad", C.c_uint8 * 3)]
+
+
 class _SbcEncodeOpts(C.Structure):
     _fields_ = [("n_streams", C.c_int), ("n_frames", C.c_int), ("frequency", C.c_int), ("blocks", C.c_int), ("mode", C.c_int),
                 ("allocation", C.c_int), ("bitpool", C.c_int), ("pcm_layout", C.c_int), ("pcm_stride", C.c_size_t),
@@ -147,6 +157,8 @@ class EncodeResult:
     status: np.ndarray     # EFX_ENCODE_* bits per stream
     recon: object = None   # (n, P, 101376) reconstruction (torch tensor or NumPy array), when asked for
     qscales: object = None  # (n, P) uint8 array: every picture's quantiser_scale (0 = not written), when bitrate is given
+    types: object = None   # (n, P) uint8 array: 1 = I, 2 = P, 5 = I placed by the scene-cut rule alone, 0 = not written
+    cut_scores: object = None  # (n, P, 2) uint32 array: every picture's (cut_i, cut_p) (efx.h "scene cuts"; 0 while they are off)
 
 
 class _IdxRec(C.Structure):
@@ -210,6 +222,8 @@ _SYMBOLS = {
     "efx_encode_rc": (C.c_int, [_P, C.POINTER(_EncodeOpts), C.POINTER(_EncodeRate), _P, _P, _P, _P, _P, _P]),
     "efx_encode_bound": (C.c_size_t, [C.c_int, C.c_int]),
     "efx_encode_set_picture_rate": (C.c_int, [_P, C.c_int]),
+    "efx_encode_set_scene_cut": (C.c_int, [_P, C.POINTER(_SceneCut)]),
+    "efx_encode_picture_info": (C.c_int, [_P, C.c_int, C.POINTER(_EncPictureInfo), C.c_int]),
     "efx_picture_pts_offset": (C.c_int64, [C.c_int, C.c_int64]),
     "efx_picture_rate_code": (C.c_int, [C.c_int64, C.c_int64]),
     "efx_conform_rate": (C.c_int, [_P, C.POINTER(_ConformOpts), _P, _P]),
@@ -1007,7 +1021,8 @@ class Decoder:
                   status: DeviceBuffer | int, *, n_streams: int, n_pictures: int, qscale: int = 8, gop: int = 12,
                   search: int = 7, fmt: int = FORMAT_TS, cont: bool = False, first_pts: int = 0, src_stride: int = 0,
                   dst_stride: int = 0, recon: DeviceBuffer | int | None = None, bitrate: int | None = None,
-                  vbv_bits: int = 250_000, qmin: int = 3, qmax: int = 31, qscale_out: DeviceBuffer | int | None = None, fps=None):
+                  vbv_bits: int = 250_000, qmin: int = 3, qmax: int = 31, qscale_out: DeviceBuffer | int | None = None, fps=None,
+                  scene_cut: int | bool | None = None, min_gop: int | None = None):
         """efx_encode on raw device memory (DeviceBuffers or pointers), asynchronous on the library's stream: stream i's
         pictures at src + i * src_stride (0 = packed), its bytes appended to dst + i * dst_stride (0 = efx_encode_bound),
         uint32 byte counts and status bits to length / status, the reconstruction to recon (optional).
@@ -1018,8 +1033,17 @@ class Decoder:
 
         fps: the picture rate of fresh streams, one of PICTURE_RATES as Fraction, "24000/1001", int or 23.976 / 29.97 /
         59.94; None = 30000/1001 (efx_encode_set_picture_rate in front of every cont=False call, so a rate never stays in
-        force from an earlier call).  With cont=True the streams keep their rate: fps must be None or that rate."""
+        force from an earlier call).  With cont=True the streams keep their rate: fps must be None or that rate.
+
+        scene_cut: fresh streams code an I picture where the content changes (efx_encode_set_scene_cut, likewise in front
+        of every cont=False call): the threshold 1 .. 256, True = SCENE_CUT_DEFAULT, None / False / 0 = off; min_gop: no
+        such I picture sooner than this after the last one, None = max(1, gop // 2).  With cont=True the streams keep what
+        they started with and both are ignored."""
         g = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else b)
+        if not cont:
+            threshold = SCENE_CUT_DEFAULT if scene_cut is True else int(scene_cut or 0)
+            sc = _SceneCut(threshold, max(1, gop // 2) if min_gop is None else int(min_gop))
+            _check(self._ctx, self._lib.efx_encode_set_scene_cut(self._ctx, C.byref(sc)))
         if cont:
             if fps is not None and _fps_code(fps) != self._enc_rate_code:
                 raise ValueError(f"fps={fps!r} with cont=True: the streams run at {PICTURE_RATES[self._enc_rate_code]}")
@@ -1040,7 +1064,8 @@ class Decoder:
 
     def encode(self, pictures, *, qscale: int = 8, gop: int = 12, search: int = 7, fmt: int = FORMAT_TS, cont: bool = False,
                first_pts: int = 0, recon: bool = False, dst_stride: int = 0, bitrate: int | None = None,
-               vbv_bits: int = 250_000, qmin: int = 3, qmax: int = 31, fps=None) -> EncodeResult:
+               vbv_bits: int = 250_000, qmin: int = 3, qmax: int = 31, fps=None, scene_cut: int | bool | None = None,
+               min_gop: int | None = None) -> EncodeResult:
         """Encode (n, P, 101376) I420 pictures (the layout export("i420") writes) into n MPEG-1 streams of P pictures: a uint8
         torch tensor on the decoder's device or a NumPy array.  Stream i takes the pictures of row i (the order export()
         gives streams).  Returns each stream's bytes, its status bits and, with recon=True, what a decoder reconstructs
@@ -1058,7 +1083,10 @@ class Decoder:
         and status may carry ENCODE_VBV.  cont=True must keep bitrate and vbv_bits.
 
         fps: the streams' picture rate as for encode_to (None = 30000/1001): picture k carries first_pts +
-        picture_pts_offset(fps, k)."""
+        picture_pts_offset(fps, k).
+
+        scene_cut, min_gop: as for encode_to.  The result's types holds every picture's type and cut_scores its two sums
+        (zeros while scene cuts are off), with or without the option."""
         lead = tuple(pictures.shape[:-1])
         if len(lead) != 2 or pictures.shape[-1] != FRAME_BYTES:
             raise ValueError(f"pictures must have shape (n, P, {FRAME_BYTES}), got {tuple(pictures.shape)}")
@@ -1098,7 +1126,8 @@ class Decoder:
             status_off = (4 * n + 15) // 16 * 16
             self.encode_to(src_ptr, dst, meta.ptr, meta.ptr + status_off, n_streams=n, n_pictures=P, qscale=qscale, gop=gop,
                            search=search, fmt=fmt, cont=cont, first_pts=first_pts, dst_stride=stride, recon=rec_ptr,
-                           bitrate=bitrate, vbv_bits=vbv_bits, qmin=qmin, qmax=qmax, qscale_out=q_buf, fps=fps)
+                           bitrate=bitrate, vbv_bits=vbv_bits, qmin=qmin, qmax=qmax, qscale_out=q_buf, fps=fps, scene_cut=scene_cut,
+                           min_gop=min_gop)
             self.sync()
             lens = meta.download(np.uint32, n)
             st = np.empty(n, dtype=np.uint32)
@@ -1115,10 +1144,27 @@ class Decoder:
             elif recon:
                 out_rec = rec_buf.download(np.uint8, n * P * FRAME_BYTES).reshape(n, P, FRAME_BYTES)
             qs = q_buf.download(np.uint8, n * P).reshape(n, P) if q_buf is not None else None
-            return EncodeResult(streams, st, out_rec, qs)
+            info = self.encode_picture_info(n)
+            types = np.ascontiguousarray(info["type"])
+            return EncodeResult(streams, st, out_rec, qs, types, np.stack([info["cut_i"], info["cut_p"]], axis=-1))
         finally:
             for b in bufs:
                 b.free()
+
+    def encode_picture_info(self, n_streams: int) -> np.ndarray:
+        """The pictures of the latest encode call (efx_encode_picture_info; synchronises): a structured array
+        (n_streams, P) with the fields cut_i, cut_p (uint32) and type (uint8: PICTURE_I, PICTURE_P, PICTURE_CUT_I, 0 = not
+        written)."""
+        dt = np.dtype([("cut_i", "<u4"), ("cut_p", "<u4"), ("type", "u1"), ("pad", "u1", 3)])
+        count = self._lib.efx_encode_picture_info(self._ctx, 0, None, 0)
+        if count < 0:
+            _check(self._ctx, count)
+        out = np.zeros((n_streams, count), dtype=dt)
+        for i in range(n_streams):
+            got = self._lib.efx_encode_picture_info(self._ctx, i, out[i].ctypes.data_as(C.POINTER(_EncPictureInfo)), count)
+            if got < 0:
+                _check(self._ctx, got)
+        return out
 
     # -- video / audio out ----------------------------------------------------------------
     def alloc(self, nbytes: int) -> DeviceBuffer:
@@ -1376,7 +1422,8 @@ class Decoder:
     def encode_av(self, pictures, pcm, *, qscale: int = 8, gop: int = 12, search: int = 7, first_pts: int = 0, blocks: int = 16,
                   allocation: int = 0, bitpool: int = 28, frequency: int = 3, sample_rate: int = 48000, frames_per_pes: int = 8,
                   audio_pid: int = 0x101, bitrate: int | None = None, vbv_bits: int = 250_000, qmin: int = 3, qmax: int = 31,
-                  pcm_rate: int | None = None, pcm_layout: str = "interleaved", fps=None):
+                  pcm_rate: int | None = None, pcm_layout: str = "interleaved", fps=None, scene_cut: int | bool | None = None,
+                  min_gop: int | None = None):
         """Pictures + PCM -> complete titles: encode (transport streams) -> sbc_encode (mono) -> mux, queued back to back on
         the library's stream with nothing synchronised in between.  pictures: (n, P, 101376) I420 as for encode(); pcm: int16
         [n, samples], a whole number of frames of blocks x 8 samples; the audio starts at the first picture's PTS.  Every
@@ -1392,7 +1439,10 @@ class Decoder:
         48 kHz) is not compensated.
 
         fps: the video's picture rate as for encode() (None = 30000/1001).  The audio's PTS come from the sample count
-        and do not depend on it."""
+        and do not depend on it.
+
+        scene_cut, min_gop: I pictures at the video's scene cuts, as for encode(); encode_picture_info(n) afterwards
+        gives the pictures' types."""
         import torch
         device = torch.device("cuda", self.device)
         to_dev = lambda t, dt: torch.from_numpy(np.ascontiguousarray(t)).to(device) if isinstance(t, np.ndarray) else t
@@ -1442,7 +1492,7 @@ class Decoder:
             torch.cuda.current_stream(device).synchronize()
             self.encode_to(pictures.data_ptr(), d_v, p_vlen, p_vst, n_streams=n, n_pictures=P, qscale=qscale, gop=gop, search=search,
                            fmt=FORMAT_TS, first_pts=first_pts, dst_stride=v_stride, bitrate=bitrate, vbv_bits=vbv_bits, qmin=qmin,
-                           qmax=qmax, fps=fps)
+                           qmax=qmax, fps=fps, scene_cut=scene_cut, min_gop=min_gop)
             if imp is not None:
                 self.import_pcm_to(imp[0].data_ptr(), d_istate, pcm.data_ptr(), n_streams=n, n_in=imp[1], in_rate=pcm_rate,
                                    out_rate=sample_rate, channels=imp[2], layout=_PCM_LAYOUTS[pcm_layout], src_stride=imp[3],
@@ -1698,7 +1748,9 @@ class Decoder:
         streams carry its code, and trick picture k is at first_pts + picture_pts_offset(fps, k).  Any other rate needs
         fps_out, a coded rate (ValueError otherwise: nothing is guessed): the pictures are conformed on the device
         (conform) before encode_av and trick_streams see them.  The PCM is not touched: the audio's PTS come from its
-        sample count.  poster: an image as make_poster takes it; the dictionaries then hold "poster.ts" as well."""
+        sample count.  poster: an image as make_poster takes it; the dictionaries then hold "poster.ts" as well.
+
+        scene_cut=, min_gop= (among **encode_av) apply to video.ts only: the trick streams keep their GOPs of trick_gop."""
         if fps is not None and fps_out is None and not picture_rate_code(fps):
             raise ValueError(f"fps={fps!r} is not a rate MPEG-1 codes; give fps_out=, one of "
                              f"{', '.join(str(r) for r in PICTURE_RATES.values())}")

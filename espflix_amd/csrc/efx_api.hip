@@ -70,6 +70,7 @@ __global__ void k_conform(ConformArgs);  // (k_conform.hip)
 __global__ void k_import_pcm(ImportPcmArgs);  // (k_import_pcm.hip)
 __global__ void k_import_pcm_state(ImportPcmArgs);
 __global__ void k_enc_begin(EncArgs);
+__global__ void k_enc_cut(EncArgs);
 __global__ void k_enc_act(EncArgs);
 __global__ void k_enc_rows(EncArgs);
 __global__ void k_enc_pack(EncArgs);
@@ -283,6 +284,9 @@ struct efx_ctx {
     uint8_t* d_enc_slices = nullptr;     // 12 slices of enc::kSliceCap bytes per stream
     uint32_t* d_enc_slice_len = nullptr;
     uint32_t* d_enc_act = nullptr;       // efx_encode_rc: two activity sums per (stream, macroblock row)
+    uint8_t* d_enc_cut_pics = nullptr;   // scene cuts: two decimated source pictures per stream (enc_cut.h)
+    uint32_t* d_enc_cut_sums = nullptr;  // ... two sums per (stream, macroblock row)
+    EncPictureInfo* d_enc_info = nullptr;  // efx_encode_picture_info: kEncInfoCap records per stream, of the latest call
     enc::Tables* d_enc_tables = nullptr;
     std::unique_ptr<enc::Tables> h_enc_tables;  // the source of d_enc_tables' upload
     uint32_t* h_enc_full = nullptr;      // host-mapped: enc_generation of the streams when one of them last filled its region
@@ -295,6 +299,9 @@ struct efx_ctx {
     int enc_next_rate_code = enc::kRateDefault;  // efx_encode_set_picture_rate: the picture_rate of the streams a cont = 0 call starts
     bool enc_rc = false;                 // ... which was efx_encode_rc, at enc_bitrate / enc_vbv_bits
     int enc_bitrate = 0, enc_vbv_bits = 0;
+    enc::CutParams enc_cut{0, 1};        // scene-cut settings of the streams cont = 1 continues
+    enc::CutParams enc_next_cut{0, 1};   // efx_encode_set_scene_cut: those of the streams a cont = 0 call starts
+    int enc_info_streams = 0, enc_info_pictures = 0;  // streams and pictures of the latest call (0: no call yet)
 
     // results of the last decode (fetch_results)
     int n_streams = 0;  // streams of the batch the last decode read
@@ -747,7 +754,7 @@ void efx_destroy(efx_ctx* ctx)
     void* bufs[] = {ctx->d_tables, ctx->d_tm_tables, ctx->d_sbc_flags, ctx->d_sbc_next, ctx->d_sbc_info, ctx->d_sbc_plan, ctx->d_sbc_extra, ctx->d_sbc_cover, ctx->d_state, ctx->d_frames, ctx->d_video[0],  ctx->d_video[1], ctx->d_video_lines[0],
                     ctx->d_video_lines[1], ctx->d_hash, ctx->d_ts, ctx->d_demux_chunks, ctx->d_sbc_tables, ctx->d_idx_info, ctx->d_ts_off, ctx->d_idx_len,
                     ctx->d_idx_base, ctx->d_idx_seq, ctx->d_enc_state, ctx->d_enc_pics, ctx->d_enc_slices, ctx->d_enc_slice_len,
-                    ctx->d_enc_act, ctx->d_enc_tables, ctx->d_sbc_enc_tables, ctx->d_mux_before, ctx->d_import_taps, ctx->d_import_pcm_table,
+                    ctx->d_enc_act, ctx->d_enc_cut_pics, ctx->d_enc_cut_sums, ctx->d_enc_info, ctx->d_enc_tables, ctx->d_sbc_enc_tables, ctx->d_mux_before, ctx->d_import_taps, ctx->d_import_pcm_table,
                     ctx->d_crop_sums};
     if (ctx->h_enc_full)
         (void)hipHostFree(ctx->h_enc_full);
@@ -2094,6 +2101,40 @@ int efx_encode_set_picture_rate(efx_ctx* ctx, int code)
     return EFX_OK;
 }
 
+int efx_encode_set_scene_cut(efx_ctx* ctx, const efx_scene_cut* cut)
+{
+    if (!ctx)
+        return EFX_ERR_ARG;
+    if (!cut) {
+        ctx->enc_next_cut = enc::CutParams{0, 1};
+        return EFX_OK;
+    }
+    if (cut->threshold < 0 || cut->threshold > 256)
+        return fail(ctx, EFX_ERR_ARG, "efx_encode_set_scene_cut: threshold outside 0 .. 256");
+    if (cut->min_gop < 1 || cut->min_gop > 255)
+        return fail(ctx, EFX_ERR_ARG, "efx_encode_set_scene_cut: min_gop outside 1 .. 255");
+    ctx->enc_next_cut = enc::CutParams{cut->threshold, cut->min_gop};
+    return EFX_OK;
+}
+
+int efx_encode_picture_info(efx_ctx* ctx, int stream, efx_enc_picture_info* out_host, int cap)
+{
+    static_assert(sizeof(efx_enc_picture_info) == sizeof(EncPictureInfo), "efx_enc_picture_info layout");
+    bind_device(ctx);
+    if (!ctx)
+        return EFX_ERR_ARG;
+    if (!ctx->enc_info_pictures)
+        return fail(ctx, EFX_ERR_STATE, "efx_encode_picture_info: no efx_encode yet");
+    if (stream < 0 || stream >= ctx->enc_info_streams || cap < 0 || (cap > 0 && !out_host))
+        return fail(ctx, EFX_ERR_ARG, "efx_encode_picture_info: stream outside the latest call's, cap negative or out_host NULL");
+    const int n = std::min(cap, ctx->enc_info_pictures);
+    if (n > 0)
+        EFX_HIP(hipMemcpyAsync(out_host, ctx->d_enc_info + (size_t)stream * kEncInfoCap, (size_t)n * sizeof(EncPictureInfo),
+                               hipMemcpyDeviceToHost, ctx->stream));
+    EFX_HIP(hipStreamSynchronize(ctx->stream));
+    return ctx->enc_info_pictures;
+}
+
 size_t efx_encode_bound(int format, int n_pictures)
 {
     if ((format != EFX_FORMAT_ES && format != EFX_FORMAT_TS) || n_pictures < 1 || n_pictures > 255)
@@ -2157,6 +2198,9 @@ static int encode_impl(efx_ctx* ctx, const efx_encode_opts* o, const efx_encode_
         if (e == hipSuccess) e = dalloc(&ctx->d_enc_slices, n * kMbH * enc::kSliceCap);
         if (e == hipSuccess) e = dalloc(&ctx->d_enc_slice_len, n * kMbH);
         if (e == hipSuccess) e = dalloc(&ctx->d_enc_act, n * kMbH * 2);
+        if (e == hipSuccess) e = dalloc(&ctx->d_enc_cut_pics, 2 * n * enc::kCutBytes);
+        if (e == hipSuccess) e = dalloc(&ctx->d_enc_cut_sums, n * kMbH * 2);
+        if (e == hipSuccess) e = dalloc(&ctx->d_enc_info, n * kEncInfoCap);
         if (e == hipSuccess) e = dalloc(&ctx->d_enc_tables, 1);
         if (e == hipSuccess) {
             ctx->h_enc_tables.reset(new enc::Tables);
@@ -2165,7 +2209,7 @@ static int encode_impl(efx_ctx* ctx, const efx_encode_opts* o, const efx_encode_
         }
         if (e != hipSuccess) {
             void* bufs[] = {ctx->d_enc_state, ctx->d_enc_pics, ctx->d_enc_slices, ctx->d_enc_slice_len, ctx->d_enc_act,
-                            ctx->d_enc_tables};
+                            ctx->d_enc_cut_pics, ctx->d_enc_cut_sums, ctx->d_enc_info, ctx->d_enc_tables};
             for (void* b : bufs)
                 (void)dev_free(b);
             if (ctx->h_enc_full)
@@ -2174,6 +2218,9 @@ static int encode_impl(efx_ctx* ctx, const efx_encode_opts* o, const efx_encode_
             ctx->d_enc_pics = ctx->d_enc_slices = nullptr;
             ctx->d_enc_slice_len = ctx->d_enc_act = ctx->h_enc_full = ctx->d_enc_full = nullptr;
             ctx->d_enc_tables = nullptr;
+            ctx->d_enc_cut_pics = nullptr;
+            ctx->d_enc_cut_sums = nullptr;
+            ctx->d_enc_info = nullptr;
             (void)hipGetLastError();
             return fail(ctx, EFX_ERR_DEVICE, "efx_encode: cannot allocate the encoder's state and scratch", e);
         }
@@ -2206,6 +2253,10 @@ static int encode_impl(efx_ctx* ctx, const efx_encode_opts* o, const efx_encode_
     a.f_code = o->search <= 7 ? 1 : 2;
     a.cont = o->cont;
     a.rate_code = o->cont ? ctx->enc_rate_code : ctx->enc_next_rate_code;
+    a.cut = o->cont ? ctx->enc_cut : ctx->enc_next_cut;
+    a.cut_pics = ctx->d_enc_cut_pics;
+    a.cut_sums = ctx->d_enc_cut_sums;
+    a.info = ctx->d_enc_info;
     if (rate) {
         a.rc = 1;
         a.rate.cap = (int64_t)rate->vbv_bits * 90000;
@@ -2220,13 +2271,18 @@ static int encode_impl(efx_ctx* ctx, const efx_encode_opts* o, const efx_encode_
     hipLaunchKernelGGL(k_enc_begin, dim3((unsigned)((o->n_streams + 63) / 64)), dim3(64), 0, ctx->stream, a);
     for (int p = 0; p < o->n_pictures; p++) {
         a.picture = p;
+        if (a.cut.threshold > 0)
+            hipLaunchKernelGGL(k_enc_cut, dim3((unsigned)o->n_streams * kMbH), dim3(64), 0, ctx->stream, a);
         if (rate)
             hipLaunchKernelGGL(k_enc_act, dim3((unsigned)o->n_streams * kMbH), dim3(64), 0, ctx->stream, a);
         hipLaunchKernelGGL(k_enc_rows, dim3((unsigned)o->n_streams * kMbH), dim3(64), 0, ctx->stream, a);
         hipLaunchKernelGGL(k_enc_pack, dim3((unsigned)o->n_streams), dim3(256), 0, ctx->stream, a);
     }
     EFX_HIP(hipGetLastError());
+    ctx->enc_info_streams = o->n_streams;
+    ctx->enc_info_pictures = o->n_pictures;
     if (!o->cont) {
+        ctx->enc_cut = a.cut;
         ctx->enc_started = true;
         ctx->enc_n_streams = o->n_streams;
         ctx->enc_format = o->format;

@@ -14,6 +14,7 @@
 #pragma once
 #include <cstdint>
 
+#include "enc_cut.h"
 #include "enc_rate.h"
 #include "import_pcm.h"
 
@@ -325,9 +326,19 @@ struct EncState {
     uint32_t full;      // the output region of a call filled up: nothing more is written until the stream starts afresh
     uint32_t out_len;   // bytes written by the current call
     uint32_t status;    // EFX_ENCODE_* bits of the current call
+    uint32_t g;         // pictures since the stream's last I picture, counting it; 0 = fresh (enc_cut.h)
+    uint32_t pad;
     int64_t first_pts;  // PTS of picture 0
     enc::RateState rate;  // efx_encode_rc: buffer level and history (enc_rate.h)
 };
+
+// efx_enc_picture_info as k_enc_pack writes it
+struct EncPictureInfo {
+    uint32_t cut_i, cut_p;
+    uint8_t type, pad[3];
+};
+static_assert(sizeof(EncPictureInfo) == 12, "EncPictureInfo layout");
+constexpr int kEncInfoCap = 255;  // pictures of one call at most
 
 // k_encode launch arguments (by value)
 struct EncArgs {
@@ -354,6 +365,11 @@ struct EncArgs {
     int64_t bitrate;
     uint32_t* act;            // per (stream, row): the row's summed dev and summed min(dev, zero-vector SAD) (k_enc_act)
     uint8_t* qscale_out;      // may be null: the quantiser of (stream i, picture p) at qscale_out + i * n_pictures + p, 0 = not written
+    // scene cuts (enc_cut.h): cut.threshold 0 = off, k_enc_cut is not launched and the sums read as 0
+    enc::CutParams cut;
+    uint8_t* cut_pics;        // two decimated source pictures (enc::kCutBytes) per stream, indexed by pictures & 1
+    uint32_t* cut_sums;       // per (stream, row): the row's cut_i and cut_p (k_enc_cut)
+    EncPictureInfo* info;     // per (stream, picture of the call): stream i's at info + i * 255 (k_enc_pack)
 };
 
 // k_conform (k_conform.hip) launch arguments (by value): efx_conform_opts, checked.  Items and runs are k_trick's.

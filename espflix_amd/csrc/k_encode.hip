@@ -1,6 +1,9 @@
 // k_encode.hip -- batched MPEG-1 I/P encoder (efx_encode): every stream advances one picture per pair of launches.
 //
 //   k_enc_begin   one lane per stream: fresh streams get their state reset, every stream its per-call output counters
+//   k_enc_cut     scene cuts only (efx_encode_set_scene_cut), before everything else of a picture: one wave per (stream,
+//                 macroblock row) decimates the row's source luma 4 x 4 into the stream's decimated picture and measures
+//                 its 22 macroblocks against the previous decimated source picture (enc_cut.h)
 //   k_enc_act     efx_encode_rc only, before every k_enc_rows: one wave per (stream, macroblock row) sums the activity of the
 //                 row's 22 macroblocks -- the luma's deviation from its own mean, and the smaller of that and the SAD
 //                 against the previous reconstruction at the same place -- with v_sad_u8 on whole 352-byte lines
@@ -18,6 +21,10 @@
 // enc::rate_decide (enc_rate.h), a pure function of the stream's state and those sums, so all twelve arrive at the same
 // quantiser; k_enc_pack evaluates it once more, then applies the buffer model to the bytes it wrote.  The model's gain is
 // the picture's own: bitrate x the ticks from its PTS to the next picture's (rate_params).
+//
+// Scene cuts: every wave of k_enc_rows, and k_enc_pack, adds the twelve row sums of k_enc_cut in row order and evaluates
+// enc::cut_picture_type (enc_cut.h), a pure function of the stream's state and those sums, so a stream's picture has one
+// type in every wave -- and the streams of one launch need not have the same.
 //
 // Every store is a vector store (global / LDS); the only serial part is the bit writer of a slice.
 #include <hip/hip_runtime.h>
@@ -39,6 +46,7 @@ __global__ void k_enc_begin(EncArgs a)
         S.cc = 0;
         S.cur = 0;
         S.full = 0;
+        S.g = 0;
         S.first_pts = a.first_pts;
         enc::rate_reset(&S.rate, a.rate);  // (not read without rate control)
     }
@@ -117,6 +125,87 @@ __global__ __launch_bounds__(64) void k_enc_act(EncArgs a)
     }
 }
 
+// Scene-cut measure of one macroblock row (enc_cut.h).  The row's 16 luma lines are read as k_enc_act reads them; the sum
+// of a word's four bytes over four lines is one decimated pel, so lane l holds column l of the row's four decimated lines
+// (lanes 0 .. 23 column 64 + l as well).  They go to LDS and, as words, to the stream's current decimated picture.  The
+// previous decimated picture's rows 4 row - 4 .. 4 row + 7 are staged next to them (its writers ran in the launch
+// before, or in the call before); a macroblock's block is four words, a candidate four v_sad_u8 on alignbyte-shifted
+// words, 22 x 81 candidates across the lanes, the minimum per macroblock kept in LDS.
+__global__ __launch_bounds__(64) void k_enc_cut(EncArgs a)
+{
+    using namespace enc;
+    constexpr int kRowW = kCutW / 4, kStride = kRowW + 2;  // words of a decimated line; staged lines carry the word alignbyte reads past the last
+    const int row = blockIdx.x % kMbRows, s = blockIdx.x / kMbRows, lane = threadIdx.x;
+    const EncState S = a.st[s];
+    const bool has_prev = S.pictures != 0, tail = lane < kW / 4 - 64;
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(a.src + (size_t)s * a.src_stride + (size_t)a.picture * kPicBytes +
+                                                            (size_t)row * 16 * kW);
+    uint8_t* cur = a.cut_pics + ((size_t)s * 2 + (S.pictures & 1)) * kCutBytes;
+    const uint8_t* prev = a.cut_pics + ((size_t)s * 2 + ((S.pictures & 1) ^ 1)) * kCutBytes;
+
+    __shared__ uint32_t cur_w[4 * kRowW];        // the row's four decimated lines
+    __shared__ uint32_t prev_w[12 * kStride];    // lines 4 row - 4 .. 4 row + 7 of the previous decimated picture
+    __shared__ uint32_t best[kMbCols];
+    uint8_t* cur_b = reinterpret_cast<uint8_t*>(cur_w);
+    for (int j = 0; j < 4; j++) {
+        uint32_t sum0 = 0, sum1 = 0;
+        for (int y = 4 * j; y < 4 * j + 4; y++) {
+            sum0 = __builtin_amdgcn_sad_u8(src[y * (kW / 4) + lane], 0u, sum0);
+            if (tail)
+                sum1 = __builtin_amdgcn_sad_u8(src[y * (kW / 4) + 64 + lane], 0u, sum1);
+        }
+        cur_b[j * kCutW + lane] = (uint8_t)((sum0 + 8) >> 4);
+        if (tail)
+            cur_b[j * kCutW + 64 + lane] = (uint8_t)((sum1 + 8) >> 4);
+    }
+    if (lane < kMbCols)
+        best[lane] = 0xFFFFFFFFu;
+    if (has_prev)
+        for (int i = lane; i < 12 * kStride; i += 64) {
+            const int y = i / kStride, x = i - y * kStride, gy = 4 * row - 4 + y;
+            prev_w[i] = (x < kRowW && gy >= 0 && gy < kCutH) ? reinterpret_cast<const uint32_t*>(prev)[gy * kRowW + x] : 0u;
+        }
+    __syncthreads();
+    // the row's 4 x 88 bytes = 88 words of the current decimated picture
+    uint32_t* out = reinterpret_cast<uint32_t*>(cur) + 4 * row * kRowW;
+    out[lane] = cur_w[lane];
+    if (tail)
+        out[64 + lane] = cur_w[64 + lane];
+    uint32_t dev = 0;
+    if (lane < kMbCols) {
+        uint32_t sum = 0;
+        for (int j = 0; j < 4; j++)
+            sum = __builtin_amdgcn_sad_u8(cur_w[j * kRowW + lane], 0u, sum);
+        const uint32_t m = ((sum + 8) >> 4) * 0x01010101u;
+        for (int j = 0; j < 4; j++)
+            dev = __builtin_amdgcn_sad_u8(cur_w[j * kRowW + lane], m, dev);
+    }
+    if (has_prev) {
+        for (int i = lane; i < kMbCols * kCutSide * kCutSide; i += 64) {
+            const int c = i / (kCutSide * kCutSide), v = i - c * (kCutSide * kCutSide);
+            const int dy = v / kCutSide - kCutRange, dx = v - (v / kCutSide) * kCutSide - kCutRange;
+            if (!cut_vector_ok(row, c, dx, dy))
+                continue;
+            const int x = 4 * c + dx, w0 = x >> 2, sh = x & 3;
+            uint32_t sad = 0;
+            for (int j = 0; j < 4; j++) {
+                const int o = (4 + dy + j) * kStride + w0;
+                sad = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(prev_w[o + 1], prev_w[o], sh), cur_w[j * kRowW + c], sad);
+            }
+            atomicMin(&best[c], sad);
+        }
+        __syncthreads();
+    }
+    const uint32_t p = lane < kMbCols ? (has_prev ? min(dev, best[lane]) : dev) : 0u;
+    const int cut_i = wave_sum((int)dev), cut_p = wave_sum((int)p);
+    if (lane == 0) {
+        uint2 w;
+        w.x = (uint32_t)cut_i;
+        w.y = (uint32_t)cut_p;
+        *reinterpret_cast<uint2*>(a.cut_sums + ((size_t)s * kMbRows + row) * 2) = w;
+    }
+}
+
 // The call's rate parameters with the gain of the stream's picture about to be coded: G_k = bitrate x (offset(k + 1) -
 // offset(k)) of the streams' picture rate, used for every picture of the look-ahead's horizon too
 __device__ inline enc::RateParams rate_params(const EncArgs& a, const EncState& S)
@@ -126,9 +215,25 @@ __device__ inline enc::RateParams rate_params(const EncArgs& a, const EncState& 
     return p;
 }
 
+// The picture's type (enc::kTypeI / kTypeP / kTypeCutI): with scene cuts, from the stream's row sums added in row order.
+// Every wave of a stream (and k_enc_pack) gets the same value.
+__device__ inline int picture_type(const EncArgs& a, const EncState& S, int s, uint32_t* cut_i, uint32_t* cut_p)
+{
+    uint32_t ci = 0, cp = 0;
+    if (a.cut.threshold > 0)
+        for (int k = 0; k < enc::kMbRows; k++) {
+            const uint2 w = *reinterpret_cast<const uint2*>(a.cut_sums + ((size_t)s * enc::kMbRows + k) * 2);
+            ci += w.x;
+            cp += w.y;
+        }
+    *cut_i = ci;
+    *cut_p = cp;
+    return enc::cut_picture_type(S.pictures, S.g, a.gop, a.cut, ci, cp);
+}
+
 // The picture's quantiser under rate control: the stream's row sums added in row order, then the controller.  Every wave
 // of a stream (and k_enc_pack) gets the same value.
-__device__ inline int rate_q(const EncArgs& a, const EncState& S, int s, uint32_t* act_i, uint32_t* act_p)
+__device__ inline int rate_q(const EncArgs& a, const EncState& S, int s, int phase, uint32_t* act_i, uint32_t* act_p)
 {
     uint32_t ai = 0, ap = 0;
     for (int k = 0; k < enc::kMbRows; k++) {
@@ -138,7 +243,7 @@ __device__ inline int rate_q(const EncArgs& a, const EncState& S, int s, uint32_
     }
     *act_i = ai;
     *act_p = ap;
-    return enc::rate_decide(S.rate, rate_params(a, S), S.pictures, (int)(S.pictures % (uint32_t)a.gop), a.gop, ai, ap);
+    return enc::rate_decide(S.rate, rate_params(a, S), S.pictures, phase, a.gop, ai, ap);
 }
 
 __global__ __launch_bounds__(64) void k_enc_rows(EncArgs a)
@@ -147,11 +252,13 @@ __global__ __launch_bounds__(64) void k_enc_rows(EncArgs a)
     const int row = blockIdx.x % kMbRows, s = blockIdx.x / kMbRows, lane = threadIdx.x;
     const Tables& T = *a.tab;
     const EncState S = a.st[s];
-    const int type = (S.pictures % (uint32_t)a.gop) == 0 ? 1 : 2;
+    uint32_t cut_i, cut_p;
+    const int ptype = picture_type(a, S, s, &cut_i, &cut_p);
+    const int type = ptype == kTypeP ? 2 : 1;
     int qscale = a.qscale;
     if (a.rc) {
         uint32_t act_i, act_p;
-        qscale = rate_q(a, S, s, &act_i, &act_p);
+        qscale = rate_q(a, S, s, cut_phase(ptype, S.g), &act_i, &act_p);
     }
     const uint8_t* src = a.src + (size_t)s * a.src_stride + (size_t)a.picture * kPicBytes;
     const uint8_t* ref = a.pics + ((size_t)s * 2 + S.cur) * kPicBytes;
@@ -283,8 +390,10 @@ __global__ __launch_bounds__(256) void k_enc_pack(EncArgs a)
     __shared__ uint32_t seg[kMbRows + 2];  // ES offsets: headers, then slice k at seg[k + 1]
     __shared__ uint32_t sh_bytes, sh_ok;
     EncState S = a.st[s];
-    const uint32_t phase = S.pictures % (uint32_t)a.gop;
-    const int type = phase == 0 ? 1 : 2;
+    uint32_t cut_i, cut_p;
+    const int ptype = picture_type(a, S, s, &cut_i, &cut_p);
+    const uint32_t phase = (uint32_t)cut_phase(ptype, S.g);
+    const int type = ptype == kTypeP ? 2 : 1;
     const bool ts = a.format == EFX_FORMAT_TS;
     if (tid == 0) {
         seg[0] = 0;
@@ -331,7 +440,7 @@ __global__ __launch_bounds__(256) void k_enc_pack(EncArgs a)
         if (a.rc) {
             // a picture that was not written changes nothing of the buffer or the history
             uint32_t act_i, act_p;
-            const int q = rate_q(a, S, s, &act_i, &act_p);
+            const int q = rate_q(a, S, s, (int)phase, &act_i, &act_p);
             if (sh_ok && rate_update(&S.rate, rate_params(a, S), (int)phase, q, bytes, act_i, act_p))
                 S.status |= EFX_ENCODE_VBV;
             if (a.qscale_out)
@@ -346,6 +455,12 @@ __global__ __launch_bounds__(256) void k_enc_pack(EncArgs a)
             S.status |= EFX_ENCODE_FULL;
             *(volatile uint32_t*)a.full_flag = a.generation;
         }
+        EncPictureInfo info{};
+        info.cut_i = cut_i;
+        info.cut_p = cut_p;
+        info.type = (uint8_t)(sh_ok ? ptype : 0);
+        a.info[(size_t)s * kEncInfoCap + a.picture] = info;
+        S.g = cut_next_g(ptype, S.g);
         S.pictures++;
         S.cur ^= 1;
         a.st[s] = S;

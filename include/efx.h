@@ -505,6 +505,53 @@ int efx_encode_rc(efx_ctx* ctx, const efx_encode_opts* opts, const efx_encode_ra
                   uint8_t* dst_device, uint32_t* len_device, uint32_t* status_device, uint8_t* recon_device,
                   uint8_t* qscale_out_device);
 
+/* -- scene cuts: an I picture where the content changes (k_encode's k_enc_cut, enc_cut.h) -- */
+/* efx_encode places an I picture every `gop` pictures and nowhere else, so a hard cut that falls between two of them is
+ * coded as a P picture whose search finds nothing, and the first seek point of the new scene is up to gop - 1 pictures
+ * into it.  With scene cuts on, the encoder measures every picture against the stream's previous SOURCE picture (not the
+ * reconstruction: the decision does not depend on the quantiser or the bit rate) and codes a cut as an I picture, with the
+ * sequence and GOP headers every I picture carries -- which makes it a seek point of efx_index_streams.
+ *
+ * The measure.  Decimated luma D[y][x] = (sum of the 4 x 4 luma pels at (4 y, 4 x) + 8) >> 4, 48 x 88.  For macroblock
+ * (r, c), B = the 4 x 4 block of the current D at (4 r, 4 c):
+ *   mean = (sum B + 8) >> 4      dev = sum |B - mean|
+ *   best = the smallest SAD of B against the previous D at (4 r + dy, 4 c + dx) over |dx|, |dy| <= 4, the candidate block
+ *          wholly inside the 48 x 88 picture (the zero vector always is)
+ * and for the picture cut_i = sum dev, cut_p = sum min(dev, best) over its 264 macroblocks.  Picture 0 of a fresh stream
+ * has no previous picture: cut_p = cut_i.
+ *
+ * The rule.  g = pictures since the stream's last I picture, counting it (0 on a fresh stream).  A picture is I when it is
+ * the stream's first, when g == gop, or when it is a cut:
+ *   threshold > 0 && g >= min_gop && cut_p > 8192 && 256 x cut_p > threshold x cut_i
+ * Afterwards g = 1 for an I picture, g + 1 otherwise.  temporal_reference is 0 for an I picture and g (before the update)
+ * for a P picture; the GOP time code and the PTS still count the stream's pictures.  The floor of 8192 keeps fades from and
+ * to black, whose sums are tiny and equal, from counting as cuts.  With threshold 0 the streams are those of efx_encode
+ * without this section, byte for byte.  Under efx_encode_rc the controller sees phase 0 for every I picture and g for a P
+ * picture; nothing else of it changes.
+ *
+ * efx_encode_set_scene_cut sets what the streams of later cont = 0 calls of efx_encode / efx_encode_rc start with; NULL
+ * or threshold 0 = off, as in a fresh context.  Streams continued with cont = 1 keep what they started with (and the
+ * decimated picture and g carry across calls), whatever was set in between.  EFX_ERR_ARG: threshold outside 0 .. 256 or
+ * min_gop outside 1 .. 255 (the earlier setting stays).  One more launch per picture while it is on, whatever n_streams is.
+ * The two decimated pictures per stream (4224 bytes each) are allocated with the encoder's other state at the first efx_encode.
+ *
+ * efx_encode_picture_info reports the pictures of the context's latest efx_encode / efx_encode_rc call for one of its
+ * streams: it waits for the context's stream, writes min(cap, n_pictures) records to out_host and returns n_pictures.
+ * type: 1 = I, 2 = P, 5 = I by the cut rule alone, 0 = not written (EFX_ENCODE_FULL).  cut_i and cut_p are 0 while scene
+ * cuts are off.  EFX_ERR_STATE before the context's first encode; EFX_ERR_ARG: stream outside the latest call's, cap < 0,
+ * out_host NULL with cap > 0. */
+typedef struct efx_scene_cut {
+    int threshold;  /* 0 = off, 1 .. 256: a cut needs 256 cut_p > threshold cut_i; 144 separates the cuts of the test clips */
+    int min_gop;    /* 1 .. 255: no cut I picture sooner than this many pictures after the last I picture */
+} efx_scene_cut;
+int efx_encode_set_scene_cut(efx_ctx* ctx, const efx_scene_cut* cut);
+typedef struct efx_enc_picture_info {
+    uint32_t cut_i, cut_p;
+    uint8_t type;
+    uint8_t pad[3];
+} efx_enc_picture_info;
+int efx_encode_picture_info(efx_ctx* ctx, int stream, efx_enc_picture_info* out_host, int cap);
+
 /* -- fast-forward and rewind streams: which pictures make them (k_trick) ------------------- */
 /* A title of the reference is four files: the player opens video_rwd.ts, video.ts and video_fwd.ts by name
  * (src/espflix.cpp:647,787-792) and maps between them with the three records of video.idx (589-628).  The indexer makes
