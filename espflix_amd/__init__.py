@@ -103,6 +103,15 @@ class _CropOpts(C.Structure):
                [("src_stride", C.c_size_t), ("sums_stride", C.c_size_t)]
 
 
+class _CompareOpts(C.Structure):
+    _fields_ = [("n_images", C.c_int), ("ref_max", C.c_int), ("ref_stride", C.c_size_t), ("test_stride", C.c_size_t),
+                ("mb_stride", C.c_size_t)]
+
+
+class _CompareRec(C.Structure):
+    _fields_ = [("sse", C.c_uint64 * 3), ("ssim", C.c_int64 * 3)]
+
+
 class _TrickOpts(C.Structure):
     _fields_ = [("n_streams", C.c_int), ("n_pictures", C.c_int), ("speed", C.c_int), ("source", C.c_int), ("first_stream", C.c_int),
                 ("first_picture", C.c_int64), ("total_pictures", C.c_int64), ("src_stride", C.c_size_t),
@@ -152,6 +161,16 @@ class _MuxOpts(C.Structure):
 
 
 @dataclass
+class CompareResult:
+    """Quality of pictures against a reference (Decoder.compare; the definition: include/efx.h).  Axis -1: Y, Cb, Cr."""
+    sse: np.ndarray        # (..., 3) uint64: sum of squared errors of each plane
+    ssim_q16: np.ndarray   # (..., 3) int64: sum over the plane's windows of the Q16 SSIM
+    psnr: np.ndarray       # (..., 3) float64: 10 log10(255^2 samples / sse), inf for sse 0
+    ssim: np.ndarray       # (..., 3) float64: ssim_q16 / (65536 x windows)
+    mb_sse: object = None  # (..., 12, 22) uint32: luma SSE of every macroblock, when asked for
+
+
+@dataclass
 class EncodeResult:
     streams: list          # bytes written per stream by the call
     status: np.ndarray     # EFX_ENCODE_* bits per stream
@@ -159,6 +178,7 @@ class EncodeResult:
     qscales: object = None  # (n, P) uint8 array: every picture's quantiser_scale (0 = not written), when bitrate is given
     types: object = None   # (n, P) uint8 array: 1 = I, 2 = P, 5 = I placed by the scene-cut rule alone, 0 = not written
     cut_scores: object = None  # (n, P, 2) uint32 array: every picture's (cut_i, cut_p) (efx.h "scene cuts"; 0 while they are off)
+    quality: object = None  # CompareResult of shape (n, P): the reconstruction against the source (ref_max=248), with quality=True
 
 
 class _IdxRec(C.Structure):
@@ -216,6 +236,9 @@ _SYMBOLS = {
     "efx_import_src_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "efx_import_frames": (C.c_int, [_P, C.POINTER(_ImportOpts), _P, _P]),
     "efx_detect_crop": (C.c_int, [_P, C.POINTER(_CropOpts), _P, _P, _P]),
+    "efx_compare_pictures": (C.c_int, [_P, C.POINTER(_CompareOpts), _P, _P, _P, _P]),
+    "efx_compare_psnr": (C.c_double, [C.c_uint64, C.c_uint64]),
+    "efx_compare_ssim": (C.c_double, [C.c_int64, C.c_int]),
     "efx_trick_pick": (C.c_int, [_P, C.POINTER(_TrickOpts), _P, _P, _P]),
     "efx_trick_count": (C.c_int64, [C.c_int64, C.c_int64, C.c_int]),
     "efx_encode": (C.c_int, [_P, C.POINTER(_EncodeOpts), _P, _P, _P, _P, _P]),
@@ -407,6 +430,30 @@ def _import_geometry(shape, fmt, width, height):
     if (width is not None and width != w) or (height is not None and height != h):
         raise ValueError(f"width= / height= disagree with shape {shape}")
     return fmt, shape[0], w, h
+
+
+COMPARE_SAMPLES = (67584, 16896, 16896)   # samples of the Y, Cb and Cr plane (efx_compare_psnr)
+
+
+def compare_psnr(sse: int, samples: int = COMPARE_SAMPLES[0]) -> float:
+    """10 log10(255^2 samples / sse) of a plane's sum of squared errors (efx_compare_psnr); inf for sse 0.  Host only."""
+    return float(load_library().efx_compare_psnr(int(sse), int(samples)))
+
+
+def compare_ssim(total: int, plane: int = 0) -> float:
+    """The mean SSIM of a plane (0 = Y, 1 / 2 = chroma) from its Q16 sum (efx_compare_ssim); NaN for another plane.
+    Host only."""
+    return float(load_library().efx_compare_ssim(int(total), int(plane)))
+
+
+def _compare_result(recs: np.ndarray, lead: tuple, mb=None) -> CompareResult:
+    """recs: (n, 6) uint64 records as downloaded."""
+    sse = np.ascontiguousarray(recs[:, :3])
+    q = np.ascontiguousarray(recs[:, 3:]).view(np.int64)
+    psnr = np.array([[compare_psnr(v, COMPARE_SAMPLES[p]) for p, v in enumerate(row)] for row in sse.tolist()], dtype=np.float64)
+    ssim = np.array([[compare_ssim(v, p) for p, v in enumerate(row)] for row in q.tolist()], dtype=np.float64)
+    return CompareResult(sse.reshape(*lead, 3), q.reshape(*lead, 3), psnr.reshape(*lead, 3), ssim.reshape(*lead, 3),
+                         None if mb is None else mb.reshape(*lead, 12, 22))
 
 
 def encode_bound(fmt: int, n_pictures: int) -> int:
@@ -939,6 +986,87 @@ class Decoder:
         finally:
             rbuf.free()
 
+    # -- picture quality (efx_compare_pictures) ------------------------------------------------
+    def compare_to(self, ref: DeviceBuffer | int, test: DeviceBuffer | int, recs: DeviceBuffer | int, *, n_images: int,
+                   ref_max: int = 0, ref_stride: int = 0, test_stride: int = 0, mb_sse: DeviceBuffer | int | None = None,
+                   mb_stride: int = 0):
+        """efx_compare_pictures on raw device memory (DeviceBuffers or pointers), asynchronous on the library's stream:
+        I420 image k of the reference at ref + k * ref_stride and of the picture under test at test + k * test_stride
+        (0 = 101376), its 48-byte record (uint64 sse[3], int64 ssim[3] for Y, Cb, Cr; the definition: include/efx.h) to
+        recs + 48 k.  ref_max: reference samples above it count as it (0 = no clamp, 248 = the decoder's).  mb_sse: when
+        given, receives every macroblock's luma SSE (uint32), image k at + 4 * k * mb_stride bytes (0 = 264)."""
+        g = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
+        o = _CompareOpts(n_images, ref_max, ref_stride, test_stride, mb_stride)
+        _check(self._ctx, self._lib.efx_compare_pictures(self._ctx, C.byref(o), g(ref), g(test), g(recs), g(mb_sse)))
+
+    def _compare_input(self, pictures, bufs: list, keep: list) -> int:
+        """(..., 101376) pictures in device memory, packed: an array is uploaded into a DeviceBuffer appended to bufs, a
+        tensor is used in place (copied when not packed or aligned) and appended to keep."""
+        if isinstance(pictures, np.ndarray):
+            buf = DeviceBuffer(self, max(16, pictures.size))
+            bufs.append(buf)
+            buf.upload(np.ascontiguousarray(pictures, dtype=np.uint8))
+            return buf.ptr
+        import torch
+        device = torch.device("cuda", self.device)
+        if not isinstance(pictures, torch.Tensor) or pictures.dtype != torch.uint8 or pictures.device != device:
+            raise ValueError(f"pictures must be uint8 tensors on {device} (or NumPy arrays)")
+        flat = pictures.contiguous()
+        if flat.data_ptr() % 16:
+            flat = flat.clone()
+        keep.append(flat)
+        return flat.data_ptr()
+
+    def _compare_download(self, ref_ptr: int, test_ptr: int, n: int, lead: tuple, ref_max: int, macroblocks: bool) -> CompareResult:
+        """Compare n packed pictures, wait, and read the records (and maps) back."""
+        out = DeviceBuffer(self, 48 * n + (264 * 4 * n if macroblocks else 0))
+        try:
+            self.compare_to(ref_ptr, test_ptr, out, n_images=n, ref_max=ref_max, mb_sse=out.ptr + 48 * n if macroblocks else None)
+            self.sync()
+            recs = out.download(np.uint64, 6 * n).reshape(n, 6)
+            mb = None
+            if macroblocks:
+                mb = np.empty(264 * n, dtype=np.uint32)
+                _check(self._ctx, self._lib.efx_memcpy_d2h(self._ctx, mb.ctypes.data, out.ptr + 48 * n, mb.nbytes))
+            return _compare_result(recs, lead, mb)
+        finally:
+            out.free()
+
+    def compare(self, ref, test, *, ref_max: int = 0, macroblocks: bool = False) -> CompareResult:
+        """PSNR and SSIM of pictures against reference pictures, measured on the device (efx_compare_pictures): ref and
+        test are (..., 101376) I420 pictures (the layout encode() takes and export("i420") gives) of the same leading
+        shape, uint8 NumPy arrays or torch tensors on the decoder's device (tensors are used in place).  ref_max:
+        reference samples above it count as it -- 0 = no clamp, 248 = the decoder's clamp, for a source against its
+        reconstruction.  Returns a CompareResult of the leading shape; macroblocks=True adds every macroblock's luma
+        SSE.  Synchronises: torch's current stream before (tensor input), the library's after."""
+        lead = tuple(ref.shape[:-1])
+        if ref.shape[-1] != FRAME_BYTES or tuple(test.shape) != tuple(ref.shape):
+            raise ValueError(f"ref and test must have the same shape (..., {FRAME_BYTES}), got {tuple(ref.shape)} and {tuple(test.shape)}")
+        n = int(np.prod(lead, dtype=np.int64))
+        if n < 1:
+            raise ValueError("no pictures to compare")
+        bufs, keep = [], []
+        try:
+            ref_ptr = self._compare_input(ref, bufs, keep)
+            test_ptr = ref_ptr if test is ref else self._compare_input(test, bufs, keep)
+            if keep:
+                import torch
+                torch.cuda.current_stream(torch.device("cuda", self.device)).synchronize()
+            return self._compare_download(ref_ptr, test_ptr, n, lead, ref_max, macroblocks)
+        finally:
+            for b in bufs:
+                b.free()
+
+    def _encode_quality(self, q_buf: DeviceBuffer, n: int, P: int, types: np.ndarray) -> CompareResult:
+        """The records encode() / encode_av() queued behind the encode; pictures that were not written give zeros."""
+        recs = q_buf.download(np.uint64, 6 * n * P).reshape(n * P, 6)
+        recs[types.reshape(-1) == 0] = 0
+        res = _compare_result(recs, (n, P))
+        unwritten = types.reshape(n, P) == 0
+        res.psnr[unwritten] = 0.0
+        res.ssim[unwritten] = 0.0
+        return res
+
     def import_pictures(self, src, *, fmt: str | None = None, width: int | None = None, height: int | None = None, crop=None,
                         fit: str = "stretch", full_range: bool = False, out=None, sync: bool = True, crop_limit: int = 24,
                         crop_round: int = 16):
@@ -1065,7 +1193,7 @@ class Decoder:
     def encode(self, pictures, *, qscale: int = 8, gop: int = 12, search: int = 7, fmt: int = FORMAT_TS, cont: bool = False,
                first_pts: int = 0, recon: bool = False, dst_stride: int = 0, bitrate: int | None = None,
                vbv_bits: int = 250_000, qmin: int = 3, qmax: int = 31, fps=None, scene_cut: int | bool | None = None,
-               min_gop: int | None = None) -> EncodeResult:
+               min_gop: int | None = None, quality: bool = False) -> EncodeResult:
         """Encode (n, P, 101376) I420 pictures (the layout export("i420") writes) into n MPEG-1 streams of P pictures: a uint8
         torch tensor on the decoder's device or a NumPy array.  Stream i takes the pictures of row i (the order export()
         gives streams).  Returns each stream's bytes, its status bits and, with recon=True, what a decoder reconstructs
@@ -1086,7 +1214,12 @@ class Decoder:
         picture_pts_offset(fps, k).
 
         scene_cut, min_gop: as for encode_to.  The result's types holds every picture's type and cut_scores its two sums
-        (zeros while scene cuts are off), with or without the option."""
+        (zeros while scene cuts are off), with or without the option.
+
+        quality=True: the reconstruction is kept on the device (in a buffer of the call's own when recon=False) and
+        compared with the source right behind the encode, on the same stream (compare_to with ref_max=248, the
+        decoder's clamp); the result's quality is the CompareResult of shape (n, P), zeros for pictures that were not
+        written.  Without it nothing is launched or allocated for this."""
         lead = tuple(pictures.shape[:-1])
         if len(lead) != 2 or pictures.shape[-1] != FRAME_BYTES:
             raise ValueError(f"pictures must have shape (n, P, {FRAME_BYTES}), got {tuple(pictures.shape)}")
@@ -1117,8 +1250,8 @@ class Decoder:
                 q_buf = DeviceBuffer(self, n * P)
                 bufs.append(q_buf)
             rec_ptr = None
-            if recon and rec_t is None:
-                rec_buf = DeviceBuffer(self, n * P * FRAME_BYTES)
+            if (recon or quality) and rec_t is None:
+                rec_buf = DeviceBuffer(self, max(16, n * P * FRAME_BYTES))
                 bufs.append(rec_buf)
                 rec_ptr = rec_buf.ptr
             elif rec_t is not None:
@@ -1128,6 +1261,11 @@ class Decoder:
                            search=search, fmt=fmt, cont=cont, first_pts=first_pts, dst_stride=stride, recon=rec_ptr,
                            bitrate=bitrate, vbv_bits=vbv_bits, qmin=qmin, qmax=qmax, qscale_out=q_buf, fps=fps, scene_cut=scene_cut,
                            min_gop=min_gop)
+            qual_buf = None
+            if quality and n * P:
+                qual_buf = DeviceBuffer(self, 48 * n * P)
+                bufs.append(qual_buf)
+                self.compare_to(src_ptr, rec_ptr, qual_buf, n_images=n * P, ref_max=248)
             self.sync()
             lens = meta.download(np.uint32, n)
             st = np.empty(n, dtype=np.uint32)
@@ -1146,7 +1284,8 @@ class Decoder:
             qs = q_buf.download(np.uint8, n * P).reshape(n, P) if q_buf is not None else None
             info = self.encode_picture_info(n)
             types = np.ascontiguousarray(info["type"])
-            return EncodeResult(streams, st, out_rec, qs, types, np.stack([info["cut_i"], info["cut_p"]], axis=-1))
+            qual = self._encode_quality(qual_buf, n, P, types) if qual_buf is not None else None
+            return EncodeResult(streams, st, out_rec, qs, types, np.stack([info["cut_i"], info["cut_p"]], axis=-1), qual)
         finally:
             for b in bufs:
                 b.free()
@@ -1423,7 +1562,7 @@ class Decoder:
                   allocation: int = 0, bitpool: int = 28, frequency: int = 3, sample_rate: int = 48000, frames_per_pes: int = 8,
                   audio_pid: int = 0x101, bitrate: int | None = None, vbv_bits: int = 250_000, qmin: int = 3, qmax: int = 31,
                   pcm_rate: int | None = None, pcm_layout: str = "interleaved", fps=None, scene_cut: int | bool | None = None,
-                  min_gop: int | None = None):
+                  min_gop: int | None = None, quality: bool = False):
         """Pictures + PCM -> complete titles: encode (transport streams) -> sbc_encode (mono) -> mux, queued back to back on
         the library's stream with nothing synchronised in between.  pictures: (n, P, 101376) I420 as for encode(); pcm: int16
         [n, samples], a whole number of frames of blocks x 8 samples; the audio starts at the first picture's PTS.  Every
@@ -1442,7 +1581,11 @@ class Decoder:
         and do not depend on it.
 
         scene_cut, min_gop: I pictures at the video's scene cuts, as for encode(); encode_picture_info(n) afterwards
-        gives the pictures' types."""
+        gives the pictures' types.
+
+        quality=True: the video's reconstruction is kept in a device buffer of the call's own and compared with the
+        pictures right behind the encode, on the same stream, as for encode(); the call then returns (titles, status,
+        quality), quality the CompareResult of shape (n, P), zeros for pictures that were not written."""
         import torch
         device = torch.device("cuda", self.device)
         to_dev = lambda t, dt: torch.from_numpy(np.ascontiguousarray(t)).to(device) if isinstance(t, np.ndarray) else t
@@ -1489,10 +1632,16 @@ class Decoder:
                 bufs.append(d_istate)
                 d_istate.upload(np.zeros(n * import_pcm_state_bytes(), dtype=np.uint8))
             p_vlen, p_vst, p_len, p_st = (d_meta.ptr + k * r16(4 * n) for k in range(4))
+            d_rec = d_qual = None
+            if quality and n * P:
+                d_rec, d_qual = DeviceBuffer(self, n * P * FRAME_BYTES), DeviceBuffer(self, 48 * n * P)
+                bufs += [d_rec, d_qual]
             torch.cuda.current_stream(device).synchronize()
             self.encode_to(pictures.data_ptr(), d_v, p_vlen, p_vst, n_streams=n, n_pictures=P, qscale=qscale, gop=gop, search=search,
                            fmt=FORMAT_TS, first_pts=first_pts, dst_stride=v_stride, bitrate=bitrate, vbv_bits=vbv_bits, qmin=qmin,
-                           qmax=qmax, fps=fps, scene_cut=scene_cut, min_gop=min_gop)
+                           qmax=qmax, fps=fps, scene_cut=scene_cut, min_gop=min_gop, recon=d_rec)
+            if d_qual is not None:
+                self.compare_to(pictures.data_ptr(), d_rec, d_qual, n_images=n * P, ref_max=248)
             if imp is not None:
                 self.import_pcm_to(imp[0].data_ptr(), d_istate, pcm.data_ptr(), n_streams=n, n_in=imp[1], in_rate=pcm_rate,
                                    out_rate=sample_rate, channels=imp[2], layout=_PCM_LAYOUTS[pcm_layout], src_stride=imp[3],
@@ -1508,6 +1657,10 @@ class Decoder:
             titles, st = self._download_streams(d_dst.ptr, stride, p_len, p_st, n)
             vst = np.empty(n, dtype=np.uint32)
             _check(self._ctx, self._lib.efx_memcpy_d2h(self._ctx, vst.ctypes.data, p_vst, 4 * n))
+            if quality:
+                types = np.ascontiguousarray(self.encode_picture_info(n)["type"]) if n * P else np.zeros((n, P), dtype=np.uint8)
+                qual = self._encode_quality(d_qual, n, P, types) if d_qual is not None else _compare_result(np.zeros((0, 6), np.uint64), (n, P))
+                return titles, st | vst, qual
             return titles, st | vst
         finally:
             for b in bufs:

@@ -22,6 +22,7 @@
 #include "enc_core.h"
 #include "import_px.h"
 #include "crop_px.h"
+#include "quality_px.h"
 #include "parse_tm.h"
 #include "sbc_enc_core.h"
 #include "trick_sel.h"
@@ -64,6 +65,9 @@ __global__ void k_crop_sums_i420(CropArgs);
 __global__ void k_crop_sums_rgb24(CropArgs);
 __global__ void k_crop_sums_rgbp(CropArgs);
 __global__ void k_crop_rects(CropArgs);
+__global__ void k_quality_zero(QualityArgs);  // (k_quality.hip)
+__global__ void k_quality(QualityArgs);
+__global__ void k_quality_clamp(QualityArgs);
 template <int SOURCE>
 __global__ void k_trick(TrickArgs);  // (k_trick.hip: the I420 and the ring instance)
 __global__ void k_conform(ConformArgs);  // (k_conform.hip)
@@ -1935,6 +1939,59 @@ int efx_detect_crop(efx_ctx* ctx, const efx_crop_opts* o, const void* src_device
     auto* const k_sums = a.format == EFX_PIX_I420 ? k_crop_sums_i420 : a.format == EFX_PIX_RGB24 ? k_crop_sums_rgb24 : k_crop_sums_rgbp;
     hipLaunchKernelGGL(k_sums, dim3((unsigned)std::min(sum_wgs, cap)), dim3(256), 0, ctx->stream, a);
     hipLaunchKernelGGL(k_crop_rects, dim3((unsigned)std::min((size_t)a.n_streams, cap)), dim3(256), 0, ctx->stream, a);
+    EFX_HIP(hipGetLastError());
+    return EFX_OK;
+}
+
+// ---- picture quality (k_quality.hip) ------------------------------------------------------------------------------------------------
+double efx_compare_psnr(uint64_t sse, uint64_t samples)
+{
+    if (!samples)
+        return NAN;
+    if (!sse)
+        return INFINITY;
+    return 10.0 * std::log10(65025.0 * (double)samples / (double)sse);
+}
+
+double efx_compare_ssim(int64_t sum, int plane)
+{
+    const int64_t w = qpx::windows(plane);
+    return w ? (double)sum / (65536.0 * (double)w) : NAN;
+}
+
+int efx_compare_pictures(efx_ctx* ctx, const efx_compare_opts* o, const uint8_t* ref_device, const uint8_t* test_device,
+                         efx_compare_rec* recs_device, uint32_t* mb_sse_device)
+{
+    bind_device(ctx);
+    if (!ctx || !o)
+        return EFX_ERR_ARG;
+    if (!ref_device || ((uintptr_t)ref_device & 15) || !test_device || ((uintptr_t)test_device & 15) || !recs_device ||
+        ((uintptr_t)recs_device & 15) || ((uintptr_t)mb_sse_device & 15))
+        return fail(ctx, EFX_ERR_ARG, "efx_compare_pictures: ref_device, test_device, recs_device and mb_sse_device (when given) must be 16-byte aligned device pointers");
+    if (o->n_images < 1)
+        return fail(ctx, EFX_ERR_ARG, "efx_compare_pictures: n_images must be >= 1");
+    if (o->ref_max < 0 || o->ref_max > 255)
+        return fail(ctx, EFX_ERR_ARG, "efx_compare_pictures: ref_max outside 0 .. 255");
+    QualityArgs a{};
+    a.ref = ref_device, a.test = test_device;
+    a.recs = reinterpret_cast<uint64_t*>(recs_device);
+    a.mb_sse = mb_sse_device;
+    a.n_images = o->n_images;
+    a.ref_max = o->ref_max ? o->ref_max : 255;
+    a.ref_stride = o->ref_stride ? o->ref_stride : (size_t)qpx::kImageBytes;
+    a.test_stride = o->test_stride ? o->test_stride : (size_t)qpx::kImageBytes;
+    a.mb_stride = o->mb_stride ? o->mb_stride : (size_t)kMbCount;
+    if (a.ref_stride < (size_t)qpx::kImageBytes || (a.ref_stride & 15) || a.test_stride < (size_t)qpx::kImageBytes || (a.test_stride & 15))
+        return fail(ctx, EFX_ERR_ARG, "efx_compare_pictures: ref_stride and test_stride must be multiples of 16 and hold an image");
+    if (a.mb_stride < (size_t)kMbCount || (a.mb_stride & 3))
+        return fail(ctx, EFX_ERR_ARG, "efx_compare_pictures: mb_stride must be a multiple of 4 and hold 264 elements");
+    // two launches whatever n_images is (a workgroup takes further items when there are more than the grid's)
+    const size_t cap = (size_t)1 << 20;
+    const size_t zero_wgs = ((size_t)a.n_images * 3 + 255) / 256;
+    const size_t band_wgs = (size_t)a.n_images * qpx::kBands;
+    hipLaunchKernelGGL(k_quality_zero, dim3((unsigned)std::min(zero_wgs, cap)), dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL(a.ref_max < 255 ? k_quality_clamp : k_quality, dim3((unsigned)std::min(band_wgs, cap)), dim3(qpx::kThreads), 0,
+                       ctx->stream, a);
     EFX_HIP(hipGetLastError());
     return EFX_OK;
 }

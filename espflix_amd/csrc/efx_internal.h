@@ -207,6 +207,16 @@ struct CropArgs {
     int format, width, height, full_range, limit, round;
 };
 
+// k_quality_zero / k_quality launch arguments (by value): efx_compare_opts, checked (k_quality.hip)
+struct QualityArgs {
+    const uint8_t* ref;     // image k of the reference at ref + k * ref_stride
+    const uint8_t* test;    // image k of the picture under test at test + k * test_stride
+    uint64_t* recs;         // image k: its efx_compare_rec, six 8-byte words at recs + 6 k
+    uint32_t* mb_sse;       // image k: 264 words at mb_sse + k * mb_stride; may be null
+    size_t ref_stride, test_stride, mb_stride;
+    int n_images, ref_max;  // ref_max 1 .. 255 (255: the launch takes the kernel without the clamp)
+};
+
 // k_import_pcm / k_import_pcm_state launch arguments (by value): efx_import_pcm_opts, checked, as import_pcm.h's plan
 struct ImportPcmArgs {
     const int16_t* src;    // stream i at src + i * src_stride

@@ -371,6 +371,72 @@ typedef struct efx_crop_rect { int32_t x, y, w, h, x1, y1, x2, y2; } efx_crop_re
 int efx_detect_crop(efx_ctx* ctx, const efx_crop_opts* opts, const void* src_device, efx_crop_rect* rects_device,
                     uint32_t* sums_device /* may be NULL */);
 
+/* -- picture quality: PSNR and SSIM of picture batches (k_quality) ------------------------- */
+/* The library tells a caller how many bytes a picture took; efx_compare_pictures tells how good it is: what ffmpeg
+ * answers with `-psnr` and the `ssim` filter, on the device, for a whole batch, as a reduction -- two picture sets are
+ * read once and 48 bytes per picture are left.  The definition is exact integer arithmetic
+ * (espflix_amd/csrc/quality_px.h), bit-reproducible anywhere.
+ *
+ *   Pictures.  Both inputs are I420 pictures in the layout efx_encode reads and efx_export_frames writes: Y 192 x 352,
+ *   Cb 96 x 176, Cr 96 x 176, 101 376 bytes.  Image k of the reference is at ref + k x ref_stride, image k of the picture
+ *   under test at test + k x test_stride.
+ *   Reference clamp.  With ref_max = m (1 .. 255) every reference sample a is taken as min(a, m) before anything else;
+ *   test samples are never changed.  ref_max = 0 means 255 (no clamp); m = 248 is the decoder's clamp: a source against
+ *   what a decoder reconstructs from it.
+ *   Blocks.  Each plane is tiled by 4 x 4 blocks, 88 x 48 for luma and 44 x 24 for each chroma plane.  For a block, with
+ *   a the clamped reference and b the test samples:  s1 = sum a,  s2 = sum b,  ss = sum (a^2 + b^2),  s12 = sum a b.
+ *   SSE.  Per plane sse = sum (a - b)^2 = sum over blocks of (ss - 2 s12), exact in uint64 (luma reaches 67584 x 65025 =
+ *   4 394 649 600, above 2^32).
+ *   Per-macroblock luma SSE (optional output).  For macroblock (r, c), r < 12, c < 22: the SSE of luma rows 16r .. 16r +
+ *   15 and columns 16c .. 16c + 15, a uint32 at index 22r + c (at most 256 x 65025).
+ *   SSIM.  x264's and ffmpeg's 8 x 8 window on a 4-pel grid, made exact.  A window is 2 x 2 adjacent blocks: windows
+ *   (i, j) with i < rows - 1 and j < cols - 1 of the block grid, 87 x 47 = 4089 for luma and 43 x 23 = 989 for each
+ *   chroma plane.  With S1, S2, SS, S12 the sums of the four blocks' values:
+ *       vars  = 64 SS - S1^2 - S2^2          covar = 64 S12 - S1 S2
+ *       c1 = 416                             c2 = 235963
+ *       num = (2 S1 S2 + c1) (2 covar + c2)
+ *       den = (S1^2 + S2^2 + c1) (vars + c2)
+ *       q   = sign(num) floor(|num| 65536 / den)        (Q16, truncated toward zero)
+ *   vars >= 0 and 2 |covar| <= vars, so |num| <= den < 2.9e17 and q lies in [-65536, 65536]; num and den fit a signed
+ *   64-bit integer, |num| x 65536 does not: the quotient is an estimate corrected exactly with its remainder.  The plane's
+ *   result is the int64 sum of q over its windows.
+ *   Record.  48 bytes per image: sse[3], ssim[3] for Y, Cb, Cr.
+ *   Derived values (host only).  PSNR = 10 log10(255^2 samples / sse), +infinity for sse 0, samples 67584 for luma and
+ *   16896 for a chroma plane; mean SSIM = ssim / (65536 windows).  Each window's q / 65536 is lower in magnitude than the
+ *   real quotient by less than 2^-16, so a plane's mean SSIM differs from a float64 evaluation by less than 2^-16.
+ *   Anchors (luma).  Identical planes: sse 0, ssim 4089 x 65536 = 267 976 704.  Reference all 0 against test all 255: sse
+ *   4 394 649 600, ssim 0.  The checkerboard ((x + y) & 1) x 255 against its inverse: sse 4 394 649 600, ssim
+ *   4089 x -65304 = -267 028 056.  Identical chroma planes: 989 x 65536 = 64 815 104 each.
+ *
+ * Memory contract.  For image k the kernels read only the 101 376 bytes at ref + k x ref_stride and at test + k x
+ * test_stride (ref_device == test_device is allowed), in 16-byte pieces; the luma rows 16b .. 16b + 3 (b = 1 .. 11) and
+ * the chroma rows 8b .. 8b + 3 are asked for twice, by adjacent workgroups.  Every call writes all n_images records in
+ * full -- it never accumulates into what the buffer held before -- and, when mb_sse_device is given, the 264 elements of
+ * each image at mb_sse_device + k x mb_stride; the bytes between images are not written in any buffer.  All offsets are
+ * computed in 64 bits.
+ *
+ * Out of scope: the frame rings as a source (export first), pictures of other sizes, Gaussian-window SSIM, MS-SSIM and
+ * VMAF. */
+typedef struct efx_compare_opts {
+    int n_images;        /* >= 1; not tied to max_streams */
+    int ref_max;         /* 0 = 255 (no clamp), else 1 .. 255 */
+    size_t ref_stride;   /* bytes between reference images; 0 = 101376; multiple of 16, >= 101376 */
+    size_t test_stride;  /* likewise */
+    size_t mb_stride;    /* uint32 elements between images in mb_sse_device; 0 = 264; multiple of 4, >= 264 */
+} efx_compare_opts;
+typedef struct efx_compare_rec { uint64_t sse[3]; int64_t ssim[3]; } efx_compare_rec;
+/* Asynchronous on the context's stream: no host synchronisation, two launches whatever n_images is (the records to zero,
+ * the sums), no scratch memory, and no decoder, encoder, SBC or import state is touched.
+ * EFX_ERR_ARG: a NULL or misaligned (16 bytes) ref_device, test_device or recs_device, a misaligned mb_sse_device,
+ * n_images < 1, ref_max outside 0 .. 255, a ref_stride or test_stride below 101376 or not a multiple of 16, an mb_stride
+ * below 264 or not a multiple of 4. */
+int efx_compare_pictures(efx_ctx* ctx, const efx_compare_opts* opts, const uint8_t* ref_device, const uint8_t* test_device,
+                         efx_compare_rec* recs_device, uint32_t* mb_sse_device /* may be NULL */);
+/* 10 log10(255^2 samples / sse); +infinity for sse 0; NaN for samples 0.  Host only. */
+double efx_compare_psnr(uint64_t sse, uint64_t samples);
+/* sum / (65536 windows of the plane): plane 0 = Y, 1 / 2 = chroma; NaN otherwise.  Host only. */
+double efx_compare_ssim(int64_t sum, int plane);
+
 /* -- MPEG-1 encode on the device (k_encode) ---------------------------------------------- */
 /* The reference plays titles that were "encoded with ffmpeg at around 1.5MBits" (README.md:87) ahead of time; nothing in it
  * writes a stream.  efx_encode turns I420 pictures in device memory (the layout efx_export_frames writes: Y 192 x 352, then
