@@ -97,29 +97,15 @@ __global__ void k_mux(MuxArgs);
 
 using namespace efx;
 
-#ifndef EFX_SBC_WG_PER_CU
-#define EFX_SBC_WG_PER_CU 4  // k_sbc_par_mono workgroups per compute unit (k_sbc.hip: EFX_SBC_WAVES)
-#endif
+constexpr int kSbcMonoWgPerCu = 4;  // k_sbc_par_mono workgroups per compute unit (k_sbc.hip: kSbcMonoWaves)
 
-#ifndef EFX_PARSE_STREAMS
-#define EFX_PARSE_STREAMS 2
-#endif
-#ifndef EFX_SLOTS
-#define EFX_SLOTS 3
-#endif
-constexpr int kParseStreams = EFX_PARSE_STREAMS;  // parse halves in flight at once (latency-bound kernels: two overlap well)
+constexpr int kParseStreams = 2;    // parse halves in flight at once (latency-bound kernels: two overlap well)
 constexpr int kMaxGroups = 16;      // an efx_decode call parses its streams in up to this many parse halves
 static_assert(kMaxGroups <= kExportMaxGroups, "k_export takes every reconstruction group of a call");
-#ifndef EFX_RECON_MERGE
-#define EFX_RECON_MERGE 1
-#endif
-constexpr int kReconMerge = EFX_RECON_MERGE;  // parse halves whose streams are reconstructed by ONE launch per picture index
-#ifndef EFX_GROUP_STREAMS
-#define EFX_GROUP_STREAMS 1024
-#endif
-constexpr int kGroupStreams = EFX_GROUP_STREAMS;
+constexpr int kReconMerge = 1;      // parse halves whose streams are reconstructed by ONE launch per picture index
+constexpr int kGroupStreams = 1024;
 constexpr int kTimingRing = 64;   // efx_decode calls whose stage times efx_get_timing can average
-constexpr int kSlots = EFX_SLOTS;         // parse -> recon hand-over buffer sets (one being reconstructed + two being parsed)
+constexpr int kSlots = 3;         // parse -> recon hand-over buffer sets (one being reconstructed + two being parsed)
 constexpr int kUploads = 3;       // bitstream buffers: up to two being parsed (two parse halves are in flight), one being filled --
                                   // with two, an upload had to wait for the parse half two calls back before its transfer could start
 // k_recon_all's hand-over words: 64 lines of 128 bytes (queue heads, spins, abort, development statistics), then one line per stream
@@ -1459,14 +1445,9 @@ int efx_decode_range(efx_ctx* ctx, int first_picture, int n_pictures)
                            u.ts_input ? sl.d_pts : nullptr, u.ts_input ? sl.d_pts + (size_t)ctx->cfg.max_streams * P : nullptr, rs0, rn,
                            P, sl.d_call_pos);
         constexpr int kGroupsPerPicture = (kMbCount * 6 + 63) / 64;
-#ifdef EFX_RECON_ITEMS2
-        constexpr int kReconGridY = (kGroupsPerPicture + 1) / 2;  // (experiment: two block groups per wave, k_recon.hip)
-#else
-        constexpr int kReconGridY = kGroupsPerPicture;
-#endif
         if (ctx->opt_recon_mode == 0) {
             for (int p = 0; p < n_pictures; p++)
-                hipLaunchKernelGGL(k_recon, dim3(rn, kReconGridY), dim3(64), 0, sr, sl.d_mbrecs, sl.d_coefs,
+                hipLaunchKernelGGL(k_recon, dim3(rn, kGroupsPerPicture), dim3(64), 0, sr, sl.d_mbrecs, sl.d_coefs,
                                    ctx->d_tables->scan, sl.d_qtab, ctx->d_frames, P, D, p, sl.d_call_pos, sl.epoch, rs0);
         } else if (rn > 0) {
             // ONE launch for all picture indices of the group: persistent waves pull (picture, stream, block group) items in
@@ -2687,11 +2668,10 @@ int efx_sbc_decode(efx_ctx* ctx, int n_streams, const uint8_t* frames_device, si
                        d_how, d_queues, d_lists, n_streams, (int)ctx->sbc_flags_cap, ret_device, pcm_count_device, ctx->d_sbc_extra,
                        ctx->d_sbc_cover);
     // Persistent workgroups take (stream, chunk of frames) items off the list of their kind, dealt round robin; a list that
-    // stayed empty costs its kernel one look.  Grids = what is resident at a time: EFX_SBC_WG_PER_CU workgroups per compute unit
-    // 
+    // stayed empty costs its kernel one look.  Grids = what is resident at a time: kSbcMonoWgPerCu workgroups per compute unit
     // for the mono kernel (16 frames per item: 36 KB of LDS), 4 for the other two (35 KB of LDS).
     const long long items = (long long)n_streams * ((n_frames + 8) / 8);
-    const int g_mono = (int)std::min<long long>(items, (long long)ctx->n_cus * EFX_SBC_WG_PER_CU), g_wide = (int)std::min<long long>(items, (long long)ctx->n_cus * 4);
+    const int g_mono = (int)std::min<long long>(items, (long long)ctx->n_cus * kSbcMonoWgPerCu), g_wide = (int)std::min<long long>(items, (long long)ctx->n_cus * 4);
     hipLaunchKernelGGL(k_sbc_par_mono, dim3(g_mono), dim3(256), 0, ctx->stream, frames_device, stream_stride, frame_bytes, n_frames, state,
                        ctx->d_sbc_next, ctx->d_sbc_tables, ctx->d_sbc_info, pcm_device, pcm_stride, pcm_count_device, flags, d_queues, d_lists,
                        (int)ctx->sbc_flags_cap, ctx->d_sbc_extra, extra_cap);
@@ -3036,8 +3016,8 @@ int efx_debug_poke(efx_ctx* ctx, void* dptr, size_t bytes, long long offset_byte
     return EFX_OK;
 }
 
-// development: the header lines of k_recon_all's hand-over words after the most recent call (word 0 of each of the 64 lines;
-// lines 16 ... carry per-phase times only in an -DEFX_RA_STATS build: tools/exp/r5_recon_check.py)
+// development: the header lines of k_recon_all's hand-over words after the most recent call (word 0 of each of the 64 lines:
+// queue heads 0-7, spins 8, abort 9, the rest zero; tools/exp/r5_recon_check.py)
 int efx_debug_recon_stats(efx_ctx* ctx, uint32_t out[64])
 {
     bind_device(ctx);

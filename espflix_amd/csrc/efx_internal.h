@@ -23,14 +23,8 @@ namespace efx {
 constexpr int kMbW = 22, kMbH = 12, kMbCount = 264;
 constexpr int kStride = 528, kStripBytes = 8448, kFrameBytes = 101376;
 constexpr int kMaxSlicesPerPicture = 16;   // slice start codes kept per picture
-#ifndef EFX_PARSE_LANES
-#define EFX_PARSE_LANES 64
-#endif
-constexpr int kParseLanes = EFX_PARSE_LANES;  // slices per k_parse wave (one lane each)
-#ifndef EFX_PARSE_WAVES
-#define EFX_PARSE_WAVES 4
-#endif
-constexpr int kParseWaves = EFX_PARSE_WAVES;  // waves of a k_parse workgroup (they share one copy of the tables in LDS)
+constexpr int kParseLanes = 64;            // slices per k_parse wave (one lane each)
+constexpr int kParseWaves = 4;             // waves of a k_parse workgroup (they share one copy of the tables in LDS)
 constexpr int kIndexWaves = 4;             // waves of a k_index workgroup (one workgroup per stream)
 constexpr int kMaxUnitsPerStream = 4096;   // start codes indexed per stream per decode
 constexpr int kCoefsPerEsByte = 4;         // stream words a slice can need per byte: < 3 (a run/level costs >= 3 bits, a motion
@@ -249,14 +243,8 @@ struct FieldArgs {
 // Packets of a transport stream a k_demux workgroup takes, and its threads (k_demux.hip); a multiple of four packets: 4 x 188
 // bytes = 47 x 16.  16 packets x one wave: the benchmark's 253-packet streams as 16 k small workgroups instead of 2 k of 128
 // packets x 256 threads, whose few long phases left the chip waiting (gather 81 -> 42 us; profiles/r5_demux.md).
-#ifndef EFX_DEMUX_CHUNK
-#define EFX_DEMUX_CHUNK 16
-#endif
-constexpr int kDemuxChunk = EFX_DEMUX_CHUNK;
-#ifndef EFX_DEMUX_THREADS
-#define EFX_DEMUX_THREADS 64
-#endif
-constexpr int kDemuxThreads = EFX_DEMUX_THREADS;
+constexpr int kDemuxChunk = 16;
+constexpr int kDemuxThreads = 64;
 constexpr uint32_t kDemuxFailedFlag = 0x80000000u;  // in a stream's PES count: k_demux_fused gave up on it (k_index: EFX_STREAM_INTERNAL)
 static_assert(kDemuxChunk % 4 == 0 && kDemuxChunk >= 4 && kDemuxChunk <= 256, "k_demux stages whole 16-byte groups");
 

@@ -133,7 +133,6 @@ __device__ constexpr double kAan[8] = {1.0,          1.3870398453221475, 1.30656
 __device__ constexpr int premul_at(int r, int c) { return (int)(32.0 * kAan[r] * kAan[c] + 0.5); }
 
 constexpr int kBlocksPerPicture = kMbCount * 6;
-constexpr int kGroupsPerPictureK = (kBlocksPerPicture + 63) / 64;  // 25 groups of 64 blocks
 constexpr int kLaneDwords = 33, kLaneData = 32;  // per-lane LDS block: 64 int16 + one dword (see k_recon)
 constexpr int kLaneHalfwords = 2 * kLaneDwords;
 
@@ -152,21 +151,7 @@ constexpr int kLaneHalfwords = 2 * kLaneDwords;
 // L1 is never refreshed by another CU's stores and the XCDs' L2s are not coherent with each other:
 // MI355X_MICROARCH.md, "Workgroup dispatch, XCD placement & inter-workgroup visibility"); the hand-over itself is the
 // per-stream counter of k_recon_all.
-#ifndef EFX_RECON_PER_ROUND
-#define EFX_RECON_PER_ROUND 3  // coefficient entries a lane takes per round of the wave's entry dealing
-#endif
-#ifndef EFX_RECON_LDS_PAD
-#define EFX_RECON_LDS_PAD 0  // (counter experiments: unused dwords of LDS per wave, to hold k_recon to fewer waves per CU)
-#endif
-#ifndef EFX_RECON_STORE
-#define EFX_RECON_STORE 0  // k_recon (one launch per picture index): plain 8-byte row stores
-#endif
-#ifndef EFX_RA_LOAD
-#define EFX_RA_LOAD 1      // k_recon_all: sc1 loads of the reference frame
-#endif
-#ifndef EFX_RA_STORE
-#define EFX_RA_STORE 2     // k_recon_all: sc1 16-byte stores by lane pairs
-#endif
+constexpr int kPerRound = 3;  // coefficient entries a lane takes per round of the wave's entry dealing (recon_group: "Three entries")
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
 constexpr int kAuxSc1 = 16;  // cache policy of the raw buffer builtins on gfx950: sc1
@@ -185,11 +170,6 @@ __device__ __forceinline__ BlockAt block_at(int g, int lane)
     // Block order inside a picture: by macroblock row, and inside it by plane row -- the 44 upper luma
     // blocks, the 44 lower ones, the 22 "cr" and the 22 "cb" blocks -- so that the lanes of a wave
     // write (and mostly read) long contiguous runs of every frame row they touch.
-#if defined(EFX_RECON_MB_MAJOR)
-    o.mb = b / 6;
-    o.blk = b - o.mb * 6;
-    return o;
-#endif
     const int mbrow = b / 132, rr = b - mbrow * 132;
     int mbx;
     if (rr < 88) {
@@ -205,20 +185,16 @@ __device__ __forceinline__ BlockAt block_at(int g, int lane)
     return o;
 }
 
-// kLoad: 0 = plain loads of the reference frame, 1 = sc1 buffer loads (bypass this CU's L1).
-// kStore: 0 = plain 8-byte row stores, 1 = the same as sc1 (write-through) stores, 2 = sc1 16-byte stores: the lanes of a wave
+// kShared = false (k_recon, one launch per picture index): plain loads of the reference frame, plain 8-byte row stores.
+// kShared = true (k_recon_all): sc1 buffer loads (bypass this CU's L1) and sc1 (write-through) 16-byte stores: the lanes of a wave
 // come in pairs that own horizontally adjacent blocks (even lane: the left / even one), so the pair's two 8-byte row segments are
 // one aligned 16-byte unit -- the even lane stores rows 0-3 of both blocks, the odd lane rows 4-7 (a write-through store is one
-// fabric write whatever its size: per byte an 8-byte one costs 2.7 x a 16-byte one, MI355X_MICROARCH.md), 3 = plain 16-byte.
-template <int kLoad, int kStore, class PreStore>
+// fabric write whatever its size: per byte an 8-byte one costs 2.7 x a 16-byte one, MI355X_MICROARCH.md).
+template <bool kShared, class PreStore>
 __device__ __forceinline__ void recon_group(uint32_t* __restrict__ lds, const uint32_t* __restrict__ coefs,
                                             const uint32_t* __restrict__ qt_custom, uint8_t* __restrict__ frames, int ring_depth,
                                             int pic, int pos0, int first_pts, int epoch, int s, int g, const uint4 rw,
-                                            PreStore&& pre_store
-#if defined(EFX_RECON_ABL) && EFX_RECON_ABL == 2
-                                            , const uint32_t (&efx_abl_early)[3]
-#endif
-                                            EFX_PROBE_PARAM)
+                                            PreStore&& pre_store EFX_PROBE_PARAM)
 {
     int16_t* const cfh = reinterpret_cast<int16_t*>(lds);
     uint16_t* const s_pre = reinterpret_cast<uint16_t*>(lds + 64 * kLaneDwords);  // entries before the block in the wave
@@ -292,7 +268,7 @@ __device__ __forceinline__ void recon_group(uint32_t* __restrict__ lds, const ui
 #pragma unroll
             for (int r = 0; r < 9; r++) {
                 const uint32_t off = off0 + (uint32_t)(r * kStride) + ((uint32_t)r >= jump ? 8u * kStride : 0u);
-                if constexpr (kLoad == 1) {
+                if constexpr (kShared) {
                     const u32x3 v = __builtin_amdgcn_raw_buffer_load_b96(ring_rsrc, (int)(ref_off + off), 0, kAuxSc1);
                     wa[r] = v.x;
                     wb[r] = v.y;
@@ -319,8 +295,8 @@ __device__ __forceinline__ void recon_group(uint32_t* __restrict__ lds, const ui
                 for (int k = 0; k < 4; k++) {
                     const int yy = clampi(py0 + r, 0, ph - 1), xx = clampi((px0 & ~3) + d * 4 + k, 0, pw - 1);
                     const uint32_t o = (uint32_t)(row_off(yy) + xx);
-                    const uint32_t byte = kLoad == 1 ? (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(ring_rsrc, (int)(ref_off + o), 0, kAuxSc1)
-                                                     : (uint32_t)ref[o];
+                    const uint32_t byte = kShared ? (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(ring_rsrc, (int)(ref_off + o), 0, kAuxSc1)
+                                                  : (uint32_t)ref[o];
                     word |= (byte & 0xFF) << (k * 8);
                 }
             w32[i] = word;
@@ -368,7 +344,6 @@ __device__ __forceinline__ void recon_group(uint32_t* __restrict__ lds, const ui
     // Three entries per lane per round: the owners are searched and all loads issued before the first entry
     // is used -- a wave is alive for as many memory round trips as it makes one after the other, and with
     // one load per loop trip the entries alone cost it three (-5.5 % per launch).
-    constexpr int kPerRound = EFX_RECON_PER_ROUND;
     int own[kPerRound], own_next[kPerRound];
     uint32_t ent[kPerRound], ent_next[kPerRound];
     auto fetch = [&](uint32_t i0, int (&own)[kPerRound], uint32_t (&ent)[kPerRound]) {
@@ -393,13 +368,7 @@ __device__ __forceinline__ void recon_group(uint32_t* __restrict__ lds, const ui
             own[k] = L | (int)(o_pf >> 16 << 8);  // owner lane | its flags << 8
             // (always a load, beyond the end from entry 0: the compiler then knows how many loads are in flight and
             // the prediction below waits for the windows only)
-#if defined(EFX_RECON_ABL) && EFX_RECON_ABL >= 1
-            // (ablation, timing only -- wrong pixels: the wave's entries as ONE contiguous run; 2: the first round's requested
-            // before the record is waited for, efx_abl_early)
-            ent[k] = coefs[(uint32_t)__builtin_amdgcn_readfirstlane((int)my_base) + (i < total ? i : 0u)];
-#else
             ent[k] = coefs[i < total ? o_base + (i - (o_pf & 0xFFFF)) : 0u];
-#endif
         }
     };
     auto apply = [&](uint32_t i0) {
@@ -442,14 +411,6 @@ __device__ __forceinline__ void recon_group(uint32_t* __restrict__ lds, const ui
         }
     };
     fetch(lane, own, ent);  // (also when the wave has no entry at all: the same three loads in flight on every path)
-#ifdef EFX_PROBE_FINE
-    EFX_PROBE_STAMP(2);  // (fine probe: the owner search is through, the first round's entries are requested)
-#endif
-#if defined(EFX_RECON_ABL) && EFX_RECON_ABL == 2
-#pragma unroll
-    for (int k = 0; k < kPerRound; k++)
-        ent[k] = efx_abl_early[k];
-#endif
 
     // ---- prediction of the 8 rows, in the shadow of the entry loads just issued (a wave's life is its chain of
     // memory round trips: record -> owner search -> entries; this arithmetic needs only the windows, which were
@@ -498,9 +459,6 @@ __device__ __forceinline__ void recon_group(uint32_t* __restrict__ lds, const ui
         }
     }
 
-#ifdef EFX_PROBE_FINE
-    EFX_PROBE_STAMP_AFTER(6, pr_lo[7]);  // (fine probe: windows arrived, prediction computed -- and, vmcnt(0), the first round's entries are there)
-#endif
     if (total) {
         for (uint32_t i0 = lane;;) {  // (uniform trip count: i0 - lane < total)
             // the next round's owners are searched and its entries requested before this round's are applied
@@ -523,39 +481,6 @@ __device__ __forceinline__ void recon_group(uint32_t* __restrict__ lds, const ui
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     const uint32_t zd = s_zd[lane];
     EFX_PROBE_STAMP_AFTER(5, zd);  // the entries have been dealt out: the IDCT starts
-#ifdef EFX_RECON_SENS
-    // (sensitivity builds, tools/exp/recon_sens.sh: which unit of the CU is the launch waiting for?  Dummy work of ONE kind
-    // is added and the launch timed: full-rate vector instructions, half-rate ones, LDS reads, L1-resident loads)
-    {
-        uint32_t d0 = zd, d1 = zd + 1, d2 = zd + 2, d3 = zd + 3;
-#if EFX_RECON_SENS == 1
-#pragma unroll
-        for (int i = 0; i < EFX_RECON_SENS_N / 4; i++)
-            asm volatile("v_add_u32 %0, %0, %1\n v_add_u32 %1, %1, %2\n v_add_u32 %2, %2, %3\n v_add_u32 %3, %3, %0" : "+v"(d0), "+v"(d1), "+v"(d2), "+v"(d3));
-#elif EFX_RECON_SENS == 2
-#pragma unroll
-        for (int i = 0; i < EFX_RECON_SENS_N / 4; i++)
-            asm volatile("v_perm_b32 %0, %0, %1, %2\n v_perm_b32 %1, %1, %2, %3\n v_perm_b32 %2, %2, %3, %0\n v_perm_b32 %3, %3, %0, %1" : "+v"(d0), "+v"(d1), "+v"(d2), "+v"(d3));
-#elif EFX_RECON_SENS == 3
-#pragma unroll
-        for (int i = 0; i < EFX_RECON_SENS_N / 4; i++) {
-            d0 += lds[(lane * kLaneDwords + (d1 & 7)) & 2047];
-            d1 += lds[(lane * kLaneDwords + 8 + (d2 & 7)) & 2047];
-            d2 += lds[(lane * kLaneDwords + 16 + (d3 & 7)) & 2047];
-            d3 += lds[(lane * kLaneDwords + 24 + (d0 & 7)) & 2047];
-            asm volatile("" : "+v"(d0), "+v"(d1), "+v"(d2), "+v"(d3));
-        }
-#elif EFX_RECON_SENS == 4
-#pragma unroll
-        for (int i = 0; i < EFX_RECON_SENS_N; i++) {
-            d0 += __builtin_nontemporal_load(coefs + (my_base & ~63u) + lane + 64 * (i & 1));   // (this wave's own entries again: L1 / L2 hits)
-            asm volatile("" : "+v"(d0));
-        }
-#endif
-        if ((d0 ^ d1 ^ d2 ^ d3) == 0x9E3779B9u)
-            s_zd[lane] = 1;
-    }
-#endif
     const bool zf = (zd & 0x80) != 0;  // an entry sits at scan position 0
     // intra DC value (22 bits: a slice adds at most 1584 differentials of +-255 to the predictor)
     const int dc_raw = (int)((uint32_t)(uint16_t)mine[0] | ((uint32_t)((int)(zd << 26) >> 26) << 16));
@@ -671,17 +596,12 @@ __device__ __forceinline__ void recon_group(uint32_t* __restrict__ lds, const ui
         // prediction only (skipped macroblock, block without coefficients) / intra DC-only replica / the clamped sum
         out_lo[r] = bitop3<0xCA>(clamped_m, w[0], flat4);
         out_hi[r] = bitop3<0xCA>(clamped_m, w[1], flat4);
-        if constexpr (kStore < 2) {
-            if (stored) {
-                if constexpr (kStore == 1) {
-                    const u32x2 o2 = {out_lo[r], out_hi[r]};
-                    __builtin_amdgcn_raw_buffer_store_b64(o2, ring_rsrc, (int)(cur_off + (uint32_t)(dst0 + r * kStride)), 0, kAuxSc1);
-                } else
-                    *reinterpret_cast<uint2*>(cur + dst0 + r * kStride) = make_uint2(out_lo[r], out_hi[r]);
-            }
+        if constexpr (!kShared) {
+            if (stored)
+                *reinterpret_cast<uint2*>(cur + dst0 + r * kStride) = make_uint2(out_lo[r], out_hi[r]);
         }
     }
-    if constexpr (kStore >= 2) {
+    if constexpr (kShared) {
         // lanes 2k, 2k + 1 own the left and the right half of a 16-byte aligned unit of every row they write (block_at: luma
         // blocks alternate left / right, chroma blocks run along the macroblock row and a row of them starts on an even lane)
         const bool odd = lane & 1;
@@ -697,22 +617,15 @@ __device__ __forceinline__ void recon_group(uint32_t* __restrict__ lds, const ui
             const uint32_t own_lo = odd ? out_lo[4 + k] : out_lo[k], own_hi = odd ? out_hi[4 + k] : out_hi[k];
             typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
             const u32x4 unit = {odd ? got_lo : own_lo, odd ? got_hi : own_hi, odd ? own_lo : got_lo, odd ? own_hi : got_hi};
-            if (both) {
-                if constexpr (kStore == 2)
-                    __builtin_amdgcn_raw_buffer_store_b128(unit, ring_rsrc, (int)(unit0 + (uint32_t)(k * kStride)), 0, kAuxSc1);
-                else
-                    *reinterpret_cast<uint4*>(ring + unit0 + (uint32_t)(k * kStride)) = make_uint4(unit.x, unit.y, unit.z, unit.w);
-            }
+            if (both)
+                __builtin_amdgcn_raw_buffer_store_b128(unit, ring_rsrc, (int)(unit0 + (uint32_t)(k * kStride)), 0, kAuxSc1);
         }
         if (__any(stored && !partner_stored)) {  // (damaged or incomplete pictures only: a block whose neighbour is not written)
             if (stored && !partner_stored) {
 #pragma unroll
                 for (int r = 0; r < 8; r++) {
                     const u32x2 o2 = {out_lo[r], out_hi[r]};
-                    if constexpr (kStore == 2)
-                        __builtin_amdgcn_raw_buffer_store_b64(o2, ring_rsrc, (int)(cur_off + (uint32_t)(dst0 + r * kStride)), 0, kAuxSc1);
-                    else
-                        *reinterpret_cast<uint2*>(cur + dst0 + r * kStride) = make_uint2(out_lo[r], out_hi[r]);
+                    __builtin_amdgcn_raw_buffer_store_b64(o2, ring_rsrc, (int)(cur_off + (uint32_t)(dst0 + r * kStride)), 0, kAuxSc1);
                 }
             }
         }
@@ -735,7 +648,7 @@ __global__ __launch_bounds__(64) void k_recon(const MbRec* __restrict__ mbrecs, 
     // What else a lane needs to know about another lane's block (first entry, quantiser) is fetched from that lane's
     // registers (ds_bpermute).  Measured: this layout at 16 / 18 / 19 waves per CU 8.07 / 8.16 / 7.85 M frames/s
     // (19 with the search through ds_bpermute as well), the previous one (9.7 KB, 16 waves) 7.78.
-    __shared__ uint32_t lds[64 * kLaneDwords + 32 + 16 + EFX_RECON_LDS_PAD];
+    __shared__ uint32_t lds[64 * kLaneDwords + 32 + 16];
     const int lane = threadIdx.x;
     const int s = stream0 + blockIdx.x;
     // (one record per wave, placed by launch: the ring holds ten launches of 512 streams)
@@ -744,51 +657,16 @@ __global__ __launch_bounds__(64) void k_recon(const MbRec* __restrict__ mbrecs, 
                        (unsigned)(epoch & 0xFF));
     EFX_PROBE_STAMP(1);
     EFX_PROBE_CYCLES_BEGIN();
-#ifndef EFX_PROBE_FINE
     EFX_PROBE_SET(6, (unsigned long long)pic | (unsigned long long)(epoch & 0xFF) << 8 | (unsigned long long)stream0 << 16);
-#endif
     // scan/quantiser table entry: zz | premultiplier << 8 | intra q << 16 | non-intra q << 24
     lds[lane * kLaneDwords + kLaneData] = scan_tab[lane];
-#if defined(EFX_RECON_ITEMS2)
-    // (experiment, round 6: TWO block groups per wave, the second group's record requested before the first group's work -- its
-    // round trip is off the chain for half the items; the grid is (streams, 13))
-    {
-        const int g0 = 2 * blockIdx.y, g1 = g0 + 1;
-        const MbRec* recs = mbrecs + ((size_t)s * max_pictures + pic) * kMbCount;
-        const uint4 rw0 = *reinterpret_cast<const uint4*>(recs + block_at(g0, lane).mb);
-        const uint4 rw1 = *reinterpret_cast<const uint4*>(recs + block_at(g1 < kGroupsPerPictureK ? g1 : g0, lane).mb);
-        recon_group<0, EFX_RECON_STORE>(lds, coefs, qtab_custom + ((size_t)s * max_pictures + pic) * 64, frames, ring_depth, pic, call_pos[2 * s],
-                                        call_pos[2 * s + 1], epoch, s, g0, rw0, [] {} EFX_PROBE_PASS);
-        if (g1 < kGroupsPerPictureK) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            recon_group<0, EFX_RECON_STORE>(lds, coefs, qtab_custom + ((size_t)s * max_pictures + pic) * 64, frames, ring_depth, pic, call_pos[2 * s],
-                                            call_pos[2 * s + 1], epoch, s, g1, rw1, [] {} EFX_PROBE_PASS);
-        }
-        return;
-    }
-#endif
     const BlockAt at = block_at(blockIdx.y, lane);
-#if defined(EFX_RECON_ABL) && EFX_RECON_ABL == 2
-    uint32_t efx_abl_early[3];
-    {
-        const uint32_t fake = (uint32_t)((((size_t)s * max_pictures + pic) * 25 + blockIdx.y) * 256u);
-        for (int k = 0; k < 3; k++)
-            efx_abl_early[k] = coefs[fake + lane + 64 * k];
-    }
-#endif
     const uint4 rw = *reinterpret_cast<const uint4*>(mbrecs + ((size_t)s * max_pictures + pic) * kMbCount + at.mb);
     EFX_PROBE_STAMP_AFTER(3, rw.x);  // the record has arrived
-    recon_group<0, EFX_RECON_STORE>(lds, coefs, qtab_custom + ((size_t)s * max_pictures + pic) * 64, frames, ring_depth, pic, call_pos[2 * s],
-                       call_pos[2 * s + 1], epoch, s, blockIdx.y, rw, [] {}
-#if defined(EFX_RECON_ABL) && EFX_RECON_ABL == 2
-                       , efx_abl_early
-#endif
-                       EFX_PROBE_PASS);
+    recon_group<false>(lds, coefs, qtab_custom + ((size_t)s * max_pictures + pic) * 64, frames, ring_depth, pic, call_pos[2 * s],
+                       call_pos[2 * s + 1], epoch, s, blockIdx.y, rw, [] {} EFX_PROBE_PASS);
     EFX_PROBE_STAMP(4);
-#ifndef EFX_PROBE_FINE
     EFX_PROBE_CYCLES_END(2);
-#endif
 }
 
 // ---- all pictures of a decode call in ONE launch ----------------------------------------------------------------------------
@@ -825,15 +703,6 @@ constexpr unsigned long long kReconAllPatienceTicks = 1000000000ull;  // 10 s of
 constexpr int kGroupsPerPicture = (kBlocksPerPicture + 63) / 64;  // 25
 constexpr uint32_t kSyncLine = 32;  // words per line
 constexpr uint32_t kSyncHeads = 0, kSyncSpins = 8 * kSyncLine, kSyncAbort = 9 * kSyncLine, kSyncDone = 64 * kSyncLine;
-#ifdef EFX_RA_STATS
-// (development build: where a wave's time goes, summed over the launch -- lines 16 ... of the header, one word per line;
-// read through efx_debug_recon_stats, tools/exp/r5_recon_check.py)
-constexpr uint32_t kSyncStats = 16 * kSyncLine;
-enum { kStWaves, kStItems, kStForeign, kStClaim, kStDep, kStBody, kStSignal, kStLife, kStXcc0 /* .. +7 */, kStCount = kStXcc0 + 8 };
-#define EFX_RA_T() wall_clock64()
-#else
-#define EFX_RA_T() 0ull
-#endif
 
 struct ItemAt {
     int pic, s, g;
@@ -906,9 +775,6 @@ __device__ __forceinline__ void recon_all_body(uint32_t* __restrict__ lds, const
     // goes out too (memory operations complete in issue order: its stores have left).  A wait anywhere else would sit out A's
     // stores: the counter of outstanding memory operations cannot tell an old atomic from a new store.
     uint32_t budget = max_items > 0 ? (uint32_t)max_items : 0xFFFFFFFFu;
-    [[maybe_unused]] const unsigned long long st_begin = EFX_RA_T();
-    [[maybe_unused]] unsigned long long st_top = 0, st_dep = 0, st_body = 0;
-    [[maybe_unused]] uint32_t st_items = 0, st_foreign = 0;
     uint32_t idx = 0;
     if (!claim_walk(idx))
         return;
@@ -924,7 +790,6 @@ __device__ __forceinline__ void recon_all_body(uint32_t* __restrict__ lds, const
     uint32_t seen_a = (uint32_t)__builtin_amdgcn_readfirstlane((int)done_of(a));
     int pending_signal = -1;  // stream of the item whose stores are still on their way
     for (;;) {
-        [[maybe_unused]] const unsigned long long st_t0 = EFX_RA_T();
         // ---- requests for the items behind this one (consumed at this item's pre-store point) -----------------------------------
         uint4 rw_b = rw_a;
         uint32_t done_b = 0, claim_c = 0;
@@ -937,7 +802,6 @@ __device__ __forceinline__ void recon_all_body(uint32_t* __restrict__ lds, const
         if (pending_c)
             claim_c = claim_issue(q_c);
         // ---- this item's predecessor: every group of the stream's previous pictures is in memory ---------------------------
-        [[maybe_unused]] const unsigned long long st_t1 = EFX_RA_T();
         const uint32_t need = (uint32_t)(kGroupsPerPicture * a.pic);
         if (seen_a < need) {
             // (the tail of a small batch: the predecessor is still in the hands of another wave -- or of THIS one: the item
@@ -970,31 +834,16 @@ __device__ __forceinline__ void recon_all_body(uint32_t* __restrict__ lds, const
             if (lane == 0)
                 __hip_atomic_fetch_add(sync + kSyncSpins, spins, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        [[maybe_unused]] const unsigned long long st_t2 = EFX_RA_T();
         uint32_t seen_b = 0, idx_c = 0;
-        recon_group<EFX_RA_LOAD, EFX_RA_STORE>(lds, coefs, qtab_custom + ((size_t)a.s * max_pictures + a.pic) * 64, frames, ring_depth, a.pic,
-                                               call_pos[2 * a.s], call_pos[2 * a.s + 1], epoch, a.s, a.g, rw_a, [&] {
-                                                   drain();
-                                                   if (pending_signal >= 0)
-                                                       signal(pending_signal);
-                                                   seen_b = (uint32_t)__builtin_amdgcn_readfirstlane((int)done_b);
-                                                   idx_c = (uint32_t)__builtin_amdgcn_readfirstlane((int)claim_c);
-                                               }
-#if defined(EFX_RECON_ABL) && EFX_RECON_ABL == 2
-                                               , {0u, 0u, 0u}
-#endif
-                                               EFX_PROBE_PASS_NONE);
+        recon_group<true>(lds, coefs, qtab_custom + ((size_t)a.s * max_pictures + a.pic) * 64, frames, ring_depth, a.pic,
+                          call_pos[2 * a.s], call_pos[2 * a.s + 1], epoch, a.s, a.g, rw_a, [&] {
+                              drain();
+                              if (pending_signal >= 0)
+                                  signal(pending_signal);
+                              seen_b = (uint32_t)__builtin_amdgcn_readfirstlane((int)done_b);
+                              idx_c = (uint32_t)__builtin_amdgcn_readfirstlane((int)claim_c);
+                          } EFX_PROBE_PASS_NONE);
         pending_signal = a.s;
-#ifdef EFX_RA_STATS
-        {
-            const unsigned long long st_t3 = EFX_RA_T();
-            st_top += st_t1 - st_t0;
-            st_dep += st_t2 - st_t1;
-            st_body += st_t3 - st_t2;
-            st_items++;
-            st_foreign += (uint32_t)((a.s - stream0) & 7) != (xcc & 7);
-        }
-#endif
         if (!have_b)
             break;
         // ---- rotate: B becomes the item worked on, C (if its claim found one) the item behind it --------------------------
@@ -1023,28 +872,12 @@ __device__ __forceinline__ void recon_all_body(uint32_t* __restrict__ lds, const
     drain();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the last item's stores)
     signal(pending_signal);
-#ifdef EFX_RA_STATS
-    if (lane == 0) {
-        auto add = [&](int k, unsigned long long v) {
-            __hip_atomic_fetch_add(sync + kSyncStats + (uint32_t)k * kSyncLine, (uint32_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        };
-        add(kStWaves, 1);
-        add(kStItems, st_items);
-        add(kStForeign, st_foreign);
-        add(kStClaim, st_top >> 2);  // (100 MHz ticks / 4 = units of 40 ns)
-        add(kStDep, st_dep >> 2);
-        add(kStBody, st_body >> 2);
-        add(kStLife, (EFX_RA_T() - st_begin) >> 2);
-        add(kStXcc0 + (int)(xcc & 7), 1);
-    }
-#endif
 }
 
-#ifndef EFX_RECON_ALL_WAVES
-#define EFX_RECON_ALL_WAVES 4  // waves per SIMD the register allocation aims at: 4 (123 registers, nothing spilled; with 5 the
-                               // 96 registers spill 14 and the launch is a quarter slower) -- 16 waves per CU
-#endif
-__global__ __launch_bounds__(64, EFX_RECON_ALL_WAVES) void k_recon_all(
+// waves per SIMD the register allocation aims at: 4 (123 registers, nothing spilled; with 5 the 96 registers spill 14 and the
+// launch is a quarter slower) -- 16 waves per CU
+constexpr int kReconAllWaves = 4;
+__global__ __launch_bounds__(64, kReconAllWaves) void k_recon_all(
     const MbRec* __restrict__ mbrecs, const uint32_t* __restrict__ coefs, const uint32_t* __restrict__ scan_tab,
     const uint32_t* __restrict__ qtab_custom, uint8_t* __restrict__ frames, int max_pictures, int ring_depth, int n_pictures,
     const int32_t* __restrict__ call_pos, int epoch, int stream0, int n_streams, uint32_t* __restrict__ sync,

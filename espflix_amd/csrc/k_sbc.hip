@@ -335,25 +335,12 @@ __global__ __launch_bounds__(64) void k_sbc(const uint8_t* __restrict__ frames, 
     sbc_serial_body(frames, stream_stride, frame_bytes, n_frames, states, tables, pcm, pcm_stride, ret, pcm_count, flags);
 }
 
-// (development switches: the alternatives measured in profiles/r5_sbc.md)
-#ifndef EFX_SBC_M
-#define EFX_SBC_M 1      // matrixing: a thread makes two outputs of 1 = two consecutive rows, 0 = one row per trip
-#endif
-#ifndef EFX_SBC_SKIP
-#define EFX_SBC_SKIP 0   // timing ablations (wrong PCM): 1 = no dequantisation, 2 = no matrixing of the chunk's rows, 4 = no windowing
-#endif
-#ifndef EFX_SBC_CHUNK_MONO
-#define EFX_SBC_CHUNK_MONO 16  // frames per work item of k_sbc_par_mono (8: 7 workgroups per compute unit; 16: 4, and 12 % faster)
-#endif
-#ifndef EFX_SBC_PITCH
-#define EFX_SBC_PITCH 18 // (16 = unpadded)
-#endif
-#ifndef EFX_SBC_WAVES
-#define EFX_SBC_WAVES 4  // k_sbc_par_mono: waves per SIMD the register allocation aims at (= workgroups per compute unit)
-#endif
-constexpr int kSbcChunk = 8;                 // frames per work item (k_sbc_par_mono: EFX_SBC_CHUNK_MONO)
-constexpr int kSbcMonoGranules = EFX_SBC_CHUNK_MONO / kSbcChunk;  // k_sbc_gen items in a k_sbc_par_mono item
-static_assert(EFX_SBC_CHUNK_MONO == kSbcChunk * kSbcMonoGranules && (kSbcMonoGranules == 1 || kSbcMonoGranules == 2), "mono chunk");
+// (the alternatives to these values were measured in profiles/r5_sbc.md)
+constexpr int kSbcChunkMono = 16;  // frames per work item of k_sbc_par_mono (8: 7 workgroups per compute unit; 16: 4, and 12 % faster)
+constexpr int kSbcMonoWaves = 4;   // k_sbc_par_mono: waves per SIMD the register allocation aims at (= workgroups per compute unit)
+constexpr int kSbcChunk = 8;                 // frames per work item (k_sbc_par_mono: kSbcChunkMono)
+constexpr int kSbcMonoGranules = kSbcChunkMono / kSbcChunk;  // k_sbc_gen items in a k_sbc_par_mono item
+static_assert(kSbcChunkMono == kSbcChunk * kSbcMonoGranules && (kSbcMonoGranules == 1 || kSbcMonoGranules == 2), "mono chunk");
 
 // ---- per frame: header and bit allocation --------------------------------------------------------------------------------
 // grid = (frames / 256, streams), one thread per frame.  parallel[] arrives set to kSbcRegularFlag; a frame that does not
@@ -669,7 +656,7 @@ __global__ __launch_bounds__(256) void k_sbc_plan(const SbcFrameInfo* __restrict
 
 // ---- the frame-parallel kernels ----------------------------------------------------------------------------------------------
 constexpr int kSbcStageDwords = 1024;        // 4 KB of frame bytes in LDS
-constexpr int kSbcRowPitch = EFX_SBC_PITCH;    // dwords between two rows of matrixing outputs in LDS
+constexpr int kSbcRowPitch = 18;             // dwords between two rows of matrixing outputs in LDS (16 = unpadded)
 constexpr uint32_t kSbcSlack = 528;          // a frame's bit fields may run past the frame size the caller states (at most 524 bytes
                                              // from its start): the reference reads on into the next frame's bytes, so does this
 
@@ -941,9 +928,6 @@ __device__ __forceinline__ void sbc_par_body(const uint8_t* __restrict__ frames,
                 rows[c][t][o] = st->hist[c][9 + vb - hist_end][o];
         }
         sbc_lds_barrier();
-#if EFX_SBC_SKIP & 1
-        sbc_lds_barrier();
-#else
         // ---- samples (get_samples(), sbc_decoder.cpp:297-343): a thread takes (frame, channel, subband) and four consecutive
         // blocks -- width, place and scale factor of the field, the divisor's constant are read once, the bit position advances
         // by the block's bits.  Of the first frame in reach only the quarters that hold the nine blocks before the chunk.
@@ -980,7 +964,6 @@ __device__ __forceinline__ void sbc_par_body(const uint8_t* __restrict__ frames,
                 tasks(field_global);
         }
         sbc_lds_barrier();
-#endif
         // ---- matrixing (sbc_decoder.cpp:86-104): rows[c][t][o] = (sum_j syn[o][j] * sb[blk][c][j]) >> 15.  The chunk's own
         // rows: below; the nine rows before them that are not the state's: one thread per output.
         const int n_t = 9 + (vb1 - vb0);
@@ -998,8 +981,6 @@ __device__ __forceinline__ void sbc_par_body(const uint8_t* __restrict__ frames,
                 acc = mad24(tb.syn[o * 8 + j], x[j], acc);
             rows[c][t][o] = (int32_t)acc >> 15;
         }
-#if EFX_SBC_SKIP & 2
-#elif EFX_SBC_M
         {
             // outputs o8 and o8 + 8 of TWO consecutive rows (blocks of one frame: a block count is even) per trip: the 16
             // coefficients and the address arithmetic serve 32 multiply-adds
@@ -1033,41 +1014,12 @@ __device__ __forceinline__ void sbc_par_body(const uint8_t* __restrict__ frames,
                 rows[c][10 + row][o8 + 8] = (int32_t)b1 >> 15;
             }
         }
-#else
-        {
-            const int o8 = tid & 7;
-            int32_t sa[8], sh[8];
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                sa[j] = tb.syn[o8 * 8 + j];
-                sh[j] = tb.syn[(o8 + 8) * 8 + j];
-            }
-            const int RB = vb1 - vb0;
-            for (int idx = tid >> 3; idx < C * RB; idx += 32) {
-                const int c = (C == 2 && idx >= RB) ? 1 : 0, row = idx - c * RB, vb = vb0 + row;
-                const int rel = vb - vb_base, fq = (int)(__umul24((uint32_t)rel, inv_b) >> 16), k = fq + k_base,
-                          blk = rel - (int)__umul24((uint32_t)fq, (uint32_t)blocks);
-                const int4* sp = reinterpret_cast<const int4*>(&sb[((k * 16 + blk) * C + c) * 8]);
-                const int4 x0 = sp[0], x1 = sp[1];
-                const int32_t x[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-                uint32_t a0 = 0, a1 = 0;
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    a0 = mad24(sa[j], x[j], a0);
-                    a1 = mad24(sh[j], x[j], a1);
-                }
-                rows[c][9 + row][o8] = (int32_t)a0 >> 15;
-                rows[c][9 + row][o8 + 8] = (int32_t)a1 >> 15;
-            }
-        }
-#endif
         sbc_lds_barrier();
         // ---- windowing (sbc_decoder.cpp:106-137): sample o of block t from rows t .. t - 9; a thread makes sample o of four
         // consecutive blocks (a frame's block count is a multiple of four) out of one pass over the thirteen rows they read
         int16_t* out = pcm + (size_t)s * pcm_stride;
         const int frame_samples = C * blocks * 8;
         const size_t pcm0 = p.pcm_base != 0xFFFFFFFFu ? (size_t)p.pcm_base : (size_t)f0 * frame_samples;  // where frame f0's PCM goes
-#if !(EFX_SBC_SKIP & 4)
         {
             const int o = tid & 7;
             int32_t p[10];
@@ -1100,7 +1052,6 @@ __device__ __forceinline__ void sbc_par_body(const uint8_t* __restrict__ frames,
                 }
             }
         }
-#endif  // (ablation)
         // ---- the workgroup of the last frames leaves the decoder state -------------------------------------------------------------
         // NOT in `states`: the workgroup of the stream's first frames reads the history there, in this same launch, whenever it
         // gets to it.  The new state goes to `states_next` as a whole (what this geometry does not touch copied over) and
@@ -1137,14 +1088,14 @@ __device__ __forceinline__ void sbc_par_body(const uint8_t* __restrict__ frames,
 }
 
 // grid = as many workgroups as fit the chip (efx_sbc_decode), block = 256
-__global__ __launch_bounds__(256, EFX_SBC_WAVES) void k_sbc_par_mono(const uint8_t* __restrict__ frames, size_t stream_stride, int frame_bytes, int n_frames,
+__global__ __launch_bounds__(256, kSbcMonoWaves) void k_sbc_par_mono(const uint8_t* __restrict__ frames, size_t stream_stride, int frame_bytes, int n_frames,
                                                       const SbcState* __restrict__ states, SbcState* __restrict__ states_next,
                                                       const SbcTables* __restrict__ tables, const SbcFrameInfo* __restrict__ info,
                                                       int16_t* __restrict__ pcm, size_t pcm_stride, uint32_t* __restrict__ pcm_count,
                                                       int flags, SbcQueues* __restrict__ queues, const uint32_t* __restrict__ lists,
                                                       int n_streams, const SbcExtraItem* __restrict__ extra, int extra_cap)
 {
-    sbc_par_body<1, EFX_SBC_CHUNK_MONO>(frames, stream_stride, frame_bytes, n_frames, states, states_next, tables, info, pcm, pcm_stride, pcm_count, flags,
+    sbc_par_body<1, kSbcChunkMono>(frames, stream_stride, frame_bytes, n_frames, states, states_next, tables, info, pcm, pcm_stride, pcm_count, flags,
                     queues, lists, n_streams, extra + (size_t)kSbcMono * extra_cap);
 }
 __global__ __launch_bounds__(256) void k_sbc_par_stereo(const uint8_t* __restrict__ frames, size_t stream_stride, int frame_bytes,

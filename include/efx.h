@@ -1038,7 +1038,7 @@ typedef enum efx_option {
  * it).  tools/guard_selftest.py uses it to show that the allocator catches what it is there to catch. */
 int efx_debug_poke(efx_ctx* ctx, void* dptr, size_t bytes, long long offset_bytes);
 /* Debugging aid: word 0 of each of the 64 header lines of k_recon_all's hand-over words after the most recent call (queue
- * heads 0-7, spins 8, abort 9; 16 ... per-phase wave times in a -DEFX_RA_STATS build). */
+ * heads 0-7, spins 8, abort 9; the rest zero). */
 int efx_debug_recon_stats(efx_ctx* ctx, uint32_t out[64]);
 int efx_set_option(efx_ctx* ctx, int option, int value);
 int efx_get_option(efx_ctx* ctx, int option, int* value);

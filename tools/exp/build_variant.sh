@@ -1,13 +1,13 @@
 #!/bin/bash
 # usage: build_variant.sh tag "flags"  -> espflix_amd/libefx_<tag>.so
-set -e
+# The Makefile's own commands for libefx.so (its OBJS, its flags, k_recon.o's extra one), with the given flags added to every
+# compile, the objects in build/variant_<tag>/ and the library under the variant's name.  The product's objects are left alone.
+set -e -o pipefail
 tag=$1; flags=$2
-d=/tmp/var_$tag; mkdir -p $d
-cd /root/repo
-for f in efx_api k_parse k_recon k_index k_demux; do
-  extra=""; [ $f = k_recon ] && extra="-mllvm -amdgpu-atomic-optimizer-strategy=None"   # (as the Makefile does)
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Iinclude -Iespflix_amd/csrc $flags $extra -c espflix_amd/csrc/$f.hip -o $d/$f.o &
-done
-wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $d/efx_api.o $d/k_parse.o $d/k_recon.o $d/k_index.o $d/k_demux.o espflix_amd/csrc/k_video.o espflix_amd/csrc/k_sbc.o espflix_amd/csrc/k_tsindex.o espflix_amd/csrc/efx_tables.o espflix_amd/csrc/efx_multi.o -o espflix_amd/libefx_$tag.so
+[ -n "$tag" ] || { echo "usage: $0 tag \"flags\"" >&2; exit 2; }
+cd "$(dirname "$0")/../.."
+d=build/variant_$tag; mkdir -p $d
+make -n -B lib | sed -e "s#espflix_amd/csrc/\([A-Za-z0-9_]*\)\.o#$d/\1.o#g" -e "s#-o espflix_amd/libefx\.so#-o espflix_amd/libefx_$tag.so#" > $d/commands
+grep -e ' -c ' $d/commands | sed -e "s# -c # $flags -c #" | xargs -d '\n' -P "${MAX_JOBS:-8}" -n 1 sh -c
+grep -e ' -shared ' $d/commands | sh -e
 echo built $tag
