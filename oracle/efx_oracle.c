@@ -612,17 +612,20 @@ static void predict(dec_t* d) /* player.cpp:870-889 */
     motion_comp(d, 2, x, y, 8);
 }
 
-static int motion_vector(dec_t* d, int m, int r_size, int* ok) /* player.cpp:891-910 */
+static int motion_vector(dec_t* d, int comp, int m, int r_size, int* ok) /* player.cpp:891-910 */
 {
     int scale = 1 << r_size;
     int code = get_vlc(d, &T_motion, ok);
-    int delta;
+    int delta, residual = -1;
     if (code != 0 && scale != 1) {
-        delta = ((abs(code) - 1) << r_size) + get_bits(d, r_size) + 1;
+        residual = get_bits(d, r_size);
+        delta = ((abs(code) - 1) << r_size) + residual + 1;
         if (code < 0)
             delta = -delta;
     } else
         delta = code;
+    if (*ok)
+        TRACE(EFXO_T_MOTION, comp, code, residual, m);
     m += delta;
     if (m > (scale << 4) - 1)
         m -= scale << 5;
@@ -711,6 +714,7 @@ static int decode_block(dec_t* d, int blk, int intra)
                 d->cnt -= size < 10 ? size : 10;
             }
         }
+        TRACE(EFXO_T_SYM, EFXO_SYM_DC_SIZE, size, blk >= 4, size ? (peek_bits(d, size) >> (size - 1) ? 1 : -1) : 0);
         if (size) {
             int delta = get_bits(d, size);
             if (delta & (1 << (size - 1)))
@@ -742,6 +746,7 @@ static int decode_block(dec_t* d, int blk, int intra)
             d->cnt -= n ? 2 : 1;
             run = 0;
             v = raw_bit(d) ? -1 : 1;
+            TRACE(EFXO_T_SYM, EFXO_SYM_DCT, 0, v, n ? 3 : 2);
         } else {
             int ok = 1;
             int rl = get_vlc(d, &T_dct, &ok);
@@ -765,6 +770,7 @@ static int decode_block(dec_t* d, int blk, int intra)
                 v = rl & 0xFF;
                 if (raw_bit(d))
                     v = -v;
+                TRACE(EFXO_T_SYM, EFXO_SYM_DCT, run, v, n ? 1 : 0);
             }
         }
         n += run;
@@ -872,6 +878,7 @@ static void decode_slice(dec_t* d, int code)
         return;
     reset_predictors(d);
     d->qscale = get_bits(d, 5);
+    TRACE(EFXO_T_SYM, EFXO_SYM_QSCALE, d->qscale, 0, 0);
     {
         int extra = 0, last = 0; /* extra_bit_slice / extra_information_slice, player.cpp:1261-1262 */
         while (get_bits(d, 1)) {
@@ -890,14 +897,18 @@ static void decode_slice(dec_t* d, int code)
         int ok = 1;
         int inc = 0;
         int i = get_vlc(d, &T_mba, &ok);
-        while (ok && i == 34)
+        while (ok && i == 34) {
+            TRACE(EFXO_T_SYM, EFXO_SYM_MBA, i, 0, 0);
             i = get_vlc(d, &T_mba, &ok);
+        }
         while (ok && i == 35) {
+            TRACE(EFXO_T_SYM, EFXO_SYM_MBA, i, 0, 0);
             inc += 33;
             i = get_vlc(d, &T_mba, &ok);
         }
         if (!ok)
             return;
+        TRACE(EFXO_T_SYM, EFXO_SYM_MBA, i, inc != 0, 0); /* c: the code follows at least one escape */
         inc += i;
 
         if (mb == 0) {
@@ -921,15 +932,18 @@ static void decode_slice(dec_t* d, int code)
         if (!ok)
             return;
         int intra = type & 1;
-        if (type & 0x10)
+        TRACE(EFXO_T_SYM, EFXO_SYM_TYPE, type, d->pic_type, 0);
+        if (type & 0x10) {
             d->qscale = get_bits(d, 5);
+            TRACE(EFXO_T_SYM, EFXO_SYM_QSCALE, d->qscale, 1, 0);
+        }
         if (intra)
             d->mv_h = d->mv_v = 0;
         else {
             d->dc_y = d->dc_cr = d->dc_cb = 128;
             if (type & 0x08) { /* motion_vectors, player.cpp:912-920 */
-                d->mv_h = motion_vector(d, d->mv_h, d->r_size, &ok);
-                d->mv_v = motion_vector(d, d->mv_v, d->r_size, &ok);
+                d->mv_h = motion_vector(d, 0, d->mv_h, d->r_size, &ok);
+                d->mv_v = motion_vector(d, 1, d->mv_v, d->r_size, &ok);
                 if (!ok)
                     return;
             } else
@@ -939,6 +953,8 @@ static void decode_slice(dec_t* d, int code)
         int cbp = (type & 2) ? get_vlc(d, &T_cbp, &ok) : (intra ? 63 : 0);
         if (!ok)
             return;
+        if (type & 2)
+            TRACE(EFXO_T_SYM, EFXO_SYM_CBP, cbp, 0, 0);
         TRACE(EFXO_T_MB, d->mb_y * d->mb_width + d->mb_x, intra | (d->qscale << 2), d->full_pel ? d->mv_h << 1 : d->mv_h,
               d->full_pel ? d->mv_v << 1 : d->mv_v);
         for (int blk = 0; blk < 6; blk++)

@@ -49,7 +49,20 @@ long efxo_decode(const uint8_t* data, size_t len, int format, int flush_last,
  *                 1 "00 xx" = xx, 2 "80 xx" = xx - 256; b = run, c = level
  *   EFXO_T_SLICE_EXTRA (after the EFXO_T_SLICE it belongs to, only when the header has any) a = number of
  *                 extra_information_slice bytes skipped (player.cpp:1261-1262), b = the last one, c = picture type */
-enum { EFXO_T_SLICE = 0, EFXO_T_MB = 1, EFXO_T_COEF = 2, EFXO_T_BLOCK = 3, EFXO_T_ESCAPE = 4, EFXO_T_SLICE_EXTRA = 5, EFXO_T_SLICE_AT = 6 };
+enum { EFXO_T_SLICE = 0, EFXO_T_MB = 1, EFXO_T_COEF = 2, EFXO_T_BLOCK = 3, EFXO_T_ESCAPE = 4, EFXO_T_SLICE_EXTRA = 5, EFXO_T_SLICE_AT = 6,
+       EFXO_T_SYM = 7, EFXO_T_MOTION = 8 };
+/* EFXO_T_SYM: one decoded syntax element, before the EFXO_T_MB / EFXO_T_COEF it leads to (tests/test_syntax_streams.py counts
+ * which entries of every table a stream reaches); a = which of the following:
+ *   EFXO_SYM_MBA      b = address-increment code 1 ... 33, 34 stuffing, 35 escape; c = 1 when the code follows an escape
+ *   EFXO_SYM_TYPE     b = macroblock_type flags (bit 0 intra, 1 pattern, 3 forward, 4 quant), c = picture_coding_type
+ *   EFXO_SYM_CBP      b = coded_block_pattern
+ *   EFXO_SYM_DCT      b = run, c = signed level, e = 0 first code of the block / 1 later (behind an intra DC too), + 2 for
+ *                     the "1s" / "11s" forms (escapes are EFXO_T_ESCAPE)
+ *   EFXO_SYM_DC_SIZE  b = dct_dc_size, c = 0 luminance / 1 chrominance, e = sign of the differential (0 when size is 0)
+ *   EFXO_SYM_QSCALE   b = quantiser_scale, c = 0 slice header / 1 macroblock
+ * EFXO_T_MOTION: a = 0 horizontal / 1 vertical, b = motion code -16 ... 16, c = residual (-1 when none is read),
+ *                e = the predictor the delta is added to, in units of the picture's f_code */
+enum { EFXO_SYM_MBA = 0, EFXO_SYM_TYPE = 1, EFXO_SYM_CBP = 2, EFXO_SYM_DCT = 3, EFXO_SYM_DC_SIZE = 4, EFXO_SYM_QSCALE = 5 };
 typedef void (*efxo_trace_fn)(void* user, int kind, int a, int b, int c, int e);
 void efxo_set_trace(efxo_trace_fn fn, void* user);
 

@@ -110,6 +110,119 @@ def trace_levels(data: np.ndarray, fmt: int) -> dict:
     return st
 
 
+def trace_syntax(data: np.ndarray, fmt: int) -> dict:
+    """Runs the oracle with its parse trace on and summarises WHICH syntax elements it decoded (trace_levels' sibling): per
+    picture its type, r_size, full_pel and every macroblock (address, type flags or "skipped", half-pel vector, pattern,
+    quantiser), and as sets over the stream
+      mba        address-increment codes 1 ... 33, 34 stuffing, 35 escape;  mba_esc: the codes read behind an escape
+      types      (picture type, macroblock_type flags);  cbp: patterns;  qscale: (0 slice header / 1 macroblock, value)
+      motion     (picture, component, motion code);  residual: (picture, component, r_size, residual)
+      wraps      (picture, component, +1 / -1): the sum left the range upwards / downwards and was wrapped
+      ends       (picture, component, vector) for vectors at -16 scale or 16 scale - 1
+      resets     what lay between a macroblock with a large vector (a component of 8 units or more) and the next one with
+                 vectors, whose predictor was zero and whose motion codes were small: "skipped", "intra", "pattern", "slice"
+      dct        (run, level, 0 first coefficient / 1 later) of the code book's entries;  dct_short likewise for "1s" / "11s"
+      escapes    (form, run, level, 0 first / 1 later);  dc: (0 luminance / 1 chrominance, size, sign);  last_pos: scan positions
+                 63 was reached by (0 table code / 1 escape)"""
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    st = {"pictures": [], "mba": set(), "mba_esc": set(), "types": set(), "cbp": set(), "qscale": set(), "motion": set(),
+          "residual": set(), "wraps": set(), "ends": set(), "resets": set(), "dct": set(), "dct_short": set(), "escapes": set(),
+          "dc": set(), "last_pos": set(), "r_sizes": set(), "full_pel": set()}
+    cur = {"pic": None, "type": None, "cbp": None, "n": 0, "esc": None, "intra": False, "big": False, "between": set(), "mo": [],
+           "picture": -1}
+
+    def cb(_user, kind, a, b, c, e):
+        if kind == 0:      # slice
+            if a != cur["picture"]:
+                cur["picture"] = a
+                cur["pic"] = dict(type=c & 15, r_size=(c >> 8) & 0xFF, full_pel=(c >> 4) & 1, mbs=[])
+                while len(st["pictures"]) <= a:
+                    st["pictures"].append(None)
+                st["pictures"][a] = cur["pic"]
+                cur["big"] = False
+                if (c & 15) == 2:
+                    st["r_sizes"].add((c >> 8) & 0xFF)
+                    st["full_pel"].add((c >> 4) & 1)
+            cur["between"].add("slice")
+        elif kind == 7:    # syntax element
+            if a == 0:
+                st["mba"].add(b)
+                if c:
+                    st["mba_esc"].add(b)
+            elif a == 1:
+                st["types"].add((c, b))
+                cur["type"], cur["cbp"], cur["mo"] = b, None, []
+            elif a == 2:
+                st["cbp"].add(b)
+                cur["cbp"] = b
+            elif a == 3:
+                (st["dct_short"] if e & 2 else st["dct"]).add((b, c, e & 1))
+            elif a == 4:
+                st["dc"].add((c, b, e))
+            elif a == 5:
+                st["qscale"].add((c, b))
+        elif kind == 8:    # motion code
+            p = cur["pic"]
+            scale = 1 << p["r_size"]
+            st["motion"].add((cur["picture"], a, b))
+            if c >= 0:
+                st["residual"].add((cur["picture"], a, p["r_size"], c))
+            delta = (((abs(b) - 1) << p["r_size"]) + c + 1) * (1 if b > 0 else -1) if c >= 0 else b
+            if e + delta > 16 * scale - 1:
+                st["wraps"].add((cur["picture"], a, 1))
+            elif e + delta < -16 * scale:
+                st["wraps"].add((cur["picture"], a, -1))
+            cur["mo"].append((b, e))
+        elif kind == 1:    # macroblock
+            p = cur["pic"]
+            if b & 2:
+                p["mbs"].append(dict(addr=a, type="skipped", mv=(0, 0), cbp=0, q=0))
+                cur["between"].add("skipped")
+                return
+            t = cur["type"]
+            cur["intra"], cur["n"] = bool(b & 1), 0
+            cbp = cur["cbp"] if cur["cbp"] is not None else (63 if b & 1 else 0)
+            p["mbs"].append(dict(addr=a, type=t, mv=(c, e), cbp=cbp, q=b >> 2))
+            if t & 8:
+                u = 2 if p["full_pel"] else 1
+                scale = 1 << p["r_size"]
+                for comp, v in ((0, c // u), (1, e // u)):
+                    if v in (-16 * scale, 16 * scale - 1):
+                        st["ends"].add((cur["picture"], comp, v))
+                if cur["big"] and all(pred == 0 and abs(code) <= 2 for code, pred in cur["mo"]):
+                    for k in cur["between"]:
+                        st["resets"].add((cur["picture"], k))
+                cur["big"] = max(abs(c), abs(e)) // u >= 8
+                cur["between"] = set()
+            elif b & 1:
+                cur["between"].add("intra")
+            else:
+                cur["between"].add("pattern")
+        elif kind == 4:    # escape (before its coefficient)
+            cur["esc"] = (a, b, c)
+        elif kind == 3:    # block end
+            cur["n"] = 0
+        elif kind == 2:    # coefficient: b = scan position
+            first = cur["n"] == 0
+            if cur["esc"] is not None:
+                st["escapes"].add(cur["esc"] + (0 if first else 1,))
+            if b == 63:
+                st["last_pos"].add(0 if cur["esc"] is None else 1)
+            cur["esc"] = None
+            cur["n"] += 1
+
+    FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int)
+    fn = FN(cb)
+    L = lib()
+    L.efxo_set_trace.argtypes = [FN, C.c_void_p]
+    L.efxo_set_trace(fn, None)
+    try:
+        L.efxo_decode(data.ctypes.data, data.size, fmt, 1, None, None, None, 0)
+    finally:
+        L.efxo_set_trace(FN(), None)
+    return st
+
+
 def ts_to_es(ts: np.ndarray) -> np.ndarray:
     ts = np.ascontiguousarray(ts, dtype=np.uint8)
     out = np.zeros(ts.size, dtype=np.uint8)
