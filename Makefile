@@ -28,9 +28,9 @@ $(CSRC)/k_cropdetect.o $(CSRC)/efx_api.o: $(CSRC)/crop_px.h
 $(CSRC)/k_quality.o $(CSRC)/efx_api.o: $(CSRC)/quality_px.h
 $(CSRC)/k_encode.o $(CSRC)/k_mux.o $(CSRC)/efx_api.o: $(CSRC)/enc_core.h $(CSRC)/mpeg1_codebook.h
 $(CSRC)/k_sbc_enc.o $(CSRC)/efx_api.o: $(CSRC)/sbc_enc_core.h $(CSRC)/sbc_proto.h
-$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/efx_internal.h $(CSRC)/import_pcm.h $(CSRC)/enc_rate.h $(CSRC)/parse_tm.h $(CSRC)/efx_probe.h include/efx.h
+$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/efx_internal.h $(CSRC)/import_pcm.h $(CSRC)/enc_rate.h $(CSRC)/enc_aq.h $(CSRC)/parse_tm.h $(CSRC)/efx_probe.h include/efx.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(CSRC)/efx_tables.o: $(CSRC)/efx_tables.cpp $(CSRC)/efx_internal.h $(CSRC)/import_pcm.h $(CSRC)/enc_rate.h $(CSRC)/parse_tm.h $(CSRC)/mpeg1_codebook.h $(CSRC)/sbc_proto.h
+$(CSRC)/efx_tables.o: $(CSRC)/efx_tables.cpp $(CSRC)/efx_internal.h $(CSRC)/import_pcm.h $(CSRC)/enc_rate.h $(CSRC)/enc_aq.h $(CSRC)/parse_tm.h $(CSRC)/mpeg1_codebook.h $(CSRC)/sbc_proto.h
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 $(CSRC)/efx_multi.o: $(CSRC)/efx_multi.cpp include/efx.h
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@

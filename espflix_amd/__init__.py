@@ -46,6 +46,7 @@ ENCODE_FULL = 512         # efx_encode: the stream's output region filled up (ef
 ENCODE_VBV = 4096         # efx_encode_rc: the buffer model's level went below zero during the call (efx.h)
 SCENE_CUT_DEFAULT = 144   # scene_cut=True: the threshold that separates the cuts of the test clips (profiles/scene_cut.md)
 PICTURE_I, PICTURE_P, PICTURE_CUT_I = 1, 2, 5   # efx_enc_picture_info.type
+AQ_DEFAULT = 256          # aq=True: Test Model 5's factor (profiles/adaptive_quant.md)
 MUX_FULL = 1024           # efx_mux_av: the stream's output region is too small, nothing written (efx.h)
 MUX_BAD_VIDEO = 2048      # efx_mux_av: the video input is not a transport stream of PID 0x100 that starts with a PES (efx.h)
 PCM_FRAME_PLANAR, PCM_INTERLEAVED = 0, 1   # efx_sbc_encode_opts.pcm_layout
@@ -135,6 +136,10 @@ class _EncodeRate(C.Structure):
 
 class _SceneCut(C.Structure):
     _fields_ = [("threshold", C.c_int), ("min_gop", C.c_int)]
+
+
+class _AdaptiveQuant(C.Structure):
+    _fields_ = [("strength", C.c_int)]
 
 
 class _EncPictureInfo(C.Structure):
@@ -247,6 +252,8 @@ _SYMBOLS = {
     "efx_encode_set_picture_rate": (C.c_int, [_P, C.c_int]),
     "efx_encode_set_scene_cut": (C.c_int, [_P, C.POINTER(_SceneCut)]),
     "efx_encode_picture_info": (C.c_int, [_P, C.c_int, C.POINTER(_EncPictureInfo), C.c_int]),
+    "efx_encode_set_adaptive_quant": (C.c_int, [_P, C.POINTER(_AdaptiveQuant)]),
+    "efx_encode_mb_quant": (C.c_int, [_P, C.c_int, C.c_int, C.c_void_p]),
     "efx_picture_pts_offset": (C.c_int64, [C.c_int, C.c_int64]),
     "efx_picture_rate_code": (C.c_int, [C.c_int64, C.c_int64]),
     "efx_conform_rate": (C.c_int, [_P, C.POINTER(_ConformOpts), _P, _P]),
@@ -1150,7 +1157,7 @@ class Decoder:
                   search: int = 7, fmt: int = FORMAT_TS, cont: bool = False, first_pts: int = 0, src_stride: int = 0,
                   dst_stride: int = 0, recon: DeviceBuffer | int | None = None, bitrate: int | None = None,
                   vbv_bits: int = 250_000, qmin: int = 3, qmax: int = 31, qscale_out: DeviceBuffer | int | None = None, fps=None,
-                  scene_cut: int | bool | None = None, min_gop: int | None = None):
+                  scene_cut: int | bool | None = None, min_gop: int | None = None, aq: int | bool | None = None):
         """efx_encode on raw device memory (DeviceBuffers or pointers), asynchronous on the library's stream: stream i's
         pictures at src + i * src_stride (0 = packed), its bytes appended to dst + i * dst_stride (0 = efx_encode_bound),
         uint32 byte counts and status bits to length / status, the reconstruction to recon (optional).
@@ -1166,9 +1173,15 @@ class Decoder:
         scene_cut: fresh streams code an I picture where the content changes (efx_encode_set_scene_cut, likewise in front
         of every cont=False call): the threshold 1 .. 256, True = SCENE_CUT_DEFAULT, None / False / 0 = off; min_gop: no
         such I picture sooner than this after the last one, None = max(1, gop // 2).  With cont=True the streams keep what
-        they started with and both are ignored."""
+        they started with and both are ignored.
+
+        aq: fresh streams give every macroblock its own quantiser around the picture's (efx_encode_set_adaptive_quant,
+        likewise in front of every cont=False call): the strength 1 .. 256, True = AQ_DEFAULT, None / False / 0 = off.
+        With cont=True the streams keep what they started with and it is ignored."""
         g = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else b)
         if not cont:
+            strength = _AdaptiveQuant(AQ_DEFAULT if aq is True else int(aq or 0))
+            _check(self._ctx, self._lib.efx_encode_set_adaptive_quant(self._ctx, C.byref(strength)))
             threshold = SCENE_CUT_DEFAULT if scene_cut is True else int(scene_cut or 0)
             sc = _SceneCut(threshold, max(1, gop // 2) if min_gop is None else int(min_gop))
             _check(self._ctx, self._lib.efx_encode_set_scene_cut(self._ctx, C.byref(sc)))
@@ -1193,7 +1206,7 @@ class Decoder:
     def encode(self, pictures, *, qscale: int = 8, gop: int = 12, search: int = 7, fmt: int = FORMAT_TS, cont: bool = False,
                first_pts: int = 0, recon: bool = False, dst_stride: int = 0, bitrate: int | None = None,
                vbv_bits: int = 250_000, qmin: int = 3, qmax: int = 31, fps=None, scene_cut: int | bool | None = None,
-               min_gop: int | None = None, quality: bool = False) -> EncodeResult:
+               min_gop: int | None = None, quality: bool = False, aq: int | bool | None = None) -> EncodeResult:
         """Encode (n, P, 101376) I420 pictures (the layout export("i420") writes) into n MPEG-1 streams of P pictures: a uint8
         torch tensor on the decoder's device or a NumPy array.  Stream i takes the pictures of row i (the order export()
         gives streams).  Returns each stream's bytes, its status bits and, with recon=True, what a decoder reconstructs
@@ -1215,6 +1228,9 @@ class Decoder:
 
         scene_cut, min_gop: as for encode_to.  The result's types holds every picture's type and cut_scores its two sums
         (zeros while scene cuts are off), with or without the option.
+
+        aq: adaptive quantisation as for encode_to; encode_mb_quant(stream, picture) afterwards gives a picture's
+        quantisers.
 
         quality=True: the reconstruction is kept on the device (in a buffer of the call's own when recon=False) and
         compared with the source right behind the encode, on the same stream (compare_to with ref_max=248, the
@@ -1260,7 +1276,7 @@ class Decoder:
             self.encode_to(src_ptr, dst, meta.ptr, meta.ptr + status_off, n_streams=n, n_pictures=P, qscale=qscale, gop=gop,
                            search=search, fmt=fmt, cont=cont, first_pts=first_pts, dst_stride=stride, recon=rec_ptr,
                            bitrate=bitrate, vbv_bits=vbv_bits, qmin=qmin, qmax=qmax, qscale_out=q_buf, fps=fps, scene_cut=scene_cut,
-                           min_gop=min_gop)
+                           min_gop=min_gop, aq=aq)
             qual_buf = None
             if quality and n * P:
                 qual_buf = DeviceBuffer(self, 48 * n * P)
@@ -1303,6 +1319,13 @@ class Decoder:
             got = self._lib.efx_encode_picture_info(self._ctx, i, out[i].ctypes.data_as(C.POINTER(_EncPictureInfo)), count)
             if got < 0:
                 _check(self._ctx, got)
+        return out
+
+    def encode_mb_quant(self, stream: int, picture: int) -> np.ndarray:
+        """The quantisers of one picture of the latest encode call, which ran with aq (efx_encode_mb_quant; synchronises):
+        a (12, 22) uint8 array, all zero for a picture that was not written."""
+        out = np.zeros((12, 22), dtype=np.uint8)
+        _check(self._ctx, self._lib.efx_encode_mb_quant(self._ctx, stream, picture, out.ctypes.data))
         return out
 
     # -- video / audio out ----------------------------------------------------------------
@@ -1562,7 +1585,7 @@ class Decoder:
                   allocation: int = 0, bitpool: int = 28, frequency: int = 3, sample_rate: int = 48000, frames_per_pes: int = 8,
                   audio_pid: int = 0x101, bitrate: int | None = None, vbv_bits: int = 250_000, qmin: int = 3, qmax: int = 31,
                   pcm_rate: int | None = None, pcm_layout: str = "interleaved", fps=None, scene_cut: int | bool | None = None,
-                  min_gop: int | None = None, quality: bool = False):
+                  min_gop: int | None = None, quality: bool = False, aq: int | bool | None = None):
         """Pictures + PCM -> complete titles: encode (transport streams) -> sbc_encode (mono) -> mux, queued back to back on
         the library's stream with nothing synchronised in between.  pictures: (n, P, 101376) I420 as for encode(); pcm: int16
         [n, samples], a whole number of frames of blocks x 8 samples; the audio starts at the first picture's PTS.  Every
@@ -1582,6 +1605,8 @@ class Decoder:
 
         scene_cut, min_gop: I pictures at the video's scene cuts, as for encode(); encode_picture_info(n) afterwards
         gives the pictures' types.
+
+        aq: adaptive quantisation of the video, as for encode().
 
         quality=True: the video's reconstruction is kept in a device buffer of the call's own and compared with the
         pictures right behind the encode, on the same stream, as for encode(); the call then returns (titles, status,
@@ -1639,7 +1664,7 @@ class Decoder:
             torch.cuda.current_stream(device).synchronize()
             self.encode_to(pictures.data_ptr(), d_v, p_vlen, p_vst, n_streams=n, n_pictures=P, qscale=qscale, gop=gop, search=search,
                            fmt=FORMAT_TS, first_pts=first_pts, dst_stride=v_stride, bitrate=bitrate, vbv_bits=vbv_bits, qmin=qmin,
-                           qmax=qmax, fps=fps, scene_cut=scene_cut, min_gop=min_gop, recon=d_rec)
+                           qmax=qmax, fps=fps, scene_cut=scene_cut, min_gop=min_gop, recon=d_rec, aq=aq)
             if d_qual is not None:
                 self.compare_to(pictures.data_ptr(), d_rec, d_qual, n_images=n * P, ref_max=248)
             if imp is not None:
@@ -1761,7 +1786,7 @@ class Decoder:
 
     def trick_streams(self, pictures=None, *, title=None, speed: int = 15, gop: int = 3, qscale: int = 8, search: int = 7,
                       bitrate: int | None = None, vbv_bits: int = 250_000, qmin: int = 3, qmax: int = 31, first_pts: int = 0,
-                      piece: int | None = None, fps=None):
+                      piece: int | None = None, fps=None, aq: int | bool | None = None):
         """The fast-forward and the rewind stream of n titles (the reference indexer's `-g 3 ... setpts=PTS/15` and
         `-vf reverse` runs, indexer/indexer.cpp:308-309): every speed-th picture of a title, encoded in playing order and in
         reverse order as transport streams with GOPs of `gop` pictures.  Returns (fwd: list of bytes, rwd: list of bytes,
@@ -1781,7 +1806,7 @@ class Decoder:
         nothing synchronised between the pick and the encode of a piece; the rewind stream is encoded after the last piece
         (the encoder keeps one set of streams per context, and a reversed stream cannot start before the title has ended).
         Both streams start at first_pts; trick picture k carries first_pts + picture_pts_offset(fps, k) (fps as for
-        encode(): None = 30000/1001, first_pts + 3003 k).  qscale, search and bitrate ... qmax as for encode().  Synchronises: torch's current stream before (tensor input), the library's after."""
+        encode(): None = 30000/1001, first_pts + 3003 k).  qscale, search, bitrate ... qmax and aq as for encode().  Synchronises: torch's current stream before (tensor input), the library's after."""
         if (pictures is None) == (title is None):
             raise ValueError("give pictures or title=, not both")
         if not 1 <= speed <= 255:
@@ -1844,7 +1869,7 @@ class Decoder:
                                         d_meta.ptr + state["meta"] + r16(4 * n), n_streams=n, n_pictures=count, qscale=qscale,
                                         gop=gop, search=search, fmt=FORMAT_TS, cont=cont, first_pts=first_pts,
                                         src_stride=src_stride, bitrate=bitrate, vbv_bits=vbv_bits, qmin=qmin, qmax=qmax,
-                                        fps=fps)
+                                        fps=fps, aq=aq)
                 done.append((side, state["dst"], stride, state["meta"]))
                 state["dst"] += n * stride
                 state["meta"] += 2 * r16(4 * n)
@@ -1885,13 +1910,14 @@ class Decoder:
             for b in bufs:
                 b.free()
 
-    def make_title(self, pictures, pcm, *, speed: int = 15, trick_gop: int = 3, fps=None, fps_out=None, poster=None, **encode_av):
+    def make_title(self, pictures, pcm, *, speed: int = 15, trick_gop: int = 3, fps=None, fps_out=None, poster=None, aq: int | bool | None = None,
+                   **encode_av):
         """A complete title directory per stream, as the reference's indexer leaves it (indexer/indexer.cpp:292-321) and its
         player opens it (src/espflix.cpp:647,787-792): returns (list of n dicts {"video.ts", "video_fwd.ts", "video_rwd.ts",
         "video.idx"} of bytes, status: uint32 [3, n], rows video.ts (ENCODE_* | MUX_* bits), video_fwd.ts, video_rwd.ts).
 
         video.ts is encode_av(pictures, pcm, **encode_av).  The trick streams are trick_streams(pictures, speed=speed,
-        gop=trick_gop) with the same qscale, search, first_pts and rate-control keywords, without audio.  They are made
+        gop=trick_gop) with the same qscale, search, first_pts, aq and rate-control keywords, without audio.  They are made
         from the SOURCE pictures, one generation better than the reference, whose ffmpeg runs recode the finished
         video.ts.  video.idx is idx_build over index_streams([main, fwd, rwd], trick_speed=[1, speed, speed]), one call per
         title -- max_stream_bytes must hold the three streams of a title -- or, on a context with max_streams below 3, one
@@ -1903,7 +1929,8 @@ class Decoder:
         (conform) before encode_av and trick_streams see them.  The PCM is not touched: the audio's PTS come from its
         sample count.  poster: an image as make_poster takes it; the dictionaries then hold "poster.ts" as well.
 
-        scene_cut=, min_gop= (among **encode_av) apply to video.ts only: the trick streams keep their GOPs of trick_gop."""
+        scene_cut=, min_gop= (among **encode_av) apply to video.ts only: the trick streams keep their GOPs of trick_gop.
+        aq: adaptive quantisation as for encode(), of video.ts and of both trick streams."""
         if fps is not None and fps_out is None and not picture_rate_code(fps):
             raise ValueError(f"fps={fps!r} is not a rate MPEG-1 codes; give fps_out=, one of "
                              f"{', '.join(str(r) for r in PICTURE_RATES.values())}")
@@ -1917,9 +1944,9 @@ class Decoder:
                     pictures = torch.from_numpy(np.ascontiguousarray(pictures)).to(torch.device("cuda", self.device))
                 pictures = self.conform(pictures, fps, fps_out)
             fps = fps_out
-        titles, st = self.encode_av(pictures, pcm, fps=fps, **encode_av)
+        titles, st = self.encode_av(pictures, pcm, fps=fps, aq=aq, **encode_av)
         keys = ("qscale", "search", "first_pts", "bitrate", "vbv_bits", "qmin", "qmax")
-        fwd, rwd, tst = self.trick_streams(pictures, speed=speed, gop=trick_gop, fps=fps,
+        fwd, rwd, tst = self.trick_streams(pictures, speed=speed, gop=trick_gop, fps=fps, aq=aq,
                                            **{k: encode_av[k] for k in keys if k in encode_av})
         poster_ts = None if poster is None else self.make_poster(poster)
         out = []

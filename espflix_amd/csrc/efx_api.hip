@@ -74,9 +74,11 @@ __global__ void k_conform(ConformArgs);  // (k_conform.hip)
 __global__ void k_import_pcm(ImportPcmArgs);  // (k_import_pcm.hip)
 __global__ void k_import_pcm_state(ImportPcmArgs);
 __global__ void k_enc_begin(EncArgs);
+__global__ void k_enc_aq(EncArgs);
 __global__ void k_enc_cut(EncArgs);
 __global__ void k_enc_act(EncArgs);
-__global__ void k_enc_rows(EncArgs);
+template <bool kAq>
+__global__ void k_enc_rows_t(EncArgs);  // k_encode.hip instantiates both
 __global__ void k_enc_pack(EncArgs);
 __global__ void k_sbc(const uint8_t*, size_t, int, int, SbcState*, const SbcTables*, int16_t*, size_t, uint32_t*, uint32_t*, int);
 __global__ void k_sbc_frames(const uint8_t*, size_t, int, int, SbcFrameInfo*, uint32_t*, uint32_t*, SbcQueues*);
@@ -292,6 +294,12 @@ struct efx_ctx {
     enc::CutParams enc_cut{0, 1};        // scene-cut settings of the streams cont = 1 continues
     enc::CutParams enc_next_cut{0, 1};   // efx_encode_set_scene_cut: those of the streams a cont = 0 call starts
     int enc_info_streams = 0, enc_info_pictures = 0;  // streams and pictures of the latest call (0: no call yet)
+    enc::AqParams enc_aq{0};             // adaptive quantisation of the streams cont = 1 continues (enc_aq.h)
+    enc::AqParams enc_next_aq{0};        // efx_encode_set_adaptive_quant: that of the streams a cont = 0 call starts
+    bool enc_info_aq = false;            // the latest call ran with adaptive quantisation: d_enc_aq_map holds its quantisers
+    uint16_t* d_enc_aq_act = nullptr;    // adaptive quantisation, allocated by the first encode with it on: 22 activities
+    uint32_t* d_enc_aq_sums = nullptr;   // ... and their sum per (stream, macroblock row)
+    uint8_t* d_enc_aq_map = nullptr;     // ... kEncInfoCap maps of 264 quantisers per stream, of the latest call
 
     // results of the last decode (fetch_results)
     int n_streams = 0;  // streams of the batch the last decode read
@@ -745,7 +753,7 @@ void efx_destroy(efx_ctx* ctx)
                     ctx->d_video_lines[1], ctx->d_hash, ctx->d_ts, ctx->d_demux_chunks, ctx->d_sbc_tables, ctx->d_idx_info, ctx->d_ts_off, ctx->d_idx_len,
                     ctx->d_idx_base, ctx->d_idx_seq, ctx->d_enc_state, ctx->d_enc_pics, ctx->d_enc_slices, ctx->d_enc_slice_len,
                     ctx->d_enc_act, ctx->d_enc_cut_pics, ctx->d_enc_cut_sums, ctx->d_enc_info, ctx->d_enc_tables, ctx->d_sbc_enc_tables, ctx->d_mux_before, ctx->d_import_taps, ctx->d_import_pcm_table,
-                    ctx->d_crop_sums};
+                    ctx->d_crop_sums, ctx->d_enc_aq_act, ctx->d_enc_aq_sums, ctx->d_enc_aq_map};
     if (ctx->h_enc_full)
         (void)hipHostFree(ctx->h_enc_full);
     for (auto& te : ctx->timing_ring)
@@ -2155,6 +2163,37 @@ int efx_encode_set_scene_cut(efx_ctx* ctx, const efx_scene_cut* cut)
     return EFX_OK;
 }
 
+int efx_encode_set_adaptive_quant(efx_ctx* ctx, const efx_adaptive_quant* aq)
+{
+    if (!ctx)
+        return EFX_ERR_ARG;
+    if (!aq) {
+        ctx->enc_next_aq = enc::AqParams{0};
+        return EFX_OK;
+    }
+    if (aq->strength < 0 || aq->strength > enc::kAqMaxStrength)
+        return fail(ctx, EFX_ERR_ARG, "efx_encode_set_adaptive_quant: strength outside 0 .. 256");
+    ctx->enc_next_aq = enc::AqParams{aq->strength};
+    return EFX_OK;
+}
+
+int efx_encode_mb_quant(efx_ctx* ctx, int stream, int picture, uint8_t* out_host)
+{
+    bind_device(ctx);
+    if (!ctx)
+        return EFX_ERR_ARG;
+    if (!ctx->enc_info_pictures)
+        return fail(ctx, EFX_ERR_STATE, "efx_encode_mb_quant: no efx_encode yet");
+    if (!ctx->enc_info_aq)
+        return fail(ctx, EFX_ERR_STATE, "efx_encode_mb_quant: the latest efx_encode ran without adaptive quantisation");
+    if (stream < 0 || stream >= ctx->enc_info_streams || picture < 0 || picture >= ctx->enc_info_pictures || !out_host)
+        return fail(ctx, EFX_ERR_ARG, "efx_encode_mb_quant: stream or picture outside the latest call's, or out_host NULL");
+    EFX_HIP(hipMemcpyAsync(out_host, ctx->d_enc_aq_map + ((size_t)stream * kEncInfoCap + picture) * enc::kAqMbs, enc::kAqMbs,
+                           hipMemcpyDeviceToHost, ctx->stream));
+    EFX_HIP(hipStreamSynchronize(ctx->stream));
+    return EFX_OK;
+}
+
 int efx_encode_picture_info(efx_ctx* ctx, int stream, efx_enc_picture_info* out_host, int cap)
 {
     static_assert(sizeof(efx_enc_picture_info) == sizeof(EncPictureInfo), "efx_enc_picture_info layout");
@@ -2264,6 +2303,24 @@ static int encode_impl(efx_ctx* ctx, const efx_encode_opts* o, const efx_encode_
         }
         ctx->enc_ready = true;
     }
+    const enc::AqParams aq = o->cont ? ctx->enc_aq : ctx->enc_next_aq;
+    if (aq.strength > 0 && !ctx->d_enc_aq_map) {
+        // only a context that uses adaptive quantisation holds its scratch; all or nothing, like the rest
+        const size_t n = (size_t)ctx->cfg.max_streams;
+        hipError_t e = dalloc(&ctx->d_enc_aq_act, n * kMbH * kMbW);
+        if (e == hipSuccess) e = dalloc(&ctx->d_enc_aq_sums, n * kMbH);
+        if (e == hipSuccess) e = dalloc(&ctx->d_enc_aq_map, n * kEncInfoCap * enc::kAqMbs);
+        if (e != hipSuccess) {
+            (void)dev_free(ctx->d_enc_aq_act);
+            (void)dev_free(ctx->d_enc_aq_sums);
+            (void)dev_free(ctx->d_enc_aq_map);
+            ctx->d_enc_aq_act = nullptr;
+            ctx->d_enc_aq_sums = nullptr;
+            ctx->d_enc_aq_map = nullptr;
+            (void)hipGetLastError();
+            return fail(ctx, EFX_ERR_DEVICE, "efx_encode: cannot allocate the scratch of adaptive quantisation", e);
+        }
+    }
     if (!o->cont)
         ctx->enc_generation = ctx->enc_generation + 1 ? ctx->enc_generation + 1 : 1;  // (0: no call has filled a region)
     EncArgs a{};
@@ -2295,6 +2352,10 @@ static int encode_impl(efx_ctx* ctx, const efx_encode_opts* o, const efx_encode_
     a.cut_pics = ctx->d_enc_cut_pics;
     a.cut_sums = ctx->d_enc_cut_sums;
     a.info = ctx->d_enc_info;
+    a.aq = aq;
+    a.aq_act = ctx->d_enc_aq_act;
+    a.aq_sums = ctx->d_enc_aq_sums;
+    a.aq_map = ctx->d_enc_aq_map;
     if (rate) {
         a.rc = 1;
         a.rate.cap = (int64_t)rate->vbv_bits * 90000;
@@ -2309,18 +2370,22 @@ static int encode_impl(efx_ctx* ctx, const efx_encode_opts* o, const efx_encode_
     hipLaunchKernelGGL(k_enc_begin, dim3((unsigned)((o->n_streams + 63) / 64)), dim3(64), 0, ctx->stream, a);
     for (int p = 0; p < o->n_pictures; p++) {
         a.picture = p;
+        if (a.aq.strength > 0)
+            hipLaunchKernelGGL(k_enc_aq, dim3((unsigned)o->n_streams * kMbH), dim3(64), 0, ctx->stream, a);
         if (a.cut.threshold > 0)
             hipLaunchKernelGGL(k_enc_cut, dim3((unsigned)o->n_streams * kMbH), dim3(64), 0, ctx->stream, a);
         if (rate)
             hipLaunchKernelGGL(k_enc_act, dim3((unsigned)o->n_streams * kMbH), dim3(64), 0, ctx->stream, a);
-        hipLaunchKernelGGL(k_enc_rows, dim3((unsigned)o->n_streams * kMbH), dim3(64), 0, ctx->stream, a);
+        hipLaunchKernelGGL(a.aq.strength > 0 ? k_enc_rows_t<true> : k_enc_rows_t<false>, dim3((unsigned)o->n_streams * kMbH), dim3(64), 0, ctx->stream, a);
         hipLaunchKernelGGL(k_enc_pack, dim3((unsigned)o->n_streams), dim3(256), 0, ctx->stream, a);
     }
     EFX_HIP(hipGetLastError());
     ctx->enc_info_streams = o->n_streams;
     ctx->enc_info_pictures = o->n_pictures;
+    ctx->enc_info_aq = a.aq.strength > 0;
     if (!o->cont) {
         ctx->enc_cut = a.cut;
+        ctx->enc_aq = a.aq;
         ctx->enc_started = true;
         ctx->enc_n_streams = o->n_streams;
         ctx->enc_format = o->format;

@@ -14,6 +14,7 @@
 #pragma once
 #include <cstdint>
 
+#include "enc_aq.h"
 #include "enc_cut.h"
 #include "enc_rate.h"
 #include "import_pcm.h"
@@ -368,6 +369,11 @@ struct EncArgs {
     uint8_t* cut_pics;        // two decimated source pictures (enc::kCutBytes) per stream, indexed by pictures & 1
     uint32_t* cut_sums;       // per (stream, row): the row's cut_i and cut_p (k_enc_cut)
     EncPictureInfo* info;     // per (stream, picture of the call): stream i's at info + i * 255 (k_enc_pack)
+    // adaptive quantisation (enc_aq.h): aq.strength 0 = off, k_enc_aq is not launched and none of the three is read or written
+    enc::AqParams aq;
+    uint16_t* aq_act;         // per (stream, row): the activities of the row's 22 macroblocks (k_enc_aq)
+    uint32_t* aq_sums;        // per (stream, row): their sum
+    uint8_t* aq_map;          // per (stream, picture of the call): 264 quantisers, stream i's at aq_map + i * 255 * 264 (k_enc_rows)
 };
 
 // k_conform (k_conform.hip) launch arguments (by value): efx_conform_opts, checked.  Items and runs are k_trick's.

@@ -26,6 +26,12 @@ constexpr int kYBytes = kW * kH, kCBytes = kCW * kCH;  // I420: Y, then Cb, then
 constexpr int kPicBytes = kYBytes + 2 * kCBytes;       // 101 376
 // Bits of one macroblock at most: address increment 11, type 6, two motion codes of 11 + 1, pattern 9, and six blocks
 // of 64 escaped coefficients (28 bits each) and end_of_block.
+// Adaptive quantisation (write_slice's mq) keeps inside this: the quant variants of the inter types cost 5 + 5 bits, 4
+// over the 6, but the budget is only reached with all six blocks coded, where the pattern 63 is a 6-bit code against
+// the 9, and an address increment inside a slice of 22 is at most 21, a 10-bit code against the 11.  Intra + quant is
+// 6 + 5 bits, 5 over, and an intra macroblock's DC sizes and differentials take up to 4 x 15 + 2 x 16 = 92 bits, but it
+// spends none of the 24 motion and 9 pattern bits and codes 63 AC coefficients per block, not 64: 6 x 28 bits to spare.
+// tests/test_encode_aq_model.py derives both sums from the code book's lengths.
 constexpr int kMbMaxBits = 11 + 6 + 24 + 9 + 6 * (64 * 28 + 2);
 // Bytes of one slice at most: start code, quantiser_scale + extra_bit_slice, 22 macroblocks; rounded to 16
 constexpr int kSliceCap = ((4 + (6 + kMbCols * kMbMaxBits + 7) / 8) + 15) / 16 * 16;
@@ -441,11 +447,20 @@ EFX_ENC_HD inline void put_motion(Bits& bw, int delta, int f_code, const Tables&
 // One slice = one macroblock row: start code row + 1, quantiser_scale q, then the 22 macroblocks.  A P macroblock with
 // vector (0, 0) and no coded block is skipped unless it is the first or last of the slice; the DC and vector predictors
 // reset as the decoder resets them.  Returns the bytes written (byte-aligned, at most kSliceCap).
-EFX_ENC_HD inline uint32_t write_slice(uint8_t* out, int row, int q, int type, int f_code, const Mb* mbs, const Tables& T)
+//
+// mq (adaptive quantisation, enc_aq.h; nullptr: every macroblock at q): the quantiser of each of the 22 macroblocks.  The
+// slice header carries mq[0]; a coded macroblock (intra, or with a pattern) whose quantiser is not the current one is
+// written with the quant variant of its type and five bits of its quantiser, which becomes the current one.  A
+// macroblock without coded blocks never changes it.  (kMq = whether mq is given: the coder without it is a function of
+// its own, the one it was before there was an mq.)
+template <bool kMq>
+EFX_ENC_HD inline uint32_t write_slice_t(uint8_t* out, int row, int q, int type, int f_code, const Mb* mbs, const Tables& T,
+                                         const uint8_t* mq)
 {
     Bits bw{out, 0, 0, 0};
     bw.start_code(row + 1);
-    bw.put((uint32_t)q, 5);
+    int cur_q = kMq ? mq[0] : q;
+    bw.put((uint32_t)cur_q, 5);
     bw.put(0, 1);  // extra_bit_slice
     int dc_pred[3] = {128, 128, 128};
     int pmv_h = 0, pmv_v = 0;
@@ -465,11 +480,16 @@ EFX_ENC_HD inline uint32_t write_slice(uint8_t* out, int row, int q, int type, i
             pending_skip = 0;
         }
         bw.put(T.mba_code[inc], T.mba_len[inc]);
+        const bool quant = kMq && (!inter || m.cbp) && mq[mbx] != cur_q;
+        if (quant)
+            cur_q = mq[mbx];
         if (!inter) {
             if (type == 1)
-                bw.put(1, 1);
+                bw.put(1, quant ? 2 : 1);
             else
-                bw.put(T.type_p_code[1], T.type_p_len[1]);
+                bw.put(T.type_p_code[quant ? 17 : 1], T.type_p_len[quant ? 17 : 1]);
+            if (quant)
+                bw.put((uint32_t)cur_q, 5);
             pmv_h = pmv_v = 0;
             for (int b = 0; b < 6; b++) {
                 const int comp = b < 4 ? 0 : b - 3;
@@ -481,8 +501,10 @@ EFX_ENC_HD inline uint32_t write_slice(uint8_t* out, int row, int q, int type, i
         }
         dc_pred[0] = dc_pred[1] = dc_pred[2] = 128;
         const bool has_mv = m.h != 0 || m.v != 0 || m.cbp == 0;  // "no motion compensation, not coded" does not exist
-        const int t = (m.cbp ? 2 : 0) | (has_mv ? 8 : 0);
+        const int t = (m.cbp ? 2 : 0) | (has_mv ? 8 : 0) | (quant ? 16 : 0);
         bw.put(T.type_p_code[t], T.type_p_len[t]);
+        if (quant)
+            bw.put((uint32_t)cur_q, 5);
         if (has_mv) {
             int dh = m.h - pmv_h, dv = m.v - pmv_v;
             dh = dh < -range ? dh + 2 * range : (dh > range - 1 ? dh - 2 * range : dh);
@@ -502,6 +524,11 @@ EFX_ENC_HD inline uint32_t write_slice(uint8_t* out, int row, int q, int type, i
     }
     bw.align();
     return bw.n;
+}
+EFX_ENC_HD inline uint32_t write_slice(uint8_t* out, int row, int q, int type, int f_code, const Mb* mbs, const Tables& T,
+                                       const uint8_t* mq = nullptr)
+{
+    return mq ? write_slice_t<true>(out, row, q, type, f_code, mbs, T, mq) : write_slice_t<false>(out, row, q, type, f_code, mbs, T, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------

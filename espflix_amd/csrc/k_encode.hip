@@ -4,10 +4,13 @@
 //   k_enc_cut     scene cuts only (efx_encode_set_scene_cut), before everything else of a picture: one wave per (stream,
 //                 macroblock row) decimates the row's source luma 4 x 4 into the stream's decimated picture and measures
 //                 its 22 macroblocks against the previous decimated source picture (enc_cut.h)
+//   k_enc_aq      adaptive quantisation only (efx_encode_set_adaptive_quant), ahead of the others: one wave per (stream,
+//                 macroblock row) measures the spatial activity of the row's 22 macroblocks on the source luma (enc_aq.h)
 //   k_enc_act     efx_encode_rc only, before every k_enc_rows: one wave per (stream, macroblock row) sums the activity of the
 //                 row's 22 macroblocks -- the luma's deviation from its own mean, and the smaller of that and the SAD
 //                 against the previous reconstruction at the same place -- with v_sad_u8 on whole 352-byte lines
-//   k_enc_rows    one wave per (stream, macroblock row): for each of the row's 22 macroblocks, full-pel search over the
+//   k_enc_rows    (k_enc_rows_t<false>; <true> with adaptive quantisation) one wave per (stream, macroblock row): for
+//                 each of the row's 22 macroblocks, full-pel search over the
 //                 previous reconstruction staged in LDS (v_sad_u8, one candidate vector per lane), the 8 half-pel
 //                 neighbours of the best one, the intra / inter decision, then transform, quantisation and reconstruction
 //                 with one lane per block (enc_core.h).  The levels stay in LDS; at the end of the row one lane codes the
@@ -25,6 +28,10 @@
 // Scene cuts: every wave of k_enc_rows, and k_enc_pack, adds the twelve row sums of k_enc_cut in row order and evaluates
 // enc::cut_picture_type (enc_cut.h), a pure function of the stream's state and those sums, so a stream's picture has one
 // type in every wave -- and the streams of one launch need not have the same.
+//
+// Adaptive quantisation: every wave of k_enc_rows adds the twelve row sums of k_enc_aq in row order, forms the picture's
+// average activity and gives each of its 22 macroblocks the quantiser of enc::aq_mb_quant (enc_aq.h) around the
+// picture's quantiser -- the fixed one, or the controller's, which never sees the macroblocks' own.
 //
 // Every store is a vector store (global / LDS); the only serial part is the bit writer of a slice.
 #include <hip/hip_runtime.h>
@@ -123,6 +130,57 @@ __global__ __launch_bounds__(64) void k_enc_act(EncArgs a)
         w.y = (uint32_t)act_p;
         *reinterpret_cast<uint2*>(a.act + ((size_t)s * kMbRows + row) * 2) = w;
     }
+}
+
+// Spatial activity of one macroblock row (enc_aq.h).  The row's 16 luma lines are read as k_enc_act reads them.  An
+// 8 x 8 block is two words of eight lines: lines 0 .. 7 and 8 .. 15 are summed separately, the lanes of a pair (2 k,
+// 2 k + 1) added for a block's sum and deviation, then the minimum taken over the two halves and across the quad's two
+// pairs.  Lane 4 m holds macroblock m's (lanes 0 .. 23 macroblock 16 + m's as well).
+__global__ __launch_bounds__(64) void k_enc_aq(EncArgs a)
+{
+    using namespace enc;
+    const int row = blockIdx.x % kMbRows, s = blockIdx.x / kMbRows, lane = threadIdx.x;
+    const bool tail = lane < kW / 4 - 64;
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(a.src + (size_t)s * a.src_stride + (size_t)a.picture * kPicBytes +
+                                                            (size_t)row * 16 * kW);
+    uint32_t c0[16], c1[16];
+    for (int y = 0; y < 16; y++) {
+        c0[y] = src[y * (kW / 4) + lane];
+        c1[y] = tail ? src[y * (kW / 4) + 64 + lane] : 0u;
+    }
+    uint32_t best0 = 0xFFFFFFFFu, best1 = 0xFFFFFFFFu;
+    for (int half = 0; half < 2; half++) {
+        uint32_t sum0 = 0, sum1 = 0;
+        for (int y = 8 * half; y < 8 * half + 8; y++) {
+            sum0 = __builtin_amdgcn_sad_u8(c0[y], 0u, sum0);
+            sum1 = __builtin_amdgcn_sad_u8(c1[y], 0u, sum1);
+        }
+        sum0 += (uint32_t)__shfl_xor((int)sum0, 1, 64);
+        sum1 += (uint32_t)__shfl_xor((int)sum1, 1, 64);
+        const uint32_t m0 = ((sum0 + 32) >> 6) * 0x01010101u, m1 = ((sum1 + 32) >> 6) * 0x01010101u;
+        uint32_t dev0 = 0, dev1 = 0;
+        for (int y = 8 * half; y < 8 * half + 8; y++) {
+            dev0 = __builtin_amdgcn_sad_u8(c0[y], m0, dev0);
+            dev1 = __builtin_amdgcn_sad_u8(c1[y], m1, dev1);
+        }
+        dev0 += (uint32_t)__shfl_xor((int)dev0, 1, 64);
+        dev1 += (uint32_t)__shfl_xor((int)dev1, 1, 64);
+        best0 = min(best0, dev0);
+        best1 = min(best1, dev1);
+    }
+    best0 = min(best0, (uint32_t)__shfl_xor((int)best0, 2, 64));
+    best1 = min(best1, (uint32_t)__shfl_xor((int)best1, 2, 64));
+    const bool lead = (lane & 3) == 0;  // one lane per macroblock: 16 in the first set of words, 6 in the second
+    const uint32_t a0 = lead ? 1 + best0 : 0u, a1 = lead && tail ? 1 + best1 : 0u;
+    uint16_t* act = a.aq_act + ((size_t)s * kMbRows + row) * kMbCols;
+    if (lead) {
+        act[lane >> 2] = (uint16_t)a0;
+        if (tail)
+            act[16 + (lane >> 2)] = (uint16_t)a1;
+    }
+    const int sum = wave_sum((int)(a0 + a1));
+    if (lane == 0)
+        a.aq_sums[(size_t)s * kMbRows + row] = (uint32_t)sum;
 }
 
 // Scene-cut measure of one macroblock row (enc_cut.h).  The row's 16 luma lines are read as k_enc_act reads them; the sum
@@ -246,7 +304,20 @@ __device__ inline int rate_q(const EncArgs& a, const EncState& S, int s, int pha
     return enc::rate_decide(S.rate, rate_params(a, S), S.pictures, phase, a.gop, ai, ap);
 }
 
-__global__ __launch_bounds__(64) void k_enc_rows(EncArgs a)
+// The picture's average activity: the stream's row sums of k_enc_aq added in row order.  Every wave of a stream gets the
+// same value.
+__device__ inline uint32_t aq_avg(const EncArgs& a, int s)
+{
+    uint32_t sum = 0;
+    for (int k = 0; k < enc::kMbRows; k++)
+        sum += a.aq_sums[(size_t)s * enc::kMbRows + k];
+    return enc::aq_average(sum);
+}
+
+// k_enc_rows: k_enc_rows_t<false>, and <true> with adaptive quantisation.  Two kernels, so that the encoder without the
+// option runs the code it ran before there was one.
+template <bool kAq>
+__global__ __launch_bounds__(64) void k_enc_rows_t(EncArgs a)
 {
     using namespace enc;
     const int row = blockIdx.x % kMbRows, s = blockIdx.x / kMbRows, lane = threadIdx.x;
@@ -269,8 +340,19 @@ __global__ __launch_bounds__(64) void k_enc_rows(EncArgs a)
     __shared__ uint32_t cur_w[64];                      // the macroblock's luma, 16 rows x 4 words
     __shared__ uint32_t win_w[kWin * kWinStride / 4 + 4];  // search window
     __shared__ int best_sad;
+    __shared__ uint8_t mq[kMbCols];  // kAq: the macroblocks' quantisers
     uint8_t* win = reinterpret_cast<uint8_t*>(win_w);
     const int R = a.search, side = 2 * R + 1, wn = 2 * R + 18;
+    if (kAq) {
+        const uint32_t avg = aq_avg(a, s);
+        if (lane < kMbCols) {
+            const uint32_t act = a.aq_act[((size_t)s * kMbRows + row) * kMbCols + lane];
+            const int q = aq_mb_quant(qscale, a.aq.strength, act, avg, a.rc ? a.rate.qmin : 1, a.rc ? a.rate.qmax : 31);
+            mq[lane] = (uint8_t)q;
+            a.aq_map[((size_t)s * kEncInfoCap + a.picture) * kAqMbs + row * kMbCols + lane] = (uint8_t)q;
+        }
+        __syncthreads();
+    }
 
     for (int mbx = 0; mbx < kMbCols; mbx++) {
         cur_w[lane] = *reinterpret_cast<const uint32_t*>(src + (row * 16 + (lane >> 2)) * kW + mbx * 16 + (lane & 3) * 4);
@@ -346,6 +428,7 @@ __global__ __launch_bounds__(64) void k_enc_rows(EncArgs a)
                 h = v = 0;
         }
         // one lane per block: prediction, transform, quantisation, reconstruction
+        const int mb_q = kAq ? __builtin_amdgcn_readfirstlane((int)mq[mbx]) : qscale;  // (the same in every lane: kept scalar)
         int coded = 0;
         if (lane < 6) {
             uint8_t blk[64];
@@ -353,7 +436,7 @@ __global__ __launch_bounds__(64) void k_enc_rows(EncArgs a)
                 predict_block(ref, lane, mbx, row, h, v, blk);
             int pitch;
             const uint8_t* sb = block_ptr(src, lane, mbx, row, &pitch);
-            coded = code_block(sb, pitch, intra, qscale, T, blk, mbs[mbx].lev[lane]);
+            coded = code_block(sb, pitch, intra, mb_q, T, blk, mbs[mbx].lev[lane]);
             uint8_t* rb = const_cast<uint8_t*>(block_ptr(rec, lane, mbx, row, &pitch));
             for (int y = 0; y < 8; y++) {
                 uint2 w;
@@ -379,8 +462,11 @@ __global__ __launch_bounds__(64) void k_enc_rows(EncArgs a)
     }
     if (lane == 0)
         a.slice_len[(size_t)s * kMbRows + row] =
-            write_slice(a.slices + ((size_t)s * kMbRows + row) * kSliceCap, row, qscale, type, a.f_code, mbs, T);
+            write_slice_t<kAq>(a.slices + ((size_t)s * kMbRows + row) * kSliceCap, row, qscale, type, a.f_code, mbs, T, kAq ? mq : nullptr);
 }
+
+template __global__ void k_enc_rows_t<false>(EncArgs);
+template __global__ void k_enc_rows_t<true>(EncArgs);
 
 __global__ __launch_bounds__(256) void k_enc_pack(EncArgs a)
 {
@@ -435,6 +521,8 @@ __global__ __launch_bounds__(256) void k_enc_pack(EncArgs a)
             out[o] = b;
         }
     }
+    if (a.aq.strength > 0 && !sh_ok && tid < kAqMbs / 4)  // a picture that was not written has no quantisers
+        reinterpret_cast<uint32_t*>(a.aq_map + ((size_t)s * kEncInfoCap + a.picture) * kAqMbs)[tid] = 0u;
     __syncthreads();
     if (tid == 0) {
         if (a.rc) {

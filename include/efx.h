@@ -549,7 +549,8 @@ int efx_picture_rate_code(int64_t num, int64_t den);
  *   - the first picture of a fresh stream is coded at clamp(opts->qscale, qmin, qmax);
  *   - a picture that starts with F <= 0 is coded at qmax;
  *   - with qmin == qmax every picture is coded at that value (the bytes are efx_encode's at that qscale).
- * No quantiser changes inside a picture, no picture is coded twice, dropped or repeated; audio is outside the model.
+ * No quantiser changes inside a picture unless adaptive quantisation (below) is on, no picture is coded twice, dropped or
+ * repeated; audio is outside the model.
  *
  * qscale_out_device (may be NULL): the quantiser of stream i, picture p at qscale_out_device + i * n_pictures + p; a
  * picture that was not written (EFX_ENCODE_FULL) gets 0.
@@ -617,6 +618,48 @@ typedef struct efx_enc_picture_info {
     uint8_t pad[3];
 } efx_enc_picture_info;
 int efx_encode_picture_info(efx_ctx* ctx, int stream, efx_enc_picture_info* out_host, int cap);
+
+/* -- adaptive quantisation: one quantiser_scale per macroblock (k_encode's k_enc_aq, enc_aq.h) -- */
+/* efx_encode and efx_encode_rc code every macroblock of a picture at the picture's quantiser q (opts->qscale, or the
+ * controller's choice).  Smooth macroblocks show blocking and banding at a quantiser that textured ones hide.  With
+ * adaptive quantisation on, every macroblock gets its own quantiser mq around q from the spatial activity of the SOURCE
+ * picture: Test Model 5's activity and normalisation, in integers.
+ *
+ * Block activity, for each of the four 8 x 8 luma blocks of a macroblock: S = the sum of its 64 pels, m = (S + 32) >> 6,
+ * d = sum |p - m|.  Macroblock activity a = 1 + min(d0, d1, d2, d3), 1 .. 8161.  Picture average avg = (A + 132) / 264,
+ * A = the sum of a over the picture's 264 macroblocks.  With the strength s, 1 .. 256:
+ *   num = (256 + s) a + 256 avg      den = 256 a + (256 + s) avg
+ *   mq  = clamp((q num + (den >> 1)) / den, lo, hi)
+ * lo, hi = 1, 31 under efx_encode and qmin, qmax under efx_encode_rc.  a == avg gives mq == q; s = 256 is TM5's factor
+ * (2 a + avg) / (a + 2 avg), which lies between 1/2 and 2.
+ *
+ * Each macroblock's six blocks are transformed, quantised, range-checked and reconstructed with its mq.  The slice header
+ * carries the mq of the slice's first macroblock; the slice coder keeps a current value, starting there.  A coded
+ * macroblock (intra, or with a coded block pattern) whose mq differs from the current value is written with the quant
+ * variant of its macroblock_type followed by five bits of mq, which becomes the current value.  A skipped macroblock or
+ * one without coded blocks never changes it.  The mode decision, the search, the skip rule, the predictors, the picture
+ * headers and scene cuts do not depend on any of this.
+ *
+ * Under efx_encode_rc the controller decides and updates exactly as without adaptive quantisation, with the picture's q;
+ * qscale_out_device reports q; with qmin == qmax the clamp leaves mq == q.  The controller does not price what mq does to
+ * a picture's size.  efx_encode_bound holds unchanged (enc_core.h, beside kMbMaxBits).
+ *
+ * efx_encode_set_adaptive_quant sets what the streams of later cont = 0 calls of efx_encode / efx_encode_rc start with;
+ * NULL or strength 0 = off, as in a fresh context, and the streams are then those of the encoder without this section, byte
+ * for byte, with the same launches and allocations.  Streams continued with cont = 1 keep what they started with, whatever
+ * was set in between.  EFX_ERR_ARG: strength outside 0 .. 256 (the earlier setting stays).  One more launch per picture
+ * while it is on, whatever n_streams is.  Its scratch (per stream 528 bytes of activities, twelve sums and 255 maps of 264
+ * bytes) is allocated at the first encode with adaptive quantisation on, for max_streams streams, and freed by efx_destroy.
+ *
+ * efx_encode_mb_quant reports the mq of one picture of the context's latest efx_encode / efx_encode_rc call: it waits for
+ * the context's stream and writes 264 bytes to out_host, macroblock (r, c) at 22 r + c; all zero for a picture that was
+ * not written (EFX_ENCODE_FULL).  EFX_ERR_STATE before the context's first encode or when the latest call ran with
+ * adaptive quantisation off; EFX_ERR_ARG: stream or picture outside the latest call's, out_host NULL. */
+typedef struct efx_adaptive_quant {
+    int strength;  /* 0 = off, 1 .. 256; 256 = TM5 */
+} efx_adaptive_quant;
+int efx_encode_set_adaptive_quant(efx_ctx* ctx, const efx_adaptive_quant* aq);
+int efx_encode_mb_quant(efx_ctx* ctx, int stream, int picture, uint8_t* out_host);
 
 /* -- fast-forward and rewind streams: which pictures make them (k_trick) ------------------- */
 /* A title of the reference is four files: the player opens video_rwd.ts, video.ts and video_fwd.ts by name
