@@ -104,6 +104,12 @@ class _CropOpts(C.Structure):
                [("src_stride", C.c_size_t), ("sums_stride", C.c_size_t)]
 
 
+class _Surface(C.Structure):
+    """efx_surface: one 4:2:0 YCbCr image in device memory by plane offsets and pitches (surface_layout() makes one)."""
+    _fields_ = [(n, C.c_int) for n in ("layout", "shift", "swap_uv", "width", "height")] + \
+               [("offset", C.c_size_t * 3), ("pitch", C.c_size_t * 3), ("bytes", C.c_size_t)]
+
+
 class _CompareOpts(C.Structure):
     _fields_ = [("n_images", C.c_int), ("ref_max", C.c_int), ("ref_stride", C.c_size_t), ("test_stride", C.c_size_t),
                 ("mb_stride", C.c_size_t)]
@@ -241,6 +247,9 @@ _SYMBOLS = {
     "efx_import_src_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "efx_import_frames": (C.c_int, [_P, C.POINTER(_ImportOpts), _P, _P]),
     "efx_detect_crop": (C.c_int, [_P, C.POINTER(_CropOpts), _P, _P, _P]),
+    "efx_import_surfaces": (C.c_int, [_P, C.POINTER(_Surface), C.POINTER(_ImportOpts), _P, _P]),
+    "efx_detect_crop_surfaces": (C.c_int, [_P, C.POINTER(_Surface), C.POINTER(_CropOpts), _P, _P, _P]),
+    "efx_surface_layout": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.POINTER(_Surface)]),
     "efx_compare_pictures": (C.c_int, [_P, C.POINTER(_CompareOpts), _P, _P, _P, _P]),
     "efx_compare_psnr": (C.c_double, [C.c_uint64, C.c_uint64]),
     "efx_compare_ssim": (C.c_double, [C.c_int64, C.c_int]),
@@ -378,6 +387,46 @@ def import_src_bytes(fmt, width: int, height: int) -> int:
     format, a width or height outside 2 .. 4096, or an odd I420 size."""
     code = _PIX_FORMATS.get(fmt, -1) if isinstance(fmt, str) else int(fmt)
     return int(load_library().efx_import_src_bytes(code, width, height))
+
+
+# efx_surface_kind: the conventional layouts of decoders' surfaces (the 16-bit kinds hold uint16 samples)
+_SURFACE_KINDS = {"i420": 0, "yv12": 1, "nv12": 2, "nv21": 3, "p010": 4, "p012": 5, "p016": 6, "i010": 7, "i012": 8, "i016": 9}
+SURF_PLANAR8, SURF_SEMI8, SURF_PLANAR16, SURF_SEMI16 = 0, 1, 2, 3  # efx_surface.layout
+
+
+def surface_layout(kind: str, width: int, height: int, pitch: int = 0, plane_rows: int = 0) -> _Surface:
+    """The efx_surface of a decoder's picture (efx_surface_layout): kind "i420", "yv12", "nv12", "nv21", "p010", "p012",
+    "p016", "i010", "i012" or "i016", Y at 0 with `pitch` bytes per row (0 = packed rows) and plane_rows rows per luma
+    plane (0 = height), the chroma plane(s) behind it; .bytes is the extent of one image.  The fields may be edited, for
+    a decoder with other offsets or for one field of an interlaced picture.  Host only."""
+    if kind not in _SURFACE_KINDS:
+        raise ValueError(f"unknown surface kind {kind!r}: one of {sorted(_SURFACE_KINDS)}")
+    s = _Surface()
+    if not load_library().efx_surface_layout(_SURFACE_KINDS[kind], width, height, pitch, plane_rows, C.byref(s)):
+        raise ValueError(f"no {kind} surface of {width} x {height} with pitch {pitch} and {plane_rows} plane rows "
+                         "(even sizes 2 .. 4096, pitch >= a row and <= 2^20, even plane_rows >= height)")
+    return s
+
+
+def _surface_source(src, kind, width, height, pitch, plane_rows):
+    """(surface, n, src as (n, bytes) uint8) of import_pictures' / detect_crop's source when fmt is a surface kind."""
+    if width is None or height is None:
+        raise ValueError(f"a {kind} source needs width= and height=")
+    surf = surface_layout(kind, width, height, pitch, plane_rows)
+    shape = tuple(src.shape)
+    if isinstance(src, np.ndarray):
+        wide = src.dtype == np.uint16
+    else:
+        import torch
+        wide = isinstance(src, torch.Tensor) and src.dtype == torch.uint16
+    if wide and surf.layout not in (SURF_PLANAR16, SURF_SEMI16):
+        raise ValueError(f"a {kind} source holds bytes, not uint16 samples")
+    if len(shape) != 2 or shape[1] * (2 if wide else 1) != surf.bytes:
+        raise ValueError(f"a {kind} source of this geometry must have shape (n, {surf.bytes}) uint8" +
+                         (f" or (n, {surf.bytes // 2}) uint16" if surf.layout in (SURF_PLANAR16, SURF_SEMI16) else "") + f", got {shape}")
+    if wide:  # the same memory as bytes (little endian)
+        src = np.ascontiguousarray(src).view(np.uint8) if isinstance(src, np.ndarray) else src.contiguous().view(torch.uint8)
+    return surf, shape[0], src
 
 
 def letterbox_rect(width: int, height: int):
@@ -897,17 +946,22 @@ class Decoder:
 
     # -- pictures in (efx_import_frames) ----------------------------------------------------
     def import_to(self, src: DeviceBuffer | int, dst: DeviceBuffer | int, *, n_images: int, fmt: str, width: int, height: int,
-                  crop=None, dst_rect=None, full_range: bool = False, src_stride: int = 0, dst_stride: int = 0):
+                  crop=None, dst_rect=None, full_range: bool = False, src_stride: int = 0, dst_stride: int = 0, surface=None):
         """efx_import_frames on raw device memory (DeviceBuffers or pointers), asynchronous on the library's stream:
         source image i (fmt "i420", "rgb24" or "rgbp", width x height) at src + i * src_stride (0 = import_src_bytes()
         rounded up to 16), its 352 x 192 I420 picture at dst + i * dst_stride (0 = 101376).  crop = (x, y, w, h) of the
         source (None: all of it), dst_rect = (x, y, w, h) of the output that receives it (None: all of it), the rest is
-        black."""
+        black.  surface: an efx_surface from surface_layout() -- the images are then read as that surface describes them
+        (efx_import_surfaces: NV12, P010, pitched planes ...), fmt must be "i420", width and height the surface's, and
+        src_stride 0 means surface.bytes rounded up to 16."""
         if fmt not in _PIX_FORMATS:
             raise ValueError(f"unknown format {fmt!r}: one of {sorted(_PIX_FORMATS)}")
         g = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
         o = _ImportOpts(n_images, _PIX_FORMATS[fmt], width, height, *(crop or (0, 0, 0, 0)), *(dst_rect or (0, 0, 0, 0)),
                         1 if full_range else 0, src_stride, dst_stride)
+        if surface is not None:
+            _check(self._ctx, self._lib.efx_import_surfaces(self._ctx, C.byref(surface), C.byref(o), g(src), g(dst)))
+            return
         _check(self._ctx, self._lib.efx_import_frames(self._ctx, C.byref(o), g(src), g(dst)))
 
     def _stage_pictures(self, src, n: int, image: int, stride: int, bufs: list, keep: list):
@@ -942,23 +996,27 @@ class Decoder:
     # -- black borders (efx_detect_crop) ----------------------------------------------------
     def detect_crop_to(self, src: DeviceBuffer | int, rects: DeviceBuffer | int, *, n_streams: int, images_per_stream: int,
                        fmt: str, width: int, height: int, limit: int = 24, round: int = 16, full_range: bool = False,
-                       src_stride: int = 0, sums: DeviceBuffer | int | None = None, sums_stride: int = 0):
+                       src_stride: int = 0, sums: DeviceBuffer | int | None = None, sums_stride: int = 0, surface=None):
         """efx_detect_crop on raw device memory (DeviceBuffers or pointers), asynchronous on the library's stream: source
         image k (fmt "i420", "rgb24" or "rgbp", width x height) at src + k * src_stride (0 = import_src_bytes() rounded
         up to 16) belongs to stream k // images_per_stream; stream i's record of eight int32 (x, y, w, h, x1, y1, x2,
         y2; the definition: include/efx.h) goes to rects + 32 i.  sums: when given, receives per image the height row
         sums and the width column sums (uint32), image k at + 4 * k * sums_stride bytes (0 = height + width rounded up
-        to 4)."""
+        to 4).  surface: an efx_surface from surface_layout() -- the luma is then read as that surface describes it
+        (efx_detect_crop_surfaces), fmt must be "i420", width and height the surface's."""
         if fmt not in _PIX_FORMATS:
             raise ValueError(f"unknown format {fmt!r}: one of {sorted(_PIX_FORMATS)}")
         g = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
         o = _CropOpts(n_streams, images_per_stream, _PIX_FORMATS[fmt], width, height, 1 if full_range else 0, limit, round,
                       src_stride, sums_stride)
+        if surface is not None:
+            _check(self._ctx, self._lib.efx_detect_crop_surfaces(self._ctx, C.byref(surface), C.byref(o), g(src), g(rects), g(sums)))
+            return
         _check(self._ctx, self._lib.efx_detect_crop(self._ctx, C.byref(o), g(src), g(rects), g(sums)))
 
     def detect_crop(self, src, *, fmt: str | None = None, width: int | None = None, height: int | None = None,
                     images_per_stream: int | None = None, limit: int = 24, round: int = 16,
-                    full_range: bool = False) -> np.ndarray:
+                    full_range: bool = False, pitch: int = 0, plane_rows: int = 0) -> np.ndarray:
         """The black borders of source pictures, found on the device (efx_detect_crop): an int32 array of shape
         (n_streams, 8) with x, y, w, h -- the crop for import_pictures(crop=...) -- and the bounds x1, y1, x2, y2 of the
         detected picture (inclusive; x2 < x1: every image was black, the crop is the whole picture).  src as
@@ -966,9 +1024,15 @@ class Decoder:
         consecutive images form a stream with one rectangle, the union of its images; None: all images are one stream.
         A row or column is picture when its mean luma exceeds limit (for RGB sources the luma import_pictures would
         write with this full_range); the rectangle's sides are multiples of round where there is room, even otherwise.
-        Waits for the result."""
-        fmt, n, width, height = _import_geometry(src.shape, fmt, width, height)
-        image = import_src_bytes(fmt, width, height)
+        fmt may also be a surface kind of surface_layout() ("nv12", "p010", ...; "i420" with pitch= or plane_rows=), as
+        import_pictures takes it.  Waits for the result."""
+        surface = None
+        if fmt in _SURFACE_KINDS and (fmt != "i420" or pitch or plane_rows):
+            surface, n, src = _surface_source(src, fmt, width, height, pitch, plane_rows)
+            fmt, image = "i420", surface.bytes
+        else:
+            fmt, n, width, height = _import_geometry(src.shape, fmt, width, height)
+            image = import_src_bytes(fmt, width, height)
         if not image or n < 1:
             raise ValueError(f"{fmt} pictures of {width} x {height} cannot be read (2 .. 4096, i420: even; n >= 1)")
         per = n if images_per_stream is None else images_per_stream
@@ -978,16 +1042,16 @@ class Decoder:
         bufs, keep = [], []
         try:
             src_ptr, _, _ = self._stage_pictures(src, n, image, stride, bufs, keep)
-            return self._detect_rects(src_ptr, n // per, per, fmt, width, height, limit, round, full_range, stride)
+            return self._detect_rects(src_ptr, n // per, per, fmt, width, height, limit, round, full_range, stride, surface)
         finally:
             for b in bufs:
                 b.free()
 
-    def _detect_rects(self, src_ptr, n_streams, per, fmt, width, height, limit, round, full_range, stride) -> np.ndarray:
+    def _detect_rects(self, src_ptr, n_streams, per, fmt, width, height, limit, round, full_range, stride, surface=None) -> np.ndarray:
         rbuf = DeviceBuffer(self, 32 * n_streams)
         try:
             self.detect_crop_to(src_ptr, rbuf, n_streams=n_streams, images_per_stream=per, fmt=fmt, width=width, height=height,
-                                limit=limit, round=round, full_range=full_range, src_stride=stride)
+                                limit=limit, round=round, full_range=full_range, src_stride=stride, surface=surface)
             self.sync()
             return rbuf.download(np.int32, 8 * n_streams).reshape(n_streams, 8)
         finally:
@@ -1076,7 +1140,7 @@ class Decoder:
 
     def import_pictures(self, src, *, fmt: str | None = None, width: int | None = None, height: int | None = None, crop=None,
                         fit: str = "stretch", full_range: bool = False, out=None, sync: bool = True, crop_limit: int = 24,
-                        crop_round: int = 16):
+                        crop_round: int = 16, pitch: int = 0, plane_rows: int = 0):
         """Pictures of any size as (n, 101376) I420 pictures of 352 x 192, the layout encode() takes, cropped, scaled and
         converted on the device (efx_import_frames; the arithmetic: include/efx.h).  src: a NumPy array, or a uint8
         torch tensor on the decoder's device, of shape (n, H, W, 3) for "rgb24", (n, 3, H, W) for "rgbp", or
@@ -1090,6 +1154,11 @@ class Decoder:
         sides, and the rest of the frame is black; fit="cover" narrows the crop (given, detected or the whole picture)
         to cover_crop(), the largest centred rectangle of the frame's shape inside it, and fills the frame with that.
         full_range: RGB sources only, False = BT.601 studio swing (what MPEG-1 carries).
+        fmt may also be a surface kind of surface_layout(): "yv12", "nv12", "nv21", "p010", "p012", "p016", "i010", "i012",
+        "i016", or "i420" with pitch= or plane_rows=, together with width=, height=, pitch= (bytes per luma row, 0 =
+        packed) and plane_rows= (rows per luma plane, 0 = height).  src then has shape (n, bytes) as uint8, bytes being
+        surface_layout(...).bytes, or for the 16-bit kinds (n, bytes / 2) as uint16; the pictures are read where they lie
+        (efx_import_surfaces), 16-bit samples rounded to 8 bits.
 
         Returns a tensor for tensor input and an array for array input.  out: a preallocated contiguous uint8 tensor
         of n * 101376 elements on this device, or a DeviceBuffer (then returned as is); with out given, array input
@@ -1103,8 +1172,13 @@ class Decoder:
             raise ValueError(f"unknown fit {fit!r}: 'stretch', 'letterbox' or 'cover'")
         if isinstance(crop, str) and crop != "auto":
             raise ValueError(f"unknown crop {crop!r}: a rectangle (x, y, w, h), None or 'auto'")
-        fmt, n, width, height = _import_geometry(src.shape, fmt, width, height)
-        image = import_src_bytes(fmt, width, height)
+        surface = None
+        if fmt in _SURFACE_KINDS and (fmt != "i420" or pitch or plane_rows):
+            surface, n, src = _surface_source(src, fmt, width, height, pitch, plane_rows)
+            fmt, image = "i420", surface.bytes
+        else:
+            fmt, n, width, height = _import_geometry(src.shape, fmt, width, height)
+            image = import_src_bytes(fmt, width, height)
         if not image or n < 1:
             raise ValueError(f"{fmt} pictures of {width} x {height} cannot be imported (2 .. 4096, i420: even; n >= 1)")
         stride = (image + 15) // 16 * 16
@@ -1114,7 +1188,7 @@ class Decoder:
             src_ptr, is_array, must_sync = self._stage_pictures(src, n, image, stride, bufs, keep)
             sync = sync or must_sync
             if isinstance(crop, str):
-                rec = self._detect_rects(src_ptr, 1, n, fmt, width, height, crop_limit, crop_round, full_range, stride)
+                rec = self._detect_rects(src_ptr, 1, n, fmt, width, height, crop_limit, crop_round, full_range, stride, surface)
                 crop = tuple(int(v) for v in rec[0, :4])
             if fit == "cover":
                 crop = cover_crop(width, height, crop)
@@ -1141,7 +1215,7 @@ class Decoder:
                     raise ValueError(f"out must be contiguous with {nbytes} elements (shape {(n, FRAME_BYTES)})")
                 result, ptr = out.view(n, FRAME_BYTES), out.data_ptr()
             self.import_to(src_ptr, ptr, n_images=n, fmt=fmt, width=width, height=height, crop=crop, dst_rect=rect,
-                           full_range=full_range, src_stride=stride)
+                           full_range=full_range, src_stride=stride, surface=surface)
             if sync or bufs:
                 self.sync()  # (a staging buffer of this call is freed below)
             if obuf is not None:

@@ -22,6 +22,7 @@
 #include "enc_core.h"
 #include "import_px.h"
 #include "crop_px.h"
+#include "surface_px.h"
 #include "quality_px.h"
 #include "parse_tm.h"
 #include "sbc_enc_core.h"
@@ -60,10 +61,16 @@ template <int FMT, int CHROMA>
 __global__ void k_export(const uint8_t*, int, ExportArgs);  // (k_export.hip: the five (format, chroma) instances)
 __global__ void k_import_taps(ImportTap*, ImportArgs);  // (k_import.hip)
 __global__ void k_import(const uint8_t*, uint8_t*, const ImportTap*, ImportArgs);
+__global__ void k_import_surf8p(const uint8_t*, uint8_t*, const ImportTap*, ImportSurfArgs);
+__global__ void k_import_surf8s(const uint8_t*, uint8_t*, const ImportTap*, ImportSurfArgs);
+__global__ void k_import_surf16p(const uint8_t*, uint8_t*, const ImportTap*, ImportSurfArgs);
+__global__ void k_import_surf16s(const uint8_t*, uint8_t*, const ImportTap*, ImportSurfArgs);
 __global__ void k_crop_zero(CropArgs);  // (k_cropdetect.hip)
 __global__ void k_crop_sums_i420(CropArgs);
 __global__ void k_crop_sums_rgb24(CropArgs);
 __global__ void k_crop_sums_rgbp(CropArgs);
+__global__ void k_crop_sums_surf8(CropSurfArgs);
+__global__ void k_crop_sums_surf16(CropSurfArgs);
 __global__ void k_crop_rects(CropArgs);
 __global__ void k_quality_zero(QualityArgs);  // (k_quality.hip)
 __global__ void k_quality(QualityArgs);
@@ -1816,18 +1823,18 @@ size_t efx_import_src_bytes(int format, int width, int height)
     }
 }
 
-int efx_import_frames(efx_ctx* ctx, const efx_import_opts* o, const void* src_device, uint8_t* dst_device)
+// The checks efx_import_frames and efx_import_surfaces share, `image` being the bytes of one source image: the pointers,
+// n_images, the crop, the destination rectangle, the ratio and the strides, into the kernels' arguments
+static int import_args(efx_ctx* ctx, const char* who, const efx_import_opts* o, size_t image, const void* src_device, uint8_t* dst_device,
+                       ImportArgs* out)
 {
-    bind_device(ctx);
-    if (!ctx || !o)
-        return EFX_ERR_ARG;
+    const std::string w = std::string(who) + ": ";
     if (!src_device || ((uintptr_t)src_device & 15) || !dst_device || ((uintptr_t)dst_device & 15))
-        return fail(ctx, EFX_ERR_ARG, "efx_import_frames: src_device and dst_device must be 16-byte aligned device pointers");
-    const size_t image = efx_import_src_bytes(o->format, o->width, o->height);
+        return fail(ctx, EFX_ERR_ARG, (w + "src_device and dst_device must be 16-byte aligned device pointers").c_str());
     if (!image)
-        return fail(ctx, EFX_ERR_ARG, "efx_import_frames: unknown format, or width / height outside 2 .. 4096 (I420: even)");
+        return fail(ctx, EFX_ERR_ARG, (w + "unknown format, or width / height outside 2 .. 4096 (I420: even)").c_str());
     if (o->n_images < 1 || o->n_images > (1 << 24))
-        return fail(ctx, EFX_ERR_ARG, "efx_import_frames: n_images outside 1 .. 2^24");
+        return fail(ctx, EFX_ERR_ARG, (w + "n_images outside 1 .. 2^24").c_str());
     ImportArgs a{};
     a.format = o->format;
     a.width = o->width;
@@ -1841,9 +1848,9 @@ int efx_import_frames(efx_ctx* ctx, const efx_import_opts* o, const void* src_de
         a.crop_x = o->crop_x, a.crop_y = o->crop_y, a.crop_w = o->crop_w, a.crop_h = o->crop_h;
         if (a.crop_x < 0 || a.crop_y < 0 || a.crop_w < 1 || a.crop_h < 1 || a.crop_x > o->width - a.crop_w ||
             a.crop_y > o->height - a.crop_h)
-            return fail(ctx, EFX_ERR_ARG, "efx_import_frames: crop outside the source picture");
+            return fail(ctx, EFX_ERR_ARG, (w + "crop outside the source picture").c_str());
         if (even && ((a.crop_x | a.crop_y | a.crop_w | a.crop_h) & 1))
-            return fail(ctx, EFX_ERR_ARG, "efx_import_frames: the crop of an I420 source must be even");
+            return fail(ctx, EFX_ERR_ARG, (w + "the crop of an I420 source must be even").c_str());
     }
     if (o->dst_w == 0) {
         a.dst_w = EFX_FRAME_WIDTH;
@@ -1851,19 +1858,31 @@ int efx_import_frames(efx_ctx* ctx, const efx_import_opts* o, const void* src_de
     } else {
         a.dst_x = o->dst_x, a.dst_y = o->dst_y, a.dst_w = o->dst_w, a.dst_h = o->dst_h;
         if ((a.dst_x | a.dst_y | a.dst_w | a.dst_h) & 1)
-            return fail(ctx, EFX_ERR_ARG, "efx_import_frames: the destination rectangle must be even");
+            return fail(ctx, EFX_ERR_ARG, (w + "the destination rectangle must be even").c_str());
         if (a.dst_x < 0 || a.dst_y < 0 || a.dst_w < 16 || a.dst_h < 16 || a.dst_x > EFX_FRAME_WIDTH - a.dst_w ||
             a.dst_y > EFX_FRAME_HEIGHT - a.dst_h)
-            return fail(ctx, EFX_ERR_ARG, "efx_import_frames: destination rectangle below 16 x 16 or outside the 352 x 192 frame");
+            return fail(ctx, EFX_ERR_ARG, (w + "destination rectangle below 16 x 16 or outside the 352 x 192 frame").c_str());
     }
     if (a.crop_w > ipx::kMaxRatio * a.dst_w || a.crop_h > ipx::kMaxRatio * a.dst_h)
-        return fail(ctx, EFX_ERR_ARG, "efx_import_frames: the crop is more than 32 times the destination rectangle");
+        return fail(ctx, EFX_ERR_ARG, (w + "the crop is more than 32 times the destination rectangle").c_str());
     a.src_stride = o->src_stride ? o->src_stride : (image + 15) / 16 * 16;
     a.dst_stride = o->dst_stride ? o->dst_stride : (size_t)kFrameBytes;
     if (a.src_stride < image || (a.src_stride & 15))
-        return fail(ctx, EFX_ERR_ARG, "efx_import_frames: src_stride must be a multiple of 16 and hold an image");
+        return fail(ctx, EFX_ERR_ARG, (w + "src_stride must be a multiple of 16 and hold an image").c_str());
     if (a.dst_stride < (size_t)kFrameBytes || (a.dst_stride & 15))
-        return fail(ctx, EFX_ERR_ARG, "efx_import_frames: dst_stride must be a multiple of 16 and hold an image");
+        return fail(ctx, EFX_ERR_ARG, (w + "dst_stride must be a multiple of 16 and hold an image").c_str());
+    *out = a;
+    return EFX_OK;
+}
+
+int efx_import_frames(efx_ctx* ctx, const efx_import_opts* o, const void* src_device, uint8_t* dst_device)
+{
+    bind_device(ctx);
+    if (!ctx || !o)
+        return EFX_ERR_ARG;
+    ImportArgs a;
+    if (const int rc = import_args(ctx, "efx_import_frames", o, efx_import_src_bytes(o->format, o->width, o->height), src_device, dst_device, &a))
+        return rc;
     // two launches whatever n_images is; the table is written on the device, behind every earlier import's reads
     hipLaunchKernelGGL(k_import_taps, dim3((kImportTapRows + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_import_taps, a);
     hipLaunchKernelGGL(k_import, dim3((unsigned)o->n_images * kImportBands), dim3(256), 0, ctx->stream,
@@ -1872,23 +1891,69 @@ int efx_import_frames(efx_ctx* ctx, const efx_import_opts* o, const void* src_de
     return EFX_OK;
 }
 
-// ---- black borders (k_cropdetect.hip) -------------------------------------------------------------------------------------------
-int efx_detect_crop(efx_ctx* ctx, const efx_crop_opts* o, const void* src_device, efx_crop_rect* rects_device, uint32_t* sums_device)
+// ---- surfaces (surface_px.h; k_import.hip, k_cropdetect.hip) ------------------------------------------------------------------------
+size_t efx_surface_layout(int kind, int width, int height, size_t pitch, int plane_rows, efx_surface* out)
+{
+    return out ? spx::layout(kind, width, height, pitch, plane_rows, out) : 0;
+}
+
+// spx::check's verdict and the agreement of the opts with the surface as an error text; nullptr: the surface can be read
+static const char* surface_fault(const efx_surface* s, int format, int width, int height)
+{
+    switch (spx::check(*s)) {
+    case spx::kOk: break;
+    case spx::kBadLayout: return "unknown surface layout";
+    case spx::kBadShift: return "shift must be 1 .. 8 for a 16-bit layout and 0 for a byte layout";
+    case spx::kBadSwap: return "swap_uv must be 0 or 1, and 0 for a planar layout";
+    case spx::kBadSize: return "surface width / height must be even, 2 .. 4096";
+    case spx::kOddWords: return "the offsets and pitches of a 16-bit layout must be even";
+    case spx::kBadPitch: return "a pitch is below its plane's row bytes or above 2^20";
+    case spx::kBadBytes: return "surface bytes must be below 2^40";
+    default: return "a plane row ends beyond the surface's bytes";
+    }
+    if (format != EFX_PIX_I420 || width != s->width || height != s->height)
+        return "opts->format must be EFX_PIX_I420, opts->width and height the surface's";
+    return nullptr;
+}
+
+int efx_import_surfaces(efx_ctx* ctx, const efx_surface* s, const efx_import_opts* o, const void* src_device, uint8_t* dst_device)
 {
     bind_device(ctx);
-    if (!ctx || !o)
+    if (!ctx || !s || !o)
         return EFX_ERR_ARG;
+    if (const char* what = surface_fault(s, o->format, o->width, o->height))
+        return fail(ctx, EFX_ERR_ARG, (std::string("efx_import_surfaces: ") + what).c_str());
+    ImportSurfArgs a{};
+    if (const int rc = import_args(ctx, "efx_import_surfaces", o, s->bytes, src_device, dst_device, &a.a))
+        return rc;
+    a.s = *s;
+    // two launches, as efx_import_frames: the canonical image is I420, so its tap table is the call's
+    auto* const k = s->layout == EFX_SURF_PLANAR8 ? k_import_surf8p : s->layout == EFX_SURF_SEMI8 ? k_import_surf8s
+                    : s->layout == EFX_SURF_PLANAR16 ? k_import_surf16p : k_import_surf16s;
+    hipLaunchKernelGGL(k_import_taps, dim3((kImportTapRows + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_import_taps, a.a);
+    hipLaunchKernelGGL(k, dim3((unsigned)o->n_images * kImportBands), dim3(256), 0, ctx->stream, static_cast<const uint8_t*>(src_device),
+                       dst_device, ctx->d_import_taps, a);
+    EFX_HIP(hipGetLastError());
+    return EFX_OK;
+}
+
+// ---- black borders (k_cropdetect.hip) -------------------------------------------------------------------------------------------
+// The checks efx_detect_crop and efx_detect_crop_surfaces share, `image` being the bytes of one source image, into the
+// kernels' arguments (the context's scratch for the sums when the caller gives none)
+static int crop_args(efx_ctx* ctx, const char* who, const efx_crop_opts* o, size_t image, const void* src_device, efx_crop_rect* rects_device,
+                     uint32_t* sums_device, CropArgs* out)
+{
+    const std::string w = std::string(who) + ": ";
     if (!src_device || ((uintptr_t)src_device & 15) || !rects_device || ((uintptr_t)rects_device & 15) || ((uintptr_t)sums_device & 15))
-        return fail(ctx, EFX_ERR_ARG, "efx_detect_crop: src_device, rects_device and sums_device (when given) must be 16-byte aligned device pointers");
-    const size_t image = efx_import_src_bytes(o->format, o->width, o->height);
+        return fail(ctx, EFX_ERR_ARG, (w + "src_device, rects_device and sums_device (when given) must be 16-byte aligned device pointers").c_str());
     if (!image)
-        return fail(ctx, EFX_ERR_ARG, "efx_detect_crop: unknown format, or width / height outside 2 .. 4096 (I420: even)");
+        return fail(ctx, EFX_ERR_ARG, (w + "unknown format, or width / height outside 2 .. 4096 (I420: even)").c_str());
     if (o->n_streams < 1 || o->images_per_stream < 1 || (int64_t)o->n_streams * o->images_per_stream > INT32_MAX)
-        return fail(ctx, EFX_ERR_ARG, "efx_detect_crop: n_streams and images_per_stream must be >= 1, their product below 2^31");
+        return fail(ctx, EFX_ERR_ARG, (w + "n_streams and images_per_stream must be >= 1, their product below 2^31").c_str());
     if (o->limit < 0 || o->limit > 255)
-        return fail(ctx, EFX_ERR_ARG, "efx_detect_crop: limit outside 0 .. 255");
+        return fail(ctx, EFX_ERR_ARG, (w + "limit outside 0 .. 255").c_str());
     if (o->round < 2 || o->round > 64 || (o->round & 1))
-        return fail(ctx, EFX_ERR_ARG, "efx_detect_crop: round must be even, 2 .. 64");
+        return fail(ctx, EFX_ERR_ARG, (w + "round must be even, 2 .. 64").c_str());
     CropArgs a{};
     a.src = static_cast<const uint8_t*>(src_device);
     a.rects = reinterpret_cast<int32_t*>(rects_device);
@@ -1901,9 +1966,9 @@ int efx_detect_crop(efx_ctx* ctx, const efx_crop_opts* o, const void* src_device
     a.src_stride = o->src_stride ? o->src_stride : (image + 15) / 16 * 16;
     a.sums_stride = o->sums_stride ? o->sums_stride : ((size_t)o->height + o->width + 3) / 4 * 4;
     if (a.src_stride < image || (a.src_stride & 15))
-        return fail(ctx, EFX_ERR_ARG, "efx_detect_crop: src_stride must be a multiple of 16 and hold an image");
+        return fail(ctx, EFX_ERR_ARG, (w + "src_stride must be a multiple of 16 and hold an image").c_str());
     if (a.sums_stride < (size_t)o->height + o->width || (a.sums_stride & 3))
-        return fail(ctx, EFX_ERR_ARG, "efx_detect_crop: sums_stride must be a multiple of 4 and hold height + width sums");
+        return fail(ctx, EFX_ERR_ARG, (w + "sums_stride must be a multiple of 4 and hold height + width sums").c_str());
     if (sums_device) {
         a.sums = sums_device;
     } else {
@@ -1920,14 +1985,51 @@ int efx_detect_crop(efx_ctx* ctx, const efx_crop_opts* o, const void* src_device
         }
         a.sums = ctx->d_crop_sums;
     }
-    // three launches whatever the counts are (a workgroup takes further items when there are more than the grid's)
-    const size_t cap = (size_t)1 << 20;
-    const size_t zero_wgs = ((size_t)a.n_images * a.width + 255) / 256;
-    const size_t sum_wgs = (size_t)a.n_images * ((a.height + cpx::kBandRows - 1) / cpx::kBandRows);
-    hipLaunchKernelGGL(k_crop_zero, dim3((unsigned)std::min(zero_wgs, cap)), dim3(256), 0, ctx->stream, a);
+    *out = a;
+    return EFX_OK;
+}
+
+// three launches whatever the counts are (a workgroup takes further items when there are more than the grid's)
+constexpr size_t kCropGridCap = (size_t)1 << 20;
+static unsigned crop_zero_wgs(const CropArgs& a) { return (unsigned)std::min(((size_t)a.n_images * a.width + 255) / 256, kCropGridCap); }
+static unsigned crop_sum_wgs(const CropArgs& a)
+{
+    return (unsigned)std::min((size_t)a.n_images * ((a.height + cpx::kBandRows - 1) / cpx::kBandRows), kCropGridCap);
+}
+static unsigned crop_rect_wgs(const CropArgs& a) { return (unsigned)std::min((size_t)a.n_streams, kCropGridCap); }
+
+int efx_detect_crop(efx_ctx* ctx, const efx_crop_opts* o, const void* src_device, efx_crop_rect* rects_device, uint32_t* sums_device)
+{
+    bind_device(ctx);
+    if (!ctx || !o)
+        return EFX_ERR_ARG;
+    CropArgs a;
+    if (const int rc = crop_args(ctx, "efx_detect_crop", o, efx_import_src_bytes(o->format, o->width, o->height), src_device, rects_device,
+                                 sums_device, &a))
+        return rc;
+    hipLaunchKernelGGL(k_crop_zero, dim3(crop_zero_wgs(a)), dim3(256), 0, ctx->stream, a);
     auto* const k_sums = a.format == EFX_PIX_I420 ? k_crop_sums_i420 : a.format == EFX_PIX_RGB24 ? k_crop_sums_rgb24 : k_crop_sums_rgbp;
-    hipLaunchKernelGGL(k_sums, dim3((unsigned)std::min(sum_wgs, cap)), dim3(256), 0, ctx->stream, a);
-    hipLaunchKernelGGL(k_crop_rects, dim3((unsigned)std::min((size_t)a.n_streams, cap)), dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL(k_sums, dim3(crop_sum_wgs(a)), dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL(k_crop_rects, dim3(crop_rect_wgs(a)), dim3(256), 0, ctx->stream, a);
+    EFX_HIP(hipGetLastError());
+    return EFX_OK;
+}
+
+int efx_detect_crop_surfaces(efx_ctx* ctx, const efx_surface* s, const efx_crop_opts* o, const void* src_device, efx_crop_rect* rects_device,
+                             uint32_t* sums_device)
+{
+    bind_device(ctx);
+    if (!ctx || !s || !o)
+        return EFX_ERR_ARG;
+    if (const char* what = surface_fault(s, o->format, o->width, o->height))
+        return fail(ctx, EFX_ERR_ARG, (std::string("efx_detect_crop_surfaces: ") + what).c_str());
+    CropSurfArgs a{};
+    if (const int rc = crop_args(ctx, "efx_detect_crop_surfaces", o, s->bytes, src_device, rects_device, sums_device, &a.c))
+        return rc;
+    a.y_offset = s->offset[0], a.y_pitch = s->pitch[0], a.shift = s->shift;
+    hipLaunchKernelGGL(k_crop_zero, dim3(crop_zero_wgs(a.c)), dim3(256), 0, ctx->stream, a.c);
+    hipLaunchKernelGGL(spx::is_words(s->layout) ? k_crop_sums_surf16 : k_crop_sums_surf8, dim3(crop_sum_wgs(a.c)), dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL(k_crop_rects, dim3(crop_rect_wgs(a.c)), dim3(256), 0, ctx->stream, a.c);
     EFX_HIP(hipGetLastError());
     return EFX_OK;
 }

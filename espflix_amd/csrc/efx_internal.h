@@ -14,6 +14,7 @@
 #pragma once
 #include <cstdint>
 
+#include "efx.h"
 #include "enc_aq.h"
 #include "enc_cut.h"
 #include "enc_rate.h"
@@ -192,6 +193,12 @@ struct ImportArgs {
     size_t src_stride, dst_stride;
 };
 
+// k_import_surf launch arguments (by value): the ImportArgs of the surface's canonical I420 image, and the surface, checked
+struct ImportSurfArgs {
+    ImportArgs a;
+    efx_surface s;
+};
+
 // k_crop_zero / k_crop_sums / k_crop_rects launch arguments (by value): efx_crop_opts, checked (k_cropdetect.hip)
 struct CropArgs {
     const uint8_t* src;  // image k at src + k * src_stride
@@ -200,6 +207,13 @@ struct CropArgs {
     size_t src_stride, sums_stride;
     int n_streams, images_per_stream, n_images;
     int format, width, height, full_range, limit, round;
+};
+
+// k_crop_sums_surf8 / _surf16 launch arguments (by value): the CropArgs of the canonical image, and the surface's luma plane
+struct CropSurfArgs {
+    CropArgs c;
+    size_t y_offset, y_pitch;  // bytes to row 0 of Y, and from a row to the next
+    int shift;                 // word samples: the reduction's (surface_px.h)
 };
 
 // k_quality_zero / k_quality launch arguments (by value): efx_compare_opts, checked (k_quality.hip)

@@ -13,6 +13,9 @@
 //               meet in LDS and leave as one 4-byte integer atomic add per column: 4 / (64 x bytes per pixel) of the
 //               source bytes, 2 % for RGB and 6 % for I420, in wave instructions of 256 contiguous bytes.  Integer sums:
 //               the order of the adds does not show.
+// k_crop_sums_surf8 / _surf16  the same for the luma plane of an efx_surface of bytes or of 16-bit words (surface_px.h):
+//               rows lie a pitch apart behind the plane's offset, a word is reduced to a byte as it is read, two samples
+//               to a dword.  The chroma planes are never read.
 // k_crop_rects  one workgroup per stream.  A wave takes an image: it classifies the image's rows and columns, finds the
 //               first and last picture row and column by min / max across its lanes, and folds a contributing image into
 //               the wave's bounds; the four waves' bounds meet in LDS, lane 0 rounds them and writes the record.
@@ -21,6 +24,7 @@
 #include "efx.h"
 #include "efx_internal.h"
 #include "crop_px.h"
+#include "surface_px.h"
 
 namespace efx {
 
@@ -30,6 +34,7 @@ constexpr int kThreads = 64 * cpx::kWaves;
 static_assert(cpx::kStageBytes % 16 == 0 && cpx::kStageBytes >= 4 * (kImportMaxWidth + 4), "the stage holds the column sums of a band");
 static_assert(cpx::kStageBytes >= 3 * (((kImportMaxWidth + 30) >> 4) * 16 + 16) && cpx::kStageBytes >= ((3 * kImportMaxWidth + 30) >> 4) * 16 + 16,
               "the stage holds a row of every format");
+static_assert(cpx::kStageBytes >= ((2 * kImportMaxWidth + 30) >> 4) * 16 + 16, "the stage holds a luma row of 16-bit words");
 static_assert(cpx::kLaneCols * 64 * cpx::kColGroups >= kImportMaxWidth && cpx::kBandRows * 255 < 65536, "a lane's 16-bit column sums");
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -56,13 +61,47 @@ __device__ inline int wave_max(int v)
     return v;
 }
 
-// One band of one image: R[y] of its rows stored, its share of C[x] added.  s_stage: kStageBytes of LDS.
+// sum_band's source: FORMAT is an efx_pixel_format and ARGS CropArgs, or FORMAT says whether the luma plane of a surface
+// holds bytes or words and ARGS is CropSurfArgs, which says where the plane lies
+constexpr int kSurf8 = 100, kSurf16 = 101;
+__device__ inline const CropArgs& crop_args(const CropArgs& a) { return a; }
+__device__ inline const CropArgs& crop_args(const CropSurfArgs& a) { return a.c; }
 template <int FORMAT>
-__device__ void sum_band(const CropArgs& a, const uint8_t* __restrict__ img, uint32_t* __restrict__ sums, int band, uint32_t* s_stage)
+__device__ inline cpx::Layout band_layout(int W)
 {
+    if (FORMAT == kSurf8 || FORMAT == kSurf16)
+        return spx::crop_layout(W, FORMAT == kSurf16 ? 2 : 1);
+    return cpx::layout(FORMAT, W);
+}
+template <int FORMAT>
+__device__ inline size_t band_seg_offset(const CropArgs&, int s, int W, int H, int y)
+{
+    return cpx::seg_offset(FORMAT, s, W, H, y);
+}
+template <int FORMAT>
+__device__ inline size_t band_seg_offset(const CropSurfArgs& a, int, int, int, int y)
+{
+    return a.y_offset + (size_t)y * a.y_pitch;
+}
+template <int FORMAT>
+__device__ inline uint32_t band_luma4(const CropArgs&, const ipx::Matrix& m, const uint32_t* seg, int seg_cap, const int shift[3], int x, int W)
+{
+    return cpx::luma4<FORMAT>(m, seg, seg_cap, shift, x, W);
+}
+template <int FORMAT>
+__device__ inline uint32_t band_luma4(const CropSurfArgs& a, const ipx::Matrix&, const uint32_t* seg, int, const int shift[3], int x, int W)
+{
+    return spx::luma4<FORMAT == kSurf16>(seg, shift[0], x, W, a.shift);
+}
+
+// One band of one image: R[y] of its rows stored, its share of C[x] added.  s_stage: kStageBytes of LDS.
+template <int FORMAT, class ARGS>
+__device__ void sum_band(const ARGS& args, const uint8_t* __restrict__ img, uint32_t* __restrict__ sums, int band, uint32_t* s_stage)
+{
+    const CropArgs& a = crop_args(args);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int W = a.width, H = a.height;
-    const cpx::Layout L = cpx::layout(FORMAT, W);
+    const cpx::Layout L = band_layout<FORMAT>(W);
     const ipx::Matrix m = ipx::matrix(a.full_range);
     const int y0 = band * cpx::kBandRows, y1 = min(y0 + cpx::kBandRows, H);
     const int slots = L.seg_cap >> 4;  // 16-byte places of a segment's slot
@@ -82,7 +121,7 @@ __device__ void sum_band(const CropArgs& a, const uint8_t* __restrict__ img, uin
                 const int row = slot / L.nseg, s = slot - row * L.nseg;
                 at[k] = -1;
                 if (q < total) {
-                    const ipx::Span sp = ipx::span(cpx::seg_offset(FORMAT, s, W, H, g0 + row), L.seg_len);
+                    const ipx::Span sp = ipx::span(band_seg_offset<FORMAT>(args, s, W, H, g0 + row), L.seg_len);
                     if (i < sp.pieces) {
                         v[k] = *reinterpret_cast<const u32x4*>(img + sp.a0 + 16 * (size_t)i);
                         at[k] = slot * L.seg_cap + 16 * i;
@@ -98,7 +137,7 @@ __device__ void sum_band(const CropArgs& a, const uint8_t* __restrict__ img, uin
         for (int r = wave; r < g; r += cpx::kWaves) {
             int shift[3] = {0, 0, 0};
             for (int s = 0; s < L.nseg; s++)
-                shift[s] = ipx::span(cpx::seg_offset(FORMAT, s, W, H, g0 + r), L.seg_len).shift;
+                shift[s] = ipx::span(band_seg_offset<FORMAT>(args, s, W, H, g0 + r), L.seg_len).shift;
             const uint32_t* seg = s_stage + ((r * L.nseg * L.seg_cap) >> 2);
             uint32_t rs = 0;
 #pragma unroll
@@ -106,7 +145,7 @@ __device__ void sum_band(const CropArgs& a, const uint8_t* __restrict__ img, uin
                 if (256 * j < W) {
                     const int x = 256 * j + cpx::kLaneCols * lane;
                     if (x < W)
-                        rs += cpx::add4(cpx::luma4<FORMAT>(m, seg, L.seg_cap, shift, x, W), &even[j], &odd[j]);
+                        rs += cpx::add4(band_luma4<FORMAT>(args, m, seg, L.seg_cap, shift, x, W), &even[j], &odd[j]);
                 }
             }
             rs = wave_sum(rs);
@@ -150,14 +189,15 @@ __global__ __launch_bounds__(256) void k_crop_zero(CropArgs a)
 }
 
 // (a kernel per format: each is compiled to its own register count)
-template <int FORMAT>
-__device__ inline void sum_items(const CropArgs& a, uint32_t* s_stage)
+template <int FORMAT, class ARGS>
+__device__ inline void sum_items(const ARGS& args, uint32_t* s_stage)
 {
+    const CropArgs& a = crop_args(args);
     const int bands = (a.height + cpx::kBandRows - 1) / cpx::kBandRows;
     const size_t total = (size_t)a.n_images * bands;
     for (size_t item = blockIdx.x; item < total; item += gridDim.x) {
         const size_t image = item / bands;
-        sum_band<FORMAT>(a, a.src + image * a.src_stride, a.sums + image * a.sums_stride, (int)(item - image * bands), s_stage);
+        sum_band<FORMAT>(args, a.src + image * a.src_stride, a.sums + image * a.sums_stride, (int)(item - image * bands), s_stage);
     }
 }
 
@@ -177,6 +217,18 @@ __global__ __launch_bounds__(256) void k_crop_sums_rgbp(CropArgs a)
 {
     __shared__ __attribute__((aligned(16))) uint32_t s_stage[cpx::kStageBytes / 4];
     sum_items<EFX_PIX_RGBP>(a, s_stage);
+}
+
+__global__ __launch_bounds__(256) void k_crop_sums_surf8(CropSurfArgs a)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t s_stage[cpx::kStageBytes / 4];
+    sum_items<kSurf8>(a, s_stage);
+}
+
+__global__ __launch_bounds__(256) void k_crop_sums_surf16(CropSurfArgs a)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t s_stage[cpx::kStageBytes / 4];
+    sum_items<kSurf16>(a, s_stage);
 }
 
 __global__ __launch_bounds__(256) void k_crop_rects(CropArgs a)

@@ -12,6 +12,10 @@
 //                owns destination columns (2 luma columns, 2 chroma columns): it forms the 16-bit horizontal sum of the
 //                row and adds k_y * h into one register per destination row.  The band is assembled in LDS on the border
 //                colour and leaves as 16-byte stores: the whole 101376 bytes of an image are written, nothing else.
+// k_import_surf8p / 8s / 16p / 16s  the same band walk for the four layouts of an efx_surface (surface_px.h): a luma or
+//                planar chroma row is staged from its plane's offset and pitch, a pair row is staged once and
+//                de-interleaved into the Cb and Cr byte rows, and 16-bit rows are reduced to bytes on the way from the
+//                raw row to the byte rows, two samples to a dword.  A kernel per layout: k_import runs what it ran.
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -19,6 +23,7 @@
 #include "efx.h"
 #include "efx_internal.h"
 #include "import_px.h"
+#include "surface_px.h"
 
 namespace efx {
 
@@ -33,7 +38,12 @@ constexpr int kRows = kImportBandRows, kCRows = kImportBandRows / 2;
 constexpr int kRowBuf = kImportMaxWidth + 32;      // a byte row behind its alignment shift (<= 15), read four taps at a time
 constexpr int kRawBuf = 3 * kRowBuf + 16;          // an RGB24 row (3 x 4096 + 15) or three RGBP rows, read 4 pixels at a time
 constexpr int kBandY = kRows * kW, kBandC = kCRows * (kW / 2), kBandBytes = kBandY + 2 * kBandC;
+constexpr int kRawHalf = (kRawBuf / 2) & ~15;      // where the second chroma row of a planar 16-bit surface is staged
 constexpr int kThreads = 256;
+// the widest surface rows: 4096 words of luma or 2048 word pairs (8192 bytes), or two rows of 2048 words side by side,
+// each behind its alignment shift (<= 15) and read as aligned dwords, one beyond the last sample's
+static_assert(kRawBuf >= 2 * kImportMaxWidth + 15 + 16 + 8 && kRawHalf >= kImportMaxWidth + 15 + 16 + 8,
+              "s_raw holds the widest 16-bit luma row, pair row and pair of planar chroma rows");
 static_assert(2 * kThreads >= kW, "a lane owns two luma columns and two chroma columns");
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -272,6 +282,202 @@ __global__ __launch_bounds__(256) void k_import(const uint8_t* __restrict__ src,
             o = out + kYBytes + kCBytes + cy0 * (kW / 2) + 16 * (i - (kBandY + kBandC) / 16);
         *reinterpret_cast<u32x4*>(o) = *reinterpret_cast<const u32x4*>(s_out + 16 * i);
     }
+}
+
+namespace {
+
+// Four word samples per lane and step from a staged raw row (it begins `sh` bytes into raw) into a byte row (the last
+// step may reduce up to three stale samples nobody reads)
+__device__ inline void reduce_row(const uint8_t* raw, int sh, int n, int shift, uint8_t* row)
+{
+    for (int x = 4 * threadIdx.x; x < n; x += 4 * kThreads) {
+        uint32_t w[2];
+        spx::dwords_at<2>(raw, sh + 2 * x, w);
+        *reinterpret_cast<uint32_t*>(row + x) = spx::reduce4(w[0], w[1], shift);
+    }
+}
+
+// Four chroma pairs per lane and step from a staged pair row into the two byte rows: `first` takes elements 2x, `second`
+// elements 2x + 1
+template <bool WORDS>
+__device__ inline void split_row(const uint8_t* raw, int sh, int n, int shift, uint8_t* first, uint8_t* second)
+{
+    for (int x = 4 * threadIdx.x; x < n; x += 4 * kThreads) {
+        uint32_t a4, b4;
+        if (WORDS) {
+            uint32_t p[4];
+            spx::dwords_at<4>(raw, sh + 4 * x, p);
+            spx::split_pairs16(p, shift, &a4, &b4);
+        } else {
+            uint32_t p[2];
+            spx::dwords_at<2>(raw, sh + 2 * x, p);
+            spx::split_pairs8(p[0], p[1], &a4, &b4);
+        }
+        *reinterpret_cast<uint32_t*>(first + x) = a4;
+        *reinterpret_cast<uint32_t*>(second + x) = b4;
+    }
+}
+
+// k_import's band for a surface of layout SRC (EFX_SURF_*): a describes the canonical I420 image, sf where its samples lie.
+// The band walk, the accumulators and the way out are k_import's, which stays as it is; only the row loaders differ.
+template <int SRC>
+__device__ inline void import_surface_band(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, const ImportTap* __restrict__ taps,
+                                           const ImportArgs& a, const efx_surface& sf)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t s_raw[kRawBuf];
+    __shared__ __attribute__((aligned(16))) uint8_t s_row[3][kRowBuf];
+    __shared__ __attribute__((aligned(16))) uint8_t s_out[kBandBytes];
+
+    const int tid = threadIdx.x;
+    const int band = (int)(blockIdx.x % kImportBands);
+    const size_t image = blockIdx.x / kImportBands;
+    const uint8_t* img = src + image * a.src_stride;
+    uint8_t* out = dst + image * a.dst_stride;
+
+    // the band on the border colour
+    {
+        const uint32_t black = 0x10101010u;
+        for (int i = tid; i < kBandBytes / 4; i += kThreads)
+            reinterpret_cast<uint32_t*>(s_out)[i] = i < kBandY / 4 ? black : 0x80808080u;
+    }
+
+    // the band's rows inside the destination rectangle, as indices into the rectangle: luma [l0, l0 + nl), chroma
+    // [c0, c0 + nc) (every coordinate of the rectangle is even, so the two agree)
+    const int y0 = band * kRows, cy0 = band * kCRows;
+    const int l0 = max(y0, a.dst_y) - a.dst_y, nl = min(y0 + kRows, a.dst_y + a.dst_h) - a.dst_y - l0;
+    const int c0 = max(cy0, a.dst_y / 2) - a.dst_y / 2, nc = min(cy0 + kCRows, (a.dst_y + a.dst_h) / 2) - a.dst_y / 2 - c0;
+    const ImportTap* tly = taps + kImportTapLY + l0;
+    const ImportTap* tcy = taps + kImportTapCY + c0;
+
+    // this lane's columns: luma tid and tid + 256; chroma items tid and tid + 256 of [Cb columns | Cr columns]
+    const int cw2 = a.dst_w / 2;
+    bool lv[2], cv[2];
+    int cplane[2], ccol[2];
+    const ImportTap* tlx[2];
+    const ImportTap* tcx[2];
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+        const int col = tid + kThreads * j;
+        lv[j] = col < a.dst_w;
+        tlx[j] = taps + kImportTapLX + (lv[j] ? col : 0);
+        cv[j] = col < a.dst_w;
+        cplane[j] = col >= cw2 ? 1 : 0;
+        ccol[j] = cv[j] ? col - cplane[j] * cw2 : 0;
+        tcx[j] = taps + kImportTapCX + ccol[j];
+    }
+    int accl[2][kRows] = {}, accc[2][kCRows] = {};
+
+    if (nl > 0) {  // (nl > 0 exactly when nc > 0)
+        const int ls0 = tly[0].start, ls1 = tly[nl - 1].start + tly[nl - 1].count;  // source rows of the supports
+        const int cs0 = tcy[0].start, cs1 = tcy[nc - 1].start + tcy[nc - 1].count;
+        constexpr bool words = SRC == EFX_SURF_PLANAR16 || SRC == EFX_SURF_SEMI16;
+        constexpr bool semi = SRC == EFX_SURF_SEMI8 || SRC == EFX_SURF_SEMI16;
+        constexpr int B = words ? 2 : 1;
+        for (int s = ls0; s < ls1; s++) {
+            // byte samples go straight to the byte row; word samples pass through s_raw and are reduced
+            const int sh = stage(img, spx::crop_row(sf, 0, a.crop_x, a.crop_y, s), B * a.crop_w, words ? s_raw : s_row[0]);
+            __syncthreads();
+            if (words) {
+                reduce_row(s_raw, sh, a.crop_w, sf.shift, s_row[0]);
+                __syncthreads();
+            }
+            int ky[kRows];
+            vcoefs<kRows>(tly, nl, s, ky);
+#pragma unroll
+            for (int j = 0; j < 2; j++)
+                if (lv[j])
+                    accumulate<kRows>(s_row[0] + (words ? 0 : sh), tlx[j], ky, accl[j]);
+            if (!words)
+                __syncthreads();  // (a word row's next fetch writes s_raw, which nobody reads any more)
+        }
+        const int cw = a.crop_w / 2;
+        for (int s = cs0; s < cs1; s++) {
+            int sh[2] = {0, 0};
+            if (semi) {
+                // the pair row once, for both planes
+                const int shp = stage(img, spx::crop_row(sf, 1, a.crop_x, a.crop_y, s), B * a.crop_w, s_raw);
+                __syncthreads();
+                split_row<words>(s_raw, shp, cw, sf.shift, s_row[1 + sf.swap_uv], s_row[2 - sf.swap_uv]);
+            } else {
+#pragma unroll
+                for (int c = 0; c < 2; c++)
+                    sh[c] = stage(img, spx::crop_row(sf, 1 + c, a.crop_x, a.crop_y, s), B * cw,
+                                  words ? s_raw + c * kRawHalf : s_row[1 + c]);
+                if (words) {
+                    __syncthreads();
+#pragma unroll
+                    for (int c = 0; c < 2; c++)
+                        reduce_row(s_raw + c * kRawHalf, sh[c], cw, sf.shift, s_row[1 + c]);
+                    sh[0] = sh[1] = 0;
+                }
+            }
+            __syncthreads();
+            int ky[kCRows];
+            vcoefs<kCRows>(tcy, nc, s, ky);
+#pragma unroll
+            for (int j = 0; j < 2; j++)
+                if (cv[j])
+                    accumulate<kCRows>(s_row[1 + cplane[j]] + sh[cplane[j]], tcx[j], ky, accc[j]);
+            if (!words && !semi)
+                __syncthreads();
+        }
+    }
+    __syncthreads();  // the border is laid out
+
+    // the lanes' columns into the band
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+        const int col = tid + kThreads * j;
+#pragma unroll
+        for (int r = 0; r < kRows; r++)
+            if (lv[j] && r < nl)
+                s_out[(a.dst_y + l0 + r - y0) * kW + a.dst_x + col] = (uint8_t)ipx::vround(accl[j][r]);
+#pragma unroll
+        for (int r = 0; r < kCRows; r++)
+            if (cv[j] && r < nc)
+                s_out[kBandY + cplane[j] * kBandC + (a.dst_y / 2 + c0 + r - cy0) * (kW / 2) + a.dst_x / 2 + ccol[j]] =
+                    (uint8_t)ipx::vround(accc[j][r]);
+    }
+    __syncthreads();
+
+    // a band is contiguous in each plane: 176 + 44 + 44 pieces of 16 bytes
+    for (int i = tid; i < kBandBytes / 16; i += kThreads) {
+        uint8_t* o;
+        if (i < kBandY / 16)
+            o = out + y0 * kW + 16 * i;
+        else if (i < (kBandY + kBandC) / 16)
+            o = out + kYBytes + cy0 * (kW / 2) + 16 * (i - kBandY / 16);
+        else
+            o = out + kYBytes + kCBytes + cy0 * (kW / 2) + 16 * (i - (kBandY + kBandC) / 16);
+        *reinterpret_cast<u32x4*>(o) = *reinterpret_cast<const u32x4*>(s_out + 16 * i);
+    }
+}
+
+}  // namespace
+
+// (a kernel per surface layout, like k_cropdetect's kernel per format: each is compiled to its own register count)
+__global__ __launch_bounds__(256) void k_import_surf8p(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                       const ImportTap* __restrict__ taps, ImportSurfArgs a)
+{
+    import_surface_band<EFX_SURF_PLANAR8>(src, dst, taps, a.a, a.s);
+}
+
+__global__ __launch_bounds__(256) void k_import_surf8s(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                       const ImportTap* __restrict__ taps, ImportSurfArgs a)
+{
+    import_surface_band<EFX_SURF_SEMI8>(src, dst, taps, a.a, a.s);
+}
+
+__global__ __launch_bounds__(256) void k_import_surf16p(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                        const ImportTap* __restrict__ taps, ImportSurfArgs a)
+{
+    import_surface_band<EFX_SURF_PLANAR16>(src, dst, taps, a.a, a.s);
+}
+
+__global__ __launch_bounds__(256) void k_import_surf16s(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                        const ImportTap* __restrict__ taps, ImportSurfArgs a)
+{
+    import_surface_band<EFX_SURF_SEMI16>(src, dst, taps, a.a, a.s);
 }
 
 }  // namespace efx

@@ -371,6 +371,72 @@ typedef struct efx_crop_rect { int32_t x, y, w, h, x1, y1, x2, y2; } efx_crop_re
 int efx_detect_crop(efx_ctx* ctx, const efx_crop_opts* opts, const void* src_device, efx_crop_rect* rects_device,
                     uint32_t* sums_device /* may be NULL */);
 
+/* -- surfaces: NV12, P010 and pitched 4:2:0 sources as decoders write them (k_import, k_cropdetect) -- */
+/* No video decoder hands out packed 8-bit I420.  Hardware decoders write NV12, or P010 for 10-bit sources: a Y plane and
+ * a plane of interleaved Cb Cr pairs, with a row pitch, often padded plane heights and therefore their own plane
+ * offsets.  Software decoders hand out pitched planar 4:2:0, for 10 and 12 bit in 16-bit words with the value in the low
+ * bits (yuv420p10le).  efx_import_surfaces and efx_detect_crop_surfaces read such pictures where they lie, each source
+ * byte once, so nobody has to repack a 1080p or 2160p picture first.
+ *
+ * A surface describes one 4:2:0 YCbCr image in device memory by plane offsets and pitches.
+ *
+ *   Sample reduction.  A byte is taken as it is.  A word w (uint16, little endian) becomes
+ *     min(255, (w + (1 << (shift - 1))) >> shift).
+ *   shift = 8 reads P010, P012 and P016, which keep the value in the most significant bits (whatever sits in the low
+ *   bits takes part in the rounding); shift = 2 reads yuv420p10le, shift = 4 yuv420p12le.  A word above the nominal range
+ *   saturates.  The reduction happens once per sample, before anything else: the filter, its tap table and its
+ *   accumulators are those of the 8-bit path (DESIGN.md section 8 says why).
+ *   Canonical image.  The packed I420 picture of width x height with Y[y][x] = the reduction of the Y plane's sample
+ *   (y, x), Cb[y][x] and Cr[y][x] = the reductions of the chroma samples (y, x); for the semi-planar layouts these are
+ *   elements 2x and 2x + 1 of the pair row, swapped with swap_uv.
+ *   Meaning.  Bit for bit, efx_import_surfaces and efx_detect_crop_surfaces produce what efx_import_frames and
+ *   efx_detect_crop produce for the canonical images.  The opts are read as for that canonical image: format must be
+ *   EFX_PIX_I420, width and height must equal the surface's; crop, destination rectangle, limit, round, sums_stride and
+ *   the output layouts are unchanged; src_stride is the number of bytes between images, 0 = `bytes` rounded up to 16, a
+ *   multiple of 16 and at least `bytes`; full_range is ignored.
+ *   Fields come free.  The top or bottom field of an interlaced surface is the same surface with every pitch doubled,
+ *   height halved, and each offset advanced by one pitch for the bottom field (height must then be a multiple of 4).
+ *   Field siting is out of scope.
+ *
+ * Memory contract (an extension of efx_import_frames').  For image k the kernels read only bytes in [src + k *
+ * src_stride, src + k * src_stride + bytes rounded up to 16), in 16-byte pieces aligned down inside that interval, and
+ * only the rows the call needs: the crop's rows for the import, the luma plane's rows for crop detection (chroma is never
+ * read for it).  Bytes in pitch padding, between planes and between images are fetched at most as part of such a piece
+ * and never influence a result.  All offsets are computed in 64 bits. */
+#define EFX_SURF_PLANAR8  0   /* three planes of bytes: Y, Cb, Cr */
+#define EFX_SURF_SEMI8    1   /* Y bytes; one plane of (Cb, Cr) byte pairs at half resolution: NV12 */
+#define EFX_SURF_PLANAR16 2   /* three planes of 16-bit little-endian words */
+#define EFX_SURF_SEMI16   3   /* Y words; one plane of (Cb, Cr) word pairs: P010 / P012 / P016 */
+typedef struct efx_surface {
+    int layout;        /* EFX_SURF_* */
+    int shift;         /* 16-bit layouts: 1 .. 8, see above; byte layouts: 0 */
+    int swap_uv;       /* semi-planar: 1 = the pairs are (Cr, Cb): NV21; planar: must be 0 (swap offset[1] / offset[2] for YV12) */
+    int width, height; /* even, 2 .. 4096 */
+    size_t offset[3];  /* bytes from the image's start to row 0 of Y, of Cb (or of the pair plane), of Cr (semi-planar: ignored) */
+    size_t pitch[3];   /* bytes from a row of that plane to the next */
+    size_t bytes;      /* extent of one image: every row of every plane ends at or before it */
+} efx_surface;
+/* Asynchronous on the context's stream like their counterparts: no host synchronisation, two launches per
+ * efx_import_surfaces call and three per efx_detect_crop_surfaces call whatever the counts are (the tap table is computed
+ * on the device in stream order, so queued calls with different surfaces keep their geometry), and no decoder, encoder,
+ * SBC or other state is touched.
+ * EFX_ERR_ARG, beyond the cases of efx_import_frames and efx_detect_crop: an unknown layout, a shift outside its range
+ * for the layout, swap_uv on a planar layout, an odd or out-of-range size, a 16-bit layout with an odd offset or pitch, a
+ * pitch below the plane's row bytes (width x B for Y and for a pair plane, width / 2 x B for a planar chroma plane, B = 1
+ * or 2) or above 2^20, a plane row ending beyond `bytes`, `bytes` of 2^40 or more, opts->format, width or height
+ * disagreeing with the surface. */
+int efx_import_surfaces(efx_ctx* ctx, const efx_surface* surface, const efx_import_opts* opts, const void* src_device,
+                        uint8_t* dst_device);
+int efx_detect_crop_surfaces(efx_ctx* ctx, const efx_surface* surface, const efx_crop_opts* opts, const void* src_device,
+                             efx_crop_rect* rects_device, uint32_t* sums_device /* may be NULL */);
+typedef enum efx_surface_kind { EFX_KIND_I420, EFX_KIND_YV12, EFX_KIND_NV12, EFX_KIND_NV21, EFX_KIND_P010, EFX_KIND_P012,
+                                EFX_KIND_P016, EFX_KIND_I010, EFX_KIND_I012, EFX_KIND_I016 } efx_surface_kind;
+/* The conventional layout.  Y at 0 with pitch P (0 = packed row), R = plane_rows (0 = height; even, >= height).  The pair
+ * plane sits at P x R with pitch P.  Planar chroma: the first chroma plane at P x R with pitch P / 2, the second at
+ * P x R + (P / 2)(R / 2); YV12 stores Cr first.  bytes = P x R x 3 / 2.  Returns bytes, 0 for arguments the calls would
+ * reject (planar: P not a multiple of 2 B).  Host only. */
+size_t efx_surface_layout(int kind, int width, int height, size_t pitch, int plane_rows, efx_surface* out);
+
 /* -- picture quality: PSNR and SSIM of picture batches (k_quality) ------------------------- */
 /* The library tells a caller how many bytes a picture took; efx_compare_pictures tells how good it is: what ffmpeg
  * answers with `-psnr` and the `ssim` filter, on the device, for a whole batch, as a reduction -- two picture sets are
