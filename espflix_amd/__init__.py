@@ -110,6 +110,11 @@ class _Surface(C.Structure):
                [("offset", C.c_size_t * 3), ("pitch", C.c_size_t * 3), ("bytes", C.c_size_t)]
 
 
+class _ImportColour(C.Structure):
+    """efx_import_colour: the source's H.273 matrix_coefficients code and its range (1 = full)."""
+    _fields_ = [("matrix", C.c_int), ("full_range", C.c_int)]
+
+
 class _CompareOpts(C.Structure):
     _fields_ = [("n_images", C.c_int), ("ref_max", C.c_int), ("ref_stride", C.c_size_t), ("test_stride", C.c_size_t),
                 ("mb_stride", C.c_size_t)]
@@ -250,6 +255,8 @@ _SYMBOLS = {
     "efx_import_surfaces": (C.c_int, [_P, C.POINTER(_Surface), C.POINTER(_ImportOpts), _P, _P]),
     "efx_detect_crop_surfaces": (C.c_int, [_P, C.POINTER(_Surface), C.POINTER(_CropOpts), _P, _P, _P]),
     "efx_surface_layout": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.POINTER(_Surface)]),
+    "efx_import_set_colour": (C.c_int, [_P, C.POINTER(_ImportColour)]),
+    "efx_import_colour_coefs": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
     "efx_compare_pictures": (C.c_int, [_P, C.POINTER(_CompareOpts), _P, _P, _P, _P]),
     "efx_compare_psnr": (C.c_double, [C.c_uint64, C.c_uint64]),
     "efx_compare_ssim": (C.c_double, [C.c_int64, C.c_int]),
@@ -387,6 +394,51 @@ def import_src_bytes(fmt, width: int, height: int) -> int:
     format, a width or height outside 2 .. 4096, or an odd I420 size."""
     code = _PIX_FORMATS.get(fmt, -1) if isinstance(fmt, str) else int(fmt)
     return int(load_library().efx_import_src_bytes(code, width, height))
+
+
+# the source matrices of efx_import_set_colour by name: H.273 matrix_coefficients codes ("auto": 2, unspecified)
+_COLOUR_MATRICES = {"bt709": 1, "auto": 2, "fcc": 4, "bt601": 6, "smpte240m": 7, "bt2020": 9}
+_COLOUR_RANGES = {"studio": 0, "full": 1}
+
+
+def _colour_setting(matrix, src_range):
+    """(matrix code, full_range) of matrix= / src_range= as the import methods take them; None when neither is given.
+    matrix None beside a src_range means BT.601: the range alone is converted."""
+    if matrix is None and src_range is None:
+        return None
+    if isinstance(matrix, str):
+        if matrix not in _COLOUR_MATRICES:
+            raise ValueError(f"unknown matrix {matrix!r}: one of {sorted(_COLOUR_MATRICES)}, an H.273 code or None")
+        matrix = _COLOUR_MATRICES[matrix]
+    if src_range is not None and src_range not in _COLOUR_RANGES:
+        raise ValueError(f"unknown src_range {src_range!r}: 'studio' or 'full'")
+    return (6 if matrix is None else int(matrix)), _COLOUR_RANGES[src_range or "studio"]
+
+
+def colour_coefs(matrix, src_range: str = "studio", height: int = 0):
+    """The conversion an import applies to a YCbCr source of this matrix ("bt601", "bt709", "fcc", "smpte240m", "bt2020",
+    "auto" or an H.273 matrix_coefficients code; "auto" and 2 mean BT.709 above 576 lines of height, else BT.601) and
+    range ("studio" or "full"): (on, q, y0) with on False for "off" (BT.601 studio swing already), q the nine
+    coefficients in steps of 2^-14, row major, and y0 the source's black (efx_import_colour_coefs; the arithmetic:
+    include/efx.h).  Raises ValueError for a matrix the library rejects.  Host only."""
+    code, full = _colour_setting(matrix, src_range)
+    q, y0 = (C.c_int32 * 9)(), C.c_int()
+    rc = load_library().efx_import_colour_coefs(code, full, height, q, C.byref(y0))
+    if rc < 0:
+        raise ValueError(f"matrix {matrix!r} is not one the import converts (H.273 codes 1, 2, 4, 5, 6, 7, 9)")
+    return bool(rc), [int(v) for v in q], int(y0.value)
+
+
+def colour_source_limit(limit: int, src_range: str = "studio") -> int:
+    """Crop detection reads source luma, and a full-range source's black is 0, not 16: the largest source luma whose
+    converted value (the chroma terms at zero) is <= limit, which is the limit to detect with.  limit itself for
+    "studio", 9 for limit=24 and "full"; 0 when even luma 0 converts to more than limit.  Host only."""
+    if src_range not in _COLOUR_RANGES:
+        raise ValueError(f"unknown src_range {src_range!r}: 'studio' or 'full'")
+    if src_range == "studio":
+        return limit
+    _, q, y0 = colour_coefs("bt601", src_range)
+    return max((y for y in range(256) if min(255, max(0, 16 + ((q[0] * (y - y0) + 8192) >> 14))) <= limit), default=0)
 
 
 # efx_surface_kind: the conventional layouts of decoders' surfaces (the 16-bit kinds hold uint16 samples)
@@ -946,23 +998,49 @@ class Decoder:
 
     # -- pictures in (efx_import_frames) ----------------------------------------------------
     def import_to(self, src: DeviceBuffer | int, dst: DeviceBuffer | int, *, n_images: int, fmt: str, width: int, height: int,
-                  crop=None, dst_rect=None, full_range: bool = False, src_stride: int = 0, dst_stride: int = 0, surface=None):
+                  crop=None, dst_rect=None, full_range: bool = False, src_stride: int = 0, dst_stride: int = 0, surface=None,
+                  matrix=None, src_range: str | None = None):
         """efx_import_frames on raw device memory (DeviceBuffers or pointers), asynchronous on the library's stream:
         source image i (fmt "i420", "rgb24" or "rgbp", width x height) at src + i * src_stride (0 = import_src_bytes()
         rounded up to 16), its 352 x 192 I420 picture at dst + i * dst_stride (0 = 101376).  crop = (x, y, w, h) of the
         source (None: all of it), dst_rect = (x, y, w, h) of the output that receives it (None: all of it), the rest is
         black.  surface: an efx_surface from surface_layout() -- the images are then read as that surface describes them
         (efx_import_surfaces: NV12, P010, pitched planes ...), fmt must be "i420", width and height the surface's, and
-        src_stride 0 means surface.bytes rounded up to 16."""
+        src_stride 0 means surface.bytes rounded up to 16.
+        matrix, src_range: the YCbCr source's matrix and range as colour_coefs() takes them; the picture is converted to
+        BT.601 studio swing in the same kernel (efx_import_set_colour around this call; the context's setting, see
+        set_import_colour(), is put back behind it).  Both None: the context's setting applies, which is "off" unless
+        set_import_colour() was called.  RGB sources take neither (ValueError): full_range names the range they write."""
         if fmt not in _PIX_FORMATS:
             raise ValueError(f"unknown format {fmt!r}: one of {sorted(_PIX_FORMATS)}")
+        colour = _colour_setting(matrix, src_range)
+        if colour is not None and fmt != "i420":
+            raise ValueError("matrix= and src_range= describe a YCbCr source; an RGB source is converted with BT.601 (full_range=)")
         g = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
         o = _ImportOpts(n_images, _PIX_FORMATS[fmt], width, height, *(crop or (0, 0, 0, 0)), *(dst_rect or (0, 0, 0, 0)),
                         1 if full_range else 0, src_stride, dst_stride)
-        if surface is not None:
-            _check(self._ctx, self._lib.efx_import_surfaces(self._ctx, C.byref(surface), C.byref(o), g(src), g(dst)))
-            return
-        _check(self._ctx, self._lib.efx_import_frames(self._ctx, C.byref(o), g(src), g(dst)))
+        if colour is not None:
+            _check(self._ctx, self._lib.efx_import_set_colour(self._ctx, C.byref(_ImportColour(*colour))))
+        try:
+            if surface is not None:
+                _check(self._ctx, self._lib.efx_import_surfaces(self._ctx, C.byref(surface), C.byref(o), g(src), g(dst)))
+            else:
+                _check(self._ctx, self._lib.efx_import_frames(self._ctx, C.byref(o), g(src), g(dst)))
+        finally:
+            if colour is not None:
+                self._apply_import_colour()
+
+    def set_import_colour(self, matrix=None, src_range: str | None = None):
+        """The matrix and range of the YCbCr sources of the imports that follow (efx_import_set_colour), as
+        colour_coefs() takes them; both None switches the conversion off, which is the default.  An import method's own
+        matrix= / src_range= overrides it for that call."""
+        colour = _colour_setting(matrix, src_range)
+        _check(self._ctx, self._lib.efx_import_set_colour(self._ctx, C.byref(_ImportColour(*colour)) if colour is not None else None))
+        self._import_colour = colour
+
+    def _apply_import_colour(self):
+        colour = getattr(self, "_import_colour", None)
+        self._lib.efx_import_set_colour(self._ctx, C.byref(_ImportColour(*colour)) if colour is not None else None)
 
     def _stage_pictures(self, src, n: int, image: int, stride: int, bufs: list, keep: list):
         """The source of import_pictures / detect_crop in device memory, image i at + i * stride: (pointer, array input?,
@@ -1016,7 +1094,7 @@ class Decoder:
 
     def detect_crop(self, src, *, fmt: str | None = None, width: int | None = None, height: int | None = None,
                     images_per_stream: int | None = None, limit: int = 24, round: int = 16,
-                    full_range: bool = False, pitch: int = 0, plane_rows: int = 0) -> np.ndarray:
+                    full_range: bool = False, pitch: int = 0, plane_rows: int = 0, src_range: str | None = None) -> np.ndarray:
         """The black borders of source pictures, found on the device (efx_detect_crop): an int32 array of shape
         (n_streams, 8) with x, y, w, h -- the crop for import_pictures(crop=...) -- and the bounds x1, y1, x2, y2 of the
         detected picture (inclusive; x2 < x1: every image was black, the crop is the whole picture).  src as
@@ -1025,7 +1103,11 @@ class Decoder:
         A row or column is picture when its mean luma exceeds limit (for RGB sources the luma import_pictures would
         write with this full_range); the rectangle's sides are multiples of round where there is room, even otherwise.
         fmt may also be a surface kind of surface_layout() ("nv12", "p010", ...; "i420" with pitch= or plane_rows=), as
-        import_pictures takes it.  Waits for the result."""
+        import_pictures takes it.  src_range: "full" for a full-range YCbCr source, whose black is 0 -- limit then names
+        the luma after conversion and the detection runs with colour_source_limit(limit, src_range) (RGB sources:
+        ValueError).  Waits for the result."""
+        if src_range is not None and src_range not in _COLOUR_RANGES:
+            raise ValueError(f"unknown src_range {src_range!r}: 'studio' or 'full'")
         surface = None
         if fmt in _SURFACE_KINDS and (fmt != "i420" or pitch or plane_rows):
             surface, n, src = _surface_source(src, fmt, width, height, pitch, plane_rows)
@@ -1035,6 +1117,10 @@ class Decoder:
             image = import_src_bytes(fmt, width, height)
         if not image or n < 1:
             raise ValueError(f"{fmt} pictures of {width} x {height} cannot be read (2 .. 4096, i420: even; n >= 1)")
+        if src_range is not None:
+            if fmt != "i420":
+                raise ValueError("src_range= describes a YCbCr source; for an RGB source full_range= chooses the luma")
+            limit = colour_source_limit(limit, src_range)
         per = n if images_per_stream is None else images_per_stream
         if per < 1 or n % per:
             raise ValueError(f"images_per_stream={images_per_stream} does not divide the {n} images")
@@ -1140,7 +1226,7 @@ class Decoder:
 
     def import_pictures(self, src, *, fmt: str | None = None, width: int | None = None, height: int | None = None, crop=None,
                         fit: str = "stretch", full_range: bool = False, out=None, sync: bool = True, crop_limit: int = 24,
-                        crop_round: int = 16, pitch: int = 0, plane_rows: int = 0):
+                        crop_round: int = 16, pitch: int = 0, plane_rows: int = 0, matrix=None, src_range: str | None = None):
         """Pictures of any size as (n, 101376) I420 pictures of 352 x 192, the layout encode() takes, cropped, scaled and
         converted on the device (efx_import_frames; the arithmetic: include/efx.h).  src: a NumPy array, or a uint8
         torch tensor on the decoder's device, of shape (n, H, W, 3) for "rgb24", (n, 3, H, W) for "rgbp", or
@@ -1159,6 +1245,12 @@ class Decoder:
         packed) and plane_rows= (rows per luma plane, 0 = height).  src then has shape (n, bytes) as uint8, bytes being
         surface_layout(...).bytes, or for the 16-bit kinds (n, bytes / 2) as uint16; the pictures are read where they lie
         (efx_import_surfaces), 16-bit samples rounded to 8 bits.
+        matrix, src_range: what a YCbCr source carries -- pass the decoder's matrix_coefficients (or "bt709", "bt601",
+        "fcc", "smpte240m", "bt2020", "auto": BT.709 above 576 lines) and "studio" or "full"; the picture is converted to
+        the BT.601 studio swing MPEG-1 carries in the same kernel (colour_coefs(); include/efx.h, "source colour").
+        Both None: the context's setting (set_import_colour(); off by default).  With src_range="full", crop="auto"
+        detects with colour_source_limit(crop_limit, src_range), since such a source's black is 0.  RGB sources take
+        neither (ValueError).
 
         Returns a tensor for tensor input and an array for array input.  out: a preallocated contiguous uint8 tensor
         of n * 101376 elements on this device, or a DeviceBuffer (then returned as is); with out given, array input
@@ -1181,6 +1273,10 @@ class Decoder:
             image = import_src_bytes(fmt, width, height)
         if not image or n < 1:
             raise ValueError(f"{fmt} pictures of {width} x {height} cannot be imported (2 .. 4096, i420: even; n >= 1)")
+        if _colour_setting(matrix, src_range) is not None and fmt != "i420":
+            raise ValueError("matrix= and src_range= describe a YCbCr source; an RGB source is converted with BT.601 (full_range=)")
+        if src_range is not None:
+            crop_limit = colour_source_limit(crop_limit, src_range)
         stride = (image + 15) // 16 * 16
         nbytes = n * FRAME_BYTES
         bufs, keep = [], []
@@ -1215,7 +1311,7 @@ class Decoder:
                     raise ValueError(f"out must be contiguous with {nbytes} elements (shape {(n, FRAME_BYTES)})")
                 result, ptr = out.view(n, FRAME_BYTES), out.data_ptr()
             self.import_to(src_ptr, ptr, n_images=n, fmt=fmt, width=width, height=height, crop=crop, dst_rect=rect,
-                           full_range=full_range, src_stride=stride, surface=surface)
+                           full_range=full_range, src_stride=stride, surface=surface, matrix=matrix, src_range=src_range)
             if sync or bufs:
                 self.sync()  # (a staging buffer of this call is freed below)
             if obuf is not None:
@@ -1825,8 +1921,8 @@ class Decoder:
     def make_poster(self, image, *, qscale: int = 2, fps=24, **import_kw) -> bytes:
         """poster.ts of a title, which the reference's player opens for every title it browses (src/espflix.cpp:1060-1068)
         and its indexer makes with `-filter:v fps=fps=24 -q 2` (indexer/indexer.cpp:306): the image -- one picture as
-        import_pictures takes it, (H, W, 3), (3, H, W) or with a leading axis of 1 -- imported (import_kw: fmt, fit, crop
-        ...), then one I picture at qscale and fps as a transport stream."""
+        import_pictures takes it, (H, W, 3), (3, H, W) or with a leading axis of 1 -- imported (import_kw: fmt, fit, crop,
+        matrix, src_range ...), then one I picture at qscale and fps as a transport stream."""
         if len(image.shape) == 3:
             image = image[None]
         if image.shape[0] != 1:

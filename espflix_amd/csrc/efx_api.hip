@@ -20,6 +20,7 @@
 #include "conform_sel.h"
 #include "efx_internal.h"
 #include "enc_core.h"
+#include "colour_px.h"
 #include "import_px.h"
 #include "crop_px.h"
 #include "surface_px.h"
@@ -65,6 +66,10 @@ __global__ void k_import_surf8p(const uint8_t*, uint8_t*, const ImportTap*, Impo
 __global__ void k_import_surf8s(const uint8_t*, uint8_t*, const ImportTap*, ImportSurfArgs);
 __global__ void k_import_surf16p(const uint8_t*, uint8_t*, const ImportTap*, ImportSurfArgs);
 __global__ void k_import_surf16s(const uint8_t*, uint8_t*, const ImportTap*, ImportSurfArgs);
+__global__ void k_import_surf8p_c(const uint8_t*, uint8_t*, const ImportTap*, ImportSurfArgs, colour::Coefs);  // (... with the colour stage)
+__global__ void k_import_surf8s_c(const uint8_t*, uint8_t*, const ImportTap*, ImportSurfArgs, colour::Coefs);
+__global__ void k_import_surf16p_c(const uint8_t*, uint8_t*, const ImportTap*, ImportSurfArgs, colour::Coefs);
+__global__ void k_import_surf16s_c(const uint8_t*, uint8_t*, const ImportTap*, ImportSurfArgs, colour::Coefs);
 __global__ void k_crop_zero(CropArgs);  // (k_cropdetect.hip)
 __global__ void k_crop_sums_i420(CropArgs);
 __global__ void k_crop_sums_rgb24(CropArgs);
@@ -248,6 +253,8 @@ struct efx_ctx {
     uint32_t* d_mux_before = nullptr;            // efx_mux_av's scratch: per (stream, audio PES) the video packets in front of it
     size_t mux_before_cap = 0;
     ImportTap* d_import_taps = nullptr;          // efx_import_frames' tap table: written and read on the device, in stream order
+    bool import_colour_on = false;               // efx_import_set_colour: the source matrix and range of the imports that follow
+    efx_import_colour import_colour = {6, 0};
     int32_t* d_import_pcm_table = nullptr;       // efx_import_pcm's prototype filter (import_pcm.h, efx_tables.cpp)
     uint32_t* d_crop_sums = nullptr;             // efx_detect_crop's row and column sums when the caller gives no buffer:
     size_t crop_sums_cap = 0;                    // allocated at the first such call, regrown when a call needs more (elements)
@@ -1875,6 +1882,40 @@ static int import_args(efx_ctx* ctx, const char* who, const efx_import_opts* o, 
     return EFX_OK;
 }
 
+// The context's colour setting for a YCbCr source of `height` lines: true = a conversion, its coefficients in *k
+static bool import_colour(const efx_ctx* ctx, int height, colour::Coefs* k)
+{
+    int32_t q[9];
+    int y0;
+    if (!ctx->import_colour_on || colour::coefs(ctx->import_colour.matrix, ctx->import_colour.full_range, height, q, &y0) != 1)
+        return false;
+    *k = colour::pack(q, y0);
+    return true;
+}
+
+int efx_import_set_colour(efx_ctx* ctx, const efx_import_colour* c)
+{
+    if (!ctx)
+        return EFX_ERR_ARG;
+    if (!c) {
+        ctx->import_colour_on = false;
+        return EFX_OK;
+    }
+    if (!colour::valid(c->matrix, c->full_range))
+        return fail(ctx, EFX_ERR_ARG, "efx_import_set_colour: matrix must be 1, 2, 4, 5, 6, 7 or 9 (H.273), full_range 0 or 1");
+    ctx->import_colour = *c;
+    ctx->import_colour_on = true;
+    return EFX_OK;
+}
+
+int efx_import_colour_coefs(int matrix, int full_range, int height, int32_t q[9], int* y0)
+{
+    if (!q || !y0)
+        return EFX_ERR_ARG;
+    const int on = colour::coefs(matrix, full_range, height, q, y0);
+    return on < 0 ? EFX_ERR_ARG : on;
+}
+
 int efx_import_frames(efx_ctx* ctx, const efx_import_opts* o, const void* src_device, uint8_t* dst_device)
 {
     bind_device(ctx);
@@ -1885,8 +1926,20 @@ int efx_import_frames(efx_ctx* ctx, const efx_import_opts* o, const void* src_de
         return rc;
     // two launches whatever n_images is; the table is written on the device, behind every earlier import's reads
     hipLaunchKernelGGL(k_import_taps, dim3((kImportTapRows + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_import_taps, a);
-    hipLaunchKernelGGL(k_import, dim3((unsigned)o->n_images * kImportBands), dim3(256), 0, ctx->stream,
-                       static_cast<const uint8_t*>(src_device), dst_device, ctx->d_import_taps, a);
+    ImportSurfArgs sa{};
+    colour::Coefs k;
+    if (o->format == EFX_PIX_I420 && import_colour(ctx, o->height, &k)) {
+        // a packed I420 image is the planar surface of pitch = width (same bytes read, same output bit for bit): the
+        // conversion runs in the surface kernel, and k_import stays the code it was
+        if (!spx::layout(EFX_KIND_I420, o->width, o->height, 0, 0, &sa.s))
+            return fail(ctx, EFX_ERR_ARG, "efx_import_frames: no planar surface of this I420 size");  // (import_args checked the size)
+        sa.a = a;
+        hipLaunchKernelGGL(k_import_surf8p_c, dim3((unsigned)o->n_images * kImportBands), dim3(256), 0, ctx->stream,
+                           static_cast<const uint8_t*>(src_device), dst_device, ctx->d_import_taps, sa, k);
+    } else {
+        hipLaunchKernelGGL(k_import, dim3((unsigned)o->n_images * kImportBands), dim3(256), 0, ctx->stream,
+                           static_cast<const uint8_t*>(src_device), dst_device, ctx->d_import_taps, a);
+    }
     EFX_HIP(hipGetLastError());
     return EFX_OK;
 }
@@ -1931,8 +1984,16 @@ int efx_import_surfaces(efx_ctx* ctx, const efx_surface* s, const efx_import_opt
     auto* const k = s->layout == EFX_SURF_PLANAR8 ? k_import_surf8p : s->layout == EFX_SURF_SEMI8 ? k_import_surf8s
                     : s->layout == EFX_SURF_PLANAR16 ? k_import_surf16p : k_import_surf16s;
     hipLaunchKernelGGL(k_import_taps, dim3((kImportTapRows + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_import_taps, a.a);
-    hipLaunchKernelGGL(k, dim3((unsigned)o->n_images * kImportBands), dim3(256), 0, ctx->stream, static_cast<const uint8_t*>(src_device),
-                       dst_device, ctx->d_import_taps, a);
+    colour::Coefs kc;
+    if (import_colour(ctx, s->height, &kc)) {
+        auto* const c = s->layout == EFX_SURF_PLANAR8 ? k_import_surf8p_c : s->layout == EFX_SURF_SEMI8 ? k_import_surf8s_c
+                        : s->layout == EFX_SURF_PLANAR16 ? k_import_surf16p_c : k_import_surf16s_c;
+        hipLaunchKernelGGL(c, dim3((unsigned)o->n_images * kImportBands), dim3(256), 0, ctx->stream, static_cast<const uint8_t*>(src_device),
+                           dst_device, ctx->d_import_taps, a, kc);
+    } else {
+        hipLaunchKernelGGL(k, dim3((unsigned)o->n_images * kImportBands), dim3(256), 0, ctx->stream, static_cast<const uint8_t*>(src_device),
+                           dst_device, ctx->d_import_taps, a);
+    }
     EFX_HIP(hipGetLastError());
     return EFX_OK;
 }

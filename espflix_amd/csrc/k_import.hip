@@ -16,12 +16,20 @@
 //                planar chroma row is staged from its plane's offset and pitch, a pair row is staged once and
 //                de-interleaved into the Cb and Cr byte rows, and 16-bit rows are reduced to bytes on the way from the
 //                raw row to the byte rows, two samples to a dword.  A kernel per layout: k_import runs what it ran.
+// k_import_surf8p_c / 8s_c / 16p_c / 16s_c  the surface kernels with the colour stage (colour_px.h; COLOUR = true): between
+//                the lanes' columns into the band and the band's stores, the samples inside the destination rectangle are
+//                converted from the source's matrix and range to BT.601 studio swing, in place in LDS.  An item is a
+//                chroma site and its 2 x 2 luma samples, luma first (it reads the unconverted chroma); no two items share
+//                a sample.  The coefficients come by value.  A packed I420 source with a conversion runs k_import_surf8p_c
+//                (it is a planar surface of pitch = width), so k_import itself and the kernels without the stage are,
+//                instruction for instruction, the code they were.
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 
 #include "efx.h"
 #include "efx_internal.h"
+#include "colour_px.h"
 #include "import_px.h"
 #include "surface_px.h"
 
@@ -92,6 +100,17 @@ __device__ inline void accumulate(const uint8_t* row, const ImportTap* __restric
 #pragma unroll
     for (int r = 0; r < R; r++)
         acc[r] += ky[r] * h;
+}
+
+// The colour stage: the band's samples inside the destination rectangle, in place (s_out: the band's luma rows, then its Cb
+// and its Cr rows).  One item per lane and step; a row of the rectangle has at most 176 items.
+__device__ inline void convert_band(const ImportArgs& a, const colour::Coefs& k, int y0, uint8_t* s_out)
+{
+    const colour::BandPart p = colour::band_part(a.dst_x, a.dst_y, a.dst_w, a.dst_h, y0, kRows);
+    for (int r = 0; r < p.rows; r++)
+        for (int c = threadIdx.x; c < p.cols; c += kThreads)
+            colour::convert_item(k, p, r, c, kW, s_out, s_out + kBandY, s_out + kBandY + kBandC);
+    __syncthreads();
 }
 
 }  // namespace
@@ -320,9 +339,9 @@ __device__ inline void split_row(const uint8_t* raw, int sh, int n, int shift, u
 
 // k_import's band for a surface of layout SRC (EFX_SURF_*): a describes the canonical I420 image, sf where its samples lie.
 // The band walk, the accumulators and the way out are k_import's, which stays as it is; only the row loaders differ.
-template <int SRC>
+template <int SRC, bool COLOUR>
 __device__ inline void import_surface_band(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, const ImportTap* __restrict__ taps,
-                                           const ImportArgs& a, const efx_surface& sf)
+                                           const ImportArgs& a, const efx_surface& sf, const colour::Coefs& k)
 {
     __shared__ __attribute__((aligned(16))) uint8_t s_raw[kRawBuf];
     __shared__ __attribute__((aligned(16))) uint8_t s_row[3][kRowBuf];
@@ -439,6 +458,8 @@ __device__ inline void import_surface_band(const uint8_t* __restrict__ src, uint
                     (uint8_t)ipx::vround(accc[j][r]);
     }
     __syncthreads();
+    if (COLOUR)
+        convert_band(a, k, y0, s_out);
 
     // a band is contiguous in each plane: 176 + 44 + 44 pieces of 16 bytes
     for (int i = tid; i < kBandBytes / 16; i += kThreads) {
@@ -459,25 +480,50 @@ __device__ inline void import_surface_band(const uint8_t* __restrict__ src, uint
 __global__ __launch_bounds__(256) void k_import_surf8p(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                                        const ImportTap* __restrict__ taps, ImportSurfArgs a)
 {
-    import_surface_band<EFX_SURF_PLANAR8>(src, dst, taps, a.a, a.s);
+    import_surface_band<EFX_SURF_PLANAR8, false>(src, dst, taps, a.a, a.s, colour::Coefs{});
 }
 
 __global__ __launch_bounds__(256) void k_import_surf8s(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                                        const ImportTap* __restrict__ taps, ImportSurfArgs a)
 {
-    import_surface_band<EFX_SURF_SEMI8>(src, dst, taps, a.a, a.s);
+    import_surface_band<EFX_SURF_SEMI8, false>(src, dst, taps, a.a, a.s, colour::Coefs{});
 }
 
 __global__ __launch_bounds__(256) void k_import_surf16p(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                                         const ImportTap* __restrict__ taps, ImportSurfArgs a)
 {
-    import_surface_band<EFX_SURF_PLANAR16>(src, dst, taps, a.a, a.s);
+    import_surface_band<EFX_SURF_PLANAR16, false>(src, dst, taps, a.a, a.s, colour::Coefs{});
 }
 
 __global__ __launch_bounds__(256) void k_import_surf16s(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                                         const ImportTap* __restrict__ taps, ImportSurfArgs a)
 {
-    import_surface_band<EFX_SURF_SEMI16>(src, dst, taps, a.a, a.s);
+    import_surface_band<EFX_SURF_SEMI16, false>(src, dst, taps, a.a, a.s, colour::Coefs{});
+}
+
+// ... and with the colour stage
+__global__ __launch_bounds__(256) void k_import_surf8p_c(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                         const ImportTap* __restrict__ taps, ImportSurfArgs a, colour::Coefs k)
+{
+    import_surface_band<EFX_SURF_PLANAR8, true>(src, dst, taps, a.a, a.s, k);
+}
+
+__global__ __launch_bounds__(256) void k_import_surf8s_c(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                         const ImportTap* __restrict__ taps, ImportSurfArgs a, colour::Coefs k)
+{
+    import_surface_band<EFX_SURF_SEMI8, true>(src, dst, taps, a.a, a.s, k);
+}
+
+__global__ __launch_bounds__(256) void k_import_surf16p_c(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                          const ImportTap* __restrict__ taps, ImportSurfArgs a, colour::Coefs k)
+{
+    import_surface_band<EFX_SURF_PLANAR16, true>(src, dst, taps, a.a, a.s, k);
+}
+
+__global__ __launch_bounds__(256) void k_import_surf16s_c(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                          const ImportTap* __restrict__ taps, ImportSurfArgs a, colour::Coefs k)
+{
+    import_surface_band<EFX_SURF_SEMI16, true>(src, dst, taps, a.a, a.s, k);
 }
 
 }  // namespace efx

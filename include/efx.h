@@ -437,6 +437,59 @@ typedef enum efx_surface_kind { EFX_KIND_I420, EFX_KIND_YV12, EFX_KIND_NV12, EFX
  * reject (planar: P not a multiple of 2 B).  Host only. */
 size_t efx_surface_layout(int kind, int width, int height, size_t pitch, int plane_rows, efx_surface* out);
 
+/* -- source colour: BT.709, full-range and other YCbCr sources to BT.601 (k_import) -------- */
+/* MPEG-1 carries BT.601 studio-swing YCbCr, and efx_import_frames / efx_import_surfaces copy a YCbCr source's samples
+ * through.  What a decoder hands over today is mostly HD with BT.709 matrix coefficients, and phone or JPEG-derived
+ * material is full range.  efx_import_set_colour names the source's matrix and range -- pass the decoder's
+ * matrix_coefficients and video_full_range_flag straight in -- and the imports that follow convert to BT.601 studio
+ * swing in the same kernel: no further launch, no further byte of memory traffic.
+ *
+ *   matrix      the H.273 matrix_coefficients code:            Kr       Kb
+ *                 1      BT.709                                0.2126   0.0722
+ *                 4      FCC                                   0.30     0.11
+ *                 5, 6   BT.601                                0.299    0.114
+ *                 7      SMPTE 240M                            0.212    0.087
+ *                 9      BT.2020 non-constant luminance        0.2627   0.0593
+ *                 2      unspecified: BT.709 when the source's height is above 576, BT.601 otherwise
+ *               Every other code (0 GBR, 8 YCgCo, 10 BT.2020 constant luminance ...) is an invalid argument.  Code 9
+ *               converts the matrix only: no transfer or gamut mapping is done.
+ *   full_range  0 = studio (Y 16 .. 235, C 16 .. 240), 1 = full (Y 0 .. 255, C centred on 128 over 255).
+ *   The target is always BT.601 studio swing.  "Off" is code 5 or 6 with studio range, or code 2 with studio range on a
+ *   source no higher than 576 lines.
+ *
+ *   Coefficients.  For the source's (Kr, Kb): R, G, B from the normalised (y, pb, pr); the BT.601 (y', pb', pr') of that
+ *   R, G, B; scaled by the source's and the target's 8-bit ranges.  That is a 3 x 3 matrix whose first column is
+ *   (., 0, 0) -- converted chroma never depends on luma -- and q = round(2^14 x exact value), computed in rational
+ *   arithmetic, a literal table (espflix_amd/csrc/colour_px.h).  BT.709 studio: 16384 1627 3141; 0 16218 -1813;
+ *   0 -1187 16112.
+ *   One pixel, y0 = 16 (studio) or 0 (full), >> arithmetic, results clamped to 0 .. 255:
+ *     Y'  = 16  + ((q00 (Y - y0) + q01 (Cb - 128) + q02 (Cr - 128) + 8192) >> 14)
+ *     Cb' = 128 + ((q11 (Cb - 128) + q12 (Cr - 128) + 8192) >> 14)
+ *     Cr' = 128 + ((q21 (Cb - 128) + q22 (Cr - 128) + 8192) >> 14)
+ *   which is within 1 of the rounded exact map for every (Y, Cb, Cr).
+ *   One picture.  The conversion applies to the 8-bit picture the import produces without it: the converted import is,
+ *   bit for bit, convert(that picture), so the scaling definition above is untouched.  Only the samples inside the
+ *   destination rectangle are converted; the border is BT.601 black already and stays (16, 128, 128).  A luma sample
+ *   uses the unconverted Cb, Cr of its 2 x 2 block (nearest siting, as ffmpeg's colormatrix; the rectangle's offsets and
+ *   sides are even, so blocks and chroma sites coincide).
+ *
+ * The setting applies to I420 sources of efx_import_frames and to every efx_import_surfaces call.  RGB sources convert
+ * with their own BT.601 matrix and ignore it (efx_import_opts.full_range names the range they write).  Crop detection
+ * reads source luma and is not touched: for a full-range source pass a limit in source terms (black is 0, not 16). */
+typedef struct efx_import_colour {
+    int matrix;      /* H.273 matrix_coefficients: 1, 2, 4, 5, 6, 7 or 9 */
+    int full_range;  /* 0 = studio, 1 = full */
+} efx_import_colour;
+/* Applies to the import calls that follow, like efx_encode_set_*; NULL switches the conversion off (the default: bytes,
+ * launches and allocations are then what they were).  Host state only: calls already queued keep their setting, the
+ * coefficients travel in each launch's arguments.  EFX_ERR_ARG: an unknown code or a range other than 0 or 1; the
+ * setting is then unchanged. */
+int efx_import_set_colour(efx_ctx* ctx, const efx_import_colour* colour);
+/* The coefficients of a setting for a source of `height` lines (it matters for code 2 only): q row major (q[3] = q[6] =
+ * 0), *y0 = 16 or 0.  Returns 0 for "off" (q is then the identity, 16384 on the diagonal), 1 for a conversion, negative
+ * (EFX_ERR_ARG) for an invalid argument or a NULL pointer.  Host only. */
+int efx_import_colour_coefs(int matrix, int full_range, int height, int32_t q[9], int* y0);
+
 /* -- picture quality: PSNR and SSIM of picture batches (k_quality) ------------------------- */
 /* The library tells a caller how many bytes a picture took; efx_compare_pictures tells how good it is: what ffmpeg
  * answers with `-psnr` and the `ssim` filter, on the device, for a whole batch, as a reduction -- two picture sets are

@@ -10,7 +10,10 @@ checked bit for bit against the NumPy model (tests/import_model.py, tests/surfac
 write with torch on the same device -- F.interpolate(..., mode="bilinear", antialias=True) on float planes plus the
 BT.601 matrix as a matrix multiply and 4:2:0 chroma by a second interpolation; for a surface the strided plane views, the
 de-interleave of the pair plane and the cast of the 16-bit samples in front of it -- timed the same way (it is not
-bit-identical to the import, it does the same job).  Prints one JSON line per case and implementation."""
+bit-identical to the import, it does the same job).  --matrix CODE --src-range R: the YCbCr cases run with the colour
+conversion (efx_import_set_colour: an H.273 matrix_coefficients code, "studio" or "full") and are checked against
+tests/colour_model.py on top of the import's model; the RGB case and the torch comparison are then left out.  Prints one
+JSON line per case and implementation."""
 import argparse
 import json
 import os
@@ -23,6 +26,7 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import colour_model  # noqa: E402
 import espflix_amd as efx  # noqa: E402
 import import_model  # noqa: E402
 import surface_model  # noqa: E402
@@ -85,14 +89,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--no-torch", action="store_true", help="skip the torch comparison")
     ap.add_argument("--formats", nargs="+", default=None, help="only these cases: rgb24, i420, nv12, p010")
+    ap.add_argument("--matrix", type=int, default=None, help="H.273 matrix_coefficients of the YCbCr sources (1 = BT.709 ...): convert to BT.601")
+    ap.add_argument("--src-range", choices=["studio", "full"], default=None, help="range of the YCbCr sources")
     args = ap.parse_args()
+    colour = args.matrix is not None or args.src_range is not None
+    ckw = dict(matrix=args.matrix, src_range=args.src_range) if colour else {}
     stream = torch.cuda.Stream()
     torch.cuda.set_stream(stream)
     dec = efx.Decoder(1, 1, device=torch.cuda.current_device(), hip_stream=stream.cuda_stream)
     matrix = torch.tensor([[66, 129, 25, 16 * 256], [-38, -74, 112, 128 * 256], [112, -94, -18, 128 * 256]],
                           dtype=torch.float32, device="cuda") / 256
     for fmt, w, h, pitch, rows in CASES:
-        if args.formats and fmt not in args.formats:
+        if (args.formats and fmt not in args.formats) or (colour and fmt == "rgb24"):
             continue
         surf = surface_model.layout(fmt, w, h, pitch, rows) if pitch else None
         image = surf.bytes if surf else efx.import_src_bytes(fmt, w, h)
@@ -103,21 +111,24 @@ def main():
             src = torch.randint(0, 256, (n, image), dtype=torch.uint8, device="cuda", generator=gen)
             out = torch.empty((n, efx.FRAME_BYTES), dtype=torch.uint8, device="cuda")
             shaped = src.view(n, h, w, 3) if fmt == "rgb24" else src
-            run = lambda: dec.import_pictures(shaped, fmt=fmt, width=w, height=h, pitch=pitch, plane_rows=rows, out=out, sync=False)
+            run = lambda: dec.import_pictures(shaped, fmt=fmt, width=w, height=h, pitch=pitch, plane_rows=rows, out=out, sync=False, **ckw)
             run()
             dec.sync()
             check = [0, n - 1]
             host = src[check].cpu().numpy()
             want = surface_model.import_images(host, surf) if surf else import_model.import_images(host, fmt, w, h)
+            if colour:
+                coefs = colour_model.coefs(6 if args.matrix is None else args.matrix, args.src_range == "full", h)
+                want = colour_model.convert(want, None, *coefs) if coefs else want
             assert np.array_equal(out[check].cpu().numpy(), want), f"{fmt} {w}x{h}: output differs from the model"
             read, written = n * samples, n * efx.FRAME_BYTES
             base = {"format": fmt, "width": w, "height": h, "pitch": pitch, "plane_rows": rows, "images": n, "bytes_read": read,
-                    "bytes_written": written, "timing": "HIP events on the library's stream, mean over back-to-back calls"}
+                    "bytes_written": written, "matrix": args.matrix, "src_range": args.src_range, "timing": "HIP events on the library's stream, mean over back-to-back calls"}
             ms = timed(stream, run, args.warmup, args.reps)
             gbps = (read + written) / ms / 1e6
             print(json.dumps({"impl": "k_import", **base, "ms": round(ms, 4), "images_per_s": round(n / ms * 1e3),
                               "gbps": round(gbps, 1), "hbm_frac": round(gbps / HBM_PEAK_GBS, 4)}), flush=True)
-            if not args.no_torch:
+            if not args.no_torch and not colour:
                 try:
                     # (chunks of 64 images: the float planes of 1024 full-HD pictures would not fit beside the source)
                     one = (lambda part: torch_import_surface(part, surf, w, h)) if surf else (lambda part: torch_import(part, fmt, w, h, matrix))
