@@ -27,6 +27,7 @@ $(CSRC)/k_import.o $(CSRC)/k_cropdetect.o $(CSRC)/efx_api.o: $(CSRC)/import_px.h
 $(CSRC)/k_cropdetect.o $(CSRC)/efx_api.o: $(CSRC)/crop_px.h
 $(CSRC)/k_import.o $(CSRC)/k_cropdetect.o $(CSRC)/efx_api.o: $(CSRC)/surface_px.h
 $(CSRC)/k_import.o $(CSRC)/efx_api.o: $(CSRC)/colour_px.h
+$(CSRC)/k_import.o $(CSRC)/efx_api.o $(CSRC)/efx_tables.o: $(CSRC)/hdr_px.h $(CSRC)/colour_px.h $(CSRC)/import_px.h
 $(CSRC)/k_quality.o $(CSRC)/efx_api.o: $(CSRC)/quality_px.h
 $(CSRC)/k_encode.o $(CSRC)/k_mux.o $(CSRC)/efx_api.o: $(CSRC)/enc_core.h $(CSRC)/mpeg1_codebook.h
 $(CSRC)/k_sbc_enc.o $(CSRC)/efx_api.o: $(CSRC)/sbc_enc_core.h $(CSRC)/sbc_proto.h

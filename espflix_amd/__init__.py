@@ -115,6 +115,11 @@ class _ImportColour(C.Structure):
     _fields_ = [("matrix", C.c_int), ("full_range", C.c_int)]
 
 
+class _ImportHdr(C.Structure):
+    """efx_import_hdr: the source's H.273 transfer, primaries and matrix codes, its range (1 = full) and its peak in nits."""
+    _fields_ = [(n, C.c_int) for n in ("transfer", "primaries", "matrix", "full_range", "peak_nits")]
+
+
 class _CompareOpts(C.Structure):
     _fields_ = [("n_images", C.c_int), ("ref_max", C.c_int), ("ref_stride", C.c_size_t), ("test_stride", C.c_size_t),
                 ("mb_stride", C.c_size_t)]
@@ -257,6 +262,8 @@ _SYMBOLS = {
     "efx_surface_layout": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.POINTER(_Surface)]),
     "efx_import_set_colour": (C.c_int, [_P, C.POINTER(_ImportColour)]),
     "efx_import_colour_coefs": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
+    "efx_import_set_hdr": (C.c_int, [_P, C.POINTER(_ImportHdr)]),
+    "efx_import_hdr_tables": (C.c_int, [C.POINTER(_ImportHdr), C.c_int, C.c_void_p, C.c_size_t]),
     "efx_compare_pictures": (C.c_int, [_P, C.POINTER(_CompareOpts), _P, _P, _P, _P]),
     "efx_compare_psnr": (C.c_double, [C.c_uint64, C.c_uint64]),
     "efx_compare_ssim": (C.c_double, [C.c_int64, C.c_int]),
@@ -439,6 +446,56 @@ def colour_source_limit(limit: int, src_range: str = "studio") -> int:
         return limit
     _, q, y0 = colour_coefs("bt601", src_range)
     return max((y for y in range(256) if min(255, max(0, 16 + ((q[0] * (y - y0) + 8192) >> 14))) <= limit), default=0)
+
+
+# efx_import_set_hdr by name: H.273 transfer_characteristics and colour_primaries codes
+_HDR_TRANSFERS = {"pq": 16, "smpte2084": 16}
+_HDR_PRIMARIES = {"bt2020": 9, "bt709": 1}
+HDR_GAMMA_ENTRIES, _HDR_GAMMA_SLOTS = 1217, 1224   # the second table's entries and its padded size (espflix_amd/csrc/hdr_px.h)
+
+
+def _hdr_setting(transfer, primaries, matrix, src_range, peak_nits):
+    """The five ints of an efx_import_hdr from transfer= / primaries= / matrix= / src_range= / peak_nits= as the import
+    methods take them (names or H.273 codes; primaries and matrix None: BT.2020, peak None: 1000); None when transfer is
+    None.  The library checks the codes."""
+    if transfer is None:
+        if primaries is not None or peak_nits is not None:
+            raise ValueError("primaries= and peak_nits= describe an HDR source: pass transfer='pq' with them")
+        return None
+    if isinstance(transfer, str):
+        if transfer not in _HDR_TRANSFERS:
+            raise ValueError(f"unknown transfer {transfer!r}: 'pq' or the H.273 code 16")
+        transfer = _HDR_TRANSFERS[transfer]
+    if isinstance(primaries, str):
+        if primaries not in _HDR_PRIMARIES:
+            raise ValueError(f"unknown primaries {primaries!r}: one of {sorted(_HDR_PRIMARIES)} or an H.273 code")
+        primaries = _HDR_PRIMARIES[primaries]
+    code, full = _colour_setting("bt2020" if matrix is None else matrix, src_range)
+    return int(transfer), 9 if primaries is None else int(primaries), code, full, 1000 if peak_nits is None else int(peak_nits)
+
+
+def hdr_tables(peak_nits: int = 1000, primaries="bt2020", matrix="bt2020", src_range: str = "studio", height: int = 0,
+               transfer="pq") -> dict:
+    """Everything the HDR stage of an import reads for a setting (efx_import_hdr_tables; the arithmetic: include/efx.h,
+    "HDR sources"): {"matrix": [qy, qrv, qgu, qgv, qbu], "y0", "gamut": nine Q14 coefficients, "peak_nits", "pq": the
+    first table (uint32, n + 1 entries: PQ code i / n -> display light relative to 100 nits in steps of 2^-24), "gamma":
+    the second (uint16, 1217 entries: inverse BT.1886 in steps of 2^-15), "raw": the bytes as the kernel reads them}.
+    Raises ValueError for a setting the library rejects.  Host only."""
+    h = _ImportHdr(*_hdr_setting(transfer, primaries, matrix, src_range, peak_nits))
+    lib = load_library()
+    size = lib.efx_import_hdr_tables(C.byref(h), height, None, 0)
+    if size < 0:
+        raise ValueError("not an HDR setting the import converts: transfer 16 (PQ), primaries 9 or 1, a matrix of colour_coefs(), "
+                         "peak_nits 0 or 200 .. 10000")
+    raw = np.zeros(size, dtype=np.uint8)
+    if lib.efx_import_hdr_tables(C.byref(h), height, raw.ctypes.data, size) != size:
+        raise ValueError("efx_import_hdr_tables failed")
+    k = raw[:64].view(np.int32)
+    pq_bytes = size - 64 - 2 * _HDR_GAMMA_SLOTS   # the first table: 2^n + 1 entries padded by three
+    pq = raw[64:64 + pq_bytes].view(np.uint32)[:pq_bytes // 4 - 3]
+    gam = raw[64 + pq_bytes:].view(np.uint16)
+    return {"matrix": [int(v) for v in k[:5]], "y0": int(k[5]), "gamut": [int(v) for v in k[6:15]], "peak_nits": int(k[15]),
+            "pq": pq.copy(), "gamma": gam[:HDR_GAMMA_ENTRIES].copy(), "raw": raw}
 
 
 # efx_surface_kind: the conventional layouts of decoders' surfaces (the 16-bit kinds hold uint16 samples)
@@ -999,7 +1056,7 @@ class Decoder:
     # -- pictures in (efx_import_frames) ----------------------------------------------------
     def import_to(self, src: DeviceBuffer | int, dst: DeviceBuffer | int, *, n_images: int, fmt: str, width: int, height: int,
                   crop=None, dst_rect=None, full_range: bool = False, src_stride: int = 0, dst_stride: int = 0, surface=None,
-                  matrix=None, src_range: str | None = None):
+                  matrix=None, src_range: str | None = None, transfer=None, primaries=None, peak_nits: int | None = None):
         """efx_import_frames on raw device memory (DeviceBuffers or pointers), asynchronous on the library's stream:
         source image i (fmt "i420", "rgb24" or "rgbp", width x height) at src + i * src_stride (0 = import_src_bytes()
         rounded up to 16), its 352 x 192 I420 picture at dst + i * dst_stride (0 = 101376).  crop = (x, y, w, h) of the
@@ -1010,12 +1067,19 @@ class Decoder:
         matrix, src_range: the YCbCr source's matrix and range as colour_coefs() takes them; the picture is converted to
         BT.601 studio swing in the same kernel (efx_import_set_colour around this call; the context's setting, see
         set_import_colour(), is put back behind it).  Both None: the context's setting applies, which is "off" unless
-        set_import_colour() was called.  RGB sources take neither (ValueError): full_range names the range they write."""
+        set_import_colour() was called.  RGB sources take neither (ValueError): full_range names the range they write.
+        transfer="pq" (with primaries= "bt2020" or "bt709", peak_nits= 200 .. 10000, default 1000): the source is HDR10
+        and is tone-mapped to SDR in the same kernel (efx_import_set_hdr around this call; set_import_hdr()'s setting is
+        put back behind it); matrix= (default "bt2020") and src_range= then describe the HDR source and the colour
+        setting is not used.  RGB sources take none of these (ValueError)."""
         if fmt not in _PIX_FORMATS:
             raise ValueError(f"unknown format {fmt!r}: one of {sorted(_PIX_FORMATS)}")
-        colour = _colour_setting(matrix, src_range)
-        if colour is not None and fmt != "i420":
-            raise ValueError("matrix= and src_range= describe a YCbCr source; an RGB source is converted with BT.601 (full_range=)")
+        hdr = _hdr_setting(transfer, primaries, matrix, src_range, peak_nits)
+        colour = _colour_setting(matrix, src_range) if hdr is None else None
+        if (colour is not None or hdr is not None) and fmt != "i420":
+            raise ValueError("matrix=, src_range= and transfer= describe a YCbCr source; an RGB source is converted with BT.601 (full_range=)")
+        if hdr is not None:
+            _check(self._ctx, self._lib.efx_import_set_hdr(self._ctx, C.byref(_ImportHdr(*hdr))))
         g = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
         o = _ImportOpts(n_images, _PIX_FORMATS[fmt], width, height, *(crop or (0, 0, 0, 0)), *(dst_rect or (0, 0, 0, 0)),
                         1 if full_range else 0, src_stride, dst_stride)
@@ -1029,6 +1093,8 @@ class Decoder:
         finally:
             if colour is not None:
                 self._apply_import_colour()
+            if hdr is not None:
+                self._apply_import_hdr()
 
     def set_import_colour(self, matrix=None, src_range: str | None = None):
         """The matrix and range of the YCbCr sources of the imports that follow (efx_import_set_colour), as
@@ -1037,6 +1103,20 @@ class Decoder:
         colour = _colour_setting(matrix, src_range)
         _check(self._ctx, self._lib.efx_import_set_colour(self._ctx, C.byref(_ImportColour(*colour)) if colour is not None else None))
         self._import_colour = colour
+
+    def set_import_hdr(self, transfer=None, primaries=None, matrix=None, src_range: str | None = None, peak_nits: int | None = None):
+        """The HDR description of the YCbCr sources of the imports that follow (efx_import_set_hdr): transfer "pq" (or
+        16), primaries "bt2020" / "bt709" (or 9 / 1), matrix and src_range as colour_coefs() takes them (default BT.2020,
+        studio), peak_nits the source's peak (MaxCLL or the mastering display's maximum, 200 .. 10000; default 1000).
+        While it is on it supersedes set_import_colour().  transfer None switches it off, which is the default.  An import
+        method's own transfer= overrides it for that call."""
+        hdr = _hdr_setting(transfer, primaries, matrix, src_range, peak_nits)
+        _check(self._ctx, self._lib.efx_import_set_hdr(self._ctx, C.byref(_ImportHdr(*hdr)) if hdr is not None else None))
+        self._import_hdr = hdr
+
+    def _apply_import_hdr(self):
+        hdr = getattr(self, "_import_hdr", None)
+        self._lib.efx_import_set_hdr(self._ctx, C.byref(_ImportHdr(*hdr)) if hdr is not None else None)
 
     def _apply_import_colour(self):
         colour = getattr(self, "_import_colour", None)
@@ -1226,7 +1306,8 @@ class Decoder:
 
     def import_pictures(self, src, *, fmt: str | None = None, width: int | None = None, height: int | None = None, crop=None,
                         fit: str = "stretch", full_range: bool = False, out=None, sync: bool = True, crop_limit: int = 24,
-                        crop_round: int = 16, pitch: int = 0, plane_rows: int = 0, matrix=None, src_range: str | None = None):
+                        crop_round: int = 16, pitch: int = 0, plane_rows: int = 0, matrix=None, src_range: str | None = None,
+                        transfer=None, primaries=None, peak_nits: int | None = None):
         """Pictures of any size as (n, 101376) I420 pictures of 352 x 192, the layout encode() takes, cropped, scaled and
         converted on the device (efx_import_frames; the arithmetic: include/efx.h).  src: a NumPy array, or a uint8
         torch tensor on the decoder's device, of shape (n, H, W, 3) for "rgb24", (n, 3, H, W) for "rgbp", or
@@ -1251,6 +1332,11 @@ class Decoder:
         Both None: the context's setting (set_import_colour(); off by default).  With src_range="full", crop="auto"
         detects with colour_source_limit(crop_limit, src_range), since such a source's black is 0.  RGB sources take
         neither (ValueError).
+        transfer="pq", primaries="bt2020" (or "bt709"), peak_nits=1000: an HDR10 source -- what a decoder reports as
+        transfer_characteristics 16 and colour_primaries 9, the peak from MaxCLL or the mastering display -- is tone-mapped
+        to the BT.601 SDR picture in the same kernel (hdr_tables(); include/efx.h, "HDR sources"); matrix= (default
+        "bt2020") and src_range= then describe the HDR source.  Crop detection needs nothing: PQ studio black is the code
+        of SDR studio black.  RGB sources take none of these (ValueError).
 
         Returns a tensor for tensor input and an array for array input.  out: a preallocated contiguous uint8 tensor
         of n * 101376 elements on this device, or a DeviceBuffer (then returned as is); with out given, array input
@@ -1273,8 +1359,9 @@ class Decoder:
             image = import_src_bytes(fmt, width, height)
         if not image or n < 1:
             raise ValueError(f"{fmt} pictures of {width} x {height} cannot be imported (2 .. 4096, i420: even; n >= 1)")
-        if _colour_setting(matrix, src_range) is not None and fmt != "i420":
-            raise ValueError("matrix= and src_range= describe a YCbCr source; an RGB source is converted with BT.601 (full_range=)")
+        if (_colour_setting(matrix, src_range) is not None or _hdr_setting(transfer, primaries, matrix, src_range, peak_nits) is not None) \
+                and fmt != "i420":
+            raise ValueError("matrix=, src_range= and transfer= describe a YCbCr source; an RGB source is converted with BT.601 (full_range=)")
         if src_range is not None:
             crop_limit = colour_source_limit(crop_limit, src_range)
         stride = (image + 15) // 16 * 16
@@ -1311,7 +1398,8 @@ class Decoder:
                     raise ValueError(f"out must be contiguous with {nbytes} elements (shape {(n, FRAME_BYTES)})")
                 result, ptr = out.view(n, FRAME_BYTES), out.data_ptr()
             self.import_to(src_ptr, ptr, n_images=n, fmt=fmt, width=width, height=height, crop=crop, dst_rect=rect,
-                           full_range=full_range, src_stride=stride, surface=surface, matrix=matrix, src_range=src_range)
+                           full_range=full_range, src_stride=stride, surface=surface, matrix=matrix, src_range=src_range,
+                           transfer=transfer, primaries=primaries, peak_nits=peak_nits)
             if sync or bufs:
                 self.sync()  # (a staging buffer of this call is freed below)
             if obuf is not None:

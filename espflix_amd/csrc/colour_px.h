@@ -1,7 +1,7 @@
 // colour_px.h -- arithmetic of the import's colour conversion (k_import.hip): a YCbCr source of another matrix or range
 // (BT.709, full range ...) to the BT.601 studio swing MPEG-1 carries.  The source matrix is named by its H.273
 // matrix_coefficients code, the range is 0 = studio (Y 16 .. 235, C 16 .. 240) or 1 = full (Y 0 .. 255, C centred on 128
-// over 255).  Code 9 (BT.2020 non-constant luminance) converts the matrix only: no transfer or gamut mapping is done.
+// over 255).  Code 9 (BT.2020 non-constant luminance) converts the matrix only: transfer and gamut mapping are hdr_px.h's.
 //
 // Host + device: the kernels run exactly these functions, tests/test_colour_model.py builds this header with a plain C++
 // compiler and checks it against the NumPy model (tests/colour_model.py), and tests/colour_model_main.cpp converts whole

@@ -21,6 +21,7 @@
 #include "efx_internal.h"
 #include "enc_core.h"
 #include "colour_px.h"
+#include "hdr_px.h"
 #include "import_px.h"
 #include "crop_px.h"
 #include "surface_px.h"
@@ -70,6 +71,10 @@ __global__ void k_import_surf8p_c(const uint8_t*, uint8_t*, const ImportTap*, Im
 __global__ void k_import_surf8s_c(const uint8_t*, uint8_t*, const ImportTap*, ImportSurfArgs, colour::Coefs);
 __global__ void k_import_surf16p_c(const uint8_t*, uint8_t*, const ImportTap*, ImportSurfArgs, colour::Coefs);
 __global__ void k_import_surf16s_c(const uint8_t*, uint8_t*, const ImportTap*, ImportSurfArgs, colour::Coefs);
+__global__ void k_import_surf8p_h(const uint8_t*, uint8_t*, const ImportTap*, ImportSurfArgs, const hdr::Tables*);  // (... with the HDR stage)
+__global__ void k_import_surf8s_h(const uint8_t*, uint8_t*, const ImportTap*, ImportSurfArgs, const hdr::Tables*);
+__global__ void k_import_surf16p_h(const uint8_t*, uint8_t*, const ImportTap*, ImportSurfArgs, const hdr::Tables*);
+__global__ void k_import_surf16s_h(const uint8_t*, uint8_t*, const ImportTap*, ImportSurfArgs, const hdr::Tables*);
 __global__ void k_crop_zero(CropArgs);  // (k_cropdetect.hip)
 __global__ void k_crop_sums_i420(CropArgs);
 __global__ void k_crop_sums_rgb24(CropArgs);
@@ -255,6 +260,13 @@ struct efx_ctx {
     ImportTap* d_import_taps = nullptr;          // efx_import_frames' tap table: written and read on the device, in stream order
     bool import_colour_on = false;               // efx_import_set_colour: the source matrix and range of the imports that follow
     efx_import_colour import_colour = {6, 0};
+    bool import_hdr_on = false;                  // efx_import_set_hdr: supersedes the colour setting while it is on
+    efx_import_hdr import_hdr = {16, 9, 9, 0, 0};
+    struct HdrCopy {                             // one per distinct setting the context has used: the launch carries `device`
+        hdr::Tables host;                        // the upload's source, alive until efx_destroy
+        hdr::Tables* device = nullptr;
+    };
+    std::vector<std::unique_ptr<HdrCopy>> import_hdr_copies;
     int32_t* d_import_pcm_table = nullptr;       // efx_import_pcm's prototype filter (import_pcm.h, efx_tables.cpp)
     uint32_t* d_crop_sums = nullptr;             // efx_detect_crop's row and column sums when the caller gives no buffer:
     size_t crop_sums_cap = 0;                    // allocated at the first such call, regrown when a call needs more (elements)
@@ -777,6 +789,8 @@ void efx_destroy(efx_ctx* ctx)
     for (void* b : bufs)
         if (b)
             (void)dev_free(b);
+    for (auto& c : ctx->import_hdr_copies)
+        (void)dev_free(c->device);
     for (auto& u : ctx->up) {
         void* ub[] = {u.d_es, u.d_stream_off, u.d_stream_perm, u.d_ts_len, u.d_pkt_base, u.d_es_len, u.d_pes_count, u.d_pes};
         for (void* b : ub)
@@ -1893,6 +1907,67 @@ static bool import_colour(const efx_ctx* ctx, int height, colour::Coefs* k)
     return true;
 }
 
+// The context's HDR setting for a YCbCr source of `height` lines: *tables = nullptr when it is off, else the device copy
+// of the setting's tables -- made at the setting's first use: built on the host, uploaded once in stream order in front
+// of the launch that reads it, kept until efx_destroy (queued calls keep theirs)
+static int import_hdr(efx_ctx* ctx, int height, const hdr::Tables** tables)
+{
+    *tables = nullptr;
+    if (!ctx->import_hdr_on)
+        return EFX_OK;
+    const efx_import_hdr& h = ctx->import_hdr;
+    hdr::Coefs k{};
+    if (!hdr::coefs(h.primaries, h.matrix, h.full_range, h.peak_nits, height, &k))
+        return fail(ctx, EFX_ERR_ARG, "efx_import_set_hdr: no coefficients for this setting");  // (the setting was checked)
+    for (const auto& c : ctx->import_hdr_copies)
+        if (!std::memcmp(&c->host.k, &k, sizeof(k))) {
+            *tables = c->device;
+            return EFX_OK;
+        }
+    auto c = std::make_unique<efx_ctx::HdrCopy>();
+    c->host.k = k;
+    if (!build_import_hdr_tables(&c->host))
+        return fail(ctx, EFX_ERR_ARG, "efx_import_set_hdr: the tables of this peak are not monotonic");
+    EFX_HIP(dalloc(&c->device, 1));
+    if (const hipError_t e = hipMemcpyAsync(c->device, &c->host, sizeof(hdr::Tables), hipMemcpyHostToDevice, ctx->stream); e != hipSuccess) {
+        (void)dev_free(c->device);
+        EFX_HIP(e);
+    }
+    *tables = c->device;
+    ctx->import_hdr_copies.push_back(std::move(c));
+    return EFX_OK;
+}
+
+int efx_import_set_hdr(efx_ctx* ctx, const efx_import_hdr* h)
+{
+    if (!ctx)
+        return EFX_ERR_ARG;
+    if (!h) {
+        ctx->import_hdr_on = false;
+        return EFX_OK;
+    }
+    if (!hdr::valid(h->transfer, h->primaries, h->matrix, h->full_range, h->peak_nits))
+        return fail(ctx, EFX_ERR_ARG,
+                    "efx_import_set_hdr: transfer must be 16 (PQ), primaries 9 or 1, matrix 1, 2, 4, 5, 6, 7 or 9 (H.273), full_range 0 or 1, "
+                    "peak_nits 0 or 200 .. 10000");
+    ctx->import_hdr = *h;
+    ctx->import_hdr_on = true;
+    return EFX_OK;
+}
+
+int efx_import_hdr_tables(const efx_import_hdr* h, int height, void* out, size_t cap)
+{
+    if (!h || !hdr::valid(h->transfer, h->primaries, h->matrix, h->full_range, h->peak_nits))
+        return EFX_ERR_ARG;
+    if (out && cap >= sizeof(hdr::Tables)) {
+        auto t = std::make_unique<hdr::Tables>();
+        if (!hdr::coefs(h->primaries, h->matrix, h->full_range, h->peak_nits, height, &t->k) || !build_import_hdr_tables(t.get()))
+            return EFX_ERR_ARG;
+        std::memcpy(out, t.get(), sizeof(hdr::Tables));
+    }
+    return (int)sizeof(hdr::Tables);
+}
+
 int efx_import_set_colour(efx_ctx* ctx, const efx_import_colour* c)
 {
     if (!ctx)
@@ -1925,9 +2000,24 @@ int efx_import_frames(efx_ctx* ctx, const efx_import_opts* o, const void* src_de
     if (const int rc = import_args(ctx, "efx_import_frames", o, efx_import_src_bytes(o->format, o->width, o->height), src_device, dst_device, &a))
         return rc;
     // two launches whatever n_images is; the table is written on the device, behind every earlier import's reads
-    hipLaunchKernelGGL(k_import_taps, dim3((kImportTapRows + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_import_taps, a);
     ImportSurfArgs sa{};
     colour::Coefs k;
+    const hdr::Tables* ht = nullptr;
+    if (o->format == EFX_PIX_I420)
+        if (const int rc = import_hdr(ctx, o->height, &ht))
+            return rc;
+    if (ht) {
+        // (as below: the planar surface of pitch = width)
+        if (!spx::layout(EFX_KIND_I420, o->width, o->height, 0, 0, &sa.s))
+            return fail(ctx, EFX_ERR_ARG, "efx_import_frames: no planar surface of this I420 size");
+        sa.a = a;
+        hipLaunchKernelGGL(k_import_taps, dim3((kImportTapRows + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_import_taps, a);
+        hipLaunchKernelGGL(k_import_surf8p_h, dim3((unsigned)o->n_images * kImportBands), dim3(256), 0, ctx->stream,
+                           static_cast<const uint8_t*>(src_device), dst_device, ctx->d_import_taps, sa, ht);
+        EFX_HIP(hipGetLastError());
+        return EFX_OK;
+    }
+    hipLaunchKernelGGL(k_import_taps, dim3((kImportTapRows + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_import_taps, a);
     if (o->format == EFX_PIX_I420 && import_colour(ctx, o->height, &k)) {
         // a packed I420 image is the planar surface of pitch = width (same bytes read, same output bit for bit): the
         // conversion runs in the surface kernel, and k_import stays the code it was
@@ -1983,9 +2073,17 @@ int efx_import_surfaces(efx_ctx* ctx, const efx_surface* s, const efx_import_opt
     // two launches, as efx_import_frames: the canonical image is I420, so its tap table is the call's
     auto* const k = s->layout == EFX_SURF_PLANAR8 ? k_import_surf8p : s->layout == EFX_SURF_SEMI8 ? k_import_surf8s
                     : s->layout == EFX_SURF_PLANAR16 ? k_import_surf16p : k_import_surf16s;
+    const hdr::Tables* ht = nullptr;
+    if (const int rc = import_hdr(ctx, s->height, &ht))
+        return rc;
     hipLaunchKernelGGL(k_import_taps, dim3((kImportTapRows + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_import_taps, a.a);
     colour::Coefs kc;
-    if (import_colour(ctx, s->height, &kc)) {
+    if (ht) {
+        auto* const h = s->layout == EFX_SURF_PLANAR8 ? k_import_surf8p_h : s->layout == EFX_SURF_SEMI8 ? k_import_surf8s_h
+                        : s->layout == EFX_SURF_PLANAR16 ? k_import_surf16p_h : k_import_surf16s_h;
+        hipLaunchKernelGGL(h, dim3((unsigned)o->n_images * kImportBands), dim3(256), 0, ctx->stream, static_cast<const uint8_t*>(src_device),
+                           dst_device, ctx->d_import_taps, a, ht);
+    } else if (import_colour(ctx, s->height, &kc)) {
         auto* const c = s->layout == EFX_SURF_PLANAR8 ? k_import_surf8p_c : s->layout == EFX_SURF_SEMI8 ? k_import_surf8s_c
                         : s->layout == EFX_SURF_PLANAR16 ? k_import_surf16p_c : k_import_surf16s_c;
         hipLaunchKernelGGL(c, dim3((unsigned)o->n_images * kImportBands), dim3(256), 0, ctx->stream, static_cast<const uint8_t*>(src_device),

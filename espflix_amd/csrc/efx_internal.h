@@ -433,6 +433,10 @@ struct MuxArgs {
 
 void build_sbc_tables(SbcTables* t);
 void build_import_pcm_table(int32_t* T);  // ipcm::kTableLen entries
+namespace hdr {
+struct Tables;
+}
+bool build_import_hdr_tables(hdr::Tables* t);  // t->k filled in (hdr_px.h): the two tables for t->k.peak_nits
 void build_parse_tables(ParseTables* t);
 void build_video_tables(int ntsc, VideoTables* t);
 

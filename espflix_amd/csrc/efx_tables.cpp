@@ -11,10 +11,13 @@
 //    against the reference-derived goldens (geometry, colour LUT, zig-zag, pre-multipliers).
 //  * the resampler's prototype of efx_import_pcm (build_import_pcm_table, at the end): a Kaiser-windowed sinc in double,
 //    pinned by tests/golden/import_pcm_table.npy.
+//  * the two tables of the import's HDR stage (build_import_hdr_tables, at the end; hdr_px.h): the ST 2084 EOTF behind the
+//    BT.2390 EETF, and the inverse BT.1886 gamma, in double, pinned by tests/golden/import_hdr_tables_1000.npy.
 #include <cmath>
 #include <cstring>
 
 #include "efx_internal.h"
+#include "hdr_px.h"
 #include "import_pcm.h"
 #include "mpeg1_codebook.h"
 #include "sbc_proto.h"
@@ -438,6 +441,52 @@ void build_import_pcm_table(int32_t* T)
         T[i] = (int32_t)std::floor((double)(1 << ipcm::kQ) * cutoff * sinc * w + 0.5);
     }
     T[ipcm::kTableLen - 1] = 0;
+}
+
+// The tables of the import's HDR stage (hdr_px.h; include/efx.h, "HDR sources") for t->k.peak_nits.
+//   pq[i], E' = i / 2^kPqBits: E1 = min(1, E' / PQ(peak)); maxLum = PQ(100) / PQ(peak), KS = 1.5 maxLum - 0.5; E2 = E1 below KS,
+//     the BT.2390 Hermite spline from KS on (no black lift: source black is 0); L = EOTF(E2 PQ(peak)) / 100; round(2^24 min(L, 1)).
+//   gam[idx]: round(2^15 (x / 2^24)^(1 / 2.4)), x = hdr::gam_x(idx).
+// pow() is the only library function.  False when the tables' steps are not what hdr_px.h's interpolations bound.
+static double pq_eotf(double e)  // PQ code 0 .. 1 -> nits (SMPTE ST 2084)
+{
+    const double m1 = 2610.0 / 16384, m2 = 2523.0 / 4096 * 128, c1 = 3424.0 / 4096, c2 = 2413.0 / 4096 * 32, c3 = 2392.0 / 4096 * 32;
+    const double p = std::pow(e, 1 / m2), n = p - c1;
+    return 10000 * std::pow((n > 0 ? n : 0) / (c2 - c3 * p), 1 / m1);
+}
+
+static double pq_inverse(double nits)
+{
+    const double m1 = 2610.0 / 16384, m2 = 2523.0 / 4096 * 128, c1 = 3424.0 / 4096, c2 = 2413.0 / 4096 * 32, c3 = 2392.0 / 4096 * 32;
+    const double y = std::pow(nits / 10000, m1);
+    return std::pow((c1 + c2 * y) / (1 + c3 * y), m2);
+}
+
+bool build_import_hdr_tables(hdr::Tables* t)
+{
+    std::memset(t->pq, 0, sizeof(t->pq));
+    std::memset(t->gam, 0, sizeof(t->gam));
+    const double pk = pq_inverse((double)t->k.peak_nits), max_lum = pq_inverse(100.0) / pk, ks = 1.5 * max_lum - 0.5;
+    for (int i = 0; i < hdr::kPqEntries; i++) {
+        const double e = (double)i / (hdr::kPqEntries - 1), e1 = e / pk < 1.0 ? e / pk : 1.0;
+        double e2 = e1;
+        if (e1 >= ks) {
+            const double T = (e1 - ks) / (1 - ks), T2 = T * T, T3 = T2 * T;
+            e2 = (2 * T3 - 3 * T2 + 1) * ks + (T3 - 2 * T2 + T) * (1 - ks) + (-2 * T3 + 3 * T2) * max_lum;
+        }
+        const double lin = pq_eotf(e2 * pk) / 100;
+        t->pq[i] = (uint32_t)std::floor((lin < 1.0 ? lin : 1.0) * hdr::kLinOne + 0.5);
+    }
+    bool ok = true;
+    for (int i = 0; i < hdr::kGamEntries; i++) {
+        t->gam[i] = (uint16_t)std::floor(std::pow((double)hdr::gam_x(i) / hdr::kLinOne, 1 / 2.4) * hdr::kEOne + 0.5);
+        if (i && (t->gam[i] < t->gam[i - 1] || t->gam[i] - t->gam[i - 1] > hdr::kGamMaxStep))
+            ok = false;
+    }
+    for (int i = 1; i < hdr::kPqEntries; i++)
+        if (t->pq[i] < t->pq[i - 1] || t->pq[i] - t->pq[i - 1] >= hdr::kPqMaxStep)
+            ok = false;
+    return ok;
 }
 
 }  // namespace efx

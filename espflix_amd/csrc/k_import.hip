@@ -23,6 +23,15 @@
 //                a sample.  The coefficients come by value.  A packed I420 source with a conversion runs k_import_surf8p_c
 //                (it is a planar surface of pitch = width), so k_import itself and the kernels without the stage are,
 //                instruction for instruction, the code they were.
+// k_import_surf8p_h / 8s_h / 16p_h / 16s_h  the surface kernels with the HDR stage (hdr_px.h; HDR = true): the lanes' columns
+//                leave the accumulators at 10 bits (vround10) into a 16-bit band of their own, and between that and the
+//                band's stores one item per lane and step -- a chroma site and its 2 x 2 luma samples inside the destination
+//                rectangle -- goes through matrix, PQ EOTF and tone curve, gamut matrix, inverse BT.1886 and the BT.601
+//                matrix into the 8-bit band, which leaves as before.  The two tables (10.7 KB for one peak) are staged into
+//                LDS once per workgroup: lanes gather different entries.  Both the 16-bit band and the tables live in the
+//                row loaders' LDS, which is free once the band walk is over, so the kernels' LDS is the _c kernels'.  The
+//                setting's coefficients and tables come through one pointer (the context keeps a device copy per
+//                setting).  A kernel per layout again, so every kernel above is the code it was.
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -30,6 +39,7 @@
 #include "efx.h"
 #include "efx_internal.h"
 #include "colour_px.h"
+#include "hdr_px.h"
 #include "import_px.h"
 #include "surface_px.h"
 
@@ -110,6 +120,19 @@ __device__ inline void convert_band(const ImportArgs& a, const colour::Coefs& k,
     for (int r = 0; r < p.rows; r++)
         for (int c = threadIdx.x; c < p.cols; c += kThreads)
             colour::convert_item(k, p, r, c, kW, s_out, s_out + kBandY, s_out + kBandY + kBandC);
+    __syncthreads();
+}
+
+// The HDR stage: the band's items inside the destination rectangle from the 10-bit band (s_b10, laid out as s_out) into
+// s_out.  tab: the setting's coefficients and first table in LDS, gam: its second table.
+__device__ inline void tonemap_band(const ImportArgs& a, const hdr::Tables* tab, const uint16_t* gam, int y0, const uint16_t* s_b10,
+                                    uint8_t* s_out)
+{
+    const colour::BandPart p = colour::band_part(a.dst_x, a.dst_y, a.dst_w, a.dst_h, y0, kRows);
+    const hdr::Coefs k = tab->k;
+    for (int r = 0; r < p.rows; r++)
+        for (int c = threadIdx.x; c < p.cols; c += kThreads)
+            hdr::tonemap_item(k, tab->pq, gam, p, r, c, kW, kRows, s_b10, s_out);
     __syncthreads();
 }
 
@@ -339,15 +362,33 @@ __device__ inline void split_row(const uint8_t* raw, int sh, int n, int shift, u
 
 // k_import's band for a surface of layout SRC (EFX_SURF_*): a describes the canonical I420 image, sf where its samples lie.
 // The band walk, the accumulators and the way out are k_import's, which stays as it is; only the row loaders differ.
-template <int SRC, bool COLOUR>
+template <int SRC, bool COLOUR, bool HDR = false>
 __device__ inline void import_surface_band(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, const ImportTap* __restrict__ taps,
-                                           const ImportArgs& a, const efx_surface& sf, const colour::Coefs& k)
+                                           const ImportArgs& a, const efx_surface& sf, const colour::Coefs& k,
+                                           const hdr::Tables* __restrict__ ht = nullptr)
 {
     __shared__ __attribute__((aligned(16))) uint8_t s_raw[kRawBuf];
     __shared__ __attribute__((aligned(16))) uint8_t s_row[3][kRowBuf];
     __shared__ __attribute__((aligned(16))) uint8_t s_out[kBandBytes];
+    // the HDR stage's own, in what the row loaders no longer need once the band walk is over: the band at 10 bits and the
+    // second table in s_raw, the coefficients and the first table in s_row.  The tables are fetched into registers now and
+    // put down behind the walk.
+    constexpr int kTabA = (int)offsetof(hdr::Tables, gam), kTabB = (int)sizeof(hdr::Tables) - kTabA;  // bytes in s_row, in s_raw
+    static_assert(kTabA % 16 == 0 && kTabB % 16 == 0 && sizeof(s_row) >= (size_t)kTabA && sizeof(s_raw) >= (size_t)(2 * kBandBytes + kTabB),
+                  "the HDR stage's LDS is the row loaders'");
+    uint16_t* const s_b10 = reinterpret_cast<uint16_t*>(s_raw);
+    uint8_t* const s_tab_b = s_raw + 2 * kBandBytes;
+    uint8_t* const s_tab_a = &s_row[0][0];
+    constexpr int kTabPieces = (int)((sizeof(hdr::Tables) / 16 + kThreads - 1) / kThreads);
 
     const int tid = threadIdx.x;
+    u32x4 tab[kTabPieces];
+    if (HDR) {
+#pragma unroll
+        for (int i = 0; i < kTabPieces; i++)
+            if (tid + kThreads * i < (int)(sizeof(hdr::Tables) / 16))
+                tab[i] = reinterpret_cast<const u32x4*>(ht)[tid + kThreads * i];
+    }
     const int band = (int)(blockIdx.x % kImportBands);
     const size_t image = blockIdx.x / kImportBands;
     const uint8_t* img = src + image * a.src_stride;
@@ -447,6 +488,19 @@ __device__ inline void import_surface_band(const uint8_t* __restrict__ src, uint
 #pragma unroll
     for (int j = 0; j < 2; j++) {
         const int col = tid + kThreads * j;
+        if (HDR) {
+            // ... at 10 bits into the band the HDR stage reads
+#pragma unroll
+            for (int r = 0; r < kRows; r++)
+                if (lv[j] && r < nl)
+                    s_b10[(a.dst_y + l0 + r - y0) * kW + a.dst_x + col] = (uint16_t)hdr::vround10(accl[j][r]);
+#pragma unroll
+            for (int r = 0; r < kCRows; r++)
+                if (cv[j] && r < nc)
+                    s_b10[kBandY + cplane[j] * kBandC + (a.dst_y / 2 + c0 + r - cy0) * (kW / 2) + a.dst_x / 2 + ccol[j]] =
+                        (uint16_t)hdr::vround10(accc[j][r]);
+            continue;
+        }
 #pragma unroll
         for (int r = 0; r < kRows; r++)
             if (lv[j] && r < nl)
@@ -457,9 +511,18 @@ __device__ inline void import_surface_band(const uint8_t* __restrict__ src, uint
                 s_out[kBandY + cplane[j] * kBandC + (a.dst_y / 2 + c0 + r - cy0) * (kW / 2) + a.dst_x / 2 + ccol[j]] =
                     (uint8_t)ipx::vround(accc[j][r]);
     }
+    if (HDR) {
+#pragma unroll
+        for (int i = 0; i < kTabPieces; i++)
+            if (tid + kThreads * i < (int)(sizeof(hdr::Tables) / 16))
+                *reinterpret_cast<u32x4*>(tid + kThreads * i < kTabA / 16 ? s_tab_a + 16 * (tid + kThreads * i)
+                                                                          : s_tab_b + 16 * (tid + kThreads * i) - kTabA) = tab[i];
+    }
     __syncthreads();
     if (COLOUR)
         convert_band(a, k, y0, s_out);
+    if (HDR)
+        tonemap_band(a, reinterpret_cast<const hdr::Tables*>(s_tab_a), reinterpret_cast<const uint16_t*>(s_tab_b), y0, s_b10, s_out);
 
     // a band is contiguous in each plane: 176 + 44 + 44 pieces of 16 bytes
     for (int i = tid; i < kBandBytes / 16; i += kThreads) {
@@ -524,6 +587,35 @@ __global__ __launch_bounds__(256) void k_import_surf16s_c(const uint8_t* __restr
                                                           const ImportTap* __restrict__ taps, ImportSurfArgs a, colour::Coefs k)
 {
     import_surface_band<EFX_SURF_SEMI16, true>(src, dst, taps, a.a, a.s, k);
+}
+
+// ... and with the HDR stage
+__global__ __launch_bounds__(256) void k_import_surf8p_h(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                         const ImportTap* __restrict__ taps, ImportSurfArgs a,
+                                                         const hdr::Tables* __restrict__ ht)
+{
+    import_surface_band<EFX_SURF_PLANAR8, false, true>(src, dst, taps, a.a, a.s, colour::Coefs{}, ht);
+}
+
+__global__ __launch_bounds__(256) void k_import_surf8s_h(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                         const ImportTap* __restrict__ taps, ImportSurfArgs a,
+                                                         const hdr::Tables* __restrict__ ht)
+{
+    import_surface_band<EFX_SURF_SEMI8, false, true>(src, dst, taps, a.a, a.s, colour::Coefs{}, ht);
+}
+
+__global__ __launch_bounds__(256) void k_import_surf16p_h(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                          const ImportTap* __restrict__ taps, ImportSurfArgs a,
+                                                          const hdr::Tables* __restrict__ ht)
+{
+    import_surface_band<EFX_SURF_PLANAR16, false, true>(src, dst, taps, a.a, a.s, colour::Coefs{}, ht);
+}
+
+__global__ __launch_bounds__(256) void k_import_surf16s_h(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                          const ImportTap* __restrict__ taps, ImportSurfArgs a,
+                                                          const hdr::Tables* __restrict__ ht)
+{
+    import_surface_band<EFX_SURF_SEMI16, false, true>(src, dst, taps, a.a, a.s, colour::Coefs{}, ht);
 }
 
 }  // namespace efx

@@ -452,7 +452,7 @@ size_t efx_surface_layout(int kind, int width, int height, size_t pitch, int pla
  *                 9      BT.2020 non-constant luminance        0.2627   0.0593
  *                 2      unspecified: BT.709 when the source's height is above 576, BT.601 otherwise
  *               Every other code (0 GBR, 8 YCgCo, 10 BT.2020 constant luminance ...) is an invalid argument.  Code 9
- *               converts the matrix only: no transfer or gamut mapping is done.
+ *               converts the matrix only: transfer and gamut mapping are efx_import_set_hdr's (below).
  *   full_range  0 = studio (Y 16 .. 235, C 16 .. 240), 1 = full (Y 0 .. 255, C centred on 128 over 255).
  *   The target is always BT.601 studio swing.  "Off" is code 5 or 6 with studio range, or code 2 with studio range on a
  *   source no higher than 576 lines.
@@ -489,6 +489,61 @@ int efx_import_set_colour(efx_ctx* ctx, const efx_import_colour* colour);
  * 0), *y0 = 16 or 0.  Returns 0 for "off" (q is then the identity, 16384 on the diagonal), 1 for a conversion, negative
  * (EFX_ERR_ARG) for an invalid argument or a NULL pointer.  Host only. */
 int efx_import_colour_coefs(int matrix, int full_range, int height, int32_t q[9], int* y0);
+
+/* -- HDR sources: HDR10 (PQ, BT.2020) tone-mapped to BT.601 SDR (k_import) ----------------- */
+/* P010 is the surface format of HDR10 material.  The colour setting above converts its matrix only; a PQ picture then
+ * comes out grey, flat and desaturated.  efx_import_set_hdr names the source's transfer, primaries, matrix, range and
+ * peak, and the imports that follow tone-map to the BT.601 studio-swing SDR picture MPEG-1 carries in the same kernel
+ * (what ffmpeg does with zscale=t=linear, tonemap, zscale=t=bt709): no further launch, no further byte of memory traffic.
+ *
+ *   import10.  The import's definition with the last rounding replaced: v10 = (sum + 2^19) >> 20, 0 .. 1020, the same
+ *   taps, hround and accumulators.  The 10-bit video scale applies: studio luma 64 .. 940, chroma 512 +- 448, full range
+ *   0 .. 1020 around 512.  Surfaces are still reduced to their canonical 8-bit image first.
+ *   Result.  tonemap(import10(canonical image)) inside the destination rectangle; the border stays (16, 128, 128).
+ *   Item.  One chroma site and its 2 x 2 luma samples; all four pixels use the site's Cb10, Cr10.  Per pixel, exact
+ *   integers (espflix_amd/csrc/hdr_px.h; >> arithmetic):
+ *     1. matrix: R' = clamp((qy (Y10 - y0) + qrv (Cr10 - 512) + 8192) >> 14, 0, 2^24), G' and B' likewise with (qgu, qgv)
+ *        and qbu: steps of 2^-24, 64-bit sums; q = round(2^14 x 2^24 x exact) from the matrix code's (Kr, Kb) and the
+ *        range, in rational arithmetic (BT.2020 studio: 313787565, 452382770, -50482164, -175281642, 577182248; y0 = 64).
+ *     2. first table, per channel, PQ code -> display light relative to 100 nits in steps of 2^-24: entry i = E' = i / 2048
+ *        is round(2^24 min(1, EOTF(E2 PQ(peak)) / 100)) with the SMPTE ST 2084 EOTF and the BT.2390 EETF in the PQ domain
+ *        (source black 0, source peak peak_nits, target peak 100 nits, no black lift: E1 = min(1, E' / PQ(peak)), maxLum =
+ *        PQ(100) / PQ(peak), KS = 1.5 maxLum - 0.5, E2 = E1 below KS and the Hermite spline from KS on).  i = R' >> 13,
+ *        f = R' & 8191: L = T[i] + (((T[i + 1] - T[i]) f + 4096) >> 13) (2049 entries).
+ *     3. gamut: primaries 9: the linear BT.2020 -> BT.709 matrix of BT.2087 in steps of 2^-28, from the primaries in
+ *        rational arithmetic, each row's diagonal entry adjusted so that the row sums to exactly 2^28 (445734659
+ *        -157743717 -19555486; -33433763 304110500 -2241281; -4872308 -26998942 300306706); primaries 1: the identity.
+ *        64-bit sums, + 2^27, >> 28, clamped to 0 .. 2^24.
+ *     4. second table, inverse BT.1886, E' = L^(1 / 2.4) in steps of 2^-15: with t the position of x's leading bit and
+ *        s = max(0, t - 6), entry 64 s + (x >> s) holds round(2^15 (x' / 2^24)^(1 / 2.4)) for x' = (x >> s) << s; the s
+ *        bits below interpolate linearly to the next entry (1217 entries, the last is x = 2^24).
+ *     5. Y' = 16 + ((16763 R' + 32910 G' + 6391 B' + 2^22) >> 23).
+ *   Cb' = 128 + ((-4838 R + -9498 G + 14336 B + 2^23) >> 24) and Cr' = 128 + ((14336 R - 12005 G - 2331 B + 2^23) >> 24)
+ *   with R, G, B the sums of the four pixels' R', G', B' (the box is MPEG-1's centred chroma site).  Everything is
+ *   rounded to 8 bits once.  Against the same map in float64 (tests/hdr_model.py) Y', Cb' and Cr' are within 1.
+ *   Grey (Cb10 = Cr10 = 512) stays grey, studio black gives 16, every luma at or above the code of peak_nits gives 235.
+ *
+ * While the setting is on it supersedes efx_import_set_colour for YCbCr sources (it carries its own matrix and range);
+ * RGB sources ignore it.  Not built: HLG, luminance-keyed or max-RGB tone mapping, highlight desaturation, dynamic
+ * metadata, targets other than 100 nits. */
+typedef struct efx_import_hdr {
+    int transfer;    /* H.273 transfer_characteristics: 16 = SMPTE ST 2084 (PQ) */
+    int primaries;   /* H.273 colour_primaries: 9 = BT.2020 (mapped to BT.709), 1 = BT.709 (no gamut step) */
+    int matrix;      /* H.273 matrix_coefficients, the codes of efx_import_set_colour; normally 9 */
+    int full_range;  /* 0 = studio, 1 = full */
+    int peak_nits;   /* source peak (MaxCLL or the mastering display's maximum): 200 .. 10000; 0 = 1000 */
+} efx_import_hdr;
+/* Applies to the import calls that follow; NULL switches the stage off (the default: bytes, launches and allocations are
+ * then what they were).  Calls already queued keep their setting: the context keeps one device copy of the tables per
+ * distinct setting it has seen (10.7 KB of host and of device memory each, made at the setting's first import, freed by
+ * efx_destroy), uploaded once in stream order, and a launch carries its pointer; no host synchronisation.  EFX_ERR_ARG:
+ * any other code or a peak outside the range; the setting is then unchanged. */
+int efx_import_set_hdr(efx_ctx* ctx, const efx_import_hdr* hdr);
+/* Everything the kernel reads for a setting and a source of `height` lines (it matters for matrix code 2 only): 16 int32
+ * (qy, qrv, qgu, qgv, qbu, y0, the nine gamut coefficients, the peak), 2052 uint32 (the first table, 2049 entries used),
+ * 1224 uint16 (the second, 1217 used).  Returns the bytes (10720) and fills out when cap holds them (out may be NULL to
+ * ask for the size), negative (EFX_ERR_ARG) for an invalid setting.  Host only. */
+int efx_import_hdr_tables(const efx_import_hdr* hdr, int height, void* out, size_t cap);
 
 /* -- picture quality: PSNR and SSIM of picture batches (k_quality) ------------------------- */
 /* The library tells a caller how many bytes a picture took; efx_compare_pictures tells how good it is: what ffmpeg

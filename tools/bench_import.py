@@ -12,8 +12,10 @@ BT.601 matrix as a matrix multiply and 4:2:0 chroma by a second interpolation; f
 de-interleave of the pair plane and the cast of the 16-bit samples in front of it -- timed the same way (it is not
 bit-identical to the import, it does the same job).  --matrix CODE --src-range R: the YCbCr cases run with the colour
 conversion (efx_import_set_colour: an H.273 matrix_coefficients code, "studio" or "full") and are checked against
-tests/colour_model.py on top of the import's model; the RGB case and the torch comparison are then left out.  Prints one
-JSON line per case and implementation."""
+tests/colour_model.py on top of the import's model; the RGB case and the torch comparison are then left out.  --hdr PEAK:
+the YCbCr cases run as HDR10 sources (efx_import_set_hdr: PQ, BT.2020 primaries and matrix, the peak in nits; --src-range
+applies) and are checked against tests/hdr_model.py.  --uhd adds 3840 x 2160 P010, the surface of HDR10 material.  Prints
+one JSON line per case and implementation."""
 import argparse
 import json
 import os
@@ -28,6 +30,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import colour_model  # noqa: E402
 import espflix_amd as efx  # noqa: E402
+import hdr_model  # noqa: E402
 import import_model  # noqa: E402
 import surface_model  # noqa: E402
 
@@ -91,15 +94,25 @@ def main():
     ap.add_argument("--formats", nargs="+", default=None, help="only these cases: rgb24, i420, nv12, p010")
     ap.add_argument("--matrix", type=int, default=None, help="H.273 matrix_coefficients of the YCbCr sources (1 = BT.709 ...): convert to BT.601")
     ap.add_argument("--src-range", choices=["studio", "full"], default=None, help="range of the YCbCr sources")
+    ap.add_argument("--hdr", type=int, nargs="?", const=1000, default=None, metavar="PEAK",
+                    help="the YCbCr sources are HDR10 (PQ, BT.2020) of this peak in nits: tone-map to BT.601 SDR")
+    ap.add_argument("--uhd", action="store_true", help="add the case 3840 x 2160 P010")
     args = ap.parse_args()
-    colour = args.matrix is not None or args.src_range is not None
+    if args.hdr is not None and args.matrix is not None:
+        ap.error("--hdr runs with the BT.2020 matrix: leave --matrix out")
+    colour = args.matrix is not None or args.src_range is not None or args.hdr is not None
     ckw = dict(matrix=args.matrix, src_range=args.src_range) if colour else {}
+    hdr = None
+    if args.hdr is not None:
+        ckw = dict(transfer="pq", primaries="bt2020", peak_nits=args.hdr, src_range=args.src_range)
+        t = efx.hdr_tables(args.hdr, src_range=args.src_range or "studio")
+        hdr = hdr_model.Setting(args.hdr, int(args.src_range == "full"), 9, 9, pq=t["pq"], gam=t["gamma"])
     stream = torch.cuda.Stream()
     torch.cuda.set_stream(stream)
     dec = efx.Decoder(1, 1, device=torch.cuda.current_device(), hip_stream=stream.cuda_stream)
     matrix = torch.tensor([[66, 129, 25, 16 * 256], [-38, -74, 112, 128 * 256], [112, -94, -18, 128 * 256]],
                           dtype=torch.float32, device="cuda") / 256
-    for fmt, w, h, pitch, rows in CASES:
+    for fmt, w, h, pitch, rows in CASES + ([("p010", 3840, 2160, 7680, 2160)] if args.uhd else []):
         if (args.formats and fmt not in args.formats) or (colour and fmt == "rgb24"):
             continue
         surf = surface_model.layout(fmt, w, h, pitch, rows) if pitch else None
@@ -117,13 +130,15 @@ def main():
             check = [0, n - 1]
             host = src[check].cpu().numpy()
             want = surface_model.import_images(host, surf) if surf else import_model.import_images(host, fmt, w, h)
-            if colour:
+            if hdr is not None:
+                want = hdr_model.import_images(hdr, surface_model.canonicals(host, surf) if surf else host, w, h)
+            elif colour:
                 coefs = colour_model.coefs(6 if args.matrix is None else args.matrix, args.src_range == "full", h)
                 want = colour_model.convert(want, None, *coefs) if coefs else want
             assert np.array_equal(out[check].cpu().numpy(), want), f"{fmt} {w}x{h}: output differs from the model"
             read, written = n * samples, n * efx.FRAME_BYTES
             base = {"format": fmt, "width": w, "height": h, "pitch": pitch, "plane_rows": rows, "images": n, "bytes_read": read,
-                    "bytes_written": written, "matrix": args.matrix, "src_range": args.src_range, "timing": "HIP events on the library's stream, mean over back-to-back calls"}
+                    "bytes_written": written, "matrix": args.matrix, "src_range": args.src_range, "hdr_peak_nits": args.hdr, "timing": "HIP events on the library's stream, mean over back-to-back calls"}
             ms = timed(stream, run, args.warmup, args.reps)
             gbps = (read + written) / ms / 1e6
             print(json.dumps({"impl": "k_import", **base, "ms": round(ms, 4), "images_per_s": round(n / ms * 1e3),
