@@ -174,6 +174,27 @@ class _ImportPcmOpts(C.Structure):
                 ("dst_stride", C.c_size_t)]
 
 
+class _LoudnessStepsOpts(C.Structure):
+    _fields_ = [("n_streams", C.c_int), ("n_samples", C.c_int), ("rate", C.c_int), ("first_step", C.c_int),
+                ("first_sample", C.c_int64), ("pcm_stride", C.c_size_t), ("steps_stride", C.c_size_t)]
+
+
+class _LoudnessGateOpts(C.Structure):
+    _fields_ = [("n_streams", C.c_int), ("n_steps", C.c_int), ("rate", C.c_int), ("abs_thr", C.c_uint64),
+                ("target_ms", C.c_uint64), ("ceiling", C.c_uint32), ("steps_stride", C.c_size_t)]
+
+
+class _PcmGainOpts(C.Structure):
+    _fields_ = [("n_streams", C.c_int), ("n_samples", C.c_int), ("fixed_gain_q12", C.c_int), ("src_stride", C.c_size_t),
+                ("dst_stride", C.c_size_t)]
+
+
+# efx_loudness_step and efx_loudness_rec as NumPy sees them
+LOUDNESS_STEP_DTYPE = np.dtype([("energy", "<u8"), ("peak", "<u4"), ("zero", "<u4")])
+LOUDNESS_REC_DTYPE = np.dtype([("gated_mean", "<u8"), ("max_block", "<u8"), ("n_gated", "<u4"), ("n_blocks", "<u4"),
+                               ("n_abs", "<u4"), ("peak", "<u2"), ("gain_q12", "<u2")])
+
+
 class _MuxOpts(C.Structure):
     _fields_ = [("n_streams", C.c_int), ("audio_pid", C.c_int), ("frame_bytes", C.c_int), ("n_frames", C.c_int),
                 ("frames_per_pes", C.c_int), ("samples_per_frame", C.c_int), ("sample_rate", C.c_int),
@@ -189,6 +210,19 @@ class CompareResult:
     psnr: np.ndarray       # (..., 3) float64: 10 log10(255^2 samples / sse), inf for sse 0
     ssim: np.ndarray       # (..., 3) float64: ssim_q16 / (65536 x windows)
     mb_sse: object = None  # (..., 12, 22) uint32: luma SSE of every macroblock, when asked for
+
+
+@dataclass
+class LoudnessResult:
+    """Programme loudness of mono PCM streams by ITU-R BS.1770-4 / EBU R 128 (Decoder.loudness; the definition:
+    include/efx.h).  One entry per stream."""
+    integrated: np.ndarray     # float64 LUFS: gated integrated loudness, -inf where no block passed the gates
+    momentary_max: np.ndarray  # float64 LUFS: the loudest 400 ms block, -inf without a block (or all silence)
+    peak_dbfs: np.ndarray      # float64: sample peak, -inf for silence
+    gain_db: np.ndarray        # float64: 20 log10(gain_q12 / 4096)
+    gain_q12: np.ndarray       # int32: the gain that takes the stream to the target under the peak ceiling
+    n_blocks: np.ndarray       # int64: 400 ms blocks
+    n_gated: np.ndarray        # int64: blocks above both gates
 
 
 @dataclass
@@ -299,6 +333,15 @@ _SYMBOLS = {
     "efx_import_pcm_delay": (C.c_int, [C.c_int, C.c_int]),
     "efx_import_pcm_state_bytes": (C.c_size_t, []),
     "efx_import_pcm_filter": (C.c_int, [_P, C.c_int]),
+    "efx_loudness_steps": (C.c_int, [_P, C.POINTER(_LoudnessStepsOpts), _P, _P, _P]),
+    "efx_loudness_gate": (C.c_int, [_P, C.POINTER(_LoudnessGateOpts), _P, _P, _P]),
+    "efx_pcm_gain": (C.c_int, [_P, C.POINTER(_PcmGainOpts), _P, _P, _P]),
+    "efx_loudness_lufs": (C.c_double, [C.c_uint64, C.c_int]),
+    "efx_loudness_thresholds": (C.c_int, [C.c_int, C.c_double, C.c_double, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_uint32)]),
+    "efx_loudness_coefs": (C.c_int, [C.c_int, C.POINTER(C.c_int32)]),
+    "efx_loudness_state_bytes": (C.c_size_t, [C.c_int]),
+    "efx_loudness_step_count": (C.c_int, [C.c_int, C.c_int64, C.c_int]),
     "efx_mux_av": (C.c_int, [_P, C.POINTER(_MuxOpts), _P, _P, _P, _P, _P, _P]),
     "efx_mux_bound": (C.c_size_t, [C.c_size_t, C.c_int, C.c_int, C.c_int]),
     "efx_mux_audio_packets": (C.c_int, [C.c_int, C.c_int, C.c_int]),
@@ -720,6 +763,40 @@ def import_pcm_filter() -> np.ndarray:
     t = np.empty(lib.efx_import_pcm_filter(None, 0), dtype=np.int32)
     lib.efx_import_pcm_filter(t.ctypes.data, t.size)
     return t
+
+
+def loudness_lufs(block_energy: int, rate: int) -> float:
+    """A block energy of an efx_loudness_rec (gated_mean: integrated, max_block: maximum momentary) in LUFS
+    (efx_loudness_lufs); -inf for 0."""
+    return float(load_library().efx_loudness_lufs(int(block_energy), rate))
+
+
+def loudness_thresholds(rate: int, target: float = -23.0, peak: float = -1.0):
+    """(abs_thr, target_ms, ceiling): the integers efx_loudness_gate takes for a target in LUFS and a peak ceiling in
+    dBFS (efx_loudness_thresholds)."""
+    a, t, c = C.c_uint64(), C.c_uint64(), C.c_uint32()
+    if load_library().efx_loudness_thresholds(rate, float(target), float(peak), C.byref(a), C.byref(t), C.byref(c)) != 0:
+        raise ValueError("rate must be 16000, 32000, 44100 or 48000, target -70 .. 0 LUFS and peak -90 .. 0 dBFS")
+    return int(a.value), int(t.value), int(c.value)
+
+
+def loudness_coefs(rate: int) -> np.ndarray:
+    """The K-weighting filter's ten Q28 coefficients at `rate` (efx_loudness_coefs): b0 b1 b2 a1 a2 of the shelf, then of
+    the high pass."""
+    out = (C.c_int32 * 10)()
+    if load_library().efx_loudness_coefs(rate, out) != 0:
+        raise ValueError("rate must be 16000, 32000, 44100 or 48000")
+    return np.array(out, dtype=np.int32)
+
+
+def loudness_state_bytes(rate: int) -> int:
+    """Bytes of loudness state per stream (efx_loudness_state_bytes; 0 for a rate that is not one of the four)."""
+    return int(load_library().efx_loudness_state_bytes(rate))
+
+
+def loudness_step_count(rate: int, first_sample: int, n_samples: int) -> int:
+    """Steps of 100 ms that become whole with n_samples more samples (efx_loudness_step_count; -1 for invalid arguments)."""
+    return int(load_library().efx_loudness_step_count(rate, first_sample, n_samples))
 
 
 def mux_bound(video_bytes: int, n_frames: int, frame_bytes: int, frames_per_pes: int) -> int:
@@ -1719,6 +1796,148 @@ class Decoder:
         self._import_pcm_state = (key, state, first_in + frames)
         return out[:, :n_out]
 
+    # -- programme loudness (efx_loudness_steps, efx_loudness_gate, efx_pcm_gain) ------------------
+    def loudness_steps_to(self, pcm: DeviceBuffer | int, state: DeviceBuffer | int, steps: DeviceBuffer | int, *, n_streams: int,
+                          n_samples: int, rate: int, first_sample: int = 0, first_step: int | None = None, pcm_stride: int = 0,
+                          steps_stride: int = 0) -> int:
+        """efx_loudness_steps on raw device memory (DeviceBuffers or pointers), asynchronous on the library's stream: stream
+        i's n_samples mono int16 samples at pcm + i x pcm_stride elements (0 = n_samples rounded up to 8); every 100 ms step
+        that becomes whole is appended as a 16-byte record (LOUDNESS_STEP_DTYPE) at steps + (i x steps_stride + first_step)
+        records (first_step None = first_sample // step; steps_stride 0 = first_step + the call's steps); the streams'
+        states (loudness_state_bytes(rate) each, zeros = fresh) are updated in place.  A title fed in pieces carries
+        first_sample (+= n_samples) and the state on.  Returns the count appended."""
+        g = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
+        if first_step is None:
+            first_step = first_sample // max(1, rate // 10)
+        n_new = loudness_step_count(rate, first_sample, n_samples) if n_samples >= 0 else -1
+        o = _LoudnessStepsOpts(n_streams, n_samples, rate, first_step, first_sample, pcm_stride or (max(0, n_samples) + 7) // 8 * 8,
+                               steps_stride or first_step + max(0, n_new))
+        ret = self._lib.efx_loudness_steps(self._ctx, C.byref(o), g(pcm), g(state), g(steps))
+        if ret < 0:
+            _check(self._ctx, ret)
+        return ret
+
+    def loudness_gate_to(self, steps: DeviceBuffer | int, state: DeviceBuffer | int | None, recs: DeviceBuffer | int, *,
+                         n_streams: int, n_steps: int, rate: int, target: float = -23.0, peak: float = -1.0, thresholds=None,
+                         steps_stride: int = 0):
+        """efx_loudness_gate on raw device memory, asynchronous on the library's stream: n_steps step records per stream
+        (steps_stride records apart, 0 = n_steps) become one 32-byte record per stream (LOUDNESS_REC_DTYPE) at recs: both
+        gates, the largest block, the peak (with a state: its samples included) and the gain to `target` LUFS under `peak`
+        dBFS.  thresholds: (abs_thr, target_ms, ceiling) instead of loudness_thresholds(rate, target, peak)."""
+        g = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else b)
+        a, t, c = thresholds if thresholds is not None else loudness_thresholds(rate, target, peak)
+        o = _LoudnessGateOpts(n_streams, n_steps, rate, a, t, c, steps_stride or max(0, n_steps))
+        _check(self._ctx, self._lib.efx_loudness_gate(self._ctx, C.byref(o), g(steps), g(state), g(recs)))
+
+    def pcm_gain_to(self, src: DeviceBuffer | int, recs: DeviceBuffer | int | None, dst: DeviceBuffer | int, *, n_streams: int,
+                    n_samples: int, fixed_gain_q12: int = 4096, src_stride: int = 0, dst_stride: int = 0):
+        """efx_pcm_gain on raw device memory, asynchronous on the library's stream: dst = clamp16((src x g + 2048) >> 12),
+        each stream's g read on the device from its record at recs (None: fixed_gain_q12 for all).  dst may be src.
+        Strides in elements, 0 = n_samples rounded up to 8."""
+        g = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else b)
+        r8 = (max(0, n_samples) + 7) // 8 * 8
+        o = _PcmGainOpts(n_streams, n_samples, fixed_gain_q12, src_stride or r8, dst_stride or r8)
+        _check(self._ctx, self._lib.efx_pcm_gain(self._ctx, C.byref(o), g(src), g(recs), g(dst)))
+
+    def _loudness_pcm(self, pcm):
+        """[n, samples] int16 on the device, rows 16-byte aligned: (tensor, n, samples, stride)."""
+        import torch
+        device = torch.device("cuda", self.device)
+        if isinstance(pcm, np.ndarray):
+            pcm = torch.from_numpy(np.ascontiguousarray(pcm, dtype=np.int16)).to(device)
+        if not isinstance(pcm, torch.Tensor) or pcm.dtype != torch.int16 or pcm.device != device or pcm.dim() != 2 or pcm.shape[1] < 1:
+            raise ValueError(f"pcm must be int16 [n_streams, samples] on {device} (or a NumPy array)")
+        n, samples = int(pcm.shape[0]), int(pcm.shape[1])
+        stride = (samples + 7) // 8 * 8
+        src = pcm.contiguous()
+        if stride != samples or src.data_ptr() % 16:
+            src = torch.zeros((n, stride), dtype=torch.int16, device=device)
+            src[:, :samples] = pcm
+        return src, n, samples, stride
+
+    def _loudness_buffers(self, n: int, samples: int, rate: int, target: float, peak: float):
+        """What measuring n fresh streams of `samples` samples needs, made ready: [state (zeroed), steps, records] on the
+        device, the step count and the thresholds.  The upload synchronises the library's stream, so this comes before
+        anything is queued that the host is not to wait for."""
+        n_steps = loudness_step_count(rate, 0, samples)
+        if n_steps < 0:
+            raise ValueError("rate must be 16000, 32000, 44100 or 48000")
+        thr = loudness_thresholds(rate, target, peak)
+        bufs = []
+        try:
+            for nbytes in (n * loudness_state_bytes(rate), 16 * n * max(1, n_steps), 32 * n):
+                bufs.append(DeviceBuffer(self, nbytes))
+            bufs[0].upload(np.zeros(n * loudness_state_bytes(rate), dtype=np.uint8))
+        except Exception:
+            for b in bufs:
+                b.free()
+            raise
+        return bufs, n_steps, thr
+
+    def _loudness_queue(self, src_ptr: int, n: int, samples: int, stride: int, rate: int, prepared):
+        """steps -> gate with _loudness_buffers' result: launches only, nothing synchronised.  Returns the records' buffer."""
+        (d_state, d_steps, d_recs), n_steps, thr = prepared
+        self.loudness_steps_to(src_ptr, d_state, d_steps, n_streams=n, n_samples=samples, rate=rate, pcm_stride=stride,
+                               steps_stride=max(1, n_steps))
+        self.loudness_gate_to(d_steps, d_state, d_recs, n_streams=n, n_steps=n_steps, rate=rate, thresholds=thr,
+                              steps_stride=max(1, n_steps))
+        return d_recs
+
+    @staticmethod
+    def _loudness_result(recs: np.ndarray, rate: int) -> LoudnessResult:
+        with np.errstate(divide="ignore"):
+            return LoudnessResult(
+                integrated=np.array([loudness_lufs(int(v), rate) for v in recs["gated_mean"]], dtype=np.float64),
+                momentary_max=np.array([loudness_lufs(int(v), rate) for v in recs["max_block"]], dtype=np.float64),
+                peak_dbfs=20.0 * np.log10(recs["peak"].astype(np.float64) / 32768.0),
+                gain_db=20.0 * np.log10(recs["gain_q12"].astype(np.float64) / 4096.0),
+                gain_q12=recs["gain_q12"].astype(np.int32), n_blocks=recs["n_blocks"].astype(np.int64),
+                n_gated=recs["n_gated"].astype(np.int64))
+
+    def loudness(self, pcm, rate: int, *, target: float = -23.0, peak: float = -1.0) -> LoudnessResult:
+        """Programme loudness of mono int16 PCM [n_streams, samples] at `rate` (16000, 32000, 44100 or 48000; a NumPy array
+        or a torch tensor on the decoder's device), every stream from its first sample, measured on the device by ITU-R
+        BS.1770-4 / EBU R 128 (include/efx.h), and the gain that would take each stream to `target` LUFS with its sample
+        peak no higher than `peak` dBFS.  Synchronises torch's current stream before and the library's after."""
+        import torch
+        src, n, samples, stride = self._loudness_pcm(pcm)
+        torch.cuda.current_stream(src.device).synchronize()
+        prepared = self._loudness_buffers(n, samples, rate, target, peak)
+        bufs = prepared[0]
+        try:
+            d_recs = self._loudness_queue(src.data_ptr(), n, samples, stride, rate, prepared)
+            self.sync()
+            return self._loudness_result(d_recs.download(np.uint8, 32 * n).view(LOUDNESS_REC_DTYPE), rate)
+        finally:
+            for b in bufs:
+                b.free()
+
+    def normalize(self, pcm, rate: int, *, target: float = -23.0, peak: float = -1.0):
+        """loudness() and the gain applied, measure -> gate -> gain queued back to back with the gain read on the device:
+        returns (pcm_out, LoudnessResult), pcm_out int16 [n_streams, samples], a NumPy array for a NumPy input, else a
+        torch tensor on the device.  The result describes the input; the output sits at target (or as close as the peak
+        ceiling and the gain's range of 1/4096 .. just under 8 allow).
+
+        A title fed in pieces needs the whole title measured before its first sample is scaled, so it takes two passes
+        over the *_to calls: loudness_steps_to over every piece (first_sample and the state carried on), one
+        loudness_gate_to over all its steps, then pcm_gain_to per piece with the records it left."""
+        import torch
+        src, n, samples, stride = self._loudness_pcm(pcm)
+        out = torch.empty((n, stride), dtype=torch.int16, device=src.device)
+        torch.cuda.current_stream(src.device).synchronize()
+        prepared = self._loudness_buffers(n, samples, rate, target, peak)
+        bufs = prepared[0]
+        try:
+            d_recs = self._loudness_queue(src.data_ptr(), n, samples, stride, rate, prepared)
+            self.pcm_gain_to(src.data_ptr(), d_recs, out.data_ptr(), n_streams=n, n_samples=samples, src_stride=stride, dst_stride=stride)
+            self.sync()
+            res = self._loudness_result(d_recs.download(np.uint8, 32 * n).view(LOUDNESS_REC_DTYPE), rate)
+        finally:
+            for b in bufs:
+                b.free()
+        out = out[:, :samples]
+        return (out.cpu().numpy() if isinstance(pcm, np.ndarray) else out), res
+
     # -- SBC encode (efx_sbc_encode) and A/V multiplexing (efx_mux_av) ------------------------------
     def sbc_encode_to(self, pcm: DeviceBuffer | int, state: DeviceBuffer | int, frames: DeviceBuffer | int, *, n_streams: int,
                       n_frames: int, blocks: int = 16, mode: int = 0, allocation: int = 0, bitpool: int = 28, frequency: int = 3,
@@ -1843,7 +2062,8 @@ class Decoder:
                   allocation: int = 0, bitpool: int = 28, frequency: int = 3, sample_rate: int = 48000, frames_per_pes: int = 8,
                   audio_pid: int = 0x101, bitrate: int | None = None, vbv_bits: int = 250_000, qmin: int = 3, qmax: int = 31,
                   pcm_rate: int | None = None, pcm_layout: str = "interleaved", fps=None, scene_cut: int | bool | None = None,
-                  min_gop: int | None = None, quality: bool = False, aq: int | bool | None = None):
+                  min_gop: int | None = None, quality: bool = False, aq: int | bool | None = None, loudness: float | None = None,
+                  peak: float = -1.0):
         """Pictures + PCM -> complete titles: encode (transport streams) -> sbc_encode (mono) -> mux, queued back to back on
         the library's stream with nothing synchronised in between.  pictures: (n, P, 101376) I420 as for encode(); pcm: int16
         [n, samples], a whole number of frames of blocks x 8 samples; the audio starts at the first picture's PTS.  Every
@@ -1865,6 +2085,12 @@ class Decoder:
         gives the pictures' types.
 
         aq: adaptive quantisation of the video, as for encode().
+
+        loudness: a target in LUFS (EBU R 128: -23.0).  The mono PCM that sbc_encode_to is about to read -- behind the
+        import, when there is one -- is measured (loudness_steps_to, loudness_gate_to) and scaled in place (pcm_gain_to)
+        to that programme loudness with its sample peak no higher than `peak` dBFS, queued in front of sbc_encode_to
+        with nothing synchronised in between: the gain stays on the device.  None (the default): no launch, no
+        allocation, the title's bytes are what they were without the keyword.
 
         quality=True: the video's reconstruction is kept in a device buffer of the call's own and compared with the
         pictures right behind the encode, on the same stream, as for encode(); the call then returns (titles, status,
@@ -1919,6 +2145,14 @@ class Decoder:
             if quality and n * P:
                 d_rec, d_qual = DeviceBuffer(self, n * P * FRAME_BYTES), DeviceBuffer(self, 48 * n * P)
                 bufs += [d_rec, d_qual]
+            loud = None
+            if loudness is not None and n_frames:
+                # (buffers and the zeroed state now: an upload waits for what is queued on the library's stream)
+                loud_rate = {v: k for k, v in _SBC_FREQUENCY.items()}[frequency]
+                loud = self._loudness_buffers(n, int(pcm.shape[1]), loud_rate, loudness, peak)
+                bufs += loud[0]
+                if imp is None:
+                    pcm = pcm.clone()  # (scaled in place: the caller's tensor stays as it is)
             torch.cuda.current_stream(device).synchronize()
             self.encode_to(pictures.data_ptr(), d_v, p_vlen, p_vst, n_streams=n, n_pictures=P, qscale=qscale, gop=gop, search=search,
                            fmt=FORMAT_TS, first_pts=first_pts, dst_stride=v_stride, bitrate=bitrate, vbv_bits=vbv_bits, qmin=qmin,
@@ -1929,6 +2163,10 @@ class Decoder:
                 self.import_pcm_to(imp[0].data_ptr(), d_istate, pcm.data_ptr(), n_streams=n, n_in=imp[1], in_rate=pcm_rate,
                                    out_rate=sample_rate, channels=imp[2], layout=_PCM_LAYOUTS[pcm_layout], src_stride=imp[3],
                                    dst_stride=int(pcm.shape[1]))
+            if loud is not None:
+                d_lrecs = self._loudness_queue(pcm.data_ptr(), n, int(pcm.shape[1]), int(pcm.shape[1]), loud_rate, loud)
+                self.pcm_gain_to(pcm.data_ptr(), d_lrecs, pcm.data_ptr(), n_streams=n, n_samples=int(pcm.shape[1]),
+                                 src_stride=int(pcm.shape[1]), dst_stride=int(pcm.shape[1]))
             if n_frames:
                 self.sbc_encode_to(pcm.data_ptr(), d_state, d_a, n_streams=n, n_frames=n_frames, blocks=blocks, mode=0,
                                    allocation=allocation, bitpool=bitpool, frequency=frequency, pcm_stride=int(pcm.shape[1]),
@@ -2188,7 +2426,9 @@ class Decoder:
         sample count.  poster: an image as make_poster takes it; the dictionaries then hold "poster.ts" as well.
 
         scene_cut=, min_gop= (among **encode_av) apply to video.ts only: the trick streams keep their GOPs of trick_gop.
-        aq: adaptive quantisation as for encode(), of video.ts and of both trick streams."""
+        aq: adaptive quantisation as for encode(), of video.ts and of both trick streams.
+
+        loudness=, peak= (among **encode_av): video.ts's sound levelled to a target in LUFS, as for encode_av()."""
         if fps is not None and fps_out is None and not picture_rate_code(fps):
             raise ValueError(f"fps={fps!r} is not a rate MPEG-1 codes; give fps_out=, one of "
                              f"{', '.join(str(r) for r in PICTURE_RATES.values())}")

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <memory>
 #include <mutex>
 #include <thread>
@@ -90,6 +91,10 @@ __global__ void k_trick(TrickArgs);  // (k_trick.hip: the I420 and the ring inst
 __global__ void k_conform(ConformArgs);  // (k_conform.hip)
 __global__ void k_import_pcm(ImportPcmArgs);  // (k_import_pcm.hip)
 __global__ void k_import_pcm_state(ImportPcmArgs);
+__global__ void k_loud_steps(LoudStepsArgs);  // (k_loudness.hip)
+__global__ void k_loud_state(LoudStepsArgs);
+__global__ void k_loud_gate(LoudGateArgs);
+__global__ void k_pcm_gain(PcmGainArgs);
 __global__ void k_enc_begin(EncArgs);
 __global__ void k_enc_aq(EncArgs);
 __global__ void k_enc_cut(EncArgs);
@@ -3163,6 +3168,178 @@ int efx_import_pcm(efx_ctx* ctx, const efx_import_pcm_opts* o, const int16_t* sr
     }
     if (!equal)
         hipLaunchKernelGGL(k_import_pcm_state, dim3((unsigned)o->n_streams), dim3(128), 0, ctx->stream, a);
+    EFX_HIP(hipGetLastError());
+    return EFX_OK;
+}
+
+// ---- programme loudness (k_loudness.hip) ----------------------------------------------------------------------------------------
+// Both stages of the K-weighting filter from their analogue prototypes by the bilinear transform (include/efx.h)
+static loud::Coefs loudness_coefs(int rate)
+{
+    const double pi = 3.14159265358979323846;
+    double c[10];
+    {
+        const double f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196;
+        const double K = std::tan(pi * f0 / rate), Vh = std::pow(10.0, G / 20.0), Vb = std::pow(Vh, 0.4996667741545416);
+        const double a0 = 1.0 + K / Q + K * K;
+        c[0] = (Vh + Vb * K / Q + K * K) / a0;
+        c[1] = 2.0 * (K * K - Vh) / a0;
+        c[2] = (Vh - Vb * K / Q + K * K) / a0;
+        c[3] = 2.0 * (K * K - 1.0) / a0;
+        c[4] = (1.0 - K / Q + K * K) / a0;
+    }
+    {
+        const double f0 = 38.13547087602444, Q = 0.5003270373238773;
+        const double K = std::tan(pi * f0 / rate), a0 = 1.0 + K / Q + K * K;
+        c[5] = 1.0, c[6] = -2.0, c[7] = 1.0;
+        c[8] = 2.0 * (K * K - 1.0) / a0;
+        c[9] = (1.0 - K / Q + K * K) / a0;
+    }
+    loud::Coefs k{};
+    for (int i = 0; i < 10; i++)
+        k.c[i] = (int32_t)std::llround(c[i] * (double)(1 << loud::kCoefBits));
+    return k;
+}
+
+int efx_loudness_coefs(int rate, int32_t out[10])
+{
+    if (!loud::rate_ok(rate) || !out)
+        return EFX_ERR_ARG;
+    const loud::Coefs k = loudness_coefs(rate);
+    std::copy(k.c, k.c + 10, out);
+    return EFX_OK;
+}
+
+size_t efx_loudness_state_bytes(int rate) { return loud::rate_ok(rate) ? 2 * (size_t)loud::hist_of(rate) : 0; }
+
+int efx_loudness_step_count(int rate, int64_t first_sample, int n_samples)
+{
+    if (!loud::rate_ok(rate) || first_sample < 0 || first_sample >= loud::kMaxFirstSample || n_samples < 0)
+        return -1;
+    return (int)loud::step_count(rate, first_sample, n_samples);
+}
+
+double efx_loudness_lufs(uint64_t block_energy, int rate)
+{
+    if (!loud::rate_ok(rate))
+        return std::nan("");
+    if (!block_energy)
+        return -HUGE_VAL;
+    return -0.691 + 10.0 * std::log10((double)block_energy / (4.0 * loud::step_of(rate) * 1073741824.0 * 256.0));
+}
+
+int efx_loudness_thresholds(int rate, double target_lufs, double peak_dbfs, uint64_t* abs_thr, uint64_t* target_ms, uint32_t* ceiling)
+{
+    if (!loud::rate_ok(rate) || !(target_lufs >= -70.0 && target_lufs <= 0.0) || !(peak_dbfs >= -90.0 && peak_dbfs <= 0.0))
+        return EFX_ERR_ARG;
+    const double unit = 1073741824.0 * 256.0;  // a full-scale square's mean square with the four fraction bits
+    if (abs_thr)
+        *abs_thr = (uint64_t)std::llround(std::pow(10.0, (-70.0 + 0.691) / 10.0) * unit * 4.0 * loud::step_of(rate));
+    if (target_ms)
+        *target_ms = (uint64_t)std::llround(std::pow(10.0, (target_lufs + 0.691) / 10.0) * unit);
+    if (ceiling)
+        *ceiling = (uint32_t)std::max(1L, std::lround(32767.0 * std::pow(10.0, peak_dbfs / 20.0)));
+    return EFX_OK;
+}
+
+int efx_loudness_steps(efx_ctx* ctx, const efx_loudness_steps_opts* o, const int16_t* pcm_device, void* state_device,
+                       efx_loudness_step* steps_device)
+{
+    bind_device(ctx);
+    if (!ctx || !o)
+        return EFX_ERR_ARG;
+    auto misaligned = [](const void* p) { return !p || ((uintptr_t)p & 15); };
+    if (o->n_streams < 1 || o->n_streams > ctx->cfg.max_streams)
+        return fail(ctx, EFX_ERR_ARG, "efx_loudness_steps: n_streams outside 1 .. max_streams");
+    if (!loud::rate_ok(o->rate))
+        return fail(ctx, EFX_ERR_ARG, "efx_loudness_steps: rate must be 16000, 32000, 44100 or 48000");
+    if (o->n_samples < 1)
+        return fail(ctx, EFX_ERR_ARG, "efx_loudness_steps: n_samples must be >= 1");
+    if (o->first_sample < 0 || o->first_sample >= loud::kMaxFirstSample)
+        return fail(ctx, EFX_ERR_ARG, "efx_loudness_steps: first_sample outside 0 .. 2^40 - 1");
+    const int64_t n_new = loud::step_count(o->rate, o->first_sample, o->n_samples);
+    if (o->first_step < 0 || (int64_t)o->first_step + n_new > 0x7FFFFFFF)
+        return fail(ctx, EFX_ERR_ARG, "efx_loudness_steps: first_step negative or past 2^31 - 1 with the call's steps");
+    if (o->pcm_stride < (size_t)o->n_samples || (o->pcm_stride & 7))
+        return fail(ctx, EFX_ERR_ARG, "efx_loudness_steps: pcm_stride must be a multiple of 8 and hold n_samples elements");
+    if (o->steps_stride < (size_t)o->first_step + (size_t)n_new)
+        return fail(ctx, EFX_ERR_ARG, "efx_loudness_steps: steps_stride must hold first_step + the call's new records");
+    if (misaligned(pcm_device) || misaligned(state_device) || misaligned(steps_device))
+        return fail(ctx, EFX_ERR_ARG, "efx_loudness_steps: pcm, state and steps must be 16-byte aligned device pointers");
+    static_assert(sizeof(efx_loudness_step) == sizeof(loud::StepRec) && sizeof(loud::StepRec) == 16, "one 16-byte store per record");
+    LoudStepsArgs a{};
+    a.pcm = pcm_device;
+    a.state = static_cast<int16_t*>(state_device);
+    a.steps = reinterpret_cast<loud::StepRec*>(steps_device);
+    a.pcm_stride = o->pcm_stride;
+    a.steps_stride = o->steps_stride;
+    a.first_step = o->first_step;
+    a.plan = loud::plan(o->rate, loudness_coefs(o->rate), o->first_sample, o->n_samples);
+    if (n_new > 0)
+        hipLaunchKernelGGL(k_loud_steps, dim3((unsigned)o->n_streams, (unsigned)((n_new + loud::kLanes - 1) / loud::kLanes)),
+                           dim3(loud::kLanes), 0, ctx->stream, a);
+    hipLaunchKernelGGL(k_loud_state, dim3((unsigned)o->n_streams), dim3(256), 0, ctx->stream, a);
+    EFX_HIP(hipGetLastError());
+    return (int)n_new;
+}
+
+int efx_loudness_gate(efx_ctx* ctx, const efx_loudness_gate_opts* o, const efx_loudness_step* steps_device, const void* state_device,
+                      efx_loudness_rec* recs_device)
+{
+    bind_device(ctx);
+    if (!ctx || !o)
+        return EFX_ERR_ARG;
+    if (o->n_streams < 1 || o->n_streams > ctx->cfg.max_streams)
+        return fail(ctx, EFX_ERR_ARG, "efx_loudness_gate: n_streams outside 1 .. max_streams");
+    if (!loud::rate_ok(o->rate))
+        return fail(ctx, EFX_ERR_ARG, "efx_loudness_gate: rate must be 16000, 32000, 44100 or 48000");
+    if (o->n_steps < 0 || o->n_steps > loud::kMaxSteps)
+        return fail(ctx, EFX_ERR_ARG, "efx_loudness_gate: n_steps outside 0 .. 2^24");
+    if (o->target_ms >= loud::kMaxTarget || o->ceiling < 1 || o->ceiling > 32767)
+        return fail(ctx, EFX_ERR_ARG, "efx_loudness_gate: target_ms must be below 2^40 and ceiling 1 .. 32767");
+    if (o->steps_stride < (size_t)o->n_steps)
+        return fail(ctx, EFX_ERR_ARG, "efx_loudness_gate: steps_stride must hold n_steps records");
+    if (!steps_device || !recs_device || ((uintptr_t)steps_device & 15) || ((uintptr_t)recs_device & 15) || ((uintptr_t)state_device & 15))
+        return fail(ctx, EFX_ERR_ARG, "efx_loudness_gate: steps and recs must be 16-byte aligned device pointers, state NULL or aligned");
+    static_assert(sizeof(efx_loudness_rec) == sizeof(loud::GateRec) && sizeof(loud::GateRec) == 32, "two 16-byte stores per record");
+    LoudGateArgs a{};
+    a.steps = reinterpret_cast<const loud::StepRec*>(steps_device);
+    a.state = static_cast<const int16_t*>(state_device);
+    a.recs = reinterpret_cast<loud::GateRec*>(recs_device);
+    a.steps_stride = o->steps_stride;
+    a.abs_thr = o->abs_thr, a.target_ms = o->target_ms, a.ceiling = o->ceiling;
+    a.n_steps = o->n_steps, a.step = loud::step_of(o->rate), a.hist = loud::hist_of(o->rate);
+    hipLaunchKernelGGL(k_loud_gate, dim3((unsigned)o->n_streams), dim3(256), 0, ctx->stream, a);
+    EFX_HIP(hipGetLastError());
+    return EFX_OK;
+}
+
+int efx_pcm_gain(efx_ctx* ctx, const efx_pcm_gain_opts* o, const int16_t* src_device, const efx_loudness_rec* recs_device,
+                 int16_t* dst_device)
+{
+    bind_device(ctx);
+    if (!ctx || !o)
+        return EFX_ERR_ARG;
+    auto misaligned = [](const void* p) { return !p || ((uintptr_t)p & 15); };
+    if (o->n_streams < 1 || o->n_streams > ctx->cfg.max_streams)
+        return fail(ctx, EFX_ERR_ARG, "efx_pcm_gain: n_streams outside 1 .. max_streams");
+    if (o->n_samples < 1)
+        return fail(ctx, EFX_ERR_ARG, "efx_pcm_gain: n_samples must be >= 1");
+    if (!recs_device && (o->fixed_gain_q12 < 1 || o->fixed_gain_q12 > loud::kMaxGain))
+        return fail(ctx, EFX_ERR_ARG, "efx_pcm_gain: fixed_gain_q12 outside 1 .. 32767");
+    if (o->src_stride < (size_t)o->n_samples || (o->src_stride & 7) || o->dst_stride < (size_t)o->n_samples || (o->dst_stride & 7))
+        return fail(ctx, EFX_ERR_ARG, "efx_pcm_gain: the strides must be multiples of 8 and hold n_samples elements");
+    if (misaligned(src_device) || misaligned(dst_device) || ((uintptr_t)recs_device & 15))
+        return fail(ctx, EFX_ERR_ARG, "efx_pcm_gain: src and dst must be 16-byte aligned device pointers, recs NULL or aligned");
+    PcmGainArgs a{};
+    a.src = src_device;
+    a.recs = reinterpret_cast<const loud::GateRec*>(recs_device);
+    a.dst = dst_device;
+    a.src_stride = o->src_stride, a.dst_stride = o->dst_stride;
+    a.n_samples = o->n_samples, a.fixed_gain = o->fixed_gain_q12;
+    // (grid.y is strided over by the kernel: the cap only bounds the launch)
+    const int per_stream = std::max(1, std::min((o->n_samples + 2047) / 2048, (8 * ctx->n_cus + o->n_streams - 1) / o->n_streams));
+    hipLaunchKernelGGL(k_pcm_gain, dim3((unsigned)o->n_streams, (unsigned)per_stream), dim3(256), 0, ctx->stream, a);
     EFX_HIP(hipGetLastError());
     return EFX_OK;
 }

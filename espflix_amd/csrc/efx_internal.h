@@ -19,6 +19,7 @@
 #include "enc_cut.h"
 #include "enc_rate.h"
 #include "import_pcm.h"
+#include "loudness_px.h"
 
 namespace efx {
 
@@ -234,6 +235,36 @@ struct ImportPcmArgs {
     const int32_t* table;  // the prototype, ipcm::kTableLen entries
     size_t src_stride, dst_stride;
     ipcm::Plan plan;
+};
+
+// k_loud_steps / k_loud_state launch arguments (by value): efx_loudness_steps_opts, checked, as loudness_px.h's plan
+struct LoudStepsArgs {
+    const int16_t* pcm;    // stream i at pcm + i * pcm_stride
+    int16_t* state;        // stream i: plan.hist int16 at state + i * plan.hist (k_loud_steps reads, k_loud_state writes)
+    loud::StepRec* steps;  // stream i's plan.n_new records at steps + i * steps_stride + first_step
+    size_t pcm_stride, steps_stride;
+    int first_step;
+    loud::Plan plan;
+};
+
+// k_loud_gate launch arguments (by value): efx_loudness_gate_opts, checked
+struct LoudGateArgs {
+    const loud::StepRec* steps;  // stream i's n_steps records at steps + i * steps_stride
+    const int16_t* state;        // may be null; stream i: hist int16 at state + i * hist
+    loud::GateRec* recs;         // stream i's record at recs + i
+    size_t steps_stride;
+    uint64_t abs_thr, target_ms;
+    uint32_t ceiling;
+    int n_steps, step, hist;
+};
+
+// k_pcm_gain launch arguments (by value): efx_pcm_gain_opts, checked
+struct PcmGainArgs {
+    const int16_t* src;          // stream i at src + i * src_stride
+    const loud::GateRec* recs;   // null: fixed_gain
+    int16_t* dst;                // stream i at dst + i * dst_stride; may be src
+    size_t src_stride, dst_stride;
+    int n_samples, fixed_gain;
 };
 
 // per-stream result of k_ts_sequences

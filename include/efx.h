@@ -1163,6 +1163,140 @@ size_t efx_import_pcm_state_bytes(void);
 /* The table T: copies min(cap, length) entries to out (may be NULL with cap 0) and returns the length, 16 P + 1.  Host only. */
 int efx_import_pcm_filter(int32_t* out, int cap);
 
+/* -- programme loudness and levelling (k_loudness.hip) ------------------------------------------- */
+/* The reference plays sound through a 1-bit pin at a fixed gain (pdm_second_order, src/video.cpp), so a title is as loud
+ * as its source was.  These calls measure the loudness of mono int16 PCM at the four SBC rates -- what efx_import_pcm
+ * writes and efx_sbc_encode reads -- by ITU-R BS.1770-4 / EBU R 128 for n_streams streams at once: gated integrated
+ * loudness, maximum momentary loudness and sample peak (ffmpeg's ebur128); derive one gain per stream for a target
+ * loudness under a peak ceiling (loudnorm in linear mode); and apply it (volume) -- all on the device, the gain never
+ * visits the host.  Sample peak with a ceiling of -1 dBFS stands in for true peak: no oversampling.  Not measured: true
+ * peak, loudness range, short-term loudness; no limiter, no dynamic mode.
+ *
+ * Meaning.  step = rate / 10 samples (100 ms: 1600, 3200, 4410, 4800), W = step / 2.  Step s of a stream covers samples
+ * s step .. (s + 1) step - 1.  Its energy is DEFINED by a K-weighting filter that starts at rest at sample s step - W and
+ * runs over the W + step samples up to the step's end (samples in front of the stream's first are zero); only the step's
+ * own samples are measured.  The high pass's double pole at 38 Hz has a time constant of 4 ms, so after 50 ms the step's
+ * energy is that of a filter with the whole history to within a few 1e-8 (tests/test_loudness_model.py measures it against
+ * a serial float64 evaluation); in exchange every (stream, step) is independent work.
+ *
+ * The arithmetic (espflix_amd/csrc/loudness_px.h) is an integer function of the samples, bit-reproducible anywhere; >> is
+ * arithmetic, floor() of non-negative operands, int32 / int64 / uint64 as stated.
+ *   Coefficients (efx_loudness_coefs).  Both stages from their analogue prototypes by the bilinear transform, in double on
+ *   the host, each rounded to an int32 as round(2^28 c).  With K = tan(pi f0 / rate):
+ *     shelf:     f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196; Vh = 10^(G / 20),
+ *                Vb = Vh^0.4996667741545416, a0 = 1 + K / Q + K^2:
+ *                b0 = (Vh + Vb K / Q + K^2) / a0, b1 = 2 (K^2 - Vh) / a0, b2 = (Vh - Vb K / Q + K^2) / a0,
+ *                a1 = 2 (K^2 - 1) / a0, a2 = (1 - K / Q + K^2) / a0
+ *     high pass: f0 = 38.13547087602444, Q = 0.5003270373238773: b = 1, -2, 1 exactly, a1, a2 as above with these K, Q
+ *   (at 48 kHz: the coefficients BS.1770 prints).  out[0 .. 4] = b0 b1 b2 a1 a2 of the shelf, out[5 .. 9] of the high pass.
+ *   Recurrence, direct form I, all values int32 with 12 fraction bits, products and sums int64:
+ *     x0 = 4096 x[n]
+ *     y[n] = (b0 x0[n] + b1 x0[n-1] + b2 x0[n-2] - a1 y[n-1] - a2 y[n-2] + 2^27) >> 28     (shelf)
+ *     z[n] = (b0' y[n] + b1' y[n-1] + b2' y[n-2] - a1' z[n-1] - a2' z[n-2] + 2^27) >> 28    (high pass)
+ *   (|y|, |z| < 3.4 x 2^27 and a sum of products < 2^61 for any input: tests/test_loudness_model.py).
+ *   Step energy (uint64).  s[n] = (z[n] + 128) >> 8 keeps four fraction bits; E = sum of s[n]^2 over the step's samples.
+ *   Step peak.  The largest |x[n]| of the step's samples, 32768 for -32768.
+ *   Blocks.  B_j = E_j + E_j+1 + E_j+2 + E_j+3, j = 0 .. n_steps - 4: 400 ms, 75 % overlap; fewer than 4 steps: no block.
+ *   Gates.  Absolute: B_j > abs_thr; n_abs of them, S_abs their sum (up to 80 bits).  Relative: 10 B_j n_abs > S_abs among
+ *   those; n_gated of them, S_gated their sum.  gated_mean = floor(S_gated / n_gated), 0 when n_gated = 0 (the sum itself
+ *   passes 64 bits after some ten minutes of full scale, so the record carries the mean); max_block = the largest B_j of
+ *   all blocks.  efx_loudness_lufs turns a block energy -- gated_mean: integrated, max_block: maximum momentary -- into LUFS.
+ *   Gain.  T = target_ms, C = ceiling (efx_loudness_thresholds), peak = the largest step peak (and state sample):
+ *     g = floor(sqrt(min(floor(2^24 T 4 step / gated_mean), 2^32)))         (128-bit dividend)
+ *     g = min(g, floor(4096 C / peak)), then clamped to 1 .. 32767          (Q12: just under +18 dB)
+ *     g = 4096 when n_gated = 0 or peak = 0.
+ *   Apply.  y = clamp16((x g + 2048) >> 12); g = 4096 returns x.
+ *
+ * State.  efx_loudness_state_bytes(rate) per stream, 16-byte aligned: the newest H = (W + step + 7) & ~7 samples of the
+ * stream as int16, oldest first (zeros in front of a stream's first sample): the pending samples of the unfinished step
+ * and the run-in before them.  All zero = a fresh stream.
+ *
+ * Memory contract.  efx_loudness_steps reads, for stream i, only the n_samples int16 from pcm + i * pcm_stride, in 16-byte
+ * pieces aligned down inside that interval (a last piece that would end behind it element by element), and the stream's
+ * state; it writes only the call's new step records, 16 bytes each with one store, and the state.  efx_loudness_gate reads
+ * n_steps records per stream (and the states) and writes 32 bytes per stream.  efx_pcm_gain reads and writes only the
+ * n_samples samples of each stream and reads gain_q12 of each record.  All device pointers are 16-byte aligned, the sample
+ * strides are multiples of 8 elements.  No decoder, encoder or SBC state is touched; every call is asynchronous on the
+ * context's stream without host synchronisation, so steps -> gate -> gain -> efx_sbc_encode queue back to back. */
+typedef struct efx_loudness_step {   /* one 100 ms step */
+    uint64_t energy;                 /* E */
+    uint32_t peak;                   /* 0 .. 32768 */
+    uint32_t zero;
+} efx_loudness_step;
+typedef struct efx_loudness_rec {    /* one stream, 32 bytes */
+    uint64_t gated_mean;             /* floor(S_gated / n_gated): the integrated loudness as a block energy; 0: nothing passed */
+    uint64_t max_block;              /* the largest block: maximum momentary loudness */
+    uint32_t n_gated;                /* blocks above both gates */
+    uint32_t n_blocks;               /* max(n_steps - 3, 0) */
+    uint32_t n_abs;                  /* blocks above the absolute gate */
+    uint16_t peak;                   /* sample peak, 0 .. 32768 */
+    uint16_t gain_q12;               /* 1 .. 32767 */
+} efx_loudness_rec;
+typedef struct efx_loudness_steps_opts {
+    int n_streams;        /* 1 .. max_streams */
+    int n_samples;        /* samples per stream in this call, >= 1 */
+    int rate;             /* 16000, 32000, 44100 or 48000 */
+    int first_step;       /* records already written for these streams: the call's first new record goes to index first_step */
+    int64_t first_sample; /* index in the stream of this call's first sample (0 on a fresh stream), 0 .. 2^40 - 1 */
+    size_t pcm_stride;    /* int16 elements between streams, >= n_samples, multiple of 8 */
+    size_t steps_stride;  /* records between streams, >= first_step + the call's new steps */
+} efx_loudness_steps_opts;
+/* Appends, per stream, every step that becomes whole with this call's samples -- efx_loudness_step_count(rate,
+ * first_sample, n_samples) records, possibly 0 -- at steps + i * steps_stride + first_step, and returns that count (>= 0).
+ * Pieces of any length: calls with first_sample and first_step carried on and the same state give the records of one long
+ * call.  At most two launches (the records; the hand-over of the state, a launch of its own because the last wave must not
+ * overwrite what the first still reads).  Errors are negative.
+ * EFX_ERR_ARG: n_streams, n_samples, first_step or first_sample out of range, a rate that is not one of the four, a NULL
+ * or misaligned (16 bytes) pointer, pcm_stride too small or not a multiple of 8, steps_stride too small. */
+int efx_loudness_steps(efx_ctx* ctx, const efx_loudness_steps_opts* opts, const int16_t* pcm_device, void* state_device,
+                       efx_loudness_step* steps_device);
+typedef struct efx_loudness_gate_opts {
+    int n_streams;        /* 1 .. max_streams */
+    int n_steps;          /* records per stream, 0 .. 2^24 */
+    int rate;
+    uint64_t abs_thr;     /* efx_loudness_thresholds */
+    uint64_t target_ms;   /* below 2^40 */
+    uint32_t ceiling;     /* 1 .. 32767 */
+    size_t steps_stride;  /* records between streams, >= n_steps */
+} efx_loudness_gate_opts;
+/* One efx_loudness_rec per stream at recs + i.  state_device may be NULL; given, every sample of the streams' states
+ * counts towards the peak: they all belong to the stream, and with n_steps = all its whole steps the peak is then that of
+ * every sample it has taken, the pending ones included.  One launch.
+ * EFX_ERR_ARG: a field out of range, a rate that is not one of the four, a NULL steps / recs pointer, a misaligned
+ * (16 bytes) pointer, steps_stride too small. */
+int efx_loudness_gate(efx_ctx* ctx, const efx_loudness_gate_opts* opts, const efx_loudness_step* steps_device,
+                      const void* state_device, efx_loudness_rec* recs_device);
+typedef struct efx_pcm_gain_opts {
+    int n_streams;        /* 1 .. max_streams */
+    int n_samples;        /* samples per stream, >= 1 */
+    int fixed_gain_q12;   /* 1 .. 32767: every stream's gain when recs_device is NULL (else ignored) */
+    size_t src_stride;    /* int16 elements between streams, >= n_samples, multiples of 8 */
+    size_t dst_stride;
+} efx_pcm_gain_opts;
+/* dst[i][n] = clamp16((src[i][n] g_i + 2048) >> 12), g_i = recs[i].gain_q12 read on the device.  dst_device == src_device
+ * (with equal strides) works in place; otherwise the two must not overlap.  One launch.  The records are those
+ * efx_loudness_gate wrote (gain_q12 1 .. 32767): the kernel takes the field as it finds it and cannot report a bad one, so a
+ * record the caller made up with gain_q12 = 0 -- a zeroed one -- silences its stream.
+ * EFX_ERR_ARG: a field out of range (fixed_gain_q12 only without records), a NULL or misaligned (16 bytes) src / dst, a
+ * misaligned recs, a stride too small or not a multiple of 8. */
+int efx_pcm_gain(efx_ctx* ctx, const efx_pcm_gain_opts* opts, const int16_t* src_device, const efx_loudness_rec* recs_device,
+                 int16_t* dst_device);
+/* -0.691 + 10 log10(block_energy / (4 step 32768^2 256)) LUFS; -HUGE_VAL for 0 (nothing passed the gates); NaN for a rate
+ * that is not one of the four.  The only logarithm.  Host only. */
+double efx_loudness_lufs(uint64_t block_energy, int rate);
+/* abs_thr = round(10^((-70 + 0.691) / 10) 32768^2 256 x 4 step), target_ms = round(10^((target_lufs + 0.691) / 10)
+ * 32768^2 256), ceiling = round(32767 x 10^(peak_dbfs / 20)).  EFX_ERR_ARG for a rate that is not one of the four,
+ * target_lufs outside -70 .. 0 or peak_dbfs outside -90 .. 0.  Host only. */
+int efx_loudness_thresholds(int rate, double target_lufs, double peak_dbfs, uint64_t* abs_thr, uint64_t* target_ms,
+                            uint32_t* ceiling);
+/* The ten coefficients; EFX_ERR_ARG for a rate that is not one of the four.  Host only. */
+int efx_loudness_coefs(int rate, int32_t out[10]);
+/* 2 H: 4800, 9600, 13232 or 14400; 0 for a rate that is not one of the four.  Host only. */
+size_t efx_loudness_state_bytes(int rate);
+/* floor((first_sample + n_samples) / step) - floor(first_sample / step); -1 for arguments efx_loudness_steps rejects.
+ * Host only. */
+int efx_loudness_step_count(int rate, int64_t first_sample, int n_samples);
+
 /* -- A/V multiplexer: video transport stream + SBC frames -> a title (espflix_amd/csrc/k_mux.hip) -- */
 /* The reference player takes its audio from PES packets on PID 0x101 / 0x102 of the transport stream that carries the
  * video on PID 0x100 (MpegDecoder::demux, src/player.cpp:421-433).  Output, byte for byte (tests/mux_model.py restates it):
