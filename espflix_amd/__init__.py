@@ -24,7 +24,7 @@ STRIPS = 12
 STRIP_BYTES = 8448
 FRAME_BYTES = 101376
 
-OPT_GROUPS, OPT_PARSE_CAP, OPT_RECON_MODE, OPT_RECON_WAVES, OPT_RECON_SPINS, OPT_RECON_ITEMS, OPT_SBC_SERIAL, OPT_DEMUX_FUSED = 1, 2, 3, 4, 5, 6, 7, 8   # efx_option
+OPT_GROUPS, OPT_PARSE_CAP, OPT_RECON_MODE, OPT_RECON_WAVES, OPT_RECON_SPINS, OPT_RECON_ITEMS, OPT_SBC_SERIAL = 1, 2, 3, 4, 5, 6, 7   # efx_option
 SBC_PROBE_FIRST = 1
 PIX_I420, PIX_RGB24, PIX_RGBP = 0, 1, 2     # efx_pixel_format
 CHROMA_NEAREST, CHROMA_BILINEAR = 0, 1
@@ -842,7 +842,7 @@ class Timing:
     ts_bytes: int = 0
     timed_calls: int = 0
     groups: int = 1  # reconstruction groups of the newest call: one k_recon launch per group and picture index
-    parse_halves: int = 1  # parse halves of the newest call (side by side on the parse streams)
+    parse_halves: int = 1  # parse halves of the newest call: one per group
     mixed: int = 0   # 1: the averaged calls did not all run with that structure
     recon_launches: int = 0  # reconstruction kernel launches of the newest call (groups x pictures, or groups with k_recon_all)
 

@@ -37,8 +37,6 @@ struct DemuxChunk;
 __global__ void k_demux_scan(const uint8_t*, const uint64_t*, const uint32_t*, const uint32_t*, DemuxChunk*);
 __global__ void k_demux_offsets(const uint32_t*, const uint32_t*, DemuxChunk*, uint8_t*, const uint64_t*, uint32_t*, uint32_t*);
 __global__ void k_demux(const uint8_t*, const uint64_t*, const uint32_t*, const uint32_t*, const DemuxChunk*, uint8_t*, PesEntry*);
-__global__ void k_demux_fused(const uint8_t*, const uint64_t*, const uint32_t*, const uint32_t*, DemuxChunk*, uint8_t*, PesEntry*, uint32_t*, uint32_t*,
-                              uint32_t*);
 __global__ void k_demux_audio_scan(const uint8_t*, const uint64_t*, const uint32_t*, const uint32_t*, DemuxChunk*);
 __global__ void k_demux_audio_offsets(const uint32_t*, const uint32_t*, DemuxChunk*, uint32_t*);
 __global__ void k_demux_audio(const uint8_t*, const uint64_t*, const uint32_t*, const uint32_t*, const DemuxChunk*, uint8_t*, const uint64_t*);
@@ -126,7 +124,6 @@ constexpr int kSbcMonoWgPerCu = 4;  // k_sbc_par_mono workgroups per compute uni
 constexpr int kParseStreams = 2;    // parse halves in flight at once (latency-bound kernels: two overlap well)
 constexpr int kMaxGroups = 16;      // an efx_decode call parses its streams in up to this many parse halves
 static_assert(kMaxGroups <= kExportMaxGroups, "k_export takes every reconstruction group of a call");
-constexpr int kReconMerge = 1;      // parse halves whose streams are reconstructed by ONE launch per picture index
 constexpr int kGroupStreams = 1024;
 constexpr int kTimingRing = 64;   // efx_decode calls whose stage times efx_get_timing can average
 constexpr int kSlots = 3;         // parse -> recon hand-over buffer sets (one being reconstructed + two being parsed)
@@ -220,22 +217,20 @@ struct efx_ctx {
                                      // stream, the newest PES PTS of the upload (k_index -> k_advance)
         int32_t* d_call_pos = nullptr;  // per stream: ring position of this call's first picture, first picture with a PTS
         uint32_t* d_recon_sync = nullptr;  // k_recon_all: queue heads, spins, abort, finished items per stream -- a 128-byte line each
-        hipEvent_t parse_done[kReconMerge] = {}, recon_done = nullptr, wrap_cleared = nullptr;
+        hipEvent_t parse_done = nullptr, recon_done = nullptr;
         int epoch = 0;
         int upload = 0;  // batch this call decoded
     } slot[kSlots];
     // stage timing: one event set per efx_decode call since efx_set_timing(1), so that a run of
     // back-to-back (overlapping) calls can be averaged afterwards without a host sync in between
     struct TimingEvents {
-        // per parse half: parse start, index end, parse end (its parse stream); the first half of a reconstruction group
-        // also carries that group's recon end [3] and recon start [4] (context stream)
+        // per group: parse start, index end, parse end (its parse stream), recon end [3] and recon start [4] (context stream)
         hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     };
     std::vector<TimingEvents> timing_ring;  // kTimingRing x kMaxGroups sets, created by efx_set_timing
     uint64_t timed_calls = 0;               // calls recorded since timing was (re-)enabled
     struct Group {
-        int slot, first, count;  // hand-over slot, streams [first, first + count)
-        int half0, halves;       // its parse halves (their counters: d_counters[half0 ...])
+        int slot, first, count;  // hand-over slot, streams [first, first + count); its counters: d_counters[its index]
     };
     Group groups[kMaxGroups];  // reconstruction groups of the most recent efx_decode
     int n_groups = 0;
@@ -252,9 +247,8 @@ struct efx_ctx {
     bool last_ts_input = false;  // have recycled the Upload record by the time the results are fetched)
     uint64_t subcalls = 0;     // reconstruction groups launched so far: group k uses slot k % kSlots
     uint64_t parse_calls = 0;  // parse halves launched so far: half k runs on parse stream k % kParseStreams
-    uint8_t timing_groups[kTimingRing] = {};    // parse halves of the timed call
+    uint8_t timing_groups[kTimingRing] = {};    // groups of the timed call
     uint16_t timing_launches[kTimingRing] = {};  // reconstruction kernel launches of the timed call
-    uint16_t timing_leaders[kTimingRing] = {};  // bit h: half h is the first of its reconstruction group (carries ev[3], ev[4])
     hipStream_t parse_streams[kParseStreams] = {};
     VideoTables* d_video[2] = {nullptr, nullptr};  // [0] PAL, [1] NTSC
     VideoLineTemplates* d_video_lines[2] = {nullptr, nullptr};
@@ -297,7 +291,6 @@ struct efx_ctx {
     size_t sbc_info_cap = 0;             // in frames: streams x (frames + 1)
     size_t sbc_gran_cap = 0;             // in granules: streams x ceil(frames / 8)
     int opt_sbc_serial = 0;              // 1 = every stream through k_sbc, one wave per stream (the tests' comparison)
-    int opt_demux_fused = 0;             // 1 = TS input through the one-pass demultiplexer (k_demux_fused: measured slower, kept as an option)
     bool sbc_flags_clean = false;        // d_sbc_flags[0, n) all kSbcRegularFlag (k_sbc_finish leaves them so)
     uint64_t* d_hash = nullptr;
 
@@ -704,8 +697,6 @@ int efx_create(const efx_config* cfg, efx_ctx** out)
             ctx->opt_recon_mode = atoi(v);
         if (const char* v = getenv("EFX_RECON_WAVES"))
             ctx->opt_recon_waves = atoi(v);
-        if (const char* v = getenv("EFX_DEMUX_FUSED"))
-            ctx->opt_demux_fused = atoi(v) != 0;
         if (const char* v = getenv("EFX_RECON_ITEMS"))
             ctx->opt_recon_items = atoi(v);
         if (const char* cap = getenv("EFX_PARSE_WG_CAP"))  // (development: 0 = no cap)
@@ -747,10 +738,8 @@ int efx_create(const efx_config* cfg, efx_ctx** out)
     A(hipMemset(ctx->d_frames, 0, n * D * kFrameBytes));
     for (auto& sl : ctx->slot) {
         A(hipMemset(sl.d_mbrecs, 0, n * P * kMbCount * sizeof(MbRec)));
-        for (auto& ev : sl.parse_done)
-            A(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        A(hipEventCreateWithFlags(&sl.parse_done, hipEventDisableTiming));
         A(hipEventCreateWithFlags(&sl.recon_done, hipEventDisableTiming));
-        A(hipEventCreateWithFlags(&sl.wrap_cleared, hipEventDisableTiming));
     }
     if (e != hipSuccess)
         return bail(EFX_ERR_DEVICE);
@@ -819,13 +808,10 @@ void efx_destroy(efx_ctx* ctx)
         for (void* b : sb)
             if (b)
                 (void)dev_free(b);
-        for (auto ev : sl.parse_done)
-            if (ev)
-                (void)hipEventDestroy(ev);
+        if (sl.parse_done)
+            (void)hipEventDestroy(sl.parse_done);
         if (sl.recon_done)
             (void)hipEventDestroy(sl.recon_done);
-        if (sl.wrap_cleared)
-            (void)hipEventDestroy(sl.wrap_cleared);
     }
     bool complete = ctx->own_stream && ctx->stream && ctx->copy_stream;
     for (auto ps : ctx->parse_streams)
@@ -864,8 +850,7 @@ static int ensure_ts_buffers(efx_ctx* ctx)
     ctx->pes_cap = ctx->es_cap / 188 + n_max;
     hipError_t e = dalloc(&ctx->d_ts, ctx->es_cap);
     if (e == hipSuccess)
-        // (the chunk descriptors, and behind them one ticket counter per stream for the one-pass kernel: zeroed together)
-        e = dev_alloc(reinterpret_cast<void**>(&ctx->d_demux_chunks), (ctx->pes_cap / kDemuxChunk + n_max + 2) * 16 + n_max * sizeof(uint32_t));
+        e = dev_alloc(reinterpret_cast<void**>(&ctx->d_demux_chunks), (ctx->pes_cap / kDemuxChunk + n_max + 2) * 16);
     for (auto& u : ctx->up) {
         if (e == hipSuccess) e = dalloc(&u.d_ts_len, n_max);
         if (e == hipSuccess) e = dalloc(&u.d_pkt_base, n_max);
@@ -1064,24 +1049,12 @@ static int upload_streams(efx_ctx* ctx, int n_streams, const uint8_t* const* dat
             for (int i = 0; i < n_streams; i++)
                 max_len = std::max(max_len, len[i]);
             const unsigned chunks = (unsigned)std::max<size_t>(1, (max_len / 188 + kDemuxChunk - 1) / kDemuxChunk);
-            if (kDemuxThreads == 64 && ctx->opt_demux_fused) {
-                // one pass, one launch: tickets + decoupled look-back over the chunk descriptors (k_demux.hip); both zeroed here.
-                // The tickets sit in front of the descriptors this batch uses, so that ONE memset covers them.
-                const size_t n_desc = packets / kDemuxChunk + (size_t)n_streams + 2;
-                uint8_t* const desc_bytes = reinterpret_cast<uint8_t*>(ctx->d_demux_chunks);
-                uint32_t* tickets = reinterpret_cast<uint32_t*>(desc_bytes + (ctx->pes_cap / kDemuxChunk + (size_t)ctx->cfg.max_streams + 2) * 16);
-                EFX_HIP(hipMemsetAsync(desc_bytes, 0, n_desc * 16, st));
-                EFX_HIP(hipMemsetAsync(tickets, 0, (size_t)n_streams * sizeof(uint32_t), st));
-                hipLaunchKernelGGL(k_demux_fused, dim3(chunks, n_streams), dim3(kDemuxThreads), 0, st, ctx->d_ts, u.d_stream_off, u.d_ts_len,
-                                   u.d_pkt_base, ctx->d_demux_chunks, u.d_es, u.d_pes, tickets, u.d_es_len, u.d_pes_count);
-            } else {
-                hipLaunchKernelGGL(k_demux_scan, dim3(chunks, n_streams), dim3(kDemuxThreads), 0, st, ctx->d_ts, u.d_stream_off, u.d_ts_len, u.d_pkt_base,
-                                   ctx->d_demux_chunks);
-                hipLaunchKernelGGL(k_demux_offsets, dim3(n_streams), dim3(64), 0, st, u.d_ts_len, u.d_pkt_base, ctx->d_demux_chunks, u.d_es,
-                                   u.d_stream_off, u.d_es_len, u.d_pes_count);
-                hipLaunchKernelGGL(k_demux, dim3(chunks, n_streams), dim3(kDemuxThreads), 0, st, ctx->d_ts, u.d_stream_off, u.d_ts_len, u.d_pkt_base,
-                                   ctx->d_demux_chunks, u.d_es, u.d_pes);
-            }
+            hipLaunchKernelGGL(k_demux_scan, dim3(chunks, n_streams), dim3(kDemuxThreads), 0, st, ctx->d_ts, u.d_stream_off, u.d_ts_len, u.d_pkt_base,
+                               ctx->d_demux_chunks);
+            hipLaunchKernelGGL(k_demux_offsets, dim3(n_streams), dim3(64), 0, st, u.d_ts_len, u.d_pkt_base, ctx->d_demux_chunks, u.d_es,
+                               u.d_stream_off, u.d_es_len, u.d_pes_count);
+            hipLaunchKernelGGL(k_demux, dim3(chunks, n_streams), dim3(kDemuxThreads), 0, st, ctx->d_ts, u.d_stream_off, u.d_ts_len, u.d_pkt_base,
+                               ctx->d_demux_chunks, u.d_es, u.d_pes);
         }
         if (ctx->timing) {
             EFX_HIP(hipEventRecord(u.ev_demux[1], st));
@@ -1219,9 +1192,6 @@ int efx_set_option(efx_ctx* ctx, int option, int value)
     case EFX_OPT_SBC_SERIAL:
         ctx->opt_sbc_serial = value != 0;
         return EFX_OK;
-    case EFX_OPT_DEMUX_FUSED:
-        ctx->opt_demux_fused = value != 0;
-        return EFX_OK;
     default:
         return EFX_ERR_ARG;
     }
@@ -1239,7 +1209,6 @@ int efx_get_option(efx_ctx* ctx, int option, int* value)
     case EFX_OPT_RECON_WAVES: *value = ctx->opt_recon_waves; return EFX_OK;
     case EFX_OPT_RECON_ITEMS: *value = ctx->opt_recon_items; return EFX_OK;
     case EFX_OPT_SBC_SERIAL: *value = ctx->opt_sbc_serial; return EFX_OK;
-    case EFX_OPT_DEMUX_FUSED: *value = ctx->opt_demux_fused; return EFX_OK;
     case EFX_OPT_RECON_SPINS: {
         int r = sync_all(ctx);
         if (r)
@@ -1397,115 +1366,99 @@ int efx_decode_range(efx_ctx* ctx, int first_picture, int n_pictures)
     if (ctx->timing && !ctx->timing_ring.empty()) {
         timing_slot = (int)(ctx->timed_calls++ % kTimingRing);
         ctx->timing_groups[timing_slot] = (uint8_t)G;
-        ctx->timing_leaders[timing_slot] = 0;
-        ctx->timing_launches[timing_slot] = (uint16_t)(((G + kReconMerge - 1) / kReconMerge) * (ctx->opt_recon_mode == 0 ? n_pictures : 1));
+        ctx->timing_launches[timing_slot] = (uint16_t)(G * (ctx->opt_recon_mode == 0 ? n_pictures : 1));
     }
     ctx->last_upload = ctx->cur_up;
     ctx->last_n_streams = u.n_streams;
     ctx->last_ts_input = u.ts_input;
-    // G parse halves; kReconMerge consecutive halves form one reconstruction group: they parse side by side on the parse
-    // streams into disjoint stream ranges of ONE hand-over slot, and one k_recon launch per picture index covers them all
-    // (a launch is a barrier: the fewer and fatter the launches, the smaller the share of their draining tails)
-    const int R = (G + kReconMerge - 1) / kReconMerge;
-    ctx->n_groups = R;
-    for (int r = 0; r < R; r++) {
-        const int h0 = r * kReconMerge, h1 = std::min(G, h0 + kReconMerge);
-        const int rs0 = group_first(n_all, G, h0), rn = group_first(n_all, G, h1) - rs0;
+    // G groups of streams, each a parse half (a parse stream, into its own hand-over slot) and behind it the group's
+    // reconstruction on the context stream
+    ctx->n_groups = G;
+    for (int g = 0; g < G; g++) {
+        const int s0 = group_first(n_all, G, g), n = group_first(n_all, G, g + 1) - s0;
         const int slot = (int)(ctx->subcalls++ % kSlots);
-        ctx->groups[r] = {slot, rs0, rn, h0, h1 - h0};
+        ctx->groups[g] = {slot, s0, n};
         efx_ctx::Slot& sl = ctx->slot[slot];
         sl.upload = ctx->cur_up;
         // macroblock records carry the epoch that wrote them; recycle the tag space by clearing
         const bool wrap = ++sl.epoch > 255;
         if (wrap)
             sl.epoch = 1;
-        efx_ctx::TimingEvents* te0 = nullptr;
-        for (int g = h0; g < h1; g++) {
-            const int s0 = group_first(n_all, G, g), n = group_first(n_all, G, g + 1) - s0;
-            const int pi = (int)(ctx->parse_calls++ % kParseStreams);
-            hipStream_t sp = ctx->parse_streams[pi];
-            DecodeCounters* counters = sl.d_counters + g;
-            uint32_t* slice_base = sl.d_slice_base + (size_t)s0 * P + g;               // this half's own lists
-            SliceDesc* descs = sl.d_descs + (size_t)s0 * P * kMaxSlicesPerPicture;
+        const int pi = (int)(ctx->parse_calls++ % kParseStreams);
+        hipStream_t sp = ctx->parse_streams[pi];
+        DecodeCounters* counters = sl.d_counters + g;
+        uint32_t* slice_base = sl.d_slice_base + (size_t)s0 * P + g;               // this group's own lists
+        SliceDesc* descs = sl.d_descs + (size_t)s0 * P * kMaxSlicesPerPicture;
 
-            // ---- parse half (a parse stream): index -> slice list -> VLC parse -----------------------------------
-            EFX_HIP(hipStreamWaitEvent(sp, u.uploaded, 0));     // the batch is in HBM (H2D and k_demux on the copy stream)
-            EFX_HIP(hipStreamWaitEvent(sp, sl.recon_done, 0));  // the group kSlots back has released this slot
-            // (the WHOLE slot: its stream ranges belong to other halves in other calls, and a record the current parse
-            // does not write must never match a tag of the previous 255-cycle)
-            if (wrap && g == h0) {
-                EFX_HIP(hipMemsetAsync(sl.d_mbrecs, 0, (size_t)ctx->cfg.max_streams * P * kMbCount * sizeof(MbRec), sp));
-                EFX_HIP(hipEventRecord(sl.wrap_cleared, sp));
-            } else if (wrap)
-                EFX_HIP(hipStreamWaitEvent(sp, sl.wrap_cleared, 0));
-            efx_ctx::TimingEvents* te = timing_slot >= 0 ? &ctx->timing_ring[(size_t)timing_slot * kMaxGroups + g] : nullptr;
-            if (te && !te->ev[0])
-                for (auto& ev : te->ev)
-                    EFX_HIP(hipEventCreate(&ev));
-            if (g == h0)
-                te0 = te;
-            if (te)
-                EFX_HIP(hipEventRecord(te->ev[0], sp));
-            hipLaunchKernelGGL(k_index, dim3(n), dim3(64 * kIndexWaves), 0, sp, u.d_es, u.d_stream_off, P, sl.d_pics, sl.d_slices_tmp,
-                               sl.d_pic_count, sl.d_status, sl.d_qtab, ctx->d_tables->scan, u.d_pes, u.d_pkt_base, u.d_pes_count,
-                               u.ts_input ? sl.d_pts : nullptr, u.ts_input ? sl.d_pts + (size_t)ctx->cfg.max_streams * P : nullptr,
-                               first_picture, s0, n_pictures);
-            hipLaunchKernelGGL(k_slice_scan, dim3(1), dim3(1024), 0, sp, sl.d_pics, sl.d_pic_count, n, P, u.d_stream_perm + s0,
-                               slice_base, counters);
-            hipLaunchKernelGGL(k_slice_emit, dim3((n * P * kMaxSlicesPerPicture + 255) / 256), dim3(256), 0, sp, sl.d_pics,
-                               sl.d_slices_tmp, sl.d_pic_count, u.d_stream_off, slice_base, n, P, u.d_stream_perm + s0, descs, sl.d_status);
-            if (te)
-                EFX_HIP(hipEventRecord(te->ev[1], sp));
-            const int max_slices = n * P * kMaxSlicesPerPicture;
-            const int parse_waves = (max_slices + kParseLanes - 1) / kParseLanes;  // (rounded UP: one lane per slice slot)
-            // k_parse's waves pull groups of slices off a counter: the grid is how many of them are resident at a time (above)
-            int parse_wgs = (parse_waves + kParseWaves - 1) / kParseWaves;
-            // The cap protects the reconstruction launches the parser runs beside.  When the reconstruction stream has
-            // nothing queued at this moment -- one call at a time, the first call after a synchronisation -- the parser
-            // may have the chip: 0.84 instead of 1.38 ms per 1024 streams x 12 pictures.
-            const bool recon_busy = ctx->opt_parse_cap == 1 || (ctx->opt_parse_cap == 0 && ctx->recon_groups_unsynced > 0);
-            if (ctx->parse_wg_cap > 0 && recon_busy)
-                parse_wgs = std::min(parse_wgs, ctx->parse_wg_cap);
-            hipLaunchKernelGGL(k_parse, dim3(parse_wgs), dim3(64 * kParseWaves), 0, sp, u.d_es,
-                               descs, counters, ctx->d_tm_tables, sl.d_mbrecs, sl.d_raw, sl.d_coefs, sl.d_status, P, sl.epoch);
-            if (te)
-                EFX_HIP(hipEventRecord(te->ev[2], sp));
-            EFX_HIP(hipEventRecord(sl.parse_done[g - h0], sp));
-            EFX_HIP(hipEventRecord(u.last_read[pi], sp));  // the bitstream buffer is free for the upload after next
-        }
+        // ---- parse half (a parse stream): index -> slice list -> VLC parse -----------------------------------
+        EFX_HIP(hipStreamWaitEvent(sp, u.uploaded, 0));     // the batch is in HBM (H2D and k_demux on the copy stream)
+        EFX_HIP(hipStreamWaitEvent(sp, sl.recon_done, 0));  // the group kSlots back has released this slot
+        // (the WHOLE slot: its stream ranges belong to other groups in other calls, and a record the current parse
+        // does not write must never match a tag of the previous 255-cycle)
+        if (wrap)
+            EFX_HIP(hipMemsetAsync(sl.d_mbrecs, 0, (size_t)ctx->cfg.max_streams * P * kMbCount * sizeof(MbRec), sp));
+        efx_ctx::TimingEvents* te = timing_slot >= 0 ? &ctx->timing_ring[(size_t)timing_slot * kMaxGroups + g] : nullptr;
+        if (te && !te->ev[0])
+            for (auto& ev : te->ev)
+                EFX_HIP(hipEventCreate(&ev));
+        if (te)
+            EFX_HIP(hipEventRecord(te->ev[0], sp));
+        hipLaunchKernelGGL(k_index, dim3(n), dim3(64 * kIndexWaves), 0, sp, u.d_es, u.d_stream_off, P, sl.d_pics, sl.d_slices_tmp,
+                           sl.d_pic_count, sl.d_status, sl.d_qtab, ctx->d_tables->scan, u.d_pes, u.d_pkt_base, u.d_pes_count,
+                           u.ts_input ? sl.d_pts : nullptr, u.ts_input ? sl.d_pts + (size_t)ctx->cfg.max_streams * P : nullptr,
+                           first_picture, s0, n_pictures);
+        hipLaunchKernelGGL(k_slice_scan, dim3(1), dim3(1024), 0, sp, sl.d_pics, sl.d_pic_count, n, P, u.d_stream_perm + s0,
+                           slice_base, counters);
+        hipLaunchKernelGGL(k_slice_emit, dim3((n * P * kMaxSlicesPerPicture + 255) / 256), dim3(256), 0, sp, sl.d_pics,
+                           sl.d_slices_tmp, sl.d_pic_count, u.d_stream_off, slice_base, n, P, u.d_stream_perm + s0, descs, sl.d_status);
+        if (te)
+            EFX_HIP(hipEventRecord(te->ev[1], sp));
+        const int max_slices = n * P * kMaxSlicesPerPicture;
+        const int parse_waves = (max_slices + kParseLanes - 1) / kParseLanes;  // (rounded UP: one lane per slice slot)
+        // k_parse's waves pull groups of slices off a counter: the grid is how many of them are resident at a time (above)
+        int parse_wgs = (parse_waves + kParseWaves - 1) / kParseWaves;
+        // The cap protects the reconstruction launches the parser runs beside.  When the reconstruction stream has
+        // nothing queued at this moment -- one call at a time, the first call after a synchronisation -- the parser
+        // may have the chip: 0.84 instead of 1.38 ms per 1024 streams x 12 pictures.
+        const bool recon_busy = ctx->opt_parse_cap == 1 || (ctx->opt_parse_cap == 0 && ctx->recon_groups_unsynced > 0);
+        if (ctx->parse_wg_cap > 0 && recon_busy)
+            parse_wgs = std::min(parse_wgs, ctx->parse_wg_cap);
+        hipLaunchKernelGGL(k_parse, dim3(parse_wgs), dim3(64 * kParseWaves), 0, sp, u.d_es,
+                           descs, counters, ctx->d_tm_tables, sl.d_mbrecs, sl.d_raw, sl.d_coefs, sl.d_status, P, sl.epoch);
+        if (te)
+            EFX_HIP(hipEventRecord(te->ev[2], sp));
+        EFX_HIP(hipEventRecord(sl.parse_done, sp));
+        EFX_HIP(hipEventRecord(u.last_read[pi], sp));  // the bitstream buffer is free for the upload after next
 
         // ---- reconstruction of the group (context stream): one launch per picture index --------------------------
-        for (int g = h0; g < h1; g++)
-            EFX_HIP(hipStreamWaitEvent(sr, sl.parse_done[g - h0], 0));
-        if (te0) {
-            EFX_HIP(hipEventRecord(te0->ev[4], sr));
-            ctx->timing_leaders[timing_slot] |= (uint16_t)(1u << h0);
-        }
+        EFX_HIP(hipStreamWaitEvent(sr, sl.parse_done, 0));
+        if (te)
+            EFX_HIP(hipEventRecord(te->ev[4], sr));
         // ring positions of this call's pictures; the reconstruction stream orders the calls
-        hipLaunchKernelGGL(k_advance, dim3((rn + 255) / 256), dim3(256), 0, sr, ctx->d_state, sl.d_pic_count,
-                           u.ts_input ? sl.d_pts : nullptr, u.ts_input ? sl.d_pts + (size_t)ctx->cfg.max_streams * P : nullptr, rs0, rn,
+        hipLaunchKernelGGL(k_advance, dim3((n + 255) / 256), dim3(256), 0, sr, ctx->d_state, sl.d_pic_count,
+                           u.ts_input ? sl.d_pts : nullptr, u.ts_input ? sl.d_pts + (size_t)ctx->cfg.max_streams * P : nullptr, s0, n,
                            P, sl.d_call_pos);
         constexpr int kGroupsPerPicture = (kMbCount * 6 + 63) / 64;
         if (ctx->opt_recon_mode == 0) {
             for (int p = 0; p < n_pictures; p++)
-                hipLaunchKernelGGL(k_recon, dim3(rn, kGroupsPerPicture), dim3(64), 0, sr, sl.d_mbrecs, sl.d_coefs,
-                                   ctx->d_tables->scan, sl.d_qtab, ctx->d_frames, P, D, p, sl.d_call_pos, sl.epoch, rs0);
-        } else if (rn > 0) {
+                hipLaunchKernelGGL(k_recon, dim3(n, kGroupsPerPicture), dim3(64), 0, sr, sl.d_mbrecs, sl.d_coefs,
+                                   ctx->d_tables->scan, sl.d_qtab, ctx->d_frames, P, D, p, sl.d_call_pos, sl.epoch, s0);
+        } else if (n > 0) {
             // ONE launch for all picture indices of the group: persistent waves pull (picture, stream, block group) items in
             // picture-major order; a per-stream counter of finished items orders a picture behind its predecessor (k_recon.hip)
-            EFX_HIP(hipMemsetAsync(sl.d_recon_sync, 0, kReconSyncWords((size_t)rn) * sizeof(uint32_t), sr));
+            EFX_HIP(hipMemsetAsync(sl.d_recon_sync, 0, kReconSyncWords((size_t)n) * sizeof(uint32_t), sr));
             // A wave takes opt_recon_items items and ends, so that wave slots (and their LDS) keep coming free for the parse
             // kernel of the next call; with 0 the grid is what the chip holds and the waves live until the last item.
-            const long long items = (long long)rn * kGroupsPerPicture * n_pictures;
+            const long long items = (long long)n * kGroupsPerPicture * n_pictures;
             const int per_cu = ctx->opt_recon_waves > 0 ? ctx->opt_recon_waves : 18;
             const long long waves = ctx->opt_recon_items > 0 ? (items + ctx->opt_recon_items - 1) / ctx->opt_recon_items
                                                              : std::min<long long>(items, (long long)ctx->n_cus * per_cu);
             hipLaunchKernelGGL(k_recon_all, dim3((unsigned)waves), dim3(64), 0, sr, sl.d_mbrecs,
-                               sl.d_coefs, ctx->d_tables->scan, sl.d_qtab, ctx->d_frames, P, D, n_pictures, sl.d_call_pos, sl.epoch, rs0, rn,
+                               sl.d_coefs, ctx->d_tables->scan, sl.d_qtab, ctx->d_frames, P, D, n_pictures, sl.d_call_pos, sl.epoch, s0, n,
                                sl.d_recon_sync, sl.d_status, ctx->opt_recon_items);
         }
-        if (te0)
-            EFX_HIP(hipEventRecord(te0->ev[3], sr));
+        if (te)
+            EFX_HIP(hipEventRecord(te->ev[3], sr));
         EFX_HIP(hipEventRecord(sl.recon_done, sr));
         ctx->last_recon_done = sl.recon_done;
         ctx->recon_groups_unsynced++;
@@ -1558,13 +1511,11 @@ static int fetch_results(efx_ctx* ctx)
         EFX_HIP(hipMemcpy(ctx->h_call_pos.data() + 2 * f, sl.d_call_pos + 2 * f, 2 * c * sizeof(int32_t), hipMemcpyDeviceToHost));
         if (ts_input)
             EFX_HIP(hipMemcpy(ctx->h_pts.data() + f * P, sl.d_pts + f * P, c * P * sizeof(int64_t), hipMemcpyDeviceToHost));
-        for (int h = gr.half0; h < gr.half0 + gr.halves; h++) {
-            DecodeCounters dc;
-            EFX_HIP(hipMemcpy(&dc, sl.d_counters + h, sizeof(dc), hipMemcpyDeviceToHost));
-            ctx->h_counters.total_slices += dc.total_slices;
-            ctx->h_counters.coefficients += dc.coefficients;
-            ctx->h_counters.macroblocks += dc.macroblocks;
-        }
+        DecodeCounters dc;
+        EFX_HIP(hipMemcpy(&dc, sl.d_counters + g, sizeof(dc), hipMemcpyDeviceToHost));
+        ctx->h_counters.total_slices += dc.total_slices;
+        ctx->h_counters.coefficients += dc.coefficients;
+        ctx->h_counters.macroblocks += dc.macroblocks;
     }
     ctx->results_valid = true;
     return EFX_OK;
@@ -3459,30 +3410,23 @@ int efx_get_timing(efx_ctx* ctx, efx_timing* out)
         // a call's stage time = the sum over its groups of streams (they run one after the other on their stream)
         const size_t call = (size_t)((ctx->timed_calls - 1 - k) % kTimingRing);
         const int G = ctx->timing_groups[call];
-        const uint32_t leaders = ctx->timing_leaders[call];
-        int last_leader = 0, n_leaders = 0;
         for (int g = 0; g < G; g++) {
             const efx_ctx::TimingEvents& te = ctx->timing_ring[call * kMaxGroups + g];
             float a = 0, b = 0, c = 0;
             EFX_HIP(hipEventElapsedTime(&a, te.ev[0], te.ev[1]));
             EFX_HIP(hipEventElapsedTime(&b, te.ev[1], te.ev[2]));
-            if (leaders >> g & 1) {
-                EFX_HIP(hipEventElapsedTime(&c, te.ev[4], te.ev[3]));
-                last_leader = g;
-                n_leaders++;
-            }
+            EFX_HIP(hipEventElapsedTime(&c, te.ev[4], te.ev[3]));
             t.index_ms += a / n_timed;
             t.parse_ms += b / n_timed;
             t.recon_ms += c / n_timed;
         }
         float d = 0;
-        EFX_HIP(hipEventElapsedTime(&d, ctx->timing_ring[call * kMaxGroups].ev[0], ctx->timing_ring[call * kMaxGroups + last_leader].ev[3]));
+        EFX_HIP(hipEventElapsedTime(&d, ctx->timing_ring[call * kMaxGroups].ev[0], ctx->timing_ring[call * kMaxGroups + G - 1].ev[3]));
         t.total_ms += d / n_timed;
         if (k == 0) {  // the launch structure of the newest call
-            t.groups = (uint32_t)n_leaders;
-            t.parse_halves = (uint32_t)G;
+            t.groups = t.parse_halves = (uint32_t)G;
             t.recon_launches = ctx->timing_launches[call];
-        } else if (t.groups != (uint32_t)n_leaders || t.parse_halves != (uint32_t)G || t.recon_launches != ctx->timing_launches[call])
+        } else if (t.groups != (uint32_t)G || t.recon_launches != ctx->timing_launches[call])
             t.mixed = 1;
     }
     t.timed_calls = (uint32_t)n_timed;

@@ -291,7 +291,6 @@ struct FieldArgs {
 // packets x 256 threads, whose few long phases left the chip waiting (gather 81 -> 42 us; profiles/r5_demux.md).
 constexpr int kDemuxChunk = 16;
 constexpr int kDemuxThreads = 64;
-constexpr uint32_t kDemuxFailedFlag = 0x80000000u;  // in a stream's PES count: k_demux_fused gave up on it (k_index: EFX_STREAM_INTERNAL)
 static_assert(kDemuxChunk % 4 == 0 && kDemuxChunk >= 4 && kDemuxChunk <= 256, "k_demux stages whole 16-byte groups");
 
 // SBC synthesis tables (sbc_decoder.cpp:41-71), generated from the A2DP definitions

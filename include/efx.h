@@ -1350,8 +1350,8 @@ typedef struct efx_timing {
     uint64_t ts_bytes; /* transport-stream bytes of the last upload */
     uint32_t groups;   /* reconstruction groups of the newest call: one k_recon launch per group and picture index; the
                           stage times above are sums over them */
-    uint16_t parse_halves; /* parse halves (k_index ... k_parse over a range of streams) of the newest call: they run side
-                              by side on the parse streams and feed the reconstruction groups */
+    uint16_t parse_halves; /* parse halves (k_index ... k_parse over a group's streams, on the parse streams) of the newest call:
+                              one per reconstruction group, so always equal to `groups` */
     uint16_t mixed;    /* 1: the averaged calls did not all run with the newest call's structure (a call that found the GPU
                           idle is split into groups, one queued behind another is not): per-launch figures derived from
                           the means are off */
@@ -1377,9 +1377,7 @@ typedef enum efx_option {
                                 slot (default 16); 0 = as many as there are (a grid of what the chip holds) */
     EFX_OPT_SBC_SERIAL = 7,  /* 1 = efx_sbc_decode runs every stream through the one-wave-per-stream kernel (the comparison the tests
                                 run the frame-parallel kernels against); 0 = default */
-    EFX_OPT_DEMUX_FUSED = 8, /* 1 = transport-stream uploads run the ONE-PASS demultiplexer (a ticket per chunk, decoupled look-back over
-                                chunk descriptors, one launch: k_demux_fused) instead of scan / prefix / gather.  Bit-exact and tested,
-                                but measured slower (82 against 63 us per 48.8 MB: profiles/r6_demux.md) -- 0 = default */
+    /* (8 selected a one-pass demultiplexer that was measured slower and was removed: EFX_ERR_ARG) */
     EFX_OPT_RECON_SPINS = 5  /* read only: polls the reconstruction waves of the most recent call spent waiting for a predecessor
                                 picture (synchronises) */
 } efx_option;

@@ -86,6 +86,15 @@ def test_decode_range_small_budgets_through_the_single_launch(efx, batch):
     dec.close()
 
 
+def test_removed_option_number_is_refused(efx):
+    """Option 8 selected the one-pass demultiplexer that was removed; its number is not reused and not accepted."""
+    dec = efx.Decoder(1, P, 2, max_stream_bytes=4096)
+    with pytest.raises(efx.EfxError) as e:
+        dec.set_option(8, 0)
+    assert e.value.status == -1  # EFX_ERR_ARG
+    dec.close()
+
+
 def test_staged_upload_never_writes_caller_memory(efx, batch):
     """Round-5 ADVICE (medium): efx_upload_streams used to choose the in-place path from the pointer pattern -- ONE stream
     lying in an arena always matched, and the library wrote its 9-byte tail and the zero fill behind it, i.e. over the first
