@@ -110,6 +110,12 @@ class _Surface(C.Structure):
                [("offset", C.c_size_t * 3), ("pitch", C.c_size_t * 3), ("bytes", C.c_size_t)]
 
 
+class _DeintOpts(C.Structure):
+    """efx_deint_opts: one efx_deinterlace call."""
+    _fields_ = [(n, C.c_int) for n in ("n_streams", "n_frames", "first_field", "mode", "lead", "tail")] + \
+               [("src_stride", C.c_size_t), ("dst_stride", C.c_size_t)]
+
+
 class _ImportColour(C.Structure):
     """efx_import_colour: the source's H.273 matrix_coefficients code and its range (1 = full)."""
     _fields_ = [("matrix", C.c_int), ("full_range", C.c_int)]
@@ -294,6 +300,8 @@ _SYMBOLS = {
     "efx_import_surfaces": (C.c_int, [_P, C.POINTER(_Surface), C.POINTER(_ImportOpts), _P, _P]),
     "efx_detect_crop_surfaces": (C.c_int, [_P, C.POINTER(_Surface), C.POINTER(_CropOpts), _P, _P, _P]),
     "efx_surface_layout": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.POINTER(_Surface)]),
+    "efx_deinterlace": (C.c_int, [_P, C.POINTER(_Surface), C.POINTER(_DeintOpts), _P, _P]),
+    "efx_deinterlace_count": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "efx_import_set_colour": (C.c_int, [_P, C.POINTER(_ImportColour)]),
     "efx_import_colour_coefs": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
     "efx_import_set_hdr": (C.c_int, [_P, C.POINTER(_ImportHdr)]),
@@ -727,6 +735,27 @@ def conform_count(fps_in, fps_out, first_picture: int, n_pictures: int) -> int:
     if f.numerator >= 1 << 31 or f.denominator >= 1 << 31:
         return -1
     return int(load_library().efx_conform_count(f.numerator, f.denominator, _fps_code(fps_out), first_picture, n_pictures))
+
+
+FIELD_TOP, FIELD_BOTTOM = 0, 1   # efx_deint_opts.first_field
+DEINT_FRAME, DEINT_FIELD = 0, 1  # efx_deint_opts.mode
+_FIRST_FIELDS = {"top": FIELD_TOP, "tff": FIELD_TOP, "bottom": FIELD_BOTTOM, "bff": FIELD_BOTTOM}
+_DEINT_RATES = {"frame": DEINT_FRAME, "field": DEINT_FIELD}
+
+
+def _deint_setting(first_field, rate):
+    if first_field not in _FIRST_FIELDS:
+        raise ValueError(f"unknown first_field {first_field!r}: 'top' (or 'tff') or 'bottom' (or 'bff')")
+    if rate not in _DEINT_RATES:
+        raise ValueError(f"unknown rate {rate!r}: 'field' (two pictures per frame) or 'frame' (one)")
+    return _FIRST_FIELDS[first_field], _DEINT_RATES[rate]
+
+
+def deinterlace_count(n_frames: int, *, rate: str = "field", lead: bool = False, tail: bool = False) -> int:
+    """Pictures per stream a deinterlace call makes of n_frames offered frames (efx_deinterlace_count; -1 for arguments
+    the call rejects): rate "field" two per frame, "frame" one; lead / tail: the first / last frame is context only."""
+    _, mode = _deint_setting("top", rate)
+    return int(load_library().efx_deinterlace_count(n_frames, 1 if lead else 0, 1 if tail else 0, mode))
 
 
 def sbc_state_bytes() -> int:
@@ -1228,6 +1257,62 @@ class Decoder:
             must_sync = flat is not src  # (torch may hand a staging copy's memory out again on its own stream)
         return flat.data_ptr(), False, must_sync
 
+    # -- interlaced sources (efx_deinterlace) -------------------------------------------------
+    def deinterlace_to(self, src: DeviceBuffer | int, dst: DeviceBuffer | int, *, surface: _Surface, n_streams: int = 1, n_frames: int,
+                       first_field: str = "top", rate: str = "field", lead: bool = False, tail: bool = False, src_stride: int = 0,
+                       dst_stride: int = 0) -> int:
+        """efx_deinterlace on raw device memory (DeviceBuffers or pointers), asynchronous on the library's stream: frame j of
+        stream i, read as `surface` (surface_layout(): I420, YV12, NV12, NV21, pitched or packed) describes it, at src +
+        (i * n_frames + j) * src_stride (0 = surface.bytes rounded up to 16); the progressive pictures, packed I420 of
+        the surface's size, at dst + (i * n_out + m) * dst_stride (0 = width * height * 3 / 2 rounded up to 16).
+        first_field "top" (tff) or "bottom" (bff); rate "field": both fields of a frame become pictures (576i25 gives 50
+        pictures a second), "frame": the first field only; lead / tail: the first / last offered frame is context only,
+        for a title that goes through in pieces with one frame of overlap.  The rule: include/efx.h, "interlaced
+        sources".  Returns n_out, the pictures per stream (deinterlace_count)."""
+        g = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
+        first, mode = _deint_setting(first_field, rate)
+        o = _DeintOpts(n_streams, n_frames, first, mode, 1 if lead else 0, 1 if tail else 0, src_stride, dst_stride)
+        _check(self._ctx, self._lib.efx_deinterlace(self._ctx, C.byref(surface), C.byref(o), g(src), g(dst)))
+        return int(self._lib.efx_deinterlace_count(n_frames, o.lead, o.tail, mode))
+
+    def deinterlace(self, src, *, fmt: str = "i420", width: int, height: int, pitch: int = 0, plane_rows: int = 0,
+                    first_field: str = "top", rate: str = "field", n_streams: int = 1, lead: bool = False, tail: bool = False):
+        """Interlaced frames as progressive pictures of the same size, made on the device (deinterlace_to).  src: a NumPy
+        array or a uint8 torch tensor on the decoder's device of shape (n_streams * n_frames, bytes), stream by stream,
+        bytes being surface_layout(fmt, width, height, pitch, plane_rows).bytes; fmt "i420", "yv12", "nv12" or "nv21",
+        width even, height a multiple of 4 from 8.  Returns (n_streams * n_out, width * height * 3 / 2) uint8 packed I420
+        pictures, n_out = deinterlace_count(n_frames, ...): what import_pictures(fmt="i420", width=, height=) and
+        detect_crop() take; a tensor for a tensor (no host round trip), an array for an array.  Synchronises: torch's
+        current stream before (tensor input), the library's after."""
+        surf, total, src = _surface_source(src, fmt, width, height, pitch, plane_rows)
+        if n_streams < 1 or total % n_streams:
+            raise ValueError(f"{total} source images do not make {n_streams} streams of equal length")
+        n_frames = total // n_streams
+        n_out = deinterlace_count(n_frames, rate=rate, lead=lead, tail=tail)
+        if n_out < 0:
+            raise ValueError(f"deinterlace: {n_frames} frames with lead={lead}, tail={tail} leave no frame with an output")
+        image = width * height * 3 // 2
+        stride, dstride = (surf.bytes + 15) // 16 * 16, (image + 15) // 16 * 16
+        bufs, keep = [], []
+        try:
+            src_ptr, is_array, _ = self._stage_pictures(src, total, surf.bytes, stride, bufs, keep)
+            kw = dict(surface=surf, n_streams=n_streams, n_frames=n_frames, first_field=first_field, rate=rate, lead=lead, tail=tail,
+                      src_stride=stride, dst_stride=dstride)
+            if is_array:
+                dbuf = DeviceBuffer(self, n_streams * n_out * dstride)
+                bufs.append(dbuf)
+                self.deinterlace_to(src_ptr, dbuf, **kw)
+                self.sync()
+                return np.ascontiguousarray(dbuf.download(np.uint8, n_streams * n_out * dstride).reshape(-1, dstride)[:, :image])
+            import torch
+            out = torch.empty((n_streams * n_out, dstride), dtype=torch.uint8, device=torch.device("cuda", self.device))
+            self.deinterlace_to(src_ptr, out.data_ptr(), **kw)
+            self.sync()
+            return out if dstride == image else out[:, :image].contiguous()
+        finally:
+            for b in bufs:
+                b.free()
+
     # -- black borders (efx_detect_crop) ----------------------------------------------------
     def detect_crop_to(self, src: DeviceBuffer | int, rects: DeviceBuffer | int, *, n_streams: int, images_per_stream: int,
                        fmt: str, width: int, height: int, limit: int = 24, round: int = 16, full_range: bool = False,
@@ -1384,7 +1469,8 @@ class Decoder:
     def import_pictures(self, src, *, fmt: str | None = None, width: int | None = None, height: int | None = None, crop=None,
                         fit: str = "stretch", full_range: bool = False, out=None, sync: bool = True, crop_limit: int = 24,
                         crop_round: int = 16, pitch: int = 0, plane_rows: int = 0, matrix=None, src_range: str | None = None,
-                        transfer=None, primaries=None, peak_nits: int | None = None):
+                        transfer=None, primaries=None, peak_nits: int | None = None, deinterlace: str | None = None,
+                        field_rate: bool = False):
         """Pictures of any size as (n, 101376) I420 pictures of 352 x 192, the layout encode() takes, cropped, scaled and
         converted on the device (efx_import_frames; the arithmetic: include/efx.h).  src: a NumPy array, or a uint8
         torch tensor on the decoder's device, of shape (n, H, W, 3) for "rgb24", (n, 3, H, W) for "rgbp", or
@@ -1414,6 +1500,11 @@ class Decoder:
         to the BT.601 SDR picture in the same kernel (hdr_tables(); include/efx.h, "HDR sources"); matrix= (default
         "bt2020") and src_range= then describe the HDR source.  Crop detection needs nothing: PQ studio black is the code
         of SDR studio black.  RGB sources take none of these (ValueError).
+        deinterlace="tff" or "bff" (YCbCr 8-bit sources: "i420", "yv12", "nv12", "nv21"; height a multiple of 4): the batch
+        is one stream of consecutive interlaced frames with that field first; it is deinterlaced on the device at the
+        source's size (deinterlace_to; include/efx.h, "interlaced sources") and the progressive pictures are imported
+        with the arguments given, crop="auto" detecting on them.  field_rate=True makes a picture of every field: 2 n
+        pictures come back, to be encoded at twice the frame rate (576i25: fps=50).  None, the default, changes nothing.
 
         Returns a tensor for tensor input and an array for array input.  out: a preallocated contiguous uint8 tensor
         of n * 101376 elements on this device, or a DeviceBuffer (then returned as is); with out given, array input
@@ -1441,12 +1532,30 @@ class Decoder:
             raise ValueError("matrix=, src_range= and transfer= describe a YCbCr source; an RGB source is converted with BT.601 (full_range=)")
         if src_range is not None:
             crop_limit = colour_source_limit(crop_limit, src_range)
+        if deinterlace is None and field_rate:
+            raise ValueError("field_rate=True needs deinterlace='tff' or 'bff'")
+        if deinterlace is not None:
+            if deinterlace not in ("tff", "bff"):
+                raise ValueError(f"unknown deinterlace {deinterlace!r}: 'tff', 'bff' or None")
+            if fmt != "i420" or (surface is not None and surface.layout not in (SURF_PLANAR8, SURF_SEMI8)):
+                raise ValueError("deinterlace= takes 8-bit YCbCr sources: 'i420', 'yv12', 'nv12' or 'nv21'")
+            if height % 4 or height < 8:
+                raise ValueError(f"an interlaced source's height must be a multiple of 4 from 8, got {height}")
         stride = (image + 15) // 16 * 16
-        nbytes = n * FRAME_BYTES
         bufs, keep = [], []
         try:
             src_ptr, is_array, must_sync = self._stage_pictures(src, n, image, stride, bufs, keep)
             sync = sync or must_sync
+            if deinterlace is not None:
+                # the progressive pictures, packed I420 at the source's size, in a buffer of this call: the import's source
+                dstride = (width * height * 3 // 2 + 15) // 16 * 16
+                rate = "field" if field_rate else "frame"
+                dbuf = DeviceBuffer(self, deinterlace_count(n, rate=rate) * dstride)
+                bufs.append(dbuf)
+                n = self.deinterlace_to(src_ptr, dbuf, surface=surface if surface is not None else surface_layout("i420", width, height),
+                                        n_frames=n, first_field=deinterlace, rate=rate, src_stride=stride, dst_stride=dstride)
+                src_ptr, stride, surface = dbuf.ptr, dstride, None
+            nbytes = n * FRAME_BYTES
             if isinstance(crop, str):
                 rec = self._detect_rects(src_ptr, 1, n, fmt, width, height, crop_limit, crop_round, full_range, stride, surface)
                 crop = tuple(int(v) for v in rec[0, :4])

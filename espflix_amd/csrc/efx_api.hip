@@ -25,6 +25,7 @@
 #include "hdr_px.h"
 #include "import_px.h"
 #include "crop_px.h"
+#include "deint_px.h"
 #include "surface_px.h"
 #include "quality_px.h"
 #include "parse_tm.h"
@@ -87,6 +88,7 @@ __global__ void k_quality_clamp(QualityArgs);
 template <int SOURCE>
 __global__ void k_trick(TrickArgs);  // (k_trick.hip: the I420 and the ring instance)
 __global__ void k_conform(ConformArgs);  // (k_conform.hip)
+__global__ void k_deint(DeintArgs);      // (k_deint.hip)
 __global__ void k_import_pcm(ImportPcmArgs);  // (k_import_pcm.hip)
 __global__ void k_import_pcm_state(ImportPcmArgs);
 __global__ void k_loud_steps(LoudStepsArgs);  // (k_loudness.hip)
@@ -2048,6 +2050,50 @@ int efx_import_surfaces(efx_ctx* ctx, const efx_surface* s, const efx_import_opt
         hipLaunchKernelGGL(k, dim3((unsigned)o->n_images * kImportBands), dim3(256), 0, ctx->stream, static_cast<const uint8_t*>(src_device),
                            dst_device, ctx->d_import_taps, a);
     }
+    EFX_HIP(hipGetLastError());
+    return EFX_OK;
+}
+
+// ---- interlaced sources (k_deint.hip) -----------------------------------------------------------------------------------------
+int efx_deinterlace_count(int n_frames, int lead, int tail, int mode) { return dpx::count(n_frames, lead, tail, mode); }
+
+int efx_deinterlace(efx_ctx* ctx, const efx_surface* s, const efx_deint_opts* o, const void* src_device, uint8_t* dst_device)
+{
+    bind_device(ctx);
+    if (!ctx || !s || !o)
+        return EFX_ERR_ARG;
+    if (const char* what = surface_fault(s, EFX_PIX_I420, s->width, s->height))
+        return fail(ctx, EFX_ERR_ARG, (std::string("efx_deinterlace: ") + what).c_str());
+    if (!dpx::surface_ok(*s))
+        return fail(ctx, EFX_ERR_ARG, "efx_deinterlace: the surface must be EFX_SURF_PLANAR8 or EFX_SURF_SEMI8, its height a multiple of 4 from 8");
+    if (!src_device || ((uintptr_t)src_device & 15) || !dst_device || ((uintptr_t)dst_device & 15))
+        return fail(ctx, EFX_ERR_ARG, "efx_deinterlace: src_device and dst_device must be 16-byte aligned device pointers");
+    if (o->first_field != EFX_FIELD_TOP && o->first_field != EFX_FIELD_BOTTOM)
+        return fail(ctx, EFX_ERR_ARG, "efx_deinterlace: unknown first_field");
+    const int n_out = dpx::count(o->n_frames, o->lead, o->tail, o->mode);
+    if (n_out < 0)
+        return fail(ctx, EFX_ERR_ARG, "efx_deinterlace: unknown mode, n_frames < 1, lead or tail not 0 / 1, or lead + tail >= n_frames");
+    if (o->n_streams < 1 || (int64_t)o->n_streams * o->n_frames > INT32_MAX || (int64_t)o->n_streams * n_out > INT32_MAX)
+        return fail(ctx, EFX_ERR_ARG, "efx_deinterlace: n_streams must be >= 1, the images in and the images out below 2^31");
+    DeintArgs a{};
+    a.src = static_cast<const uint8_t*>(src_device), a.dst = dst_device;
+    const size_t image = (size_t)s->width * s->height * 3 / 2;
+    a.src_stride = o->src_stride ? o->src_stride : (s->bytes + 15) / 16 * 16;
+    a.dst_stride = o->dst_stride ? o->dst_stride : (image + 15) / 16 * 16;
+    if (a.src_stride < s->bytes || (a.src_stride & 15))
+        return fail(ctx, EFX_ERR_ARG, "efx_deinterlace: src_stride must be a multiple of 16 and hold an image");
+    if (a.dst_stride < image || (a.dst_stride & 15))
+        return fail(ctx, EFX_ERR_ARG, "efx_deinterlace: dst_stride must be a multiple of 16 and hold an image");
+    a.s = *s;
+    a.n_streams = o->n_streams, a.n_frames = o->n_frames;
+    a.lead = o->lead, a.frames_out = o->n_frames - o->lead - o->tail;
+    a.per_frame = o->mode == EFX_DEINT_FIELD ? 2 : 1;
+    a.first_field = o->first_field;
+    a.frame_items = dpx::frame_items(s->width, s->height);
+    // one launch whatever the counts are (a workgroup takes further items when there are more than the grid's)
+    const size_t items = (size_t)a.n_streams * a.frames_out * a.frame_items;
+    const size_t wgs = (items + dpx::kWaves - 1) / dpx::kWaves;
+    hipLaunchKernelGGL(k_deint, dim3((unsigned)std::min(wgs, (size_t)1 << 20)), dim3(64 * dpx::kWaves), 0, ctx->stream, a);
     EFX_HIP(hipGetLastError());
     return EFX_OK;
 }

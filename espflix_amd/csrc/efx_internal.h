@@ -431,6 +431,19 @@ struct ConformArgs {
     int n_streams, n_out;
 };
 
+// k_deint (k_deint.hip) launch arguments (by value): efx_deint_opts, checked, and the surface, checked (deint_px.h)
+struct DeintArgs {
+    const uint8_t* src;  // stream i, frame j of the call at src + (i * n_frames + j) * src_stride
+    uint8_t* dst;        // stream i, output m at dst + (i * n_out + m) * dst_stride: packed I420, width x height
+    size_t src_stride, dst_stride;
+    efx_surface s;
+    int n_streams, n_frames;
+    int lead, frames_out;  // frames lead .. lead + frames_out - 1 of a stream have outputs
+    int per_frame;         // outputs per frame: 1 (frame rate) or 2 (field rate)
+    int first_field;
+    int frame_items;       // dpx::frame_items(width, height)
+};
+
 // k_sbc_enc launch arguments (by value): efx_sbc_encode_opts, checked, with the context's tables
 namespace sbcenc {
 struct Tables;

@@ -396,7 +396,8 @@ int efx_detect_crop(efx_ctx* ctx, const efx_crop_opts* opts, const void* src_dev
  *   multiple of 16 and at least `bytes`; full_range is ignored.
  *   Fields come free.  The top or bottom field of an interlaced surface is the same surface with every pitch doubled,
  *   height halved, and each offset advanced by one pitch for the bottom field (height must then be a multiple of 4).
- *   Field siting is out of scope.
+ *   That reads one field as a picture of its own; making progressive pictures of an interlaced source is
+ *   efx_deinterlace's work ("interlaced sources" below).  Field-sited chroma resampling is out of scope.
  *
  * Memory contract (an extension of efx_import_frames').  For image k the kernels read only bytes in [src + k *
  * src_stride, src + k * src_stride + bytes rounded up to 16), in 16-byte pieces aligned down inside that interval, and
@@ -436,6 +437,97 @@ typedef enum efx_surface_kind { EFX_KIND_I420, EFX_KIND_YV12, EFX_KIND_NV12, EFX
  * P x R + (P / 2)(R / 2); YV12 stores Cr first.  bytes = P x R x 3 / 2.  Returns bytes, 0 for arguments the calls would
  * reject (planar: P not a multiple of 2 B).  Host only. */
 size_t efx_surface_layout(int kind, int width, int height, size_t pitch, int plane_rows, efx_surface* out);
+
+/* -- interlaced sources: fields to progressive pictures (k_deint) --------------------------- */
+/* DVD material (480i / 576i) and broadcast or camcorder 1080i carry two fields per frame, taken at two moments.  Scaling
+ * the woven frame blends those moments into ghosts wherever something moves; importing one field throws half of the
+ * vertical detail of every still area away.  efx_deinterlace completes each field to a full picture at the source's
+ * size, before anything is scaled: the step the reference indexer leaves to ffmpeg's yadif.  The rule is yadif's
+ * spatial-temporal rule with its spatial interlacing check, stated here as this library's own, with its own edge rule:
+ * an integer function of the source bytes (espflix_amd/csrc/deint_px.h), bit-reproducible anywhere.  Byte compatibility
+ * with ffmpeg at picture edges is not promised.
+ *
+ * The rule is applied to each of the three planes of the canonical image of a surface ("surfaces" above), each with its
+ * own w, h (luma: width x height; Cb, Cr: half of each).
+ *
+ *   Setting.  A stream is a run of frames F[0 .. N-1].  first_field says which field of a frame is earlier in time:
+ *   EFX_FIELD_TOP (tff) or EFX_FIELD_BOTTOM (bff).  Output (t, i) is frame t's first (i = 0) or second (i = 1) field
+ *   completed to a full picture.  Its kept parity p is the parity of that field; the top field is the even lines, p = 0.
+ *   Lines y = p (mod 2) are copied from F[t] unchanged.  Lines y = 1 - p (mod 2) are made as below, from
+ *
+ *                                                   i = 0      i = 1
+ *     cur                                           F[t]       F[t]
+ *     prev                                          F[t-1]     F[t-1]
+ *     next                                          F[t+1]     F[t+1]
+ *     B  (the opposite-parity field just before)    F[t-1]     F[t]
+ *     A  (the opposite-parity field just after)     F[t]       F[t+1]
+ *
+ *   A neighbour that does not exist (t - 1 < 0, t + 1 >= N) is replaced by F[t] itself.
+ *   Index rule.  A row index r outside 0 .. h - 1 is replaced by r + 2 (r < 0) or r - 2 (r >= h); only -2 .. h + 1 occur.
+ *   A column index is clamped to 0 .. w - 1.
+ *   One missing sample at (x, y).  All values are int, >> is arithmetic.
+ *     c = cur[y-1][x]   e = cur[y+1][x]
+ *     d  = (B[y][x] + A[y][x]) >> 1
+ *     t0 = |B[y][x] - A[y][x]| >> 1
+ *     t1 = (|prev[y-1][x] - c| + |prev[y+1][x] - e|) >> 1
+ *     t2 = (|next[y-1][x] - c| + |next[y+1][x] - e|) >> 1
+ *     diff = max(t0, t1, t2)
+ *     score(j) = sum over k in {-1, 0, 1} of |cur[y-1][x+k+j] - cur[y+1][x+k-j]|
+ *     pred(j)  = (cur[y-1][x+j] + cur[y+1][x-j]) >> 1
+ *     best = score(0) - 1;  sp = pred(0)
+ *     for s in (-1, +1), in this order:
+ *         if score(s) < best:  best = score(s);  sp = pred(s)
+ *             if score(2s) < best:  best = score(2s);  sp = pred(2s)        (tried only when s improved)
+ *     b = (B[y-2][x] + A[y-2][x]) >> 1;  f = (B[y+2][x] + A[y+2][x]) >> 1
+ *     mx = max(d - e, d - c, min(b - c, f - e))
+ *     mn = min(d - e, d - c, max(b - c, f - e))
+ *     diff = max(diff, mn, -mx)
+ *     out = min(max(sp, d - diff), d + diff)                                (lies in 0 .. 255 by construction)
+ *
+ *   Layout.  Source image i * n_frames + j is stream i's frame j, at src_device + (i * n_frames + j) * src_stride.  Outputs
+ *   are packed I420 pictures of the surface's width x height, so efx_import_frames and efx_detect_crop read them as they
+ *   are; with n_out = efx_deinterlace_count(), output m of stream i lies at dst_device + (i * n_out + m) * dst_stride.
+ *   EFX_DEINT_FRAME writes output (t, 0) per frame (the source's frame rate), EFX_DEINT_FIELD (t, 0) then (t, 1) (its field
+ *   rate: 576i25 becomes 50 pictures a second, picture_rate code 6; 480i 59.94, code 7).
+ *   Pieces.  lead / tail = 1 make the first / last offered frame context only: it is read as a neighbour and has no
+ *   output.  A title goes through piece by piece with one frame of overlap -- the first piece with lead = 0, tail = 1,
+ *   middle pieces with 1, 1, the last with 1, 0 -- and the concatenated outputs equal those of one long call.  With
+ *   lead = 0 the first frame's missing prev is the frame itself (the title's start); tail = 0 does the same at the end.
+ *   Streams never see each other's frames.
+ *   Surfaces.  EFX_SURF_PLANAR8 (YV12 by swapped offsets) and EFX_SURF_SEMI8 (NV12 / NV21, de-interleaved on load); width
+ *   even, 2 .. 4096; height a multiple of 4, 8 .. 4096, so that chroma has whole field pairs.
+ *
+ * Memory contract.  For source image k the kernel reads only bytes in [src + k * src_stride, src + k * src_stride + bytes
+ * rounded up to 16), 16 bytes at a time wherever a plane's rows begin, and only rows of the three planes; bytes in pitch
+ * padding, between planes and between images are fetched at most as part of such an access and never influence a result.
+ * It writes only the width x height x 3 / 2 bytes of each output image.  All offsets are computed in 64 bits.  The source
+ * and destination regions must not overlap.
+ *
+ * Out of scope: the 16-bit layouts, 4:2:2, bwdif's longer filter, motion-compensated deinterlacing, inverse telecine,
+ * detecting whether a source is interlaced at all, per-frame parity flags, field-sited chroma resampling, efx_multi_*. */
+#define EFX_FIELD_TOP    0   /* the top field (even lines) is the earlier one: tff */
+#define EFX_FIELD_BOTTOM 1   /* bff */
+#define EFX_DEINT_FRAME  0   /* one output per frame: (t, 0) */
+#define EFX_DEINT_FIELD  1   /* two outputs per frame: (t, 0) then (t, 1) */
+typedef struct efx_deint_opts {
+    int n_streams;        /* >= 1 */
+    int n_frames;         /* frames per stream offered by this call, >= 1 */
+    int first_field;      /* EFX_FIELD_TOP / EFX_FIELD_BOTTOM */
+    int mode;             /* EFX_DEINT_FRAME / EFX_DEINT_FIELD */
+    int lead, tail;       /* 0 / 1: the first / last offered frame is context only (no output for it) */
+    size_t src_stride;    /* bytes between source images; 0 = the surface's bytes rounded up to 16; multiple of 16 */
+    size_t dst_stride;    /* bytes between output images; 0 = efx_import_src_bytes(I420, w, h) rounded up to 16; multiple of 16 */
+} efx_deint_opts;
+/* Asynchronous on the context's stream: no host synchronisation, one launch whatever the counts are, and no decoder,
+ * encoder, SBC, import or other state is touched.
+ * EFX_ERR_ARG: everything efx_import_surfaces rejects about a surface, a 16-bit layout, a height that is not a multiple
+ * of 4 or below 8, n_streams < 1, lead or tail other than 0 / 1, lead + tail >= n_frames, an unknown mode or first_field,
+ * more than 2^31 - 1 images in or out, a NULL or misaligned (16 bytes) pointer, a stride that is too small or not a
+ * multiple of 16.  A refused call writes nothing. */
+int efx_deinterlace(efx_ctx* ctx, const efx_surface* surface, const efx_deint_opts* opts, const void* src_device,
+                    uint8_t* dst_device);
+/* outputs per stream of such a call; -1 for arguments it rejects.  Host only. */
+int efx_deinterlace_count(int n_frames, int lead, int tail, int mode);
 
 /* -- source colour: BT.709, full-range and other YCbCr sources to BT.601 (k_import) -------- */
 /* MPEG-1 carries BT.601 studio-swing YCbCr, and efx_import_frames / efx_import_surfaces copy a YCbCr source's samples
