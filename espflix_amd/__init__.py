@@ -116,6 +116,12 @@ class _DeintOpts(C.Structure):
                [("src_stride", C.c_size_t), ("dst_stride", C.c_size_t)]
 
 
+class _DetelecineOpts(C.Structure):
+    """efx_detelecine_opts: one efx_detelecine call."""
+    _fields_ = [(n, C.c_int) for n in ("n_streams", "n_frames", "first_field", "lead", "nt")] + \
+               [("src_stride", C.c_size_t), ("dst_stride", C.c_size_t)]
+
+
 class _ImportColour(C.Structure):
     """efx_import_colour: the source's H.273 matrix_coefficients code and its range (1 = full)."""
     _fields_ = [("matrix", C.c_int), ("full_range", C.c_int)]
@@ -302,6 +308,8 @@ _SYMBOLS = {
     "efx_surface_layout": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.POINTER(_Surface)]),
     "efx_deinterlace": (C.c_int, [_P, C.POINTER(_Surface), C.POINTER(_DeintOpts), _P, _P]),
     "efx_deinterlace_count": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "efx_detelecine": (C.c_int, [_P, C.POINTER(_Surface), C.POINTER(_DetelecineOpts), _P, _P, _P]),
+    "efx_detelecine_count": (C.c_int, [C.c_int, C.c_int]),
     "efx_import_set_colour": (C.c_int, [_P, C.POINTER(_ImportColour)]),
     "efx_import_colour_coefs": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
     "efx_import_set_hdr": (C.c_int, [_P, C.POINTER(_ImportHdr)]),
@@ -756,6 +764,16 @@ def deinterlace_count(n_frames: int, *, rate: str = "field", lead: bool = False,
     the call rejects): rate "field" two per frame, "frame" one; lead / tail: the first / last frame is context only."""
     _, mode = _deint_setting("top", rate)
     return int(load_library().efx_deinterlace_count(n_frames, 1 if lead else 0, 1 if tail else 0, mode))
+
+
+# efx_telecine_info: the record efx_detelecine writes per processed frame
+TELECINE_INFO = np.dtype([("comb_c", "<u8"), ("comb_p", "<u8"), ("diff", "<u8"), ("match", "<i4"), ("out", "<i4")])
+
+
+def detelecine_count(n_frames: int, *, lead: bool = False) -> int:
+    """Film frames per stream a detelecine call makes of n_frames offered frames (efx_detelecine_count; -1 for arguments
+    the call rejects): of the n = n_frames - lead processed frames one in every whole cycle of five is dropped."""
+    return int(load_library().efx_detelecine_count(n_frames, 1 if lead else 0))
 
 
 def sbc_state_bytes() -> int:
@@ -1309,6 +1327,72 @@ class Decoder:
             self.deinterlace_to(src_ptr, out.data_ptr(), **kw)
             self.sync()
             return out if dstride == image else out[:, :image].contiguous()
+        finally:
+            for b in bufs:
+                b.free()
+
+    # -- telecined sources (efx_detelecine) ---------------------------------------------------
+    def detelecine_to(self, src: DeviceBuffer | int, dst: DeviceBuffer | int, info: DeviceBuffer | int, *, surface: _Surface,
+                      n_streams: int = 1, n_frames: int, first_field: str = "top", lead: bool = False, nt: int = 10, src_stride: int = 0,
+                      dst_stride: int = 0) -> int:
+        """efx_detelecine on raw device memory (DeviceBuffers or pointers), asynchronous on the library's stream: frame j of
+        stream i, read as `surface` (surface_layout(): I420, YV12, NV12, NV21, pitched or packed) describes it, at src +
+        (i * n_frames + j) * src_stride (0 = surface.bytes rounded up to 16); the film frames, packed I420 of the
+        surface's size, at dst + (i * n_out + m) * dst_stride (0 = width * height * 3 / 2 rounded up to 16); one 32-byte
+        record (TELECINE_INFO) per processed frame at info + (i * n + j) * 32, n = n_frames - lead, whatever info held
+        before.  first_field "top" (tff) or "bottom" (bff); lead: the first offered frame is context only, for a title
+        that goes through in pieces with one frame of overlap (every piece but the last processes a multiple of 5
+        frames); nt: the noise threshold of the comb score in pels.  The rule: include/efx.h, "telecined sources".
+        Returns n_out, the film frames per stream (detelecine_count)."""
+        g = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
+        if first_field not in _FIRST_FIELDS:
+            raise ValueError(f"unknown first_field {first_field!r}: 'top' (or 'tff') or 'bottom' (or 'bff')")
+        o = _DetelecineOpts(n_streams, n_frames, _FIRST_FIELDS[first_field], 1 if lead else 0, nt, src_stride, dst_stride)
+        _check(self._ctx, self._lib.efx_detelecine(self._ctx, C.byref(surface), C.byref(o), g(src), g(dst), g(info)))
+        return int(self._lib.efx_detelecine_count(n_frames, o.lead))
+
+    def detelecine(self, src, *, fmt: str = "i420", width: int, height: int, pitch: int = 0, plane_rows: int = 0,
+                   first_field: str = "top", n_streams: int = 1, lead: bool = False, nt: int = 10, info: bool = False):
+        """Telecined frames (3:2 pulldown) as the film's frames, of the same size, made on the device (detelecine_to).  src:
+        a NumPy array or a uint8 torch tensor on the decoder's device of shape (n_streams * n_frames, bytes), stream by
+        stream, bytes being surface_layout(fmt, width, height, pitch, plane_rows).bytes; fmt "i420", "yv12", "nv12" or
+        "nv21", width even, height a multiple of 4 from 8.  Returns (n_streams * n_out, width * height * 3 / 2) uint8
+        packed I420 pictures, n_out = detelecine_count(n_frames, lead=lead): what import_pictures(fmt="i420", width=,
+        height=) and detect_crop() take, to be encoded at fps=23.976; a tensor for a tensor (no host round trip), an
+        array for an array.  With info=True it returns (pictures, records): the records a structured NumPy array
+        (TELECINE_INFO) of shape (n_streams, n_frames - lead).  Synchronises: torch's current stream before (tensor
+        input), the library's after."""
+        surf, total, src = _surface_source(src, fmt, width, height, pitch, plane_rows)
+        if n_streams < 1 or total % n_streams:
+            raise ValueError(f"{total} source images do not make {n_streams} streams of equal length")
+        n_frames = total // n_streams
+        n_out = detelecine_count(n_frames, lead=lead)
+        if n_out < 0:
+            raise ValueError(f"detelecine: {n_frames} frames with lead={lead} leave no frame to process")
+        n = n_frames - (1 if lead else 0)
+        image = width * height * 3 // 2
+        stride, dstride = (surf.bytes + 15) // 16 * 16, (image + 15) // 16 * 16
+        bufs, keep = [], []
+        try:
+            src_ptr, is_array, _ = self._stage_pictures(src, total, surf.bytes, stride, bufs, keep)
+            ibuf = DeviceBuffer(self, n_streams * n * TELECINE_INFO.itemsize)
+            bufs.append(ibuf)
+            kw = dict(surface=surf, n_streams=n_streams, n_frames=n_frames, first_field=first_field, lead=lead, nt=nt, src_stride=stride,
+                      dst_stride=dstride)
+            records = lambda: ibuf.download(TELECINE_INFO, n_streams * n).reshape(n_streams, n)
+            if is_array:
+                dbuf = DeviceBuffer(self, n_streams * n_out * dstride)
+                bufs.append(dbuf)
+                self.detelecine_to(src_ptr, dbuf, ibuf, **kw)
+                self.sync()
+                out = np.ascontiguousarray(dbuf.download(np.uint8, n_streams * n_out * dstride).reshape(-1, dstride)[:, :image])
+                return (out, records()) if info else out
+            import torch
+            out = torch.empty((n_streams * n_out, dstride), dtype=torch.uint8, device=torch.device("cuda", self.device))
+            self.detelecine_to(src_ptr, out.data_ptr(), ibuf, **kw)
+            self.sync()
+            out = out if dstride == image else out[:, :image].contiguous()
+            return (out, records()) if info else out
         finally:
             for b in bufs:
                 b.free()

@@ -26,6 +26,7 @@
 #include "import_px.h"
 #include "crop_px.h"
 #include "deint_px.h"
+#include "telecine_px.h"
 #include "surface_px.h"
 #include "quality_px.h"
 #include "parse_tm.h"
@@ -89,6 +90,9 @@ template <int SOURCE>
 __global__ void k_trick(TrickArgs);  // (k_trick.hip: the I420 and the ring instance)
 __global__ void k_conform(ConformArgs);  // (k_conform.hip)
 __global__ void k_deint(DeintArgs);      // (k_deint.hip)
+__global__ void k_telecine_measure(TelecineArgs);  // (k_telecine.hip)
+__global__ void k_telecine_decide(TelecineArgs);
+__global__ void k_telecine_weave(TelecineArgs);
 __global__ void k_import_pcm(ImportPcmArgs);  // (k_import_pcm.hip)
 __global__ void k_import_pcm_state(ImportPcmArgs);
 __global__ void k_loud_steps(LoudStepsArgs);  // (k_loudness.hip)
@@ -2094,6 +2098,56 @@ int efx_deinterlace(efx_ctx* ctx, const efx_surface* s, const efx_deint_opts* o,
     const size_t items = (size_t)a.n_streams * a.frames_out * a.frame_items;
     const size_t wgs = (items + dpx::kWaves - 1) / dpx::kWaves;
     hipLaunchKernelGGL(k_deint, dim3((unsigned)std::min(wgs, (size_t)1 << 20)), dim3(64 * dpx::kWaves), 0, ctx->stream, a);
+    EFX_HIP(hipGetLastError());
+    return EFX_OK;
+}
+
+// ---- telecined sources (k_telecine.hip) ---------------------------------------------------------------------------------------
+int efx_detelecine_count(int n_frames, int lead) { return tpx::count(n_frames, lead); }
+
+int efx_detelecine(efx_ctx* ctx, const efx_surface* s, const efx_detelecine_opts* o, const void* src_device, uint8_t* dst_device,
+                   efx_telecine_info* info_device)
+{
+    bind_device(ctx);
+    if (!ctx || !s || !o)
+        return EFX_ERR_ARG;
+    if (const char* what = surface_fault(s, EFX_PIX_I420, s->width, s->height))
+        return fail(ctx, EFX_ERR_ARG, (std::string("efx_detelecine: ") + what).c_str());
+    if (!dpx::surface_ok(*s))
+        return fail(ctx, EFX_ERR_ARG, "efx_detelecine: the surface must be EFX_SURF_PLANAR8 or EFX_SURF_SEMI8, its height a multiple of 4 from 8");
+    if (!src_device || ((uintptr_t)src_device & 15) || !dst_device || ((uintptr_t)dst_device & 15) || !info_device || ((uintptr_t)info_device & 15))
+        return fail(ctx, EFX_ERR_ARG, "efx_detelecine: src_device, dst_device and info_device must be 16-byte aligned device pointers");
+    if (o->first_field != EFX_FIELD_TOP && o->first_field != EFX_FIELD_BOTTOM)
+        return fail(ctx, EFX_ERR_ARG, "efx_detelecine: unknown first_field");
+    if (o->nt < 0 || o->nt > 255)
+        return fail(ctx, EFX_ERR_ARG, "efx_detelecine: nt must be 0 .. 255");
+    const int n = tpx::processed(o->n_frames, o->lead);
+    if (n < 0)
+        return fail(ctx, EFX_ERR_ARG, "efx_detelecine: n_frames < 1, lead not 0 / 1, or lead >= n_frames");
+    if (o->n_streams < 1 || (int64_t)o->n_streams * o->n_frames > INT32_MAX)
+        return fail(ctx, EFX_ERR_ARG, "efx_detelecine: n_streams must be >= 1, the images in below 2^31");
+    TelecineArgs a{};
+    a.src = static_cast<const uint8_t*>(src_device), a.dst = dst_device, a.info = info_device;
+    const size_t image = (size_t)s->width * s->height * 3 / 2;
+    a.src_stride = o->src_stride ? o->src_stride : (s->bytes + 15) / 16 * 16;
+    a.dst_stride = o->dst_stride ? o->dst_stride : (image + 15) / 16 * 16;
+    if (a.src_stride < s->bytes || (a.src_stride & 15))
+        return fail(ctx, EFX_ERR_ARG, "efx_detelecine: src_stride must be a multiple of 16 and hold an image");
+    if (a.dst_stride < image || (a.dst_stride & 15))
+        return fail(ctx, EFX_ERR_ARG, "efx_detelecine: dst_stride must be a multiple of 16 and hold an image");
+    a.s = *s;
+    a.n_streams = o->n_streams, a.n_frames = o->n_frames;
+    a.lead = o->lead, a.n = n, a.n_out = tpx::count(o->n_frames, o->lead);
+    a.first_field = o->first_field, a.nt = o->nt;
+    a.measure_items = tpx::measure_items(s->width, s->height), a.weave_items = tpx::weave_items(*s);
+    // three launches whatever the counts are (a workgroup takes further frames, cycles or items when there are more than
+    // the grid's); the records carry everything from one to the next
+    const size_t frames = (size_t)a.n_streams * a.n, cap = (size_t)1 << 20;
+    hipLaunchKernelGGL(k_telecine_measure, dim3((unsigned)std::min(frames, cap)), dim3(64 * tpx::kMeasureWaves), 0, ctx->stream, a);
+    const size_t cycles = (size_t)a.n_streams * ((a.n + tpx::kCycle - 1) / tpx::kCycle);
+    hipLaunchKernelGGL(k_telecine_decide, dim3((unsigned)std::min((cycles + 255) / 256, cap)), dim3(256), 0, ctx->stream, a);
+    const size_t wgs = (frames * a.weave_items + tpx::kWeaveWaves - 1) / tpx::kWeaveWaves;
+    hipLaunchKernelGGL(k_telecine_weave, dim3((unsigned)std::min(wgs, cap)), dim3(64 * tpx::kWeaveWaves), 0, ctx->stream, a);
     EFX_HIP(hipGetLastError());
     return EFX_OK;
 }

@@ -444,6 +444,19 @@ struct DeintArgs {
     int frame_items;       // dpx::frame_items(width, height)
 };
 
+// k_telecine_* (k_telecine.hip) launch arguments (by value): efx_detelecine_opts, checked, and the surface, checked
+struct TelecineArgs {
+    const uint8_t* src;       // stream i, frame j of the call at src + (i * n_frames + j) * src_stride
+    uint8_t* dst;             // stream i, output m at dst + (i * n_out + m) * dst_stride: packed I420, width x height
+    efx_telecine_info* info;  // stream i, processed frame j at info + i * n + j
+    size_t src_stride, dst_stride;
+    efx_surface s;
+    int n_streams, n_frames;
+    int lead, n, n_out;       // frames lead .. lead + n - 1 of a stream are processed and give n_out outputs
+    int first_field, nt;
+    int measure_items, weave_items;  // tpx::measure_items(width, height), tpx::weave_items(surface)
+};
+
 // k_sbc_enc launch arguments (by value): efx_sbc_encode_opts, checked, with the context's tables
 namespace sbcenc {
 struct Tables;

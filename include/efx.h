@@ -503,8 +503,9 @@ size_t efx_surface_layout(int kind, int width, int height, size_t pitch, int pla
  * It writes only the width x height x 3 / 2 bytes of each output image.  All offsets are computed in 64 bits.  The source
  * and destination regions must not overlap.
  *
- * Out of scope: the 16-bit layouts, 4:2:2, bwdif's longer filter, motion-compensated deinterlacing, inverse telecine,
- * detecting whether a source is interlaced at all, per-frame parity flags, field-sited chroma resampling, efx_multi_*. */
+ * Out of scope: the 16-bit layouts, 4:2:2, bwdif's longer filter, motion-compensated deinterlacing, inverse telecine
+ * (efx_detelecine: "telecined sources" below), detecting whether a source is interlaced at all, per-frame parity flags,
+ * field-sited chroma resampling, efx_multi_*. */
 #define EFX_FIELD_TOP    0   /* the top field (even lines) is the earlier one: tff */
 #define EFX_FIELD_BOTTOM 1   /* bff */
 #define EFX_DEINT_FRAME  0   /* one output per frame: (t, 0) */
@@ -528,6 +529,91 @@ int efx_deinterlace(efx_ctx* ctx, const efx_surface* surface, const efx_deint_op
                     uint8_t* dst_device);
 /* outputs per stream of such a call; -1 for arguments it rejects.  Host only. */
 int efx_deinterlace_count(int n_frames, int lead, int tail, int mode);
+
+/* -- telecined sources: fields back to film frames (k_telecine) ----------------------------- */
+/* Most NTSC DVD film material is hard-telecined: four film frames are spread over ten fields (3:2 pulldown), so two of
+ * every five video frames weave fields of two different film frames.  efx_deinterlace is the wrong tool for such a
+ * title: it interpolates lines whose true partner field sits one field slot away, leaves one repeated picture in every
+ * five, and hands the encoder 29.97 pictures a second where the film has 23.976.  efx_detelecine finds each field's
+ * partner, weaves the film frames back together and drops the repeated one: the step the reference indexer leaves to
+ * ffmpeg's fieldmatch,decimate.  MPEG-1 codes 23.976 Hz as picture_rate code 1 (efx_encode_set_picture_rate).  The rule
+ * is this library's own exact integer rule (espflix_amd/csrc/telecine_px.h), bit-reproducible anywhere.  Byte
+ * compatibility with ffmpeg is not promised.
+ *
+ *   Setting.  A stream is a run of frames F[0 .. N-1] of a surface ("surfaces" above).  first_field is EFX_FIELD_TOP or
+ *   EFX_FIELD_BOTTOM, with parity p = 0 or 1.  E[t] is the lines y = p (mod 2) of F[t], the earlier field; L[t] is the
+ *   other lines.  weave(E[t], L[x]) is the frame with E[t]'s lines and L[x]'s lines, for each of the three planes of the
+ *   canonical image; chroma lines split by their own parity, as in efx_deinterlace.  A film frame occupies two or three
+ *   consecutive field slots, so the partner of E[t] is L[t] or L[t-1], never anything further away: a two-way match is
+ *   complete for 3:2 and 2:2 cadences.
+ *   Comb score of a woven luma plane W of width w and height h.  With nt the noise threshold in pels, 0 .. 255:
+ *     v(x, y) = | W[y-2][x] + 4 W[y][x] + W[y+2][x] - 3 (W[y-1][x] + W[y+1][x]) |      for 2 <= y <= h - 3 and all x
+ *     score   = sum of max(0, v - 6 nt), as uint64
+ *   v is 6 x the comb amplitude on a flat area and at most 1530.  Rows 0, 1, h - 2 and h - 1 have no v: no edge rule.
+ *   Per frame t.
+ *     cc = score(F[t])                              (the luma plane)
+ *     cp = score(weave(E[t], L[t-1]))
+ *     D  = sum of |E[t] - E[t-1]| over the luma lines of parity p, all columns
+ *     match = p iff 4 cp < 3 cc, else c
+ *   A frame with no predecessor (t = 0 and no lead) has match c, cp = 0 and D = 2^64 - 1.
+ *   Decimation.  The processed frames of a call are taken in cycles of 5 from the first processed frame on.  In every
+ *   whole cycle the frame with the smallest D is dropped; a tie drops the lowest t.  A last partial cycle drops nothing.
+ *   Every kept frame t gives one output, weave(E[t], L[t - match]) (match c: F[t] itself), in order.
+ *   n_out = n - floor(n / 5) with n = n_frames - lead: efx_detelecine_count().
+ *   Pieces.  lead = 1 makes the first offered frame context only: it supplies E[t-1] and L[t-1] and has no output and no
+ *   record.  No tail is needed.  A title goes through piece by piece with one frame of overlap; every piece but the last
+ *   must process a multiple of 5 frames; the concatenated outputs and records then equal those of one long call (a
+ *   piece's `out` counts from 0: add the outputs of the pieces before it).  Streams never see each other's frames.
+ *   Layout.  Source image i * n_frames + j is stream i's frame j, at src_device + (i * n_frames + j) * src_stride.  Outputs
+ *   are packed I420 pictures of the surface's width x height, which efx_import_frames and efx_detect_crop take as they
+ *   are; output m of stream i lies at dst_device + (i * n_out + m) * dst_stride.
+ *   Report.  One efx_telecine_info per processed frame, stream i's processed frame j (frame lead + j) at info_device +
+ *   (i * n + j): its cc, cp and D, its match, and its output index within the stream's call or -1 where it was dropped.
+ *   The buffer also serves as the kernels' only scratch -- the context allocates nothing -- and its content before the
+ *   call does not matter.  From it a caller reads whether a title is film at all (no frame ever matches p, no D stands
+ *   out in its cycle) and which kept frames stayed combed (video inserts); acting on that is the caller's business.
+ *   Surfaces.  EFX_SURF_PLANAR8 (YV12 by swapped offsets) and EFX_SURF_SEMI8 (NV12 / NV21, de-interleaved on load); width
+ *   even, 2 .. 4096; height a multiple of 4, 8 .. 4096.
+ *
+ * Memory contract.  For source image k the kernels read only bytes in [src + k * src_stride, src + k * src_stride + bytes
+ * rounded up to 16), 16 bytes at a time wherever a plane's rows begin, and only rows of the three planes: the measuring
+ * launch the luma rows of every processed frame and of its predecessor, the weaving launch exactly the rows it writes (a
+ * dropped frame's only where the next frame matched p).  Bytes in pitch padding, between planes and between images are
+ * fetched at most as part of such an access and never influence a result.  The kernels write only the width x height x
+ * 3 / 2 bytes of each output image and the n_streams x n records.  All offsets are computed in 64 bits.  The source,
+ * destination and record regions must not overlap.
+ *
+ * Out of scope: a third (next-frame) match candidate; post-deinterlacing of frames that stay combed; deciding whether a
+ * title is telecined; cadences other than cycles of 5 (PAL speed-up needs none; 2:2 phase-shifted material is matched, but
+ * nothing of it should be decimated: such a caller uses the records' match only); the 16-bit layouts; chaining into
+ * efx_import_surfaces; efx_multi_*. */
+typedef struct efx_telecine_info {
+    uint64_t comb_c;      /* cc */
+    uint64_t comb_p;      /* cp */
+    uint64_t diff;        /* D */
+    int32_t match;        /* 0 = c, 1 = p */
+    int32_t out;          /* the output index within the stream's call; -1 = dropped */
+} efx_telecine_info;
+typedef struct efx_detelecine_opts {
+    int n_streams;        /* >= 1 */
+    int n_frames;         /* frames per stream offered by this call, >= 1 */
+    int first_field;      /* EFX_FIELD_TOP / EFX_FIELD_BOTTOM */
+    int lead;             /* 0 / 1: the first offered frame is context only */
+    int nt;               /* the noise threshold in pels, 0 .. 255; 10 suits DVD material */
+    size_t src_stride;    /* bytes between source images; 0 = the surface's bytes rounded up to 16; multiple of 16 */
+    size_t dst_stride;    /* bytes between output images; 0 = efx_import_src_bytes(I420, w, h) rounded up to 16; multiple of 16 */
+} efx_detelecine_opts;
+/* Asynchronous on the context's stream: no host synchronisation and no read-back (n_out is known on the host), three
+ * launches whatever the counts are -- measure, decide, weave -- and no decoder, encoder, SBC, import or other state is
+ * touched.
+ * EFX_ERR_ARG: everything efx_deinterlace rejects about a surface, n_streams < 1, lead other than 0 / 1, lead >=
+ * n_frames, an unknown first_field, nt outside 0 .. 255, more than 2^31 - 1 images in, a NULL or misaligned (16 bytes)
+ * src_device, dst_device or info_device, a stride that is too small or not a multiple of 16.  A refused call writes
+ * nothing. */
+int efx_detelecine(efx_ctx* ctx, const efx_surface* surface, const efx_detelecine_opts* opts, const void* src_device,
+                   uint8_t* dst_device, efx_telecine_info* info_device);
+/* outputs per stream of such a call; -1 for arguments it rejects.  Host only. */
+int efx_detelecine_count(int n_frames, int lead);
 
 /* -- source colour: BT.709, full-range and other YCbCr sources to BT.601 (k_import) -------- */
 /* MPEG-1 carries BT.601 studio-swing YCbCr, and efx_import_frames / efx_import_surfaces copy a YCbCr source's samples
