@@ -16,6 +16,13 @@ from fractions import Fraction
 
 import numpy as np
 
+# the C-ABI's structs, record dtypes and signatures live in _abi.py; they are part of this module's surface
+from ._abi import (ENC_PICTURE_INFO_DTYPE, LOUDNESS_REC_DTYPE, LOUDNESS_STEP_DTYPE, TELECINE_INFO, _P, _SYMBOLS,  # noqa: F401
+                   _AdaptiveQuant, _CompareOpts, _CompareRec, _Config, _ConformOpts, _CropOpts, _DeintOpts, _DetelecineOpts,
+                   _EncodeOpts, _EncodeRate, _EncPictureInfo, _ExportOpts, _FieldOpts, _IdxRec, _ImportColour, _ImportHdr,
+                   _ImportOpts, _ImportPcmOpts, _LoudnessGateOpts, _LoudnessStepsOpts, _MuxOpts, _PcmGainOpts, _SbcEncodeOpts,
+                   _SceneCut, _Surface, _Timing, _TrickOpts, _VideoParams)
+
 FRAME_WIDTH = 352
 FRAME_HEIGHT = 192
 FRAME_STRIDE = 528
@@ -65,155 +72,6 @@ class EfxError(RuntimeError):
         self.status = status
 
 
-class _Config(C.Structure):
-    _fields_ = [
-        ("device", C.c_int),
-        ("max_streams", C.c_int),
-        ("max_pictures", C.c_int),
-        ("ring_depth", C.c_int),
-        ("max_stream_bytes", C.c_size_t),
-        ("hip_stream", C.c_void_p),
-    ]
-
-
-class _VideoParams(C.Structure):
-    _fields_ = [(n, C.c_int) for n in ("line_width", "line_count", "hsync", "hsync_long", "hsync_short",
-                                       "burst_start", "burst_width", "active_start")]
-
-
-class _FieldOpts(C.Structure):
-    _fields_ = [("first_stream", C.c_int), ("n_streams", C.c_int), ("slot", C.c_int), ("other_slot", C.c_int),
-                ("ntsc", C.c_int), ("frame_counter", C.c_int), ("hscroll", C.c_int), ("overlay", C.c_void_p),
-                ("overlay_stride", C.c_size_t), ("overlay_blend", C.c_int), ("overlay_progress", C.c_int)]
-
-
-class _ExportOpts(C.Structure):
-    _fields_ = [("first_stream", C.c_int), ("n_streams", C.c_int), ("slot", C.c_int), ("picture", C.c_int), ("format", C.c_int),
-                ("chroma", C.c_int), ("full_range", C.c_int), ("dst_stride", C.c_size_t)]
-
-
-class _ImportOpts(C.Structure):
-    _fields_ = [(n, C.c_int) for n in ("n_images", "format", "width", "height", "crop_x", "crop_y", "crop_w", "crop_h",
-                                       "dst_x", "dst_y", "dst_w", "dst_h", "full_range")] + \
-               [("src_stride", C.c_size_t), ("dst_stride", C.c_size_t)]
-
-
-class _CropOpts(C.Structure):
-    _fields_ = [(n, C.c_int) for n in ("n_streams", "images_per_stream", "format", "width", "height", "full_range", "limit",
-                                       "round")] + \
-               [("src_stride", C.c_size_t), ("sums_stride", C.c_size_t)]
-
-
-class _Surface(C.Structure):
-    """efx_surface: one 4:2:0 YCbCr image in device memory by plane offsets and pitches (surface_layout() makes one)."""
-    _fields_ = [(n, C.c_int) for n in ("layout", "shift", "swap_uv", "width", "height")] + \
-               [("offset", C.c_size_t * 3), ("pitch", C.c_size_t * 3), ("bytes", C.c_size_t)]
-
-
-class _DeintOpts(C.Structure):
-    """efx_deint_opts: one efx_deinterlace call."""
-    _fields_ = [(n, C.c_int) for n in ("n_streams", "n_frames", "first_field", "mode", "lead", "tail")] + \
-               [("src_stride", C.c_size_t), ("dst_stride", C.c_size_t)]
-
-
-class _DetelecineOpts(C.Structure):
-    """efx_detelecine_opts: one efx_detelecine call."""
-    _fields_ = [(n, C.c_int) for n in ("n_streams", "n_frames", "first_field", "lead", "nt")] + \
-               [("src_stride", C.c_size_t), ("dst_stride", C.c_size_t)]
-
-
-class _ImportColour(C.Structure):
-    """efx_import_colour: the source's H.273 matrix_coefficients code and its range (1 = full)."""
-    _fields_ = [("matrix", C.c_int), ("full_range", C.c_int)]
-
-
-class _ImportHdr(C.Structure):
-    """efx_import_hdr: the source's H.273 transfer, primaries and matrix codes, its range (1 = full) and its peak in nits."""
-    _fields_ = [(n, C.c_int) for n in ("transfer", "primaries", "matrix", "full_range", "peak_nits")]
-
-
-class _CompareOpts(C.Structure):
-    _fields_ = [("n_images", C.c_int), ("ref_max", C.c_int), ("ref_stride", C.c_size_t), ("test_stride", C.c_size_t),
-                ("mb_stride", C.c_size_t)]
-
-
-class _CompareRec(C.Structure):
-    _fields_ = [("sse", C.c_uint64 * 3), ("ssim", C.c_int64 * 3)]
-
-
-class _TrickOpts(C.Structure):
-    _fields_ = [("n_streams", C.c_int), ("n_pictures", C.c_int), ("speed", C.c_int), ("source", C.c_int), ("first_stream", C.c_int),
-                ("first_picture", C.c_int64), ("total_pictures", C.c_int64), ("src_stride", C.c_size_t),
-                ("fwd_stride", C.c_size_t), ("rwd_stride", C.c_size_t)]
-
-
-class _ConformOpts(C.Structure):
-    _fields_ = [("n_streams", C.c_int), ("n_pictures", C.c_int), ("in_num", C.c_int32), ("in_den", C.c_int32), ("out_code", C.c_int),
-                ("first_picture", C.c_int64), ("src_stride", C.c_size_t), ("dst_stride", C.c_size_t)]
-
-
-class _EncodeOpts(C.Structure):
-    _fields_ = [("n_streams", C.c_int), ("n_pictures", C.c_int), ("format", C.c_int), ("qscale", C.c_int), ("gop", C.c_int),
-                ("search", C.c_int), ("cont", C.c_int), ("first_pts", C.c_int64), ("src_stride", C.c_size_t),
-                ("dst_stride", C.c_size_t)]
-
-
-class _EncodeRate(C.Structure):
-    _fields_ = [("bitrate", C.c_int), ("vbv_bits", C.c_int), ("qmin", C.c_int), ("qmax", C.c_int)]
-
-
-class _SceneCut(C.Structure):
-    _fields_ = [("threshold", C.c_int), ("min_gop", C.c_int)]
-
-
-class _AdaptiveQuant(C.Structure):
-    _fields_ = [("strength", C.c_int)]
-
-
-class _EncPictureInfo(C.Structure):
-    _fields_ = [("cut_i", C.c_uint32), ("cut_p", C.c_uint32), ("type", C.c_uint8), ("pad", C.c_uint8 * 3)]
-
-
-class _SbcEncodeOpts(C.Structure):
-    _fields_ = [("n_streams", C.c_int), ("n_frames", C.c_int), ("frequency", C.c_int), ("blocks", C.c_int), ("mode", C.c_int),
-                ("allocation", C.c_int), ("bitpool", C.c_int), ("pcm_layout", C.c_int), ("pcm_stride", C.c_size_t),
-                ("frame_stride", C.c_size_t)]
-
-
-class _ImportPcmOpts(C.Structure):
-    _fields_ = [("n_streams", C.c_int), ("n_in", C.c_int), ("in_rate", C.c_int), ("out_rate", C.c_int), ("channels", C.c_int),
-                ("layout", C.c_int), ("mix_q15", C.c_int * 8), ("first_in", C.c_int64), ("src_stride", C.c_size_t),
-                ("dst_stride", C.c_size_t)]
-
-
-class _LoudnessStepsOpts(C.Structure):
-    _fields_ = [("n_streams", C.c_int), ("n_samples", C.c_int), ("rate", C.c_int), ("first_step", C.c_int),
-                ("first_sample", C.c_int64), ("pcm_stride", C.c_size_t), ("steps_stride", C.c_size_t)]
-
-
-class _LoudnessGateOpts(C.Structure):
-    _fields_ = [("n_streams", C.c_int), ("n_steps", C.c_int), ("rate", C.c_int), ("abs_thr", C.c_uint64),
-                ("target_ms", C.c_uint64), ("ceiling", C.c_uint32), ("steps_stride", C.c_size_t)]
-
-
-class _PcmGainOpts(C.Structure):
-    _fields_ = [("n_streams", C.c_int), ("n_samples", C.c_int), ("fixed_gain_q12", C.c_int), ("src_stride", C.c_size_t),
-                ("dst_stride", C.c_size_t)]
-
-
-# efx_loudness_step and efx_loudness_rec as NumPy sees them
-LOUDNESS_STEP_DTYPE = np.dtype([("energy", "<u8"), ("peak", "<u4"), ("zero", "<u4")])
-LOUDNESS_REC_DTYPE = np.dtype([("gated_mean", "<u8"), ("max_block", "<u8"), ("n_gated", "<u4"), ("n_blocks", "<u4"),
-                               ("n_abs", "<u4"), ("peak", "<u2"), ("gain_q12", "<u2")])
-
-
-class _MuxOpts(C.Structure):
-    _fields_ = [("n_streams", C.c_int), ("audio_pid", C.c_int), ("frame_bytes", C.c_int), ("n_frames", C.c_int),
-                ("frames_per_pes", C.c_int), ("samples_per_frame", C.c_int), ("sample_rate", C.c_int),
-                ("audio_first_pts", C.c_int64), ("audio_first_frame", C.c_int64), ("audio_cc", C.c_int),
-                ("video_stride", C.c_size_t), ("audio_stride", C.c_size_t), ("dst_stride", C.c_size_t)]
-
-
 @dataclass
 class CompareResult:
     """Quality of pictures against a reference (Decoder.compare; the definition: include/efx.h).  Axis -1: Y, Cb, Cr."""
@@ -247,144 +105,6 @@ class EncodeResult:
     cut_scores: object = None  # (n, P, 2) uint32 array: every picture's (cut_i, cut_p) (efx.h "scene cuts"; 0 while they are off)
     quality: object = None  # CompareResult of shape (n, P): the reconstruction against the source (ref_max=248), with quality=True
 
-
-class _IdxRec(C.Structure):
-    _fields_ = [("first_pts", C.c_int64), ("last_pts", C.c_int64), ("bin_size", C.c_uint32), ("trick_speed", C.c_uint32),
-                ("sample_count", C.c_uint32), ("reserved", C.c_uint32)]
-
-
-class _Timing(C.Structure):
-    _fields_ = [("index_ms", C.c_float), ("parse_ms", C.c_float), ("recon_ms", C.c_float), ("total_ms", C.c_float),
-                ("pictures", C.c_uint64), ("slices", C.c_uint64), ("coefficients", C.c_uint64), ("es_bytes", C.c_uint64),
-                ("demux_ms", C.c_float), ("timed_calls", C.c_uint32), ("ts_bytes", C.c_uint64), ("groups", C.c_uint32),
-                ("parse_halves", C.c_uint16), ("mixed", C.c_uint16), ("recon_launches", C.c_uint32)]
-
-
-# every symbol include/efx.h declares: (name, restype, argtypes)
-_P = C.c_void_p
-_SYMBOLS = {
-    "efx_create": (C.c_int, [C.POINTER(_Config), C.POINTER(_P)]),
-    "efx_destroy": (None, [_P]),
-    "efx_last_error": (C.c_char_p, [_P]),
-    "efx_status_string": (C.c_char_p, [C.c_int]),
-    "efx_upload_streams": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(C.c_size_t), C.c_int]),
-    "efx_upload_streams_inplace": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(C.c_size_t), C.c_int]),
-    "efx_download_es": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
-    "efx_host_alloc": (C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),
-    "efx_host_free": (C.c_int, [_P, _P]),
-    "efx_host_register": (C.c_int, [_P, _P, C.c_size_t]),
-    "efx_host_unregister": (C.c_int, [_P, _P]),
-    "efx_stream_layout": (C.c_int, [C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
-    "efx_upload_done": (C.c_int, [_P]),
-    "efx_debug_poke": (C.c_int, [_P, _P, C.c_size_t, C.c_longlong]),
-    "efx_debug_recon_stats": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
-    "efx_set_option": (C.c_int, [_P, C.c_int, C.c_int]),
-    "efx_get_option": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
-    "efx_reset": (C.c_int, [_P]),
-    "efx_erase_frames": (C.c_int, [_P]),
-    "efx_play_reset": (C.c_int, [_P]),
-    "efx_stream_state": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
-    "efx_decode": (C.c_int, [_P]),
-    "efx_decode_from": (C.c_int, [_P, C.c_int]),
-    "efx_decode_range": (C.c_int, [_P, C.c_int, C.c_int]),
-    "efx_stream_picture_slot": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int)]),
-    "efx_sync": (C.c_int, [_P]),
-    "efx_picture_count": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
-    "efx_stream_status": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint32)]),
-    "efx_picture_pts": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
-    "efx_picture_slot": (C.c_int, [_P, C.c_int]),
-    "efx_frame_device_ptr": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(_P)]),
-    "efx_download_frame": (C.c_int, [_P, C.c_int, C.c_int, _P]),
-    "efx_frame_hashes": (C.c_int, [_P, C.c_int, C.c_int, _P]),
-    "efx_upload_frame": (C.c_int, [_P, C.c_int, C.c_int, _P]),
-    "efx_video_get_params": (C.c_int, [C.c_int, C.POINTER(_VideoParams)]),
-    "efx_export_bytes": (C.c_size_t, [C.c_int]),
-    "efx_export_frames": (C.c_int, [_P, C.POINTER(_ExportOpts), _P]),
-    "efx_import_src_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "efx_import_frames": (C.c_int, [_P, C.POINTER(_ImportOpts), _P, _P]),
-    "efx_detect_crop": (C.c_int, [_P, C.POINTER(_CropOpts), _P, _P, _P]),
-    "efx_import_surfaces": (C.c_int, [_P, C.POINTER(_Surface), C.POINTER(_ImportOpts), _P, _P]),
-    "efx_detect_crop_surfaces": (C.c_int, [_P, C.POINTER(_Surface), C.POINTER(_CropOpts), _P, _P, _P]),
-    "efx_surface_layout": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.POINTER(_Surface)]),
-    "efx_deinterlace": (C.c_int, [_P, C.POINTER(_Surface), C.POINTER(_DeintOpts), _P, _P]),
-    "efx_deinterlace_count": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    "efx_detelecine": (C.c_int, [_P, C.POINTER(_Surface), C.POINTER(_DetelecineOpts), _P, _P, _P]),
-    "efx_detelecine_count": (C.c_int, [C.c_int, C.c_int]),
-    "efx_import_set_colour": (C.c_int, [_P, C.POINTER(_ImportColour)]),
-    "efx_import_colour_coefs": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
-    "efx_import_set_hdr": (C.c_int, [_P, C.POINTER(_ImportHdr)]),
-    "efx_import_hdr_tables": (C.c_int, [C.POINTER(_ImportHdr), C.c_int, C.c_void_p, C.c_size_t]),
-    "efx_compare_pictures": (C.c_int, [_P, C.POINTER(_CompareOpts), _P, _P, _P, _P]),
-    "efx_compare_psnr": (C.c_double, [C.c_uint64, C.c_uint64]),
-    "efx_compare_ssim": (C.c_double, [C.c_int64, C.c_int]),
-    "efx_trick_pick": (C.c_int, [_P, C.POINTER(_TrickOpts), _P, _P, _P]),
-    "efx_trick_count": (C.c_int64, [C.c_int64, C.c_int64, C.c_int]),
-    "efx_encode": (C.c_int, [_P, C.POINTER(_EncodeOpts), _P, _P, _P, _P, _P]),
-    "efx_encode_rc": (C.c_int, [_P, C.POINTER(_EncodeOpts), C.POINTER(_EncodeRate), _P, _P, _P, _P, _P, _P]),
-    "efx_encode_bound": (C.c_size_t, [C.c_int, C.c_int]),
-    "efx_encode_set_picture_rate": (C.c_int, [_P, C.c_int]),
-    "efx_encode_set_scene_cut": (C.c_int, [_P, C.POINTER(_SceneCut)]),
-    "efx_encode_picture_info": (C.c_int, [_P, C.c_int, C.POINTER(_EncPictureInfo), C.c_int]),
-    "efx_encode_set_adaptive_quant": (C.c_int, [_P, C.POINTER(_AdaptiveQuant)]),
-    "efx_encode_mb_quant": (C.c_int, [_P, C.c_int, C.c_int, C.c_void_p]),
-    "efx_picture_pts_offset": (C.c_int64, [C.c_int, C.c_int64]),
-    "efx_picture_rate_code": (C.c_int, [C.c_int64, C.c_int64]),
-    "efx_conform_rate": (C.c_int, [_P, C.POINTER(_ConformOpts), _P, _P]),
-    "efx_conform_count": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64]),
-    "efx_conform_source": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int64]),
-    "efx_composite_fields": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
-    "efx_composite_fields_ex": (C.c_int, [_P, C.POINTER(_FieldOpts), _P]),
-    "efx_demux_audio": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(C.c_size_t), _P, C.c_size_t, _P]),
-    "efx_index_streams": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(C.c_size_t), _P, C.c_uint32, _P, _P, C.c_size_t]),
-    "efx_idx_build": (C.c_size_t, [_P, C.POINTER(_P), _P, C.c_size_t]),
-    "efx_idx_pts2offset": (C.c_uint32, [_P, C.c_int64, C.c_int]),
-    "efx_idx_pts2pts": (C.c_int64, [_P, C.c_int64, C.c_int]),
-    "efx_sbc_state_bytes": (C.c_size_t, []),
-    "efx_sbc_decode": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.c_int, C.c_int, _P, _P, C.c_size_t, _P, _P, C.c_int]),
-    "efx_sbc_frame_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "efx_sbc_enc_state_bytes": (C.c_size_t, []),
-    "efx_sbc_encode": (C.c_int, [_P, C.POINTER(_SbcEncodeOpts), _P, _P, _P]),
-    "efx_import_pcm": (C.c_int, [_P, C.POINTER(_ImportPcmOpts), _P, _P, _P]),
-    "efx_import_pcm_out_samples": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int]),
-    "efx_import_pcm_delay": (C.c_int, [C.c_int, C.c_int]),
-    "efx_import_pcm_state_bytes": (C.c_size_t, []),
-    "efx_import_pcm_filter": (C.c_int, [_P, C.c_int]),
-    "efx_loudness_steps": (C.c_int, [_P, C.POINTER(_LoudnessStepsOpts), _P, _P, _P]),
-    "efx_loudness_gate": (C.c_int, [_P, C.POINTER(_LoudnessGateOpts), _P, _P, _P]),
-    "efx_pcm_gain": (C.c_int, [_P, C.POINTER(_PcmGainOpts), _P, _P, _P]),
-    "efx_loudness_lufs": (C.c_double, [C.c_uint64, C.c_int]),
-    "efx_loudness_thresholds": (C.c_int, [C.c_int, C.c_double, C.c_double, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
-                                          C.POINTER(C.c_uint32)]),
-    "efx_loudness_coefs": (C.c_int, [C.c_int, C.POINTER(C.c_int32)]),
-    "efx_loudness_state_bytes": (C.c_size_t, [C.c_int]),
-    "efx_loudness_step_count": (C.c_int, [C.c_int, C.c_int64, C.c_int]),
-    "efx_mux_av": (C.c_int, [_P, C.POINTER(_MuxOpts), _P, _P, _P, _P, _P, _P]),
-    "efx_mux_bound": (C.c_size_t, [C.c_size_t, C.c_int, C.c_int, C.c_int]),
-    "efx_mux_audio_packets": (C.c_int, [C.c_int, C.c_int, C.c_int]),
-    "efx_pdm": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P]),
-    "efx_set_timing": (C.c_int, [_P, C.c_int]),
-    "efx_get_timing": (C.c_int, [_P, C.POINTER(_Timing)]),
-    "efx_partition_first": (C.c_int, [C.c_int, C.c_int, C.c_int]),
-    "efx_numa_node_of_pci": (C.c_int, [C.c_char_p]),
-    "efx_numa_cpus_of_node": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.c_int]),
-    "efx_numa_bind_thread": (C.c_int, [C.c_int]),
-    "efx_multi_create": (C.c_int, [C.POINTER(_Config), C.POINTER(C.c_int), C.c_int, C.POINTER(_P)]),
-    "efx_multi_destroy": (None, [_P]),
-    "efx_multi_device_count": (C.c_int, [_P]),
-    "efx_multi_context": (_P, [_P, C.c_int]),
-    "efx_multi_last_error": (C.c_char_p, [_P]),
-    "efx_multi_upload_streams": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(C.c_size_t), C.c_int]),
-    "efx_multi_locate": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "efx_multi_decode": (C.c_int, [_P]),
-    "efx_multi_sync": (C.c_int, [_P]),
-    "efx_multi_reset": (C.c_int, [_P]),
-    "efx_multi_results": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
-    "efx_multi_frame_hashes": (C.c_int, [_P, _P]),
-    "efx_device_alloc": (C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),
-    "efx_device_free": (C.c_int, [_P, _P]),
-    "efx_memcpy_h2d": (C.c_int, [_P, _P, _P, C.c_size_t]),
-    "efx_memcpy_d2h": (C.c_int, [_P, _P, _P, C.c_size_t]),
-}
 
 _lib = None
 
@@ -766,10 +486,6 @@ def deinterlace_count(n_frames: int, *, rate: str = "field", lead: bool = False,
     return int(load_library().efx_deinterlace_count(n_frames, 1 if lead else 0, 1 if tail else 0, mode))
 
 
-# efx_telecine_info: the record efx_detelecine writes per processed frame
-TELECINE_INFO = np.dtype([("comb_c", "<u8"), ("comb_p", "<u8"), ("diff", "<u8"), ("match", "<i4"), ("out", "<i4")])
-
-
 def detelecine_count(n_frames: int, *, lead: bool = False) -> int:
     """Film frames per stream a detelecine call makes of n_frames offered frames (efx_detelecine_count; -1 for arguments
     the call rejects): of the n = n_frames - lead processed frames one in every whole cycle of five is dropped."""
@@ -919,6 +635,58 @@ class DeviceBuffer:
         if self.ptr:
             self._dec._lib.efx_device_free(self._dec._ctx, self.ptr)
             self.ptr = None
+
+
+def _ptr(b):
+    """What the *_to calls pass on: a DeviceBuffer's pointer, a raw pointer or None as it is (where the C side takes no
+    null it says so itself)."""
+    return b.ptr if isinstance(b, DeviceBuffer) else b
+
+
+def _r16(v: int) -> int:
+    return (v + 15) // 16 * 16
+
+
+def _r8(v: int) -> int:
+    return (v + 7) // 8 * 8
+
+
+class _Scratch:
+    """The temporaries of one convenience call (Decoder._scratch()): device buffers, freed on exit, and tensors, held
+    until then.  On exit through an exception the library's stream is waited for first: queued calls may still use
+    them."""
+
+    def __init__(self, dec: "Decoder"):
+        self._dec, self._bufs, self._kept = dec, [], []
+
+    def alloc(self, nbytes: int) -> DeviceBuffer:
+        """At least 16 bytes, so that an empty batch needs no guard."""
+        buf = DeviceBuffer(self._dec, max(16, nbytes))
+        self._bufs.append(buf)
+        return buf
+
+    def zeros(self, nbytes: int) -> DeviceBuffer:
+        """alloc() and an upload of zeros, which synchronises the library's stream: before anything is queued."""
+        buf = self.alloc(nbytes)
+        buf.upload(np.zeros(nbytes, dtype=np.uint8))
+        return buf
+
+    def keep(self, tensor):
+        self._kept.append(tensor)
+        return tensor
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is not None:
+            try:
+                self._dec.sync()
+            except EfxError:
+                pass
+        for b in self._bufs:
+            b.free()
+        return False
 
 
 class Decoder:
@@ -1137,8 +905,8 @@ class Decoder:
         tensor of that size on this device, or a DeviceBuffer (then returned as is).
 
         The kernel runs on the library's stream.  sync=True (default) waits for it, so the tensor is ready for any torch
-        stream.  sync=False is only safe when the decoder was created with
-        hip_stream=torch.cuda.current_stream().cuda_stream and that stream is a torch.cuda.Stream(), not the default
+        stream.  sync=False is only safe when the decoder was created with hip_stream= the handle (.cuda_stream) of
+        torch's current stream and that stream is a torch.cuda.Stream(), not the default
         stream (whose handle, 0, makes the library create a private stream) -- the tensor is then ordered like any torch
         op on that stream -- or when the caller calls sync() before using the tensor."""
         import torch
@@ -1204,16 +972,15 @@ class Decoder:
             raise ValueError("matrix=, src_range= and transfer= describe a YCbCr source; an RGB source is converted with BT.601 (full_range=)")
         if hdr is not None:
             _check(self._ctx, self._lib.efx_import_set_hdr(self._ctx, C.byref(_ImportHdr(*hdr))))
-        g = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
         o = _ImportOpts(n_images, _PIX_FORMATS[fmt], width, height, *(crop or (0, 0, 0, 0)), *(dst_rect or (0, 0, 0, 0)),
                         1 if full_range else 0, src_stride, dst_stride)
         if colour is not None:
             _check(self._ctx, self._lib.efx_import_set_colour(self._ctx, C.byref(_ImportColour(*colour))))
         try:
             if surface is not None:
-                _check(self._ctx, self._lib.efx_import_surfaces(self._ctx, C.byref(surface), C.byref(o), g(src), g(dst)))
+                _check(self._ctx, self._lib.efx_import_surfaces(self._ctx, C.byref(surface), C.byref(o), _ptr(src), _ptr(dst)))
             else:
-                _check(self._ctx, self._lib.efx_import_frames(self._ctx, C.byref(o), g(src), g(dst)))
+                _check(self._ctx, self._lib.efx_import_frames(self._ctx, C.byref(o), _ptr(src), _ptr(dst)))
         finally:
             if colour is not None:
                 self._apply_import_colour()
@@ -1246,34 +1013,80 @@ class Decoder:
         colour = getattr(self, "_import_colour", None)
         self._lib.efx_import_set_colour(self._ctx, C.byref(_ImportColour(*colour)) if colour is not None else None)
 
-    def _stage_pictures(self, src, n: int, image: int, stride: int, bufs: list, keep: list):
-        """The source of import_pictures / detect_crop in device memory, image i at + i * stride: (pointer, array input?,
-        must the caller synchronise before it returns?).  An array is uploaded into a DeviceBuffer appended to bufs (the
-        caller frees it after a sync); a tensor is used in place when it is packed and aligned, else copied; it is
-        appended to keep, and torch's current stream is synchronised first unless it is the decoder's."""
+    # -- what the convenience methods share: temporaries, staging, the wait for torch, rows back ------
+    def _scratch(self) -> _Scratch:
+        return _Scratch(self)
+
+    def _wait_for_torch(self, own_stream_ok: bool = False) -> bool:
+        """Synchronise torch's current stream on the decoder's device, so that the library's stream may read what torch
+        wrote; returns whether it waited.  own_stream_ok: no wait when that stream is the decoder's own (hip_stream=),
+        where the calls are ordered behind torch's work anyway."""
+        import torch
+        cur = torch.cuda.current_stream(torch.device("cuda", self.device))
+        if own_stream_ok and self.hip_stream and cur.cuda_stream == self.hip_stream:
+            return False
+        cur.synchronize()
+        return True
+
+    def _stage(self, s: _Scratch, src, n: int, row: int, *, stride: int | None = None, dtype=np.uint8, what: str = "src"):
+        """n rows of `row` elements of src in device memory, row i at i * stride elements (None: row rounded up so that
+        every row starts 16-byte aligned): (pointer, array input?, copied?).  A NumPy array is uploaded into a buffer of
+        s, zero-padded where stride != row.  A tensor of that dtype on the decoder's device is used in place when it is
+        packed (stride == row) and 16-byte aligned, else copied to a zeroed (n, stride) tensor; s keeps it, and the
+        caller waits for torch (_wait_for_torch) before it queues what reads it."""
+        dtype = np.dtype(dtype)
+        if stride is None:
+            stride = _r16(row * dtype.itemsize) // dtype.itemsize
         if isinstance(src, np.ndarray):
-            host = np.zeros((n, stride), dtype=np.uint8)
-            host[:, :image] = np.ascontiguousarray(src, dtype=np.uint8).reshape(n, image)
-            sbuf = DeviceBuffer(self, n * stride)
-            bufs.append(sbuf)
-            sbuf.upload(host)
-            return sbuf.ptr, True, False
+            host = np.ascontiguousarray(src, dtype=dtype).reshape(n, row)
+            if stride != row:
+                host, packed = np.zeros((n, stride), dtype=dtype), host
+                host[:, :row] = packed
+            buf = s.alloc(host.nbytes)
+            buf.upload(host)
+            return buf.ptr, True, False
         import torch
         device = torch.device("cuda", self.device)
-        if not isinstance(src, torch.Tensor) or src.dtype != torch.uint8 or src.device != device:
-            raise ValueError(f"src must be a uint8 tensor on {device} (or a NumPy array)")
+        if not isinstance(src, torch.Tensor) or src.dtype != getattr(torch, dtype.name) or src.device != device:
+            raise ValueError(f"{what} must be a {dtype.name} tensor on {device} (or a NumPy array)")
         flat = src.contiguous()
-        if stride != image or flat.data_ptr() % 16:
-            padded = torch.zeros((n, stride), dtype=torch.uint8, device=device)
-            padded[:, :image] = flat.view(n, image)
-            flat = padded
-        keep.append(flat)
-        must_sync = False
-        cur = torch.cuda.current_stream(device)
-        if not self.hip_stream or cur.cuda_stream != self.hip_stream:
-            cur.synchronize()
-            must_sync = flat is not src  # (torch may hand a staging copy's memory out again on its own stream)
-        return flat.data_ptr(), False, must_sync
+        if stride != row or flat.data_ptr() % 16:
+            flat, packed = torch.zeros((n, stride), dtype=src.dtype, device=device), flat
+            flat[:, :row] = packed.view(n, row)
+        s.keep(flat)
+        return flat.data_ptr(), False, flat is not src
+
+    def _rows_out(self, s: _Scratch, is_array: bool, n: int, row: int, stride: int):
+        """Where a call writes n rows of `row` bytes, `stride` apart, and how they come back: (pointer, fetch).  For array
+        input a buffer of s, and fetch() -- after the sync -- downloads it and crops the rows; for tensor input a fresh
+        tensor, which fetch() returns, cropped and made contiguous only where stride != row."""
+        if is_array:
+            buf = s.alloc(n * stride)
+            return buf.ptr, lambda: np.ascontiguousarray(buf.download(np.uint8, n * stride).reshape(n, stride)[:, :row])
+        import torch
+        out = torch.empty((n, stride), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        return out.data_ptr(), lambda: out if stride == row else out[:, :row].contiguous()
+
+    def _frames_to_pictures(self, src, fmt, width, height, pitch, plane_rows, n_streams, count, queue):
+        """What deinterlace() and detelecine() share.  count(n_frames) gives (pictures, records) per stream or raises;
+        queue(src, dst, records, **kw) is the *_to call, kw the surface, the counts and the strides.  Returns (pictures,
+        records as TELECINE_INFO of shape (n_streams, records), None where count asks for none)."""
+        surf, total, src = _surface_source(src, fmt, width, height, pitch, plane_rows)
+        if n_streams < 1 or total % n_streams:
+            raise ValueError(f"{total} source images do not make {n_streams} streams of equal length")
+        n_frames = total // n_streams
+        n_out, n_rec = count(n_frames)
+        image = width * height * 3 // 2
+        stride, dstride = _r16(surf.bytes), _r16(image)
+        with self._scratch() as s:
+            src_ptr, is_array, _ = self._stage(s, src, total, surf.bytes, stride=stride)
+            if not is_array:
+                self._wait_for_torch(own_stream_ok=True)
+            ibuf = s.alloc(n_streams * n_rec * TELECINE_INFO.itemsize) if n_rec else None
+            dst_ptr, fetch = self._rows_out(s, is_array, n_streams * n_out, image, dstride)
+            queue(src_ptr, dst_ptr, ibuf, surface=surf, n_streams=n_streams, n_frames=n_frames, src_stride=stride, dst_stride=dstride)
+            self.sync()
+            return fetch(), ibuf.download(TELECINE_INFO, n_streams * n_rec).reshape(n_streams, n_rec) if ibuf else None
 
     # -- interlaced sources (efx_deinterlace) -------------------------------------------------
     def deinterlace_to(self, src: DeviceBuffer | int, dst: DeviceBuffer | int, *, surface: _Surface, n_streams: int = 1, n_frames: int,
@@ -1287,10 +1100,9 @@ class Decoder:
         pictures a second), "frame": the first field only; lead / tail: the first / last offered frame is context only,
         for a title that goes through in pieces with one frame of overlap.  The rule: include/efx.h, "interlaced
         sources".  Returns n_out, the pictures per stream (deinterlace_count)."""
-        g = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
         first, mode = _deint_setting(first_field, rate)
         o = _DeintOpts(n_streams, n_frames, first, mode, 1 if lead else 0, 1 if tail else 0, src_stride, dst_stride)
-        _check(self._ctx, self._lib.efx_deinterlace(self._ctx, C.byref(surface), C.byref(o), g(src), g(dst)))
+        _check(self._ctx, self._lib.efx_deinterlace(self._ctx, C.byref(surface), C.byref(o), _ptr(src), _ptr(dst)))
         return int(self._lib.efx_deinterlace_count(n_frames, o.lead, o.tail, mode))
 
     def deinterlace(self, src, *, fmt: str = "i420", width: int, height: int, pitch: int = 0, plane_rows: int = 0,
@@ -1302,34 +1114,16 @@ class Decoder:
         pictures, n_out = deinterlace_count(n_frames, ...): what import_pictures(fmt="i420", width=, height=) and
         detect_crop() take; a tensor for a tensor (no host round trip), an array for an array.  Synchronises: torch's
         current stream before (tensor input), the library's after."""
-        surf, total, src = _surface_source(src, fmt, width, height, pitch, plane_rows)
-        if n_streams < 1 or total % n_streams:
-            raise ValueError(f"{total} source images do not make {n_streams} streams of equal length")
-        n_frames = total // n_streams
-        n_out = deinterlace_count(n_frames, rate=rate, lead=lead, tail=tail)
-        if n_out < 0:
-            raise ValueError(f"deinterlace: {n_frames} frames with lead={lead}, tail={tail} leave no frame with an output")
-        image = width * height * 3 // 2
-        stride, dstride = (surf.bytes + 15) // 16 * 16, (image + 15) // 16 * 16
-        bufs, keep = [], []
-        try:
-            src_ptr, is_array, _ = self._stage_pictures(src, total, surf.bytes, stride, bufs, keep)
-            kw = dict(surface=surf, n_streams=n_streams, n_frames=n_frames, first_field=first_field, rate=rate, lead=lead, tail=tail,
-                      src_stride=stride, dst_stride=dstride)
-            if is_array:
-                dbuf = DeviceBuffer(self, n_streams * n_out * dstride)
-                bufs.append(dbuf)
-                self.deinterlace_to(src_ptr, dbuf, **kw)
-                self.sync()
-                return np.ascontiguousarray(dbuf.download(np.uint8, n_streams * n_out * dstride).reshape(-1, dstride)[:, :image])
-            import torch
-            out = torch.empty((n_streams * n_out, dstride), dtype=torch.uint8, device=torch.device("cuda", self.device))
-            self.deinterlace_to(src_ptr, out.data_ptr(), **kw)
-            self.sync()
-            return out if dstride == image else out[:, :image].contiguous()
-        finally:
-            for b in bufs:
-                b.free()
+        def count(n_frames):
+            n_out = deinterlace_count(n_frames, rate=rate, lead=lead, tail=tail)
+            if n_out < 0:
+                raise ValueError(f"deinterlace: {n_frames} frames with lead={lead}, tail={tail} leave no frame with an output")
+            return n_out, 0
+
+        def queue(src_ptr, dst_ptr, _, **kw):
+            self.deinterlace_to(src_ptr, dst_ptr, first_field=first_field, rate=rate, lead=lead, tail=tail, **kw)
+
+        return self._frames_to_pictures(src, fmt, width, height, pitch, plane_rows, n_streams, count, queue)[0]
 
     # -- telecined sources (efx_detelecine) ---------------------------------------------------
     def detelecine_to(self, src: DeviceBuffer | int, dst: DeviceBuffer | int, info: DeviceBuffer | int, *, surface: _Surface,
@@ -1344,11 +1138,10 @@ class Decoder:
         that goes through in pieces with one frame of overlap (every piece but the last processes a multiple of 5
         frames); nt: the noise threshold of the comb score in pels.  The rule: include/efx.h, "telecined sources".
         Returns n_out, the film frames per stream (detelecine_count)."""
-        g = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
         if first_field not in _FIRST_FIELDS:
             raise ValueError(f"unknown first_field {first_field!r}: 'top' (or 'tff') or 'bottom' (or 'bff')")
         o = _DetelecineOpts(n_streams, n_frames, _FIRST_FIELDS[first_field], 1 if lead else 0, nt, src_stride, dst_stride)
-        _check(self._ctx, self._lib.efx_detelecine(self._ctx, C.byref(surface), C.byref(o), g(src), g(dst), g(info)))
+        _check(self._ctx, self._lib.efx_detelecine(self._ctx, C.byref(surface), C.byref(o), _ptr(src), _ptr(dst), _ptr(info)))
         return int(self._lib.efx_detelecine_count(n_frames, o.lead))
 
     def detelecine(self, src, *, fmt: str = "i420", width: int, height: int, pitch: int = 0, plane_rows: int = 0,
@@ -1362,40 +1155,17 @@ class Decoder:
         array for an array.  With info=True it returns (pictures, records): the records a structured NumPy array
         (TELECINE_INFO) of shape (n_streams, n_frames - lead).  Synchronises: torch's current stream before (tensor
         input), the library's after."""
-        surf, total, src = _surface_source(src, fmt, width, height, pitch, plane_rows)
-        if n_streams < 1 or total % n_streams:
-            raise ValueError(f"{total} source images do not make {n_streams} streams of equal length")
-        n_frames = total // n_streams
-        n_out = detelecine_count(n_frames, lead=lead)
-        if n_out < 0:
-            raise ValueError(f"detelecine: {n_frames} frames with lead={lead} leave no frame to process")
-        n = n_frames - (1 if lead else 0)
-        image = width * height * 3 // 2
-        stride, dstride = (surf.bytes + 15) // 16 * 16, (image + 15) // 16 * 16
-        bufs, keep = [], []
-        try:
-            src_ptr, is_array, _ = self._stage_pictures(src, total, surf.bytes, stride, bufs, keep)
-            ibuf = DeviceBuffer(self, n_streams * n * TELECINE_INFO.itemsize)
-            bufs.append(ibuf)
-            kw = dict(surface=surf, n_streams=n_streams, n_frames=n_frames, first_field=first_field, lead=lead, nt=nt, src_stride=stride,
-                      dst_stride=dstride)
-            records = lambda: ibuf.download(TELECINE_INFO, n_streams * n).reshape(n_streams, n)
-            if is_array:
-                dbuf = DeviceBuffer(self, n_streams * n_out * dstride)
-                bufs.append(dbuf)
-                self.detelecine_to(src_ptr, dbuf, ibuf, **kw)
-                self.sync()
-                out = np.ascontiguousarray(dbuf.download(np.uint8, n_streams * n_out * dstride).reshape(-1, dstride)[:, :image])
-                return (out, records()) if info else out
-            import torch
-            out = torch.empty((n_streams * n_out, dstride), dtype=torch.uint8, device=torch.device("cuda", self.device))
-            self.detelecine_to(src_ptr, out.data_ptr(), ibuf, **kw)
-            self.sync()
-            out = out if dstride == image else out[:, :image].contiguous()
-            return (out, records()) if info else out
-        finally:
-            for b in bufs:
-                b.free()
+        def count(n_frames):
+            n_out = detelecine_count(n_frames, lead=lead)
+            if n_out < 0:
+                raise ValueError(f"detelecine: {n_frames} frames with lead={lead} leave no frame to process")
+            return n_out, n_frames - (1 if lead else 0)
+
+        def queue(src_ptr, dst_ptr, records, **kw):
+            self.detelecine_to(src_ptr, dst_ptr, records, first_field=first_field, lead=lead, nt=nt, **kw)
+
+        out, records = self._frames_to_pictures(src, fmt, width, height, pitch, plane_rows, n_streams, count, queue)
+        return (out, records) if info else out
 
     # -- black borders (efx_detect_crop) ----------------------------------------------------
     def detect_crop_to(self, src: DeviceBuffer | int, rects: DeviceBuffer | int, *, n_streams: int, images_per_stream: int,
@@ -1410,13 +1180,12 @@ class Decoder:
         (efx_detect_crop_surfaces), fmt must be "i420", width and height the surface's."""
         if fmt not in _PIX_FORMATS:
             raise ValueError(f"unknown format {fmt!r}: one of {sorted(_PIX_FORMATS)}")
-        g = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
         o = _CropOpts(n_streams, images_per_stream, _PIX_FORMATS[fmt], width, height, 1 if full_range else 0, limit, round,
                       src_stride, sums_stride)
         if surface is not None:
-            _check(self._ctx, self._lib.efx_detect_crop_surfaces(self._ctx, C.byref(surface), C.byref(o), g(src), g(rects), g(sums)))
+            _check(self._ctx, self._lib.efx_detect_crop_surfaces(self._ctx, C.byref(surface), C.byref(o), _ptr(src), _ptr(rects), _ptr(sums)))
             return
-        _check(self._ctx, self._lib.efx_detect_crop(self._ctx, C.byref(o), g(src), g(rects), g(sums)))
+        _check(self._ctx, self._lib.efx_detect_crop(self._ctx, C.byref(o), _ptr(src), _ptr(rects), _ptr(sums)))
 
     def detect_crop(self, src, *, fmt: str | None = None, width: int | None = None, height: int | None = None,
                     images_per_stream: int | None = None, limit: int = 24, round: int = 16,
@@ -1450,24 +1219,20 @@ class Decoder:
         per = n if images_per_stream is None else images_per_stream
         if per < 1 or n % per:
             raise ValueError(f"images_per_stream={images_per_stream} does not divide the {n} images")
-        stride = (image + 15) // 16 * 16
-        bufs, keep = [], []
-        try:
-            src_ptr, _, _ = self._stage_pictures(src, n, image, stride, bufs, keep)
-            return self._detect_rects(src_ptr, n // per, per, fmt, width, height, limit, round, full_range, stride, surface)
-        finally:
-            for b in bufs:
-                b.free()
+        stride = _r16(image)
+        with self._scratch() as s:
+            src_ptr, is_array, _ = self._stage(s, src, n, image, stride=stride)
+            if not is_array:
+                self._wait_for_torch(own_stream_ok=True)
+            return self._detect_rects(s, src_ptr, n // per, per, fmt, width, height, limit, round, full_range, stride, surface)
 
-    def _detect_rects(self, src_ptr, n_streams, per, fmt, width, height, limit, round, full_range, stride, surface=None) -> np.ndarray:
-        rbuf = DeviceBuffer(self, 32 * n_streams)
-        try:
-            self.detect_crop_to(src_ptr, rbuf, n_streams=n_streams, images_per_stream=per, fmt=fmt, width=width, height=height,
-                                limit=limit, round=round, full_range=full_range, src_stride=stride, surface=surface)
-            self.sync()
-            return rbuf.download(np.int32, 8 * n_streams).reshape(n_streams, 8)
-        finally:
-            rbuf.free()
+    def _detect_rects(self, s: _Scratch, src_ptr, n_streams, per, fmt, width, height, limit, round, full_range, stride,
+                      surface=None) -> np.ndarray:
+        rbuf = s.alloc(32 * n_streams)
+        self.detect_crop_to(src_ptr, rbuf, n_streams=n_streams, images_per_stream=per, fmt=fmt, width=width, height=height,
+                            limit=limit, round=round, full_range=full_range, src_stride=stride, surface=surface)
+        self.sync()
+        return rbuf.download(np.int32, 8 * n_streams).reshape(n_streams, 8)
 
     # -- picture quality (efx_compare_pictures) ------------------------------------------------
     def compare_to(self, ref: DeviceBuffer | int, test: DeviceBuffer | int, recs: DeviceBuffer | int, *, n_images: int,
@@ -1478,42 +1243,8 @@ class Decoder:
         (0 = 101376), its 48-byte record (uint64 sse[3], int64 ssim[3] for Y, Cb, Cr; the definition: include/efx.h) to
         recs + 48 k.  ref_max: reference samples above it count as it (0 = no clamp, 248 = the decoder's).  mb_sse: when
         given, receives every macroblock's luma SSE (uint32), image k at + 4 * k * mb_stride bytes (0 = 264)."""
-        g = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
         o = _CompareOpts(n_images, ref_max, ref_stride, test_stride, mb_stride)
-        _check(self._ctx, self._lib.efx_compare_pictures(self._ctx, C.byref(o), g(ref), g(test), g(recs), g(mb_sse)))
-
-    def _compare_input(self, pictures, bufs: list, keep: list) -> int:
-        """(..., 101376) pictures in device memory, packed: an array is uploaded into a DeviceBuffer appended to bufs, a
-        tensor is used in place (copied when not packed or aligned) and appended to keep."""
-        if isinstance(pictures, np.ndarray):
-            buf = DeviceBuffer(self, max(16, pictures.size))
-            bufs.append(buf)
-            buf.upload(np.ascontiguousarray(pictures, dtype=np.uint8))
-            return buf.ptr
-        import torch
-        device = torch.device("cuda", self.device)
-        if not isinstance(pictures, torch.Tensor) or pictures.dtype != torch.uint8 or pictures.device != device:
-            raise ValueError(f"pictures must be uint8 tensors on {device} (or NumPy arrays)")
-        flat = pictures.contiguous()
-        if flat.data_ptr() % 16:
-            flat = flat.clone()
-        keep.append(flat)
-        return flat.data_ptr()
-
-    def _compare_download(self, ref_ptr: int, test_ptr: int, n: int, lead: tuple, ref_max: int, macroblocks: bool) -> CompareResult:
-        """Compare n packed pictures, wait, and read the records (and maps) back."""
-        out = DeviceBuffer(self, 48 * n + (264 * 4 * n if macroblocks else 0))
-        try:
-            self.compare_to(ref_ptr, test_ptr, out, n_images=n, ref_max=ref_max, mb_sse=out.ptr + 48 * n if macroblocks else None)
-            self.sync()
-            recs = out.download(np.uint64, 6 * n).reshape(n, 6)
-            mb = None
-            if macroblocks:
-                mb = np.empty(264 * n, dtype=np.uint32)
-                _check(self._ctx, self._lib.efx_memcpy_d2h(self._ctx, mb.ctypes.data, out.ptr + 48 * n, mb.nbytes))
-            return _compare_result(recs, lead, mb)
-        finally:
-            out.free()
+        _check(self._ctx, self._lib.efx_compare_pictures(self._ctx, C.byref(o), _ptr(ref), _ptr(test), _ptr(recs), _ptr(mb_sse)))
 
     def compare(self, ref, test, *, ref_max: int = 0, macroblocks: bool = False) -> CompareResult:
         """PSNR and SSIM of pictures against reference pictures, measured on the device (efx_compare_pictures): ref and
@@ -1528,17 +1259,22 @@ class Decoder:
         n = int(np.prod(lead, dtype=np.int64))
         if n < 1:
             raise ValueError("no pictures to compare")
-        bufs, keep = [], []
-        try:
-            ref_ptr = self._compare_input(ref, bufs, keep)
-            test_ptr = ref_ptr if test is ref else self._compare_input(test, bufs, keep)
-            if keep:
-                import torch
-                torch.cuda.current_stream(torch.device("cuda", self.device)).synchronize()
-            return self._compare_download(ref_ptr, test_ptr, n, lead, ref_max, macroblocks)
-        finally:
-            for b in bufs:
-                b.free()
+        with self._scratch() as s:
+            ref_ptr, ref_is_array, _ = self._stage(s, ref, n, FRAME_BYTES, what="pictures")
+            test_ptr, test_is_array = ref_ptr, ref_is_array
+            if test is not ref:
+                test_ptr, test_is_array, _ = self._stage(s, test, n, FRAME_BYTES, what="pictures")
+            if not (ref_is_array and test_is_array):
+                self._wait_for_torch()
+            out = s.alloc(48 * n + (264 * 4 * n if macroblocks else 0))
+            self.compare_to(ref_ptr, test_ptr, out, n_images=n, ref_max=ref_max, mb_sse=out.ptr + 48 * n if macroblocks else None)
+            self.sync()
+            recs = out.download(np.uint64, 6 * n).reshape(n, 6)
+            mb = None
+            if macroblocks:
+                mb = np.empty(264 * n, dtype=np.uint32)
+                _check(self._ctx, self._lib.efx_memcpy_d2h(self._ctx, mb.ctypes.data, out.ptr + 48 * n, mb.nbytes))
+            return _compare_result(recs, lead, mb)
 
     def _encode_quality(self, q_buf: DeviceBuffer, n: int, P: int, types: np.ndarray) -> CompareResult:
         """The records encode() / encode_av() queued behind the encode; pictures that were not written give zeros."""
@@ -1625,23 +1361,22 @@ class Decoder:
                 raise ValueError("deinterlace= takes 8-bit YCbCr sources: 'i420', 'yv12', 'nv12' or 'nv21'")
             if height % 4 or height < 8:
                 raise ValueError(f"an interlaced source's height must be a multiple of 4 from 8, got {height}")
-        stride = (image + 15) // 16 * 16
-        bufs, keep = [], []
-        try:
-            src_ptr, is_array, must_sync = self._stage_pictures(src, n, image, stride, bufs, keep)
-            sync = sync or must_sync
+        stride = _r16(image)
+        with self._scratch() as s:
+            src_ptr, is_array, copied = self._stage(s, src, n, image, stride=stride)
+            waited = not is_array and self._wait_for_torch(own_stream_ok=True)
+            sync = sync or (copied and waited)  # (torch may hand a staging copy's memory out again on its own stream)
             if deinterlace is not None:
                 # the progressive pictures, packed I420 at the source's size, in a buffer of this call: the import's source
-                dstride = (width * height * 3 // 2 + 15) // 16 * 16
+                dstride = _r16(width * height * 3 // 2)
                 rate = "field" if field_rate else "frame"
-                dbuf = DeviceBuffer(self, deinterlace_count(n, rate=rate) * dstride)
-                bufs.append(dbuf)
+                dbuf = s.alloc(deinterlace_count(n, rate=rate) * dstride)
                 n = self.deinterlace_to(src_ptr, dbuf, surface=surface if surface is not None else surface_layout("i420", width, height),
                                         n_frames=n, first_field=deinterlace, rate=rate, src_stride=stride, dst_stride=dstride)
                 src_ptr, stride, surface = dbuf.ptr, dstride, None
             nbytes = n * FRAME_BYTES
             if isinstance(crop, str):
-                rec = self._detect_rects(src_ptr, 1, n, fmt, width, height, crop_limit, crop_round, full_range, stride, surface)
+                rec = self._detect_rects(s, src_ptr, 1, n, fmt, width, height, crop_limit, crop_round, full_range, stride, surface)
                 crop = tuple(int(v) for v in rec[0, :4])
             if fit == "cover":
                 crop = cover_crop(width, height, crop)
@@ -1654,8 +1389,7 @@ class Decoder:
                     raise ValueError(f"out holds {out.nbytes} bytes, the import needs {nbytes}")
                 result, ptr = out, out.ptr
             elif out is None and is_array:
-                obuf = DeviceBuffer(self, nbytes)
-                bufs.append(obuf)
+                obuf = s.alloc(nbytes)
                 result, ptr = None, obuf.ptr
             else:
                 import torch
@@ -1670,14 +1404,11 @@ class Decoder:
             self.import_to(src_ptr, ptr, n_images=n, fmt=fmt, width=width, height=height, crop=crop, dst_rect=rect,
                            full_range=full_range, src_stride=stride, surface=surface, matrix=matrix, src_range=src_range,
                            transfer=transfer, primaries=primaries, peak_nits=peak_nits)
-            if sync or bufs:
-                self.sync()  # (a staging buffer of this call is freed below)
+            if sync or is_array or deinterlace is not None:
+                self.sync()  # (the buffers of this call that the import reads or writes are freed on the way out)
             if obuf is not None:
                 result = obuf.download(np.uint8, nbytes).reshape(n, FRAME_BYTES)
             return result
-        finally:
-            for b in bufs:
-                b.free()
 
     # -- MPEG-1 encode (efx_encode) ------------------------------------------------------------
     def encode_to(self, src: DeviceBuffer | int, dst: DeviceBuffer | int, length: DeviceBuffer | int,
@@ -1706,7 +1437,6 @@ class Decoder:
         aq: fresh streams give every macroblock its own quantiser around the picture's (efx_encode_set_adaptive_quant,
         likewise in front of every cont=False call): the strength 1 .. 256, True = AQ_DEFAULT, None / False / 0 = off.
         With cont=True the streams keep what they started with and it is ignored."""
-        g = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else b)
         if not cont:
             strength = _AdaptiveQuant(AQ_DEFAULT if aq is True else int(aq or 0))
             _check(self._ctx, self._lib.efx_encode_set_adaptive_quant(self._ctx, C.byref(strength)))
@@ -1722,11 +1452,11 @@ class Decoder:
         o = _EncodeOpts(n_streams, n_pictures, fmt, qscale, gop, search, 1 if cont else 0, first_pts,
                         src_stride or n_pictures * FRAME_BYTES, dst_stride or encode_bound(fmt, n_pictures))
         if bitrate is None:
-            _check(self._ctx, self._lib.efx_encode(self._ctx, C.byref(o), g(src), g(dst), g(length), g(status), g(recon)))
+            _check(self._ctx, self._lib.efx_encode(self._ctx, C.byref(o), _ptr(src), _ptr(dst), _ptr(length), _ptr(status), _ptr(recon)))
         else:
             r = _EncodeRate(bitrate, vbv_bits, qmin, qmax)
-            _check(self._ctx, self._lib.efx_encode_rc(self._ctx, C.byref(o), C.byref(r), g(src), g(dst), g(length), g(status),
-                                                      g(recon), g(qscale_out)))
+            _check(self._ctx, self._lib.efx_encode_rc(self._ctx, C.byref(o), C.byref(r), _ptr(src), _ptr(dst), _ptr(length), _ptr(status),
+                                                      _ptr(recon), _ptr(qscale_out)))
         if not cont:
             self._enc_rate_code = code
         return o.dst_stride
@@ -1768,81 +1498,51 @@ class Decoder:
         if len(lead) != 2 or pictures.shape[-1] != FRAME_BYTES:
             raise ValueError(f"pictures must have shape (n, P, {FRAME_BYTES}), got {tuple(pictures.shape)}")
         n, P = lead
-        bufs = []
-        try:
+        with self._scratch() as s:
+            src_ptr, is_array, _ = self._stage(s, pictures, n * P, FRAME_BYTES, what="pictures")
             rec_t = None
-            if isinstance(pictures, np.ndarray):
-                src = DeviceBuffer(self, max(1, pictures.size))
-                bufs.append(src)
-                src.upload(np.ascontiguousarray(pictures, dtype=np.uint8))
-                src_ptr = src.ptr
-            else:
-                import torch
-                device = torch.device("cuda", self.device)
-                if pictures.dtype != torch.uint8 or pictures.device != device:
-                    raise ValueError(f"pictures must be a uint8 tensor on {device} (or a NumPy array)")
-                pictures = pictures.contiguous()
-                torch.cuda.current_stream(device).synchronize()
-                src_ptr = pictures.data_ptr()
+            if not is_array:
+                self._wait_for_torch()
                 if recon:
-                    rec_t = torch.empty((n, P, FRAME_BYTES), dtype=torch.uint8, device=device)
+                    import torch
+                    rec_t = torch.empty((n, P, FRAME_BYTES), dtype=torch.uint8, device=torch.device("cuda", self.device))
             stride = dst_stride or encode_bound(fmt, P)
-            dst, meta = DeviceBuffer(self, n * stride), DeviceBuffer(self, 2 * 4 * n + 16)
-            bufs += [dst, meta]
-            q_buf = None
-            if bitrate is not None:
-                q_buf = DeviceBuffer(self, n * P)
-                bufs.append(q_buf)
-            rec_ptr = None
-            if (recon or quality) and rec_t is None:
-                rec_buf = DeviceBuffer(self, max(16, n * P * FRAME_BYTES))
-                bufs.append(rec_buf)
-                rec_ptr = rec_buf.ptr
-            elif rec_t is not None:
+            dst, meta = s.alloc(n * stride), s.alloc(2 * 4 * n + 16)
+            q_buf = s.alloc(n * P) if bitrate is not None else None
+            rec_buf = rec_ptr = None
+            if rec_t is not None:
                 rec_ptr = rec_t.data_ptr()
-            status_off = (4 * n + 15) // 16 * 16
+            elif recon or quality:
+                rec_buf = s.alloc(n * P * FRAME_BYTES)
+                rec_ptr = rec_buf.ptr
+            status_off = _r16(4 * n)
             self.encode_to(src_ptr, dst, meta.ptr, meta.ptr + status_off, n_streams=n, n_pictures=P, qscale=qscale, gop=gop,
                            search=search, fmt=fmt, cont=cont, first_pts=first_pts, dst_stride=stride, recon=rec_ptr,
                            bitrate=bitrate, vbv_bits=vbv_bits, qmin=qmin, qmax=qmax, qscale_out=q_buf, fps=fps, scene_cut=scene_cut,
                            min_gop=min_gop, aq=aq)
             qual_buf = None
             if quality and n * P:
-                qual_buf = DeviceBuffer(self, 48 * n * P)
-                bufs.append(qual_buf)
+                qual_buf = s.alloc(48 * n * P)
                 self.compare_to(src_ptr, rec_ptr, qual_buf, n_images=n * P, ref_max=248)
             self.sync()
-            lens = meta.download(np.uint32, n)
-            st = np.empty(n, dtype=np.uint32)
-            _check(self._ctx, self._lib.efx_memcpy_d2h(self._ctx, st.ctypes.data, meta.ptr + status_off, 4 * n))
-            streams = []
-            for i in range(n):
-                b = np.empty(int(lens[i]), dtype=np.uint8)
-                if b.size:
-                    _check(self._ctx, self._lib.efx_memcpy_d2h(self._ctx, b.ctypes.data, dst.ptr + i * stride, b.size))
-                streams.append(b.tobytes())
-            out_rec = None
-            if rec_t is not None:
-                out_rec = rec_t
-            elif recon:
+            streams, st = self._download_streams(dst.ptr, stride, meta.ptr, meta.ptr + status_off, n)
+            out_rec = rec_t
+            if rec_t is None and recon:
                 out_rec = rec_buf.download(np.uint8, n * P * FRAME_BYTES).reshape(n, P, FRAME_BYTES)
             qs = q_buf.download(np.uint8, n * P).reshape(n, P) if q_buf is not None else None
             info = self.encode_picture_info(n)
             types = np.ascontiguousarray(info["type"])
             qual = self._encode_quality(qual_buf, n, P, types) if qual_buf is not None else None
             return EncodeResult(streams, st, out_rec, qs, types, np.stack([info["cut_i"], info["cut_p"]], axis=-1), qual)
-        finally:
-            for b in bufs:
-                b.free()
 
     def encode_picture_info(self, n_streams: int) -> np.ndarray:
         """The pictures of the latest encode call (efx_encode_picture_info; synchronises): a structured array
         (n_streams, P) with the fields cut_i, cut_p (uint32) and type (uint8: PICTURE_I, PICTURE_P, PICTURE_CUT_I, 0 = not
         written)."""
-        dt = np.dtype([("cut_i", "<u4"), ("cut_p", "<u4"), ("type", "u1"), ("pad", "u1", 3)])
         count = self._lib.efx_encode_picture_info(self._ctx, 0, None, 0)
         if count < 0:
             _check(self._ctx, count)
-        out = np.zeros((n_streams, count), dtype=dt)
+        out = np.zeros((n_streams, count), dtype=ENC_PICTURE_INFO_DTYPE)
         for i in range(n_streams):
             got = self._lib.efx_encode_picture_info(self._ctx, i, out[i].ctypes.data_as(C.POINTER(_EncPictureInfo)), count)
             if got < 0:
@@ -1871,10 +1571,9 @@ class Decoder:
                             overlay: DeviceBuffer | int | None = None, overlay_stride: int = 0, overlay_blend: int = 0,
                             overlay_progress: int = 0):
         """video_isr with the two-frame slide (_hscroll) and the overlay / progress bar (composite())."""
-        g = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else b)
         o = _FieldOpts(first_stream, n_streams, slot, slot if other_slot is None else other_slot, 1 if ntsc else 0,
-                       frame_counter, hscroll, g(overlay), overlay_stride, overlay_blend, overlay_progress)
-        _check(self._ctx, self._lib.efx_composite_fields_ex(self._ctx, C.byref(o), g(dst)))
+                       frame_counter, hscroll, _ptr(overlay), overlay_stride, overlay_blend, overlay_progress)
+        _check(self._ctx, self._lib.efx_composite_fields_ex(self._ctx, C.byref(o), _ptr(dst)))
 
     def demux_audio(self, streams, audio: DeviceBuffer | int, stride: int, audio_len: DeviceBuffer | int):
         """Audio elementary streams (push_audio's input) of a batch of transport streams, on the device."""
@@ -1883,8 +1582,7 @@ class Decoder:
         n = len(arrs)
         ptrs = (_P * n)(*[a.ctypes.data for a in arrs])
         lens = (C.c_size_t * n)(*[a.size for a in arrs])
-        g = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
-        _check(self._ctx, self._lib.efx_demux_audio(self._ctx, n, ptrs, lens, g(audio), stride, g(audio_len)))
+        _check(self._ctx, self._lib.efx_demux_audio(self._ctx, n, ptrs, lens, _ptr(audio), stride, _ptr(audio_len)))
 
     def index_streams(self, streams, trick_speed=None, bin_size: int = 7500, samples_cap: int = 0):
         """make_index + pts2seq for a batch of transport streams.  Returns [(rec dict, samples)]."""
@@ -1904,9 +1602,8 @@ class Decoder:
     def sbc_decode(self, n_streams: int, frames: DeviceBuffer | int, stream_stride: int, frame_bytes: int, n_frames: int,
                    state: DeviceBuffer | int, pcm: DeviceBuffer | int, pcm_stride: int, ret: DeviceBuffer | int | None = None,
                    pcm_count: DeviceBuffer | int | None = None, probe_first: bool = False):
-        g = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else b)
-        _check(self._ctx, self._lib.efx_sbc_decode(self._ctx, n_streams, g(frames), stream_stride, frame_bytes, n_frames,
-                                                   g(state), g(pcm), pcm_stride, g(ret), g(pcm_count), 1 if probe_first else 0))
+        _check(self._ctx, self._lib.efx_sbc_decode(self._ctx, n_streams, _ptr(frames), stream_stride, frame_bytes, n_frames,
+                                                   _ptr(state), _ptr(pcm), pcm_stride, _ptr(ret), _ptr(pcm_count), 1 if probe_first else 0))
 
     # -- sound in (efx_import_pcm) -----------------------------------------------------------
     def import_pcm_to(self, src: DeviceBuffer | int, state: DeviceBuffer | int | None, dst: DeviceBuffer | int, *, n_streams: int,
@@ -1917,15 +1614,13 @@ class Decoder:
         mono samples at out_rate at dst + i x dst_stride elements (0 = the call's output count rounded up to 8), the
         streams' states (import_pcm_state_bytes() each, zeros = fresh; None only for equal rates) updated in place.
         weights: up to 8 Q15 downmix weights (None: 32768 // channels each).  Returns the call's output count."""
-        g = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else b)
         w = [int(v) for v in (weights if weights is not None else ())]
         if len(w) > 8:
             raise ValueError("at most 8 downmix weights")
         n_out = import_pcm_out_samples(in_rate, out_rate, first_in, n_in) if n_in >= 0 else -1
-        r8 = lambda v: (v + 7) // 8 * 8
         o = _ImportPcmOpts(n_streams, n_in, in_rate, out_rate, channels, layout, (C.c_int * 8)(*(w + [0] * (8 - len(w)))), first_in,
-                           src_stride or r8(max(0, n_in * channels)), dst_stride or r8(max(0, n_out)))
-        _check(self._ctx, self._lib.efx_import_pcm(self._ctx, C.byref(o), g(src), g(state), g(dst)))
+                           src_stride or _r8(max(0, n_in * channels)), dst_stride or _r8(max(0, n_out)))
+        _check(self._ctx, self._lib.efx_import_pcm(self._ctx, C.byref(o), _ptr(src), _ptr(state), _ptr(dst)))
         return n_out
 
     def import_pcm(self, pcm, *, rate: int, out_rate: int = 48000, layout: str = "interleaved", weights=None, cont: bool = False,
@@ -1969,23 +1664,18 @@ class Decoder:
                 raise EfxError(-5, "import_pcm: cont without a previous import_pcm of as many streams, channels and the same rates")
             st = (key, torch.zeros((n, import_pcm_state_bytes()), dtype=torch.uint8, device=device), 0)
         _, state, first_in = st
-        r8 = lambda v: (v + 7) // 8 * 8
-        src_stride = r8(frames * channels)
-        src = pcm.contiguous().view(n, frames * channels)
-        if src_stride != frames * channels or src.data_ptr() % 16:
-            padded = torch.zeros((n, src_stride), dtype=torch.int16, device=device)
-            padded[:, :frames * channels] = src
-            src = padded
         n_out = import_pcm_out_samples(rate, out_rate, first_in, frames)
         if n_out < 0:
             raise ValueError("too many frames for one call")
-        dst_stride = r8(max(n_out, 1))
-        out = torch.zeros((n, dst_stride), dtype=torch.int16, device=device)
-        torch.cuda.current_stream(device).synchronize()
-        self.import_pcm_to(src.data_ptr(), state.data_ptr(), out.data_ptr(), n_streams=n, n_in=frames, in_rate=rate,
-                           out_rate=out_rate, channels=channels, layout=_PCM_LAYOUTS[layout], weights=weights, first_in=first_in,
-                           src_stride=src_stride, dst_stride=dst_stride)
-        self.sync()
+        src_stride, dst_stride = _r8(frames * channels), _r8(max(n_out, 1))
+        with self._scratch() as s:
+            src_ptr, _, _ = self._stage(s, pcm, n, frames * channels, stride=src_stride, dtype=np.int16, what="pcm")
+            out = torch.zeros((n, dst_stride), dtype=torch.int16, device=device)
+            self._wait_for_torch()
+            self.import_pcm_to(src_ptr, state.data_ptr(), out.data_ptr(), n_streams=n, n_in=frames, in_rate=rate,
+                               out_rate=out_rate, channels=channels, layout=_PCM_LAYOUTS[layout], weights=weights, first_in=first_in,
+                               src_stride=src_stride, dst_stride=dst_stride)
+            self.sync()
         self._import_pcm_state = (key, state, first_in + frames)
         return out[:, :n_out]
 
@@ -1999,13 +1689,12 @@ class Decoder:
         records (first_step None = first_sample // step; steps_stride 0 = first_step + the call's steps); the streams'
         states (loudness_state_bytes(rate) each, zeros = fresh) are updated in place.  A title fed in pieces carries
         first_sample (+= n_samples) and the state on.  Returns the count appended."""
-        g = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
         if first_step is None:
             first_step = first_sample // max(1, rate // 10)
         n_new = loudness_step_count(rate, first_sample, n_samples) if n_samples >= 0 else -1
         o = _LoudnessStepsOpts(n_streams, n_samples, rate, first_step, first_sample, pcm_stride or (max(0, n_samples) + 7) // 8 * 8,
                                steps_stride or first_step + max(0, n_new))
-        ret = self._lib.efx_loudness_steps(self._ctx, C.byref(o), g(pcm), g(state), g(steps))
+        ret = self._lib.efx_loudness_steps(self._ctx, C.byref(o), _ptr(pcm), _ptr(state), _ptr(steps))
         if ret < 0:
             _check(self._ctx, ret)
         return ret
@@ -2017,55 +1706,28 @@ class Decoder:
         (steps_stride records apart, 0 = n_steps) become one 32-byte record per stream (LOUDNESS_REC_DTYPE) at recs: both
         gates, the largest block, the peak (with a state: its samples included) and the gain to `target` LUFS under `peak`
         dBFS.  thresholds: (abs_thr, target_ms, ceiling) instead of loudness_thresholds(rate, target, peak)."""
-        g = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else b)
         a, t, c = thresholds if thresholds is not None else loudness_thresholds(rate, target, peak)
         o = _LoudnessGateOpts(n_streams, n_steps, rate, a, t, c, steps_stride or max(0, n_steps))
-        _check(self._ctx, self._lib.efx_loudness_gate(self._ctx, C.byref(o), g(steps), g(state), g(recs)))
+        _check(self._ctx, self._lib.efx_loudness_gate(self._ctx, C.byref(o), _ptr(steps), _ptr(state), _ptr(recs)))
 
     def pcm_gain_to(self, src: DeviceBuffer | int, recs: DeviceBuffer | int | None, dst: DeviceBuffer | int, *, n_streams: int,
                     n_samples: int, fixed_gain_q12: int = 4096, src_stride: int = 0, dst_stride: int = 0):
         """efx_pcm_gain on raw device memory, asynchronous on the library's stream: dst = clamp16((src x g + 2048) >> 12),
         each stream's g read on the device from its record at recs (None: fixed_gain_q12 for all).  dst may be src.
         Strides in elements, 0 = n_samples rounded up to 8."""
-        g = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else b)
         r8 = (max(0, n_samples) + 7) // 8 * 8
         o = _PcmGainOpts(n_streams, n_samples, fixed_gain_q12, src_stride or r8, dst_stride or r8)
-        _check(self._ctx, self._lib.efx_pcm_gain(self._ctx, C.byref(o), g(src), g(recs), g(dst)))
+        _check(self._ctx, self._lib.efx_pcm_gain(self._ctx, C.byref(o), _ptr(src), _ptr(recs), _ptr(dst)))
 
-    def _loudness_pcm(self, pcm):
-        """[n, samples] int16 on the device, rows 16-byte aligned: (tensor, n, samples, stride)."""
-        import torch
-        device = torch.device("cuda", self.device)
-        if isinstance(pcm, np.ndarray):
-            pcm = torch.from_numpy(np.ascontiguousarray(pcm, dtype=np.int16)).to(device)
-        if not isinstance(pcm, torch.Tensor) or pcm.dtype != torch.int16 or pcm.device != device or pcm.dim() != 2 or pcm.shape[1] < 1:
-            raise ValueError(f"pcm must be int16 [n_streams, samples] on {device} (or a NumPy array)")
-        n, samples = int(pcm.shape[0]), int(pcm.shape[1])
-        stride = (samples + 7) // 8 * 8
-        src = pcm.contiguous()
-        if stride != samples or src.data_ptr() % 16:
-            src = torch.zeros((n, stride), dtype=torch.int16, device=device)
-            src[:, :samples] = pcm
-        return src, n, samples, stride
-
-    def _loudness_buffers(self, n: int, samples: int, rate: int, target: float, peak: float):
-        """What measuring n fresh streams of `samples` samples needs, made ready: [state (zeroed), steps, records] on the
-        device, the step count and the thresholds.  The upload synchronises the library's stream, so this comes before
-        anything is queued that the host is not to wait for."""
+    def _loudness_buffers(self, s: _Scratch, n: int, samples: int, rate: int, target: float, peak: float):
+        """What measuring n fresh streams of `samples` samples needs, made ready in the scratch s: (state (zeroed), steps,
+        records) on the device, the step count and the thresholds.  The upload synchronises the library's stream, so
+        this comes before anything is queued that the host is not to wait for."""
         n_steps = loudness_step_count(rate, 0, samples)
         if n_steps < 0:
             raise ValueError("rate must be 16000, 32000, 44100 or 48000")
         thr = loudness_thresholds(rate, target, peak)
-        bufs = []
-        try:
-            for nbytes in (n * loudness_state_bytes(rate), 16 * n * max(1, n_steps), 32 * n):
-                bufs.append(DeviceBuffer(self, nbytes))
-            bufs[0].upload(np.zeros(n * loudness_state_bytes(rate), dtype=np.uint8))
-        except Exception:
-            for b in bufs:
-                b.free()
-            raise
-        return bufs, n_steps, thr
+        return (s.zeros(n * loudness_state_bytes(rate)), s.alloc(16 * n * max(1, n_steps)), s.alloc(32 * n)), n_steps, thr
 
     def _loudness_queue(self, src_ptr: int, n: int, samples: int, stride: int, rate: int, prepared):
         """steps -> gate with _loudness_buffers' result: launches only, nothing synchronised.  Returns the records' buffer."""
@@ -2092,18 +1754,7 @@ class Decoder:
         or a torch tensor on the decoder's device), every stream from its first sample, measured on the device by ITU-R
         BS.1770-4 / EBU R 128 (include/efx.h), and the gain that would take each stream to `target` LUFS with its sample
         peak no higher than `peak` dBFS.  Synchronises torch's current stream before and the library's after."""
-        import torch
-        src, n, samples, stride = self._loudness_pcm(pcm)
-        torch.cuda.current_stream(src.device).synchronize()
-        prepared = self._loudness_buffers(n, samples, rate, target, peak)
-        bufs = prepared[0]
-        try:
-            d_recs = self._loudness_queue(src.data_ptr(), n, samples, stride, rate, prepared)
-            self.sync()
-            return self._loudness_result(d_recs.download(np.uint8, 32 * n).view(LOUDNESS_REC_DTYPE), rate)
-        finally:
-            for b in bufs:
-                b.free()
+        return self._measure(pcm, rate, target, peak, gain=False)[1]
 
     def normalize(self, pcm, rate: int, *, target: float = -23.0, peak: float = -1.0):
         """loudness() and the gain applied, measure -> gate -> gain queued back to back with the gain read on the device:
@@ -2114,22 +1765,30 @@ class Decoder:
         A title fed in pieces needs the whole title measured before its first sample is scaled, so it takes two passes
         over the *_to calls: loudness_steps_to over every piece (first_sample and the state carried on), one
         loudness_gate_to over all its steps, then pcm_gain_to per piece with the records it left."""
+        out, res = self._measure(pcm, rate, target, peak, gain=True)
+        return (out.cpu().numpy() if isinstance(pcm, np.ndarray) else out), res
+
+    def _measure(self, pcm, rate: int, target: float, peak: float, gain: bool):
+        """loudness() and normalize(): (the scaled PCM as a tensor [n_streams, samples] when gain, else None, the result)."""
         import torch
-        src, n, samples, stride = self._loudness_pcm(pcm)
-        out = torch.empty((n, stride), dtype=torch.int16, device=src.device)
-        torch.cuda.current_stream(src.device).synchronize()
-        prepared = self._loudness_buffers(n, samples, rate, target, peak)
-        bufs = prepared[0]
-        try:
-            d_recs = self._loudness_queue(src.data_ptr(), n, samples, stride, rate, prepared)
-            self.pcm_gain_to(src.data_ptr(), d_recs, out.data_ptr(), n_streams=n, n_samples=samples, src_stride=stride, dst_stride=stride)
+        device = torch.device("cuda", self.device)
+        if isinstance(pcm, np.ndarray):
+            pcm = torch.from_numpy(np.ascontiguousarray(pcm, dtype=np.int16)).to(device)
+        if len(getattr(pcm, "shape", ())) != 2 or pcm.shape[1] < 1:
+            raise ValueError(f"pcm must be int16 [n_streams, samples] on {device} (or a NumPy array)")
+        n, samples = int(pcm.shape[0]), int(pcm.shape[1])
+        stride = _r8(samples)
+        with self._scratch() as s:
+            src_ptr, _, _ = self._stage(s, pcm, n, samples, stride=stride, dtype=np.int16, what="pcm")
+            out = torch.empty((n, stride), dtype=torch.int16, device=device) if gain else None
+            self._wait_for_torch()
+            prepared = self._loudness_buffers(s, n, samples, rate, target, peak)
+            d_recs = self._loudness_queue(src_ptr, n, samples, stride, rate, prepared)
+            if gain:
+                self.pcm_gain_to(src_ptr, d_recs, out.data_ptr(), n_streams=n, n_samples=samples, src_stride=stride, dst_stride=stride)
             self.sync()
             res = self._loudness_result(d_recs.download(np.uint8, 32 * n).view(LOUDNESS_REC_DTYPE), rate)
-        finally:
-            for b in bufs:
-                b.free()
-        out = out[:, :samples]
-        return (out.cpu().numpy() if isinstance(pcm, np.ndarray) else out), res
+        return (out[:, :samples] if gain else None), res
 
     # -- SBC encode (efx_sbc_encode) and A/V multiplexing (efx_mux_av) ------------------------------
     def sbc_encode_to(self, pcm: DeviceBuffer | int, state: DeviceBuffer | int, frames: DeviceBuffer | int, *, n_streams: int,
@@ -2139,12 +1798,11 @@ class Decoder:
         pcm_stride elements (0 = packed), its frames back to back from frames + i x frame_stride bytes (0 = the frames'
         size rounded up to 16), the encoders' states (sbc_enc_state_bytes() each, zeros = fresh) updated in place.  Returns
         the frame stride used."""
-        g = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
         ch = 2 if mode else 1
         fb = sbc_frame_bytes(blocks, ch, bitpool)
         o = _SbcEncodeOpts(n_streams, n_frames, frequency, blocks, mode, allocation, bitpool, pcm_layout,
                            pcm_stride or n_frames * blocks * 8 * ch, frame_stride or (n_frames * fb + 15) // 16 * 16)
-        _check(self._ctx, self._lib.efx_sbc_encode(self._ctx, C.byref(o), g(pcm), g(state), g(frames)))
+        _check(self._ctx, self._lib.efx_sbc_encode(self._ctx, C.byref(o), _ptr(pcm), _ptr(state), _ptr(frames)))
         return o.frame_stride
 
     def sbc_encode(self, pcm, *, blocks: int = 16, mode: int = 0, allocation: int = 0, bitpool: int = 28, frequency: int = 3,
@@ -2158,9 +1816,8 @@ class Decoder:
         device = torch.device("cuda", self.device)
         if isinstance(pcm, np.ndarray):
             pcm = torch.from_numpy(np.ascontiguousarray(pcm, dtype=np.int16)).to(device)
-        if pcm.dtype != torch.int16 or pcm.device != device or pcm.dim() != 2:
+        if len(getattr(pcm, "shape", ())) != 2:
             raise ValueError(f"pcm must be an int16 [n_streams, samples] tensor on {device} (or a NumPy array)")
-        pcm = pcm.contiguous()
         ch = 2 if mode else 1
         n, per = pcm.shape[0], blocks * 8 * ch
         if pcm.shape[1] == 0 or pcm.shape[1] % per:
@@ -2174,13 +1831,16 @@ class Decoder:
             if cont:
                 raise EfxError(-5, "sbc_encode: cont without a previous sbc_encode of as many streams")
             st = torch.zeros((n, sbc_enc_state_bytes()), dtype=torch.uint8, device=device)
-        stride = (n_frames * fb + 15) // 16 * 16
+        stride = _r16(n_frames * fb)
         out = torch.empty((n, stride), dtype=torch.uint8, device=device)
-        torch.cuda.current_stream(device).synchronize()
-        self.sbc_encode_to(pcm.data_ptr(), st.data_ptr(), out.data_ptr(), n_streams=n, n_frames=n_frames, blocks=blocks, mode=mode,
-                           allocation=allocation, bitpool=bitpool, frequency=frequency, pcm_layout=pcm_layout,
-                           pcm_stride=pcm.shape[1], frame_stride=stride)
-        self.sync()
+        with self._scratch() as s:
+            # (a whole number of frames: rows of a multiple of 32 samples, packed)
+            pcm_ptr, _, _ = self._stage(s, pcm, n, pcm.shape[1], stride=pcm.shape[1], dtype=np.int16, what="pcm")
+            self._wait_for_torch()
+            self.sbc_encode_to(pcm_ptr, st.data_ptr(), out.data_ptr(), n_streams=n, n_frames=n_frames, blocks=blocks, mode=mode,
+                               allocation=allocation, bitpool=bitpool, frequency=frequency, pcm_layout=pcm_layout,
+                               pcm_stride=pcm.shape[1], frame_stride=stride)
+            self.sync()
         self._sbc_enc_state = st
         return out[:, :n_frames * fb].reshape(n, n_frames, fb)
 
@@ -2191,10 +1851,9 @@ class Decoder:
                audio_first_frame: int = 0, audio_cc: int = 0):
         """efx_mux_av on raw device memory, asynchronous on the library's stream: video / video_len are what encode_to left in
         dst / length, so encode_to -> sbc_encode_to -> mux_to needs no synchronisation in between."""
-        g = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else b)
         o = _MuxOpts(n_streams, audio_pid, frame_bytes, n_frames, frames_per_pes, samples_per_frame, sample_rate, audio_first_pts,
                      audio_first_frame, audio_cc, video_stride, audio_stride, dst_stride)
-        _check(self._ctx, self._lib.efx_mux_av(self._ctx, C.byref(o), g(video), g(video_len), g(audio), g(dst), g(length), g(status)))
+        _check(self._ctx, self._lib.efx_mux_av(self._ctx, C.byref(o), _ptr(video), _ptr(video_len), _ptr(audio), _ptr(dst), _ptr(length), _ptr(status)))
 
     def mux(self, video_streams, frames, *, frames_per_pes: int = 8, audio_pid: int = 0x101, samples_per_frame: int = 128,
             sample_rate: int = 48000, audio_first_pts: int = 0, audio_first_frame: int = 0, audio_cc: int = 0,
@@ -2211,33 +1870,24 @@ class Decoder:
         if frames.ndim != 3 or frames.shape[0] != n:
             raise ValueError("frames must have shape (n_streams, n_frames, frame_bytes)")
         n_frames, fb = frames.shape[1], frames.shape[2]
-        r16 = lambda v: (v + 15) // 16 * 16
-        v_stride = r16(max(1, max(a.size for a in arrs)))
-        a_stride = r16(max(1, n_frames * fb))
+        v_stride = _r16(max(1, max(a.size for a in arrs)))
+        a_stride = _r16(max(1, n_frames * fb))
         stride = dst_stride or mux_bound(v_stride, n_frames, fb, frames_per_pes)
-        bufs = []
-        try:
-            d_v, d_a, d_dst = (DeviceBuffer(self, n * v_stride), DeviceBuffer(self, n * a_stride), DeviceBuffer(self, n * stride))
-            d_meta = DeviceBuffer(self, 3 * r16(4 * n))
-            bufs += [d_v, d_a, d_dst, d_meta]
+        with self._scratch() as s:
             host_v = np.zeros((n, v_stride), dtype=np.uint8)
             for i, a in enumerate(arrs):
                 host_v[i, :a.size] = a
-            d_v.upload(host_v)
-            host_a = np.zeros((n, a_stride), dtype=np.uint8)
-            host_a[:, :n_frames * fb] = frames.reshape(n, -1)
-            d_a.upload(host_a)
+            v_ptr, _, _ = self._stage(s, host_v, n, v_stride)
+            a_ptr, _, _ = self._stage(s, frames, n, n_frames * fb, stride=a_stride)
+            d_dst, d_meta = s.alloc(n * stride), s.alloc(3 * _r16(4 * n))
             d_meta.upload(np.array([a.size for a in arrs], dtype=np.uint32))
-            p_len, p_st = d_meta.ptr + r16(4 * n), d_meta.ptr + 2 * r16(4 * n)
-            self.mux_to(d_v, d_meta.ptr, d_a, d_dst, p_len, p_st, n_streams=n, frame_bytes=fb, n_frames=n_frames,
+            p_len, p_st = d_meta.ptr + _r16(4 * n), d_meta.ptr + 2 * _r16(4 * n)
+            self.mux_to(v_ptr, d_meta.ptr, a_ptr, d_dst, p_len, p_st, n_streams=n, frame_bytes=fb, n_frames=n_frames,
                         video_stride=v_stride, audio_stride=a_stride, dst_stride=stride, frames_per_pes=frames_per_pes,
                         audio_pid=audio_pid, samples_per_frame=samples_per_frame, sample_rate=sample_rate,
                         audio_first_pts=audio_first_pts, audio_first_frame=audio_first_frame, audio_cc=audio_cc)
             self.sync()
             return self._download_streams(d_dst.ptr, stride, p_len, p_st, n)
-        finally:
-            for b in bufs:
-                b.free()
 
     def _download_streams(self, dst_ptr: int, stride: int, len_ptr: int, status_ptr: int, n: int):
         lens, st = np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint32)
@@ -2304,65 +1954,57 @@ class Decoder:
             n_out = import_pcm_out_samples(pcm_rate, sample_rate, 0, in_frames)
             if in_frames < 1 or not 1 <= in_ch <= 8 or n_out < 0:
                 raise ValueError("pcm: no frames, too many frames or more than 8 channels")
-            src_stride = (in_frames * in_ch + 7) // 8 * 8
-            src = torch.zeros((int(pcm.shape[0]), src_stride), dtype=torch.int16, device=device)
-            src[:, :in_frames * in_ch] = pcm.contiguous().view(int(pcm.shape[0]), -1)
             frequency = _SBC_FREQUENCY[sample_rate]
+            imp = (pcm, in_frames, in_ch, _r8(in_frames * in_ch))
             # the resampled stream, zero-padded to whole frames: what sbc_encode_to reads
             pcm = torch.zeros((int(pcm.shape[0]), -(-n_out // (blocks * 8)) * blocks * 8), dtype=torch.int16, device=device)
-            imp = (src, in_frames, in_ch, src_stride)
         if pictures.dtype != torch.uint8 or pictures.dim() != 3 or pictures.shape[-1] != FRAME_BYTES or pictures.device != device:
             raise ValueError(f"pictures must be uint8 (n, P, {FRAME_BYTES}) on {device}")
         n, P = int(pictures.shape[0]), int(pictures.shape[1])
         if pcm.dtype != torch.int16 or pcm.dim() != 2 or pcm.shape[0] != n or pcm.device != device or pcm.shape[1] % (blocks * 8):
             raise ValueError("pcm must be int16 [n, samples], samples a multiple of blocks x 8")
-        pictures, pcm = pictures.contiguous(), pcm.contiguous()
-        n_frames = int(pcm.shape[1]) // (blocks * 8)
+        samples = int(pcm.shape[1])
+        n_frames = samples // (blocks * 8)
         fb = sbc_frame_bytes(blocks, 1, bitpool)
-        r16 = lambda v: (v + 15) // 16 * 16
         v_stride = encode_bound(FORMAT_TS, P)
-        a_stride = r16(max(1, n_frames * fb))
+        a_stride = _r16(max(1, n_frames * fb))
         stride = mux_bound(v_stride, n_frames, fb, frames_per_pes)
-        bufs = []
-        try:
-            d_v, d_a, d_dst = DeviceBuffer(self, n * v_stride), DeviceBuffer(self, n * a_stride), DeviceBuffer(self, n * stride)
-            d_meta, d_state = DeviceBuffer(self, 4 * r16(4 * n)), DeviceBuffer(self, n * sbc_enc_state_bytes())
-            bufs += [d_v, d_a, d_dst, d_meta, d_state]
-            d_state.upload(np.zeros(n * sbc_enc_state_bytes(), dtype=np.uint8))
+        with self._scratch() as s:
+            d_v, d_a, d_dst = s.alloc(n * v_stride), s.alloc(n * a_stride), s.alloc(n * stride)
+            d_meta, d_state = s.alloc(4 * _r16(4 * n)), s.zeros(n * sbc_enc_state_bytes())
             if imp is not None:
-                d_istate = DeviceBuffer(self, n * import_pcm_state_bytes())
-                bufs.append(d_istate)
-                d_istate.upload(np.zeros(n * import_pcm_state_bytes(), dtype=np.uint8))
-            p_vlen, p_vst, p_len, p_st = (d_meta.ptr + k * r16(4 * n) for k in range(4))
+                d_istate = s.zeros(n * import_pcm_state_bytes())
+            p_vlen, p_vst, p_len, p_st = (d_meta.ptr + k * _r16(4 * n) for k in range(4))
             d_rec = d_qual = None
             if quality and n * P:
-                d_rec, d_qual = DeviceBuffer(self, n * P * FRAME_BYTES), DeviceBuffer(self, 48 * n * P)
-                bufs += [d_rec, d_qual]
+                d_rec, d_qual = s.alloc(n * P * FRAME_BYTES), s.alloc(48 * n * P)
             loud = None
             if loudness is not None and n_frames:
                 # (buffers and the zeroed state now: an upload waits for what is queued on the library's stream)
                 loud_rate = {v: k for k, v in _SBC_FREQUENCY.items()}[frequency]
-                loud = self._loudness_buffers(n, int(pcm.shape[1]), loud_rate, loudness, peak)
-                bufs += loud[0]
+                loud = self._loudness_buffers(s, n, samples, loud_rate, loudness, peak)
                 if imp is None:
                     pcm = pcm.clone()  # (scaled in place: the caller's tensor stays as it is)
-            torch.cuda.current_stream(device).synchronize()
-            self.encode_to(pictures.data_ptr(), d_v, p_vlen, p_vst, n_streams=n, n_pictures=P, qscale=qscale, gop=gop, search=search,
+            pic_ptr, _, _ = self._stage(s, pictures, n * P, FRAME_BYTES, what="pictures")
+            pcm_ptr, _, _ = self._stage(s, pcm, n, samples, stride=samples, dtype=np.int16, what="pcm")  # (whole frames: packed)
+            if imp is not None:
+                imp_ptr, _, _ = self._stage(s, imp[0], n, imp[1] * imp[2], stride=imp[3], dtype=np.int16, what="pcm")
+            self._wait_for_torch()
+            self.encode_to(pic_ptr, d_v, p_vlen, p_vst, n_streams=n, n_pictures=P, qscale=qscale, gop=gop, search=search,
                            fmt=FORMAT_TS, first_pts=first_pts, dst_stride=v_stride, bitrate=bitrate, vbv_bits=vbv_bits, qmin=qmin,
                            qmax=qmax, fps=fps, scene_cut=scene_cut, min_gop=min_gop, recon=d_rec, aq=aq)
             if d_qual is not None:
-                self.compare_to(pictures.data_ptr(), d_rec, d_qual, n_images=n * P, ref_max=248)
+                self.compare_to(pic_ptr, d_rec, d_qual, n_images=n * P, ref_max=248)
             if imp is not None:
-                self.import_pcm_to(imp[0].data_ptr(), d_istate, pcm.data_ptr(), n_streams=n, n_in=imp[1], in_rate=pcm_rate,
+                self.import_pcm_to(imp_ptr, d_istate, pcm_ptr, n_streams=n, n_in=imp[1], in_rate=pcm_rate,
                                    out_rate=sample_rate, channels=imp[2], layout=_PCM_LAYOUTS[pcm_layout], src_stride=imp[3],
-                                   dst_stride=int(pcm.shape[1]))
+                                   dst_stride=samples)
             if loud is not None:
-                d_lrecs = self._loudness_queue(pcm.data_ptr(), n, int(pcm.shape[1]), int(pcm.shape[1]), loud_rate, loud)
-                self.pcm_gain_to(pcm.data_ptr(), d_lrecs, pcm.data_ptr(), n_streams=n, n_samples=int(pcm.shape[1]),
-                                 src_stride=int(pcm.shape[1]), dst_stride=int(pcm.shape[1]))
+                d_lrecs = self._loudness_queue(pcm_ptr, n, samples, samples, loud_rate, loud)
+                self.pcm_gain_to(pcm_ptr, d_lrecs, pcm_ptr, n_streams=n, n_samples=samples, src_stride=samples, dst_stride=samples)
             if n_frames:
-                self.sbc_encode_to(pcm.data_ptr(), d_state, d_a, n_streams=n, n_frames=n_frames, blocks=blocks, mode=0,
-                                   allocation=allocation, bitpool=bitpool, frequency=frequency, pcm_stride=int(pcm.shape[1]),
+                self.sbc_encode_to(pcm_ptr, d_state, d_a, n_streams=n, n_frames=n_frames, blocks=blocks, mode=0,
+                                   allocation=allocation, bitpool=bitpool, frequency=frequency, pcm_stride=samples,
                                    frame_stride=a_stride)
             self.mux_to(d_v, p_vlen, d_a, d_dst, p_len, p_st, n_streams=n, frame_bytes=fb, n_frames=n_frames, video_stride=v_stride,
                         audio_stride=a_stride, dst_stride=stride, frames_per_pes=frames_per_pes, audio_pid=audio_pid,
@@ -2376,9 +2018,6 @@ class Decoder:
                 qual = self._encode_quality(d_qual, n, P, types) if d_qual is not None else _compare_result(np.zeros((0, 6), np.uint64), (n, P))
                 return titles, st | vst, qual
             return titles, st | vst
-        finally:
-            for b in bufs:
-                b.free()
 
     # -- picture rates (efx_conform_rate) ----------------------------------------------------------------
     def conform_to(self, src: DeviceBuffer | int, dst: DeviceBuffer | int, *, n_streams: int, n_pictures: int, fps_in, fps_out,
@@ -2388,7 +2027,6 @@ class Decoder:
         "num/den", int or float), stream i's at src + i * src_stride (0 = packed), become the output pictures at fps_out
         (a coded rate) that show them, by dropping and repeating pictures (the rule: include/efx.h), stream i's at dst + i *
         dst_stride (0 = packed: the call's outputs).  Returns the call's outputs (conform_count)."""
-        g = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
         f, code = _rate(fps_in), _fps_code(fps_out)
         n_out = conform_count(f, fps_out, first_picture, n_pictures)
         if n_out < 0:
@@ -2396,7 +2034,7 @@ class Decoder:
                              f"n_pictures={n_pictures} are out of range (efx_conform_rate)")
         o = _ConformOpts(n_streams, n_pictures, f.numerator, f.denominator, code, first_picture,
                          src_stride or n_pictures * FRAME_BYTES, dst_stride or n_out * FRAME_BYTES)
-        _check(self._ctx, self._lib.efx_conform_rate(self._ctx, C.byref(o), g(src), g(dst)))
+        _check(self._ctx, self._lib.efx_conform_rate(self._ctx, C.byref(o), _ptr(src), _ptr(dst)))
         return n_out
 
     def conform(self, pictures, fps_in, fps_out, *, first_picture: int = 0):
@@ -2410,32 +2048,15 @@ class Decoder:
         n_out = conform_count(fps_in, fps_out, first_picture, P)
         if n_out < 0:
             raise ValueError(f"conform {fps_in!r} -> {fps_out!r}: out of range (efx_conform_rate)")
-        bufs = []
-        try:
-            if isinstance(pictures, np.ndarray):
-                sbuf, dbuf = DeviceBuffer(self, pictures.size), DeviceBuffer(self, max(1, n * n_out * FRAME_BYTES))
-                bufs += [sbuf, dbuf]
-                sbuf.upload(np.ascontiguousarray(pictures, dtype=np.uint8))
-                self.conform_to(sbuf, dbuf, n_streams=n, n_pictures=P, fps_in=fps_in, fps_out=fps_out, first_picture=first_picture)
-                self.sync()
-                return dbuf.download(np.uint8, n * n_out * FRAME_BYTES).reshape(n, n_out, FRAME_BYTES)
-            import torch
-            device = torch.device("cuda", self.device)
-            if not isinstance(pictures, torch.Tensor) or pictures.dtype != torch.uint8 or pictures.device != device:
-                raise ValueError(f"pictures must be a uint8 tensor on {device} (or a NumPy array)")
-            src = pictures.contiguous()
-            if src.data_ptr() % 16:
-                src = src.clone()
-            out = torch.empty((n, n_out, FRAME_BYTES), dtype=torch.uint8, device=device)
-            torch.cuda.current_stream(device).synchronize()
-            if n_out:
-                self.conform_to(src.data_ptr(), out.data_ptr(), n_streams=n, n_pictures=P, fps_in=fps_in, fps_out=fps_out,
-                                first_picture=first_picture)
+        with self._scratch() as s:
+            src_ptr, is_array, _ = self._stage(s, pictures, n * P, FRAME_BYTES, what="pictures")
+            if not is_array:
+                self._wait_for_torch()
+            dst_ptr, fetch = self._rows_out(s, is_array, n, n_out * FRAME_BYTES, n_out * FRAME_BYTES)
+            if n_out:  # (no output pictures: nothing to queue, and an empty tensor has no address)
+                self.conform_to(src_ptr, dst_ptr, n_streams=n, n_pictures=P, fps_in=fps_in, fps_out=fps_out, first_picture=first_picture)
             self.sync()
-            return out
-        finally:
-            for b in bufs:
-                b.free()
+            return fetch().reshape(n, n_out, FRAME_BYTES)
 
     def make_poster(self, image, *, qscale: int = 2, fps=24, **import_kw) -> bytes:
         """poster.ts of a title, which the reference's player opens for every title it browses (src/espflix.cpp:1060-1068)
@@ -2464,13 +2085,12 @@ class Decoder:
         source TRICK_FROM_I420: stream i's pictures at src + i * src_stride (0 = packed); TRICK_FROM_RING: src is None,
         picture j is picture j of the most recent decode of stream first_stream + i.  fwd_stride / rwd_stride 0 = packed
         (the call's picks / K images).  Returns the call's picks (trick_count)."""
-        g = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else b)
         picks = trick_count(first_picture, n_pictures, speed)
         K = trick_count(0, max(0, total_pictures), speed)
         o = _TrickOpts(n_streams, n_pictures, speed, source, first_stream, first_picture, total_pictures,
                        src_stride or max(0, n_pictures) * FRAME_BYTES, fwd_stride or max(0, picks) * FRAME_BYTES,
                        rwd_stride or max(0, K) * FRAME_BYTES)
-        _check(self._ctx, self._lib.efx_trick_pick(self._ctx, C.byref(o), g(src), g(fwd), g(rwd)))
+        _check(self._ctx, self._lib.efx_trick_pick(self._ctx, C.byref(o), _ptr(src), _ptr(fwd), _ptr(rwd)))
         return picks
 
     def trick_streams(self, pictures=None, *, title=None, speed: int = 15, gop: int = 3, qscale: int = 8, search: int = 7,
@@ -2501,28 +2121,14 @@ class Decoder:
         if not 1 <= speed <= 255:
             raise ValueError("speed must be 1 .. 255")
         _fps_code(fps)
-        bufs, keep = [], []
-        try:
+        with self._scratch() as s:
             if pictures is not None:
                 if len(pictures.shape) != 3 or pictures.shape[-1] != FRAME_BYTES or pictures.shape[1] < 1 or pictures.shape[0] < 1:
                     raise ValueError(f"pictures must have shape (n, P, {FRAME_BYTES}), got {tuple(pictures.shape)}")
                 n, P = int(pictures.shape[0]), int(pictures.shape[1])
-                if isinstance(pictures, np.ndarray):
-                    sbuf = DeviceBuffer(self, pictures.size)
-                    bufs.append(sbuf)
-                    sbuf.upload(np.ascontiguousarray(pictures, dtype=np.uint8))
-                    src_ptr = sbuf.ptr
-                else:
-                    import torch
-                    device = torch.device("cuda", self.device)
-                    if not isinstance(pictures, torch.Tensor) or pictures.dtype != torch.uint8 or pictures.device != device:
-                        raise ValueError(f"pictures must be a uint8 tensor on {device} (or a NumPy array)")
-                    pictures = pictures.contiguous()
-                    if pictures.data_ptr() % 16:
-                        pictures = pictures.clone()
-                    keep.append(pictures)
-                    torch.cuda.current_stream(device).synchronize()
-                    src_ptr = pictures.data_ptr()
+                src_ptr, is_array, _ = self._stage(s, pictures, n * P, FRAME_BYTES, what="pictures")
+                if not is_array:
+                    self._wait_for_torch()
                 step = P if piece is None else piece
                 if step < 1:
                     raise ValueError("piece must be >= 1")
@@ -2541,27 +2147,24 @@ class Decoder:
             pieces = [(first, min(step, P - first)) for first in range(0, P, step)]
             picks = [trick_count(first, cnt, speed) for first, cnt in pieces]
             fwd_cap = max(picks)
-            d_fwd, d_rwd = DeviceBuffer(self, n * fwd_cap * FRAME_BYTES), DeviceBuffer(self, n * K * FRAME_BYTES)
-            bufs += [d_fwd, d_rwd]
+            d_fwd, d_rwd = s.alloc(n * fwd_cap * FRAME_BYTES), s.alloc(n * K * FRAME_BYTES)
             # every encode call (at most 255 pictures) writes a region of its own; the bytes are put together at the end
             split = lambda c: [(a, min(255, c - a)) for a in range(0, c, 255)]
             calls = [[sub for c in picks for sub in split(c)], split(K)]
-            r16 = lambda v: (v + 15) // 16 * 16
             total = sum(n * encode_bound(FORMAT_TS, c) for side in calls for _, c in side)
-            d_dst, d_meta = DeviceBuffer(self, total), DeviceBuffer(self, 2 * r16(4 * n) * sum(len(side) for side in calls))
-            bufs += [d_dst, d_meta]
+            d_dst, d_meta = s.alloc(total), s.alloc(2 * _r16(4 * n) * sum(len(side) for side in calls))
             done = []  # (side, offset of the region in d_dst, its stride, offset of the byte counts in d_meta)
             state = {"dst": 0, "meta": 0}
 
             def encode_call(side, src, src_stride, count, cont):
                 stride = self.encode_to(src, d_dst.ptr + state["dst"], d_meta.ptr + state["meta"],
-                                        d_meta.ptr + state["meta"] + r16(4 * n), n_streams=n, n_pictures=count, qscale=qscale,
+                                        d_meta.ptr + state["meta"] + _r16(4 * n), n_streams=n, n_pictures=count, qscale=qscale,
                                         gop=gop, search=search, fmt=FORMAT_TS, cont=cont, first_pts=first_pts,
                                         src_stride=src_stride, bitrate=bitrate, vbv_bits=vbv_bits, qmin=qmin, qmax=qmax,
                                         fps=fps, aq=aq)
                 done.append((side, state["dst"], stride, state["meta"]))
                 state["dst"] += n * stride
-                state["meta"] += 2 * r16(4 * n)
+                state["meta"] += 2 * _r16(4 * n)
 
             started = False
             for (first, cnt), c in zip(pieces, picks):
@@ -2587,17 +2190,10 @@ class Decoder:
             self.sync()
             out, status = ([b""] * n, [b""] * n), np.zeros((2, n), dtype=np.uint32)
             for side, off, stride, meta in done:
-                part, st = self._download_streams(d_dst.ptr + off, stride, d_meta.ptr + meta, d_meta.ptr + meta + r16(4 * n), n)
+                part, st = self._download_streams(d_dst.ptr + off, stride, d_meta.ptr + meta, d_meta.ptr + meta + _r16(4 * n), n)
                 out[side][:] = [x + y for x, y in zip(out[side], part)]
                 status[side] |= st
             return out[0], out[1], status
-        finally:
-            try:
-                self.sync()  # (after an error: queued calls may still use the buffers)
-            except EfxError:
-                pass
-            for b in bufs:
-                b.free()
 
     def make_title(self, pictures, pcm, *, speed: int = 15, trick_gop: int = 3, fps=None, fps_out=None, poster=None, aq: int | bool | None = None,
                    **encode_av):
@@ -2655,8 +2251,7 @@ class Decoder:
 
     def pdm(self, n_streams: int, pcm: DeviceBuffer | int, n_samples: int, state: DeviceBuffer | int,
             dst: DeviceBuffer | int):
-        g = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
-        _check(self._ctx, self._lib.efx_pdm(self._ctx, n_streams, g(pcm), n_samples, g(state), g(dst)))
+        _check(self._ctx, self._lib.efx_pdm(self._ctx, n_streams, _ptr(pcm), n_samples, _ptr(state), _ptr(dst)))
 
     # -- measurement ----------------------------------------------------------------------
     def set_timing(self, enable: bool):
