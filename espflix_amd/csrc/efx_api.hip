@@ -2746,6 +2746,9 @@ int efx_pdm(efx_ctx* ctx, int n_streams, const int16_t* pcm_device, int n_sample
     bind_device(ctx);
     if (!ctx || !pcm_device || !state_device || !dst_device || n_streams <= 0 || n_samples <= 0)
         return EFX_ERR_ARG;
+    // k_pdm stores a sample's two words as one dword and reads the states as int32
+    if (((uintptr_t)dst_device | (uintptr_t)state_device) & 3)
+        return fail(ctx, EFX_ERR_ARG, "efx_pdm: dst_device and state_device must be 4-byte aligned");
     hipLaunchKernelGGL(k_pdm, dim3((n_streams + 63) / 64), dim3(64), 0, ctx->stream, pcm_device, n_streams, n_samples,
                        state_device, dst_device);
     EFX_HIP(hipGetLastError());

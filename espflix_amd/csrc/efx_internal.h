@@ -269,7 +269,7 @@ struct PcmGainArgs {
 
 // per-stream result of k_ts_sequences
 struct IdxInfo {
-    int64_t first_pts, last_pts;  // origin (PTS of the first sequence start), PTS of the last video PES
+    int64_t first_pts, last_pts;  // origin (PTS of the first sequence start whose PTS is not -1; -1: none), last video PES' PTS
     uint32_t n_seq;
     uint32_t fast;                // list sorted and short enough for the binary search
 };

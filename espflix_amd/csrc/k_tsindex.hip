@@ -54,6 +54,7 @@ __global__ __launch_bounds__(kThreads) void k_ts_sequences(const uint8_t* __rest
     __shared__ int64_t sh_pts[kThreads];   // this chunk's sequence PTS values in order
     __shared__ int64_t sh_last_video;      // PTS of the latest video PES header
     __shared__ int sh_last_tid;
+    __shared__ int sh_first_valid;         // rank of this chunk's first sequence start whose PTS parsed (kThreads: none)
     __shared__ int sh_unsorted;
 
     const int s = blockIdx.x, tid = threadIdx.x;
@@ -101,8 +102,10 @@ __global__ __launch_bounds__(kThreads) void k_ts_sequences(const uint8_t* __rest
         const uint32_t incl = wave_incl_scan_u32(is_seq ? 1u : 0u);
         if (lane == 63)
             sh_wave[wave] = incl;
-        if (tid == 0)
+        if (tid == 0) {
             sh_last_tid = -1;
+            sh_first_valid = kThreads;
+        }
         __syncthreads();
         uint32_t before = 0, total = 0;
 #pragma unroll
@@ -119,6 +122,8 @@ __global__ __launch_bounds__(kThreads) void k_ts_sequences(const uint8_t* __rest
             e.pts = pts;
             out[n_seq + rank] = e;
             sh_pts[rank] = pts;
+            if (pts != -1)
+                atomicMin(&sh_first_valid, (int)rank);
         }
         if (vstart)
             atomicMax(&sh_last_tid, tid);
@@ -131,10 +136,12 @@ __global__ __launch_bounds__(kThreads) void k_ts_sequences(const uint8_t* __rest
                 sh_unsorted = 1;
         }
         if (total) {  // wave-uniform bookkeeping, identical in every thread
-            if (!n_seq) {
-                origin = sh_pts[0];
-                min_pts = max_pts = origin;
-            }
+            // indexer.cpp:130-131: the origin is taken at every sequence start while it is still -1, so a damaged PTS
+            // (parsed as -1) leaves it to the next sequence start
+            if (origin == -1 && sh_first_valid < kThreads)
+                origin = sh_pts[sh_first_valid];
+            if (!n_seq)
+                min_pts = max_pts = sh_pts[0];
             // sorted lists only need the ends; unsorted ones take the slow path anyway
             min_pts = min(min_pts, min(sh_pts[0], sh_pts[total - 1]));
             max_pts = max(max_pts, max(sh_pts[0], sh_pts[total - 1]));

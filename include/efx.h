@@ -1164,7 +1164,11 @@ int efx_composite_fields_ex(efx_ctx* ctx, const efx_field_opts* opts, uint16_t* 
 /* -- PDM audio out (pdm_second_order / write_pcm_16, espflix.ino:73-145) ------------------ */
 /* n_streams independent modulators.  pcm: n_streams x n_samples int16 (stream-major, device);
  * state: n_streams x 3 int32 (_i0,_i1,_i2; device, updated in place); dst: n_streams x
- * 2*n_samples uint16 (device).  Asynchronous. */
+ * 2*n_samples uint16 (device).  Asynchronous.
+ * Alignment: dst_device and state_device must be 4-byte aligned (a sample's two words leave as one
+ * 32-bit store; EFX_ERR_ARG otherwise), pcm_device 2-byte aligned.  Streams whose PCM and output
+ * both start on a 16-byte boundary are read and written eight samples at a time; any other n_samples
+ * or alignment gives the same words, sample by sample. */
 int efx_pdm(efx_ctx* ctx, int n_streams, const int16_t* pcm_device, int n_samples, int32_t* state_device,
             uint16_t* dst_device);
 
@@ -1189,7 +1193,12 @@ typedef struct efx_idx_rec {
  * bin of bin_size ticks between the first such PTS and the last video PTS gets the packet number
  * of the nearest one.  recs[i] describes stream i (trick_speed[i] is recorded, 1 if the array is
  * NULL); its samples are written to samples + i * samples_cap.  A stream without a sequence header
- * gets sample_count 0.  Host pointers; synchronous. */
+ * gets sample_count 0.  efx_idx_rec.first_pts is the PTS of the first sequence start, in stream
+ * order, whose PTS is not -1 (a PTS field with a wrong marker nibble parses as -1, a PES without a
+ * PTS as 0; indexer.cpp:129-131); -1 if there is none (the bins then start at -1, as the
+ * indexer's do).  sample_count is also 0 when last_pts < first_pts.  EFX_ERR_CAPACITY: a stream
+ * needs more than samples_cap samples (its sample_count is 0, the other streams' records are
+ * complete).  Host pointers; synchronous. */
 int efx_index_streams(efx_ctx* ctx, int n_streams, const uint8_t* const* ts, const size_t* len, const uint32_t* trick_speed,
                       uint32_t bin_size, efx_idx_rec* recs, uint32_t* samples, size_t samples_cap);
 /* merge_index (indexer/indexer.cpp:219-237): the bytes of video.idx -- 'IDX', 3, the main /

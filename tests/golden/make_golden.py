@@ -16,7 +16,8 @@ Everything in golden.json is an output of the reference itself:
   composite  FNV of video_isr() fields (NTSC and PAL, 3 fields) for LCG / random / decoded frames
   pdm        FNV of write_pcm_16() output incl. silence and beep calls
   tables     zig_zag, scale_dct_q, _color_tab, video geometry
-(The directed streams of tests/syntax_streams.py have a file and a maker of their own: syntax.json, make_syntax_golden.py.)
+(The directed streams of tests/syntax_streams.py have a file and a maker of their own: syntax.json, make_syntax_golden.py;
+so have the index edge streams of tests/common.py: index_edges.json, make_index_edges_golden.py.)
 """
 import json
 import os

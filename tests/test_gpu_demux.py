@@ -95,7 +95,7 @@ def test_malformed_packets(efx):
 
 
 def test_chunk_boundaries_and_tiny_payloads(efx):
-    """> 128 packets per stream (k_demux works in chunks of 128) with 1..4-byte payloads: every
+    """Many chunks per stream (k_demux works in chunks of 16 packets) with 1..4-byte payloads: every
     ragged dword edge and zero-length packet case of the gather."""
     rng = np.random.default_rng(11)
     blobs = []

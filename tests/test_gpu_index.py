@@ -1,6 +1,9 @@
 """the trick-play index (indexer/indexer.cpp) built on the device for a batch
 of transport streams, the video.idx file, the player's index arithmetic (espflix.cpp:589-627) and
 a seek: decoding from the packet the index names."""
+import json
+import os
+
 import numpy as np
 import pytest
 
@@ -8,6 +11,7 @@ import common
 import oracle
 
 pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -93,4 +97,77 @@ def test_unsorted_and_degenerate_streams(efx):
         cnt = int(np.frombuffer(want[8 + 24:8 + 28], dtype=np.uint32)[0])
         assert rec["sample_count"] == cnt, i
         assert np.array_equal(samples, np.frombuffer(want[104:104 + 4 * cnt], dtype=np.uint32)), i
+    dec.close()
+
+
+def load_index_edges():
+    with open(os.path.join(ROOT, "tests", "golden", "index_edges.json")) as f:
+        return json.load(f)
+
+
+def test_directed_edge_streams(efx):
+    """common.index_edge_streams(): damaged / absent PTS and the origin rule (indexer.cpp:129-131), lists that cross the
+    256-packet chunk of k_ts_sequences sorted and unsorted, exact ties, bins with nothing nearer than 0x7FFFFFF, spans
+    beyond 2^31.  first_pts, last_pts, sample_count and every sample against the oracle, the whole video.idx against the
+    oracle's and its hash against what the reference indexer wrote (tests/golden/index_edges.json)."""
+    cases = common.index_edge_streams()
+    names = [n for n, _ in cases]
+    arrs = [np.frombuffer(ts, dtype=np.uint8) for _, ts in cases]
+    small = np.frombuffer(common.index_small_ts(), dtype=np.uint8)
+    seqs = {n: oracle.ts_sequences(a) for n, a in zip(names, arrs)}
+
+    # each case does what it is for, judged from the oracle's side
+    first, last, sp, so = seqs["bad_first"]
+    assert sp[0] == -1 and first == sp[1] == 135000
+    first, last, sp, so = seqs["bad_first_two"]
+    assert list(sp[:2]) == [-1, -1] and first == sp[2] != -1
+    first, last, sp, so = seqs["late_bad_first"]
+    assert so[0] >= 256 and sp[0] == -1 and first == sp[1] != -1
+    first, last, sp, so = seqs["bad_chunk"]
+    assert (sp[so < 256] == -1).all() and (so < 256).sum() == 128 and first == sp[128] != -1
+    assert seqs["nopts_first"][0] == 0 and seqs["nopts_first"][2][0] == 0
+    assert seqs["all_bad"][0] == -1 and (seqs["all_bad"][2] == -1).all() and seqs["all_bad"][1] > 0
+    assert seqs["late_first"][3][0] >= 256 and (np.diff(seqs["late_first"][2]) >= 0).all()
+    assert (np.diff(seqs["bad_mid"][2]) < 0).sum() == 1
+    first, last, sp, so = seqs["gap27"]
+    assert (np.diff(sp) >= 0).all() and max(last, sp.max()) - min(first, sp.min()) < 0x7FFFFFF0   # the binary search runs
+    far = [b for b in common.index_bins(first, last, sp) if b[1] >= 0x7FFFFFF]
+    assert far and all(b[0] == 0 for b in far)
+    for name in ("tie", "tie_plain", "cross256_sorted"):
+        first, last, sp, so = seqs[name]
+        assert (np.diff(sp) >= 0).all()
+        assert any(b[2] for b in common.index_bins(first, last, sp)), name
+    first, last, sp, so = seqs["tie"]
+    assert 3 in [b[0] for b in common.index_bins(first, last, sp) if b[2]] and sp[3] == sp[4] == sp[5]
+    first, last, sp, so = seqs["cross256_sorted"]
+    won = [b[0] for b in common.index_bins(first, last, sp) if b[2] and sp[b[0]] == sp[b[0] + 1]]
+    assert won and so[won[0]] < 256 and so[sp == sp[won[0]]].max() >= 256   # the first of the equals lies one chunk back
+    first, last, sp, so = seqs["cross256"]
+    down = np.nonzero(np.diff(sp) < 0)[0]
+    assert len(so) >= 300 and len(down) == 1 and so[down[0]] // 256 + 1 == so[down[0] + 1] // 256
+    first, last, sp, so = seqs["span32"]
+    assert sp.max() - sp.min() >= 1 << 32
+
+    streams = arrs + [small]
+    dec = efx.Decoder(len(streams), 1, 2, max_stream_bytes=sum(a.size for a in streams) + 4096)
+    res = dec.index_streams(streams, trick_speed=[1] * len(arrs) + [15], samples_cap=700000)
+    rec_small, smp_small = res[-1]
+    golden = load_index_edges()
+    assert set(golden) == set(names) - set(common.INDEX_EDGE_NOT_FOR_REFERENCE)
+    for name, a, (rec, samples) in zip(names, arrs, res):
+        first, last, sp, so = seqs[name]
+        print(name, "first_pts", rec["first_pts"], "oracle", first, "sample_count", rec["sample_count"])
+        assert (rec["first_pts"], rec["last_pts"]) == (first, last), name
+        want = oracle.make_idx([a, small, small])
+        cnt = int(np.frombuffer(want[8 + 24:8 + 28], dtype=np.uint32)[0])
+        assert cnt > 0 and rec["sample_count"] == cnt, name
+        assert np.array_equal(samples, np.frombuffer(want[104:104 + 4 * cnt], dtype=np.uint32)), name
+        idx = efx.idx_build([rec, rec_small, rec_small], [samples, smp_small, smp_small])
+        assert idx == want, name
+        if name in golden:
+            assert f"{oracle.fnv1a64(oracle.idx_masked(idx)):016x}" == golden[name], name
+    # a samples_cap too small for one stream: EFX_ERR_CAPACITY
+    with pytest.raises(efx.EfxError) as err:
+        dec.index_streams([small, arrs[names.index("gap27")]], samples_cap=1000)
+    assert err.value.status == -4   # EFX_ERR_CAPACITY
     dec.close()

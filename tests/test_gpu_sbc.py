@@ -468,8 +468,9 @@ def test_batch_of_streams_and_pdm_chain(efx):
 
 
 def hostile_audio_ts(seed: int) -> bytes:
-    """Hostile audio (common.hostile_audio_packets) inside a valid video stream: > 128 packets, so the
-    gate crosses k_demux's chunk boundary."""
+    """Hostile audio (common.hostile_audio_packets) inside a valid video stream: about 340 packets, so the
+    gate crosses k_demux's chunks of 16 packets, all within one round of 64 chunks (the rounds:
+    tests/test_gpu_demux_audio.py)."""
     from espflix_amd import gen
     return common.interleave_audio(gen.Batch(400 + seed, 1, 8).ts(0).tobytes(), seed)
 

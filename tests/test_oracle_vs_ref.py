@@ -163,6 +163,45 @@ def test_trick_play_index_file(clips):
         assert [oracle.idx_query(ref, p, s) for p, s in q] == want, name
 
 
+def test_trick_play_index_edge_streams():
+    """common.index_edge_streams() as the main stream of a title whose trick streams are two short valid ones: the
+    restatement's origin rule (indexer.cpp:129-131), its (int)abs(int64) truncation and `mine = 0x7FFFFFF` (185-189)
+    against what the reference indexer writes, and the recorded hashes of tests/golden/index_edges.json.
+    Left out, because the reference cannot take them (they run against the restatement only, tests/test_gpu_index.py):
+    common.INDEX_EDGE_NOT_FOR_REFERENCE -- `tie` and `cross256_sorted`, whose runs of equal sequence PTS make
+    indexer.cpp:136 divide by zero.  (Streams without a sequence start, which the indexer indexes an empty vector for,
+    are not among the edge streams.)"""
+    import json
+    import os
+    with open(os.path.join(oracle.ROOT, "tests", "golden", "index_edges.json")) as f:
+        recorded = json.load(f)
+    small = np.frombuffer(common.index_small_ts(), dtype=np.uint8)
+    assert sorted(common.INDEX_EDGE_NOT_FOR_REFERENCE) == ["cross256_sorted", "tie"]
+    ran = []
+    for name, ts in common.index_edge_streams():
+        if name in common.INDEX_EDGE_NOT_FOR_REFERENCE:
+            continue
+        title = [np.frombuffer(ts, dtype=np.uint8), small, small]
+        ref = oracle.ref_make_idx(title)
+        got = oracle.make_idx(title)
+        assert len(got) == len(ref) > oracle.IDX_HDR_BYTES, name
+        assert np.array_equal(oracle.idx_masked(got), oracle.idx_masked(ref)), name
+        assert f"{oracle.fnv1a64(oracle.idx_masked(ref)):016x}" == recorded[name], name
+        ran.append(name)
+    assert sorted(ran) == sorted(recorded) and len(ran) >= 13
+
+
+@pytest.mark.parametrize("name", ["late_open", "long_open_long_closed", "boundaries", "hostile_long"])
+def test_audio_bytes_pushed_across_chunks_and_rounds(name):
+    """common.audio_gate_streams(): the _audio_pts gate held open and closed over thousands of packets, inside whole
+    video streams the reference player reads to the end.  (common.audio_gate_cut_streams() cut the video, so the player
+    does not return from them: restatement only, tests/test_gpu_demux_audio.py.)"""
+    a = np.frombuffer(common.audio_gate_streams()[name], dtype=np.uint8)
+    ref = oracle.ref_audio_es(a)
+    got = oracle.ts_audio_es(a)
+    assert 0 < ref.size < common.audio_payload_offered(a.tobytes()) and np.array_equal(ref, got)
+
+
 @pytest.mark.parametrize("seed", [1, 2, 3])
 def test_audio_bytes_pushed(seed, clips):
     """What push_audio() receives (MpegDecoder::demux, player.cpp:421-433): for the clips and for a
