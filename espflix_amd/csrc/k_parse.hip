@@ -15,9 +15,18 @@
 // (tm_finish), into the MbRec + coefficient entries k_recon reads:
 //   entry = raw bits << 16 | value << 6 | scan position  (level = tm_level(entry); intra DC: DC value << 6 | 0).
 //
-// Bit reader: a bit POSITION into a per-lane 64-byte LDS ring, refilled by wave-synchronous top-ups (16-byte loads,
-// unconditional ring writes: no vmcnt wait inside the loop); the current three dwords sit in registers,
-// so the chain  position -> window -> table -> length -> position  holds ONE LDS round trip.
+// Bit reader: a bit POSITION into a per-lane 64-byte LDS ring, refilled by wave-synchronous top-ups (two to four 16-byte
+// loads, all in flight before the first is waited for, then unconditional ring writes); the current three dwords sit in
+// registers, so the chain  position -> window -> table -> length -> position  holds ONE LDS round trip.
+//
+// What the loops wait for in memory (s_waitcnt vmcnt in the compiled kernel; profiles/parse_waits.md has the counts):
+//   pass 1  a group of trips that tops the ring up waits for the top-up's own loads, all together: ONE L2 round trip, which
+//           also covers the 16-byte stream-word store of the group before (issued four trips earlier).  Groups that do not
+//           top up wait for nothing; the rewind of an abandoned block (damaged streams) reads its words back and waits.
+//   pass 2  a trip whose wave holds an intra lane waits up to eight times: at its head, in front of each of the six DC
+//           regions (a full wait directly behind the DC store of the block before: a store acknowledgement each) and
+//           behind the record store.  A straight-line trip with its stores at the end brought k_parse alone down by 3 %
+//           and the pipelined step up, and was taken out again (tools/exp/rejected/README.md, "Parse waits").
 #include <hip/hip_runtime.h>
 
 #include "efx_internal.h"
@@ -35,6 +44,9 @@ constexpr int kRingDwords = 16;  // per-lane bitstream ring in LDS (64 bytes)
 constexpr int kTripsPerTopup = 4;
 constexpr int kRingLow = kTripsPerTopup + 4;  // top up when any lane of the wave has fewer dwords than this ahead (a trip consumes less
                                               // than a dword, the window reads two dwords ahead)
+// A top-up fills the ring to at most kRingDwords dwords beyond the dword of the lane's position, and a lane that needs fewer
+// groups than its wave re-reads the first group it has not taken: never more than 4 * kRingDwords + 16 bytes ahead.
+static_assert(4 * kRingDwords + 16 <= 128 && 128 <= kEsGuardBytes, "a lane reads at most 128 bytes ahead, inside the zero guard");
 // stream words a lane stores at a time: one 16-byte store (whole 32-byte sectors, 8 words, were bit-exact and 2 to 10 % slower:
 // profiles/r6_parse_stores.md)
 constexpr int kDrainWords = 4;
@@ -60,20 +72,36 @@ struct BitReader {
             // whole 16-byte groups: one load instruction fetches what four did, and a wave's 64 lanes read 64 different
             // lines whatever the width
             const uint32_t groups = (kRingDwords - (wr - (pos >> 5))) >> 2;  // 0..4 (the lane that ran low: >= 2)
-#pragma unroll
-            for (uint32_t g = 0; g < (uint32_t)kRingDwords / 4; g++) {
-                if (!__any(g < groups))
-                    break;
-                // UNCONDITIONAL load and ring writes (a lane that needs no more aims the surplus at the scratch rows): no
-                // load is left pending on any path
-                const bool need = g < groups;
-                const uint4 v = gp[(wr >> 2) + (need ? g : 0u)];
-                const uint32_t slot = need ? (wr + 4 * g) % kRingDwords : (uint32_t)kRingDwords;
+            // How many groups the WAVE fetches is taken once, and every load of the top-up is in flight before the first
+            // is waited for: one L2 round trip per top-up, not one per group.  Groups 0 and 1 are always wanted by the lane
+            // that ran low; a lane that needs less aims the surplus at group 0 and at the scratch rows, so the loads and the
+            // ring writes are unconditional and no load is left pending on any path.
+            static_assert(((kRingDwords - (kRingLow - 1)) >> 2) >= 2 && kRingDwords == 16, "a lane that ran low takes two groups or more");
+            const bool three = __any(groups > 2), four = __any(groups > 3);
+            const uint4* const p = gp + (wr >> 2);
+            auto fetch = [&](uint32_t g) { return p[g < groups ? g : 0u]; };
+            auto land = [&](uint32_t g, const uint4& v) {
+                const uint32_t slot = g < groups ? (wr + 4 * g) % kRingDwords : (uint32_t)kRingDwords;
                 ring[(slot + 0) * 64] = __builtin_bswap32(v.x);
                 ring[(slot + 1) * 64] = __builtin_bswap32(v.y);
                 ring[(slot + 2) * 64] = __builtin_bswap32(v.z);
                 ring[(slot + 3) * 64] = __builtin_bswap32(v.w);
-            }
+            };
+            const uint4 v0 = fetch(0), v1 = fetch(1);
+            uint4 v2 = make_uint4(0, 0, 0, 0), v3 = v2;
+            if (three)
+                v2 = fetch(2);
+            if (four)
+                v3 = fetch(3);
+            // (an empty statement that reads groups 2 and 3: the top-up's wait sits here, behind its last load -- without it
+            // the byte swaps of a group move up to its load, and the wait for them with it)
+            asm volatile("" : "+v"(v2.x), "+v"(v2.y), "+v"(v2.z), "+v"(v2.w), "+v"(v3.x), "+v"(v3.y), "+v"(v3.z), "+v"(v3.w));
+            land(0, v0);
+            land(1, v1);
+            if (three)
+                land(2, v2);
+            if (four)
+                land(3, v3);
             wr += 4 * groups;
         }
     }
