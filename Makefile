@@ -16,9 +16,6 @@ all: lib gen oracle
 lib: espflix_amd/libefx.so
 gen: espflix_amd/gen/libefx_gen.so
 
-# k_recon.hip: the atomic optimizer would turn k_recon_all's one-lane dequeue into "atomic, wait, readfirstlane" on the spot --
-# the wait is the point of issuing the claim an item ahead (the value is consumed at the pre-store drain)
-$(CSRC)/k_recon.o: HIPFLAGS += -mllvm -amdgpu-atomic-optimizer-strategy=None
 $(CSRC)/k_export.o: $(CSRC)/export_px.h
 $(CSRC)/k_export.o $(CSRC)/k_trick.o: $(CSRC)/ring_px.h
 $(CSRC)/k_trick.o $(CSRC)/k_conform.o $(CSRC)/efx_api.o: $(CSRC)/trick_sel.h

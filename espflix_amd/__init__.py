@@ -31,7 +31,7 @@ STRIPS = 12
 STRIP_BYTES = 8448
 FRAME_BYTES = 101376
 
-OPT_GROUPS, OPT_PARSE_CAP, OPT_RECON_MODE, OPT_RECON_WAVES, OPT_RECON_SPINS, OPT_RECON_ITEMS, OPT_SBC_SERIAL = 1, 2, 3, 4, 5, 6, 7   # efx_option
+OPT_GROUPS, OPT_PARSE_CAP, OPT_SBC_SERIAL = 1, 2, 7   # efx_option (3 ... 6 and 8 belonged to removed paths and are refused)
 SBC_PROBE_FIRST = 1
 PIX_I420, PIX_RGB24, PIX_RGBP = 0, 1, 2     # efx_pixel_format
 CHROMA_NEAREST, CHROMA_BILINEAR = 0, 1
@@ -47,7 +47,6 @@ STREAM_BAD_VLC = 8
 STREAM_MB_OVERRUN = 16
 STREAM_COEF_OVERRUN = 32
 STREAM_SERIAL_HUNT = 64   # the reference would misread bits between two start codes (its marker hunt is bit-serial): see efx.h
-STREAM_INTERNAL = 256     # never expected: a lost hand-over inside the reconstruction kernel (efx.h)
 STREAM_SLICE_ORDER = 128  # slice start codes of a picture not strictly rising in bitstream order: see efx.h
 ENCODE_FULL = 512         # efx_encode: the stream's output region filled up (efx.h)
 ENCODE_VBV = 4096         # efx_encode_rc: the buffer model's level went below zero during the call (efx.h)
@@ -607,7 +606,7 @@ class Timing:
     groups: int = 1  # reconstruction groups of the newest call: one k_recon launch per group and picture index
     parse_halves: int = 1  # parse halves of the newest call: one per group
     mixed: int = 0   # 1: the averaged calls did not all run with that structure
-    recon_launches: int = 0  # reconstruction kernel launches of the newest call (groups x pictures, or groups with k_recon_all)
+    recon_launches: int = 0  # reconstruction kernel launches of the newest call (groups x pictures)
 
 
 class DeviceBuffer:
@@ -775,12 +774,6 @@ class Decoder:
 
     def set_option(self, option: int, value: int):
         _check(self._ctx, self._lib.efx_set_option(self._ctx, option, value))
-
-    def recon_stats(self):
-        """Header words of k_recon_all's hand-over buffer after the most recent call (development aid)."""
-        out = (C.c_uint32 * 64)()
-        _check(self._ctx, self._lib.efx_debug_recon_stats(self._ctx, out))
-        return list(out)
 
     def get_option(self, option: int) -> int:
         v = C.c_int()

@@ -187,7 +187,6 @@ _SYMBOLS = {
     "efx_stream_layout": (C.c_int, [C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "efx_upload_done": (C.c_int, [_P]),
     "efx_debug_poke": (C.c_int, [_P, _P, C.c_size_t, C.c_longlong]),
-    "efx_debug_recon_stats": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
     "efx_set_option": (C.c_int, [_P, C.c_int, C.c_int]),
     "efx_get_option": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     "efx_reset": (C.c_int, [_P]),

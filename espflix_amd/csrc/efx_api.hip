@@ -53,8 +53,6 @@ __global__ void k_slice_emit(const PicInfo*, const SliceTmp*, const uint32_t*, c
 __global__ void k_parse(const uint8_t*, const SliceDesc*, DecodeCounters*, const TmTables*, MbRec*, TmU4*, uint32_t*, uint32_t*,
                         int, int);
 __global__ void k_recon(const MbRec*, const uint32_t*, const uint32_t*, const uint32_t*, uint8_t*, int, int, int, const int32_t*, int, int);
-__global__ void k_recon_all(const MbRec*, const uint32_t*, const uint32_t*, const uint32_t*, uint8_t*, int, int, int, const int32_t*, int, int,
-                            int, uint32_t*, uint32_t*, int);
 
 __global__ void k_frame_hash(const uint8_t*, int, uint64_t*);
 __global__ void k_fill(uint32_t*, uint32_t, size_t);
@@ -135,8 +133,6 @@ constexpr int kTimingRing = 64;   // efx_decode calls whose stage times efx_get_
 constexpr int kSlots = 3;         // parse -> recon hand-over buffer sets (one being reconstructed + two being parsed)
 constexpr int kUploads = 3;       // bitstream buffers: up to two being parsed (two parse halves are in flight), one being filled --
                                   // with two, an upload had to wait for the parse half two calls back before its transfer could start
-// k_recon_all's hand-over words: 64 lines of 128 bytes (queue heads, spins, abort, development statistics), then one line per stream
-constexpr size_t kReconSyncWords(size_t streams) { return (64 + streams) * 32; }
 
 struct efx_ctx {
     efx_config cfg{};
@@ -222,7 +218,6 @@ struct efx_ctx {
         int64_t* d_pts = nullptr;    // per (stream, picture): PTS latched at the picture header (TS input); then, per
                                      // stream, the newest PES PTS of the upload (k_index -> k_advance)
         int32_t* d_call_pos = nullptr;  // per stream: ring position of this call's first picture, first picture with a PTS
-        uint32_t* d_recon_sync = nullptr;  // k_recon_all: queue heads, spins, abort, finished items per stream -- a 128-byte line each
         hipEvent_t parse_done = nullptr, recon_done = nullptr;
         int epoch = 0;
         int upload = 0;  // batch this call decoded
@@ -280,10 +275,6 @@ struct efx_ctx {
     int opt_groups = 0;        // reconstruction groups per call: 0 = one group behind a busy reconstruction stream, groups of
                                // kGroupStreams streams when it is idle; n >= 1: always n
     int opt_parse_cap = 0;     // 0 = cap the parse kernel's residency only while reconstruction is queued; 1 always; 2 never
-    int opt_recon_mode = 0;    // 0 = one k_recon launch per picture index (default: measured faster beside the parse halves,
-                               // profiles/r5_recon_all.md); 1, 2 = one k_recon_all launch per group
-    int opt_recon_waves = 0;   // k_recon_all with opt_recon_items = 0: workgroups per compute unit (0 = 18, what its LDS admits)
-    int opt_recon_items = 16;  // k_recon_all: items a wave takes before it ends (0: until none is left)
     int n_cus = 256;
     // efx_sbc_decode's scratch.  d_sbc_flags: n words per stream-indexed array -- [0, n) which kernel decodes the stream
     // (k_sbc_frames / k_sbc_plan), [n, 4n) the three work lists; then the SbcQueues
@@ -479,8 +470,8 @@ hipError_t guard_alloc(void** out, size_t bytes)
     }
     // mode 1: the buffer ENDS with the mapping, so its start is 16-byte aligned and no more (round-5 ADVICE: the comment here
     // claimed 256): every kernel is correct at 16 bytes -- the widest access is a dwordx4 -- and layouts that are tuned to
-    // 128-byte lines (one hand-over word per line in d_recon_sync) merely straddle lines in this debugging mode.  Mode 2
-    // (the buffer STARTS with the mapping) keeps the allocator's natural alignment.
+    // 128-byte lines merely straddle lines in this debugging mode.  Mode 2 (the buffer STARTS with the mapping) keeps the
+    // allocator's natural alignment.
     const size_t span = (bytes + 255) & ~(size_t)255;
     void* p = guard_mode() == 2 ? base : base + (r.map_bytes - span) + (span - ((bytes + 15) & ~(size_t)15));
     {
@@ -668,7 +659,6 @@ int efx_create(const efx_config* cfg, efx_ctx** out)
         A(dalloc(&sl.d_slice_base, n * P + kMaxGroups));  // (one list per parse half, each with an end entry)
         A(dalloc(&sl.d_descs, n * P * kMaxSlicesPerPicture));
         A(dalloc(&sl.d_call_pos, 2 * n));
-        A(dalloc(&sl.d_recon_sync, kReconSyncWords(n)));
     }
     A(dalloc(&ctx->d_frames, n * D * kFrameBytes + 8192));  // slack: k_recon's window rows may over-read the last frame
     A(dalloc(&ctx->d_video[0], 1));
@@ -699,12 +689,6 @@ int efx_create(const efx_config* cfg, efx_ctx** out)
             ctx->opt_groups = atoi(v);
         if (const char* v = getenv("EFX_FORCE_PARSE_CAP"))
             ctx->opt_parse_cap = atoi(v);
-        if (const char* v = getenv("EFX_RECON_MODE"))
-            ctx->opt_recon_mode = atoi(v);
-        if (const char* v = getenv("EFX_RECON_WAVES"))
-            ctx->opt_recon_waves = atoi(v);
-        if (const char* v = getenv("EFX_RECON_ITEMS"))
-            ctx->opt_recon_items = atoi(v);
         if (const char* cap = getenv("EFX_PARSE_WG_CAP"))  // (development: 0 = no cap)
             ctx->parse_wg_cap = atoi(cap);
     }
@@ -809,7 +793,7 @@ void efx_destroy(efx_ctx* ctx)
                 (void)hipEventDestroy(ev);
     }
     for (auto& sl : ctx->slot) {
-        void* sb[] = {sl.d_pic_count, sl.d_status, sl.d_counters, sl.d_mbrecs, sl.d_raw, sl.d_coefs, sl.d_pts, sl.d_call_pos, sl.d_recon_sync,
+        void* sb[] = {sl.d_pic_count, sl.d_status, sl.d_counters, sl.d_mbrecs, sl.d_raw, sl.d_coefs, sl.d_pts, sl.d_call_pos,
                       sl.d_pics,      sl.d_slices_tmp, sl.d_qtab, sl.d_slice_base, sl.d_descs};
         for (void* b : sb)
             if (b)
@@ -1182,19 +1166,6 @@ int efx_set_option(efx_ctx* ctx, int option, int value)
             return EFX_ERR_ARG;
         ctx->opt_parse_cap = value;
         return EFX_OK;
-    case EFX_OPT_RECON_MODE:
-        if (value > 2)
-            return EFX_ERR_ARG;
-        ctx->opt_recon_mode = value;
-        return EFX_OK;
-    case EFX_OPT_RECON_WAVES:
-        if (value > 64)
-            return EFX_ERR_ARG;
-        ctx->opt_recon_waves = value;
-        return EFX_OK;
-    case EFX_OPT_RECON_ITEMS:
-        ctx->opt_recon_items = value;
-        return EFX_OK;
     case EFX_OPT_SBC_SERIAL:
         ctx->opt_sbc_serial = value != 0;
         return EFX_OK;
@@ -1211,23 +1182,7 @@ int efx_get_option(efx_ctx* ctx, int option, int* value)
     switch (option) {
     case EFX_OPT_GROUPS: *value = ctx->opt_groups; return EFX_OK;
     case EFX_OPT_PARSE_CAP: *value = ctx->opt_parse_cap; return EFX_OK;
-    case EFX_OPT_RECON_MODE: *value = ctx->opt_recon_mode; return EFX_OK;
-    case EFX_OPT_RECON_WAVES: *value = ctx->opt_recon_waves; return EFX_OK;
-    case EFX_OPT_RECON_ITEMS: *value = ctx->opt_recon_items; return EFX_OK;
     case EFX_OPT_SBC_SERIAL: *value = ctx->opt_sbc_serial; return EFX_OK;
-    case EFX_OPT_RECON_SPINS: {
-        int r = sync_all(ctx);
-        if (r)
-            return r;
-        uint32_t total = 0;
-        for (int g = 0; g < ctx->n_groups && ctx->decoded; g++) {
-            uint32_t v = 0;
-            EFX_HIP(hipMemcpy(&v, ctx->slot[ctx->groups[g].slot].d_recon_sync + 8 * 32, sizeof(v), hipMemcpyDeviceToHost));
-            total += v;
-        }
-        *value = (int)std::min<uint32_t>(total, 0x7FFFFFFFu);
-        return EFX_OK;
-    }
     default:
         return EFX_ERR_ARG;
     }
@@ -1372,7 +1327,7 @@ int efx_decode_range(efx_ctx* ctx, int first_picture, int n_pictures)
     if (ctx->timing && !ctx->timing_ring.empty()) {
         timing_slot = (int)(ctx->timed_calls++ % kTimingRing);
         ctx->timing_groups[timing_slot] = (uint8_t)G;
-        ctx->timing_launches[timing_slot] = (uint16_t)(G * (ctx->opt_recon_mode == 0 ? n_pictures : 1));
+        ctx->timing_launches[timing_slot] = (uint16_t)(G * n_pictures);
     }
     ctx->last_upload = ctx->cur_up;
     ctx->last_n_streams = u.n_streams;
@@ -1445,24 +1400,9 @@ int efx_decode_range(efx_ctx* ctx, int first_picture, int n_pictures)
                            u.ts_input ? sl.d_pts : nullptr, u.ts_input ? sl.d_pts + (size_t)ctx->cfg.max_streams * P : nullptr, s0, n,
                            P, sl.d_call_pos);
         constexpr int kGroupsPerPicture = (kMbCount * 6 + 63) / 64;
-        if (ctx->opt_recon_mode == 0) {
-            for (int p = 0; p < n_pictures; p++)
-                hipLaunchKernelGGL(k_recon, dim3(n, kGroupsPerPicture), dim3(64), 0, sr, sl.d_mbrecs, sl.d_coefs,
-                                   ctx->d_tables->scan, sl.d_qtab, ctx->d_frames, P, D, p, sl.d_call_pos, sl.epoch, s0);
-        } else if (n > 0) {
-            // ONE launch for all picture indices of the group: persistent waves pull (picture, stream, block group) items in
-            // picture-major order; a per-stream counter of finished items orders a picture behind its predecessor (k_recon.hip)
-            EFX_HIP(hipMemsetAsync(sl.d_recon_sync, 0, kReconSyncWords((size_t)n) * sizeof(uint32_t), sr));
-            // A wave takes opt_recon_items items and ends, so that wave slots (and their LDS) keep coming free for the parse
-            // kernel of the next call; with 0 the grid is what the chip holds and the waves live until the last item.
-            const long long items = (long long)n * kGroupsPerPicture * n_pictures;
-            const int per_cu = ctx->opt_recon_waves > 0 ? ctx->opt_recon_waves : 18;
-            const long long waves = ctx->opt_recon_items > 0 ? (items + ctx->opt_recon_items - 1) / ctx->opt_recon_items
-                                                             : std::min<long long>(items, (long long)ctx->n_cus * per_cu);
-            hipLaunchKernelGGL(k_recon_all, dim3((unsigned)waves), dim3(64), 0, sr, sl.d_mbrecs,
-                               sl.d_coefs, ctx->d_tables->scan, sl.d_qtab, ctx->d_frames, P, D, n_pictures, sl.d_call_pos, sl.epoch, s0, n,
-                               sl.d_recon_sync, sl.d_status, ctx->opt_recon_items);
-        }
+        for (int p = 0; p < n_pictures; p++)
+            hipLaunchKernelGGL(k_recon, dim3(n, kGroupsPerPicture), dim3(64), 0, sr, sl.d_mbrecs, sl.d_coefs, ctx->d_tables->scan,
+                               sl.d_qtab, ctx->d_frames, P, D, p, sl.d_call_pos, sl.epoch, s0);
         if (te)
             EFX_HIP(hipEventRecord(te->ev[3], sr));
         EFX_HIP(hipEventRecord(sl.recon_done, sr));
@@ -3563,23 +3503,6 @@ int efx_debug_poke(efx_ctx* ctx, void* dptr, size_t bytes, long long offset_byte
     EFX_HIP(hipGetLastError());
     EFX_HIP(hipStreamSynchronize(ctx->stream));
     ctx->recon_groups_unsynced = 0;  // (the host knows the reconstruction stream idle)
-    return EFX_OK;
-}
-
-// development: the header lines of k_recon_all's hand-over words after the most recent call (word 0 of each of the 64 lines:
-// queue heads 0-7, spins 8, abort 9, the rest zero; tools/exp/r5_recon_check.py)
-int efx_debug_recon_stats(efx_ctx* ctx, uint32_t out[64])
-{
-    bind_device(ctx);
-    if (!ctx || !out || !ctx->decoded || ctx->n_groups < 1)
-        return EFX_ERR_ARG;
-    int r = sync_all(ctx);
-    if (r)
-        return r;
-    std::vector<uint32_t> all(64 * 32);
-    EFX_HIP(hipMemcpy(all.data(), ctx->slot[ctx->groups[ctx->n_groups - 1].slot].d_recon_sync, all.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    for (int k = 0; k < 64; k++)
-        out[k] = all[(size_t)k * 32];
     return EFX_OK;
 }
 

@@ -145,16 +145,7 @@ constexpr int kLaneHalfwords = 2 * kLaneDwords;
 // 2-D IDCT in registers, forms the prediction of its 8 x 8 pixels from nine 12-byte row fetches and
 // stores eight 8-byte rows.  No lane ever waits for another: no barrier, no shuffle, no scalar
 // bookkeeping, every lane busy.
-//
-// kShared = the frames this wave reads were written, and the frames it writes will be read, by OTHER workgroups of the
-// SAME launch (k_recon_all): every frame access is then a write-through / L1-bypassing `sc1` buffer access (a CU's vector
-// L1 is never refreshed by another CU's stores and the XCDs' L2s are not coherent with each other:
-// MI355X_MICROARCH.md, "Workgroup dispatch, XCD placement & inter-workgroup visibility"); the hand-over itself is the
-// per-stream counter of k_recon_all.
 constexpr int kPerRound = 3;  // coefficient entries a lane takes per round of the wave's entry dealing (recon_group: "Three entries")
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
-constexpr int kAuxSc1 = 16;  // cache policy of the raw buffer builtins on gfx950: sc1
 
 // which block of the picture lane `lane` of block group `g` owns: macroblock, block inside it
 struct BlockAt {
@@ -185,16 +176,11 @@ __device__ __forceinline__ BlockAt block_at(int g, int lane)
     return o;
 }
 
-// kShared = false (k_recon, one launch per picture index): plain loads of the reference frame, plain 8-byte row stores.
-// kShared = true (k_recon_all): sc1 buffer loads (bypass this CU's L1) and sc1 (write-through) 16-byte stores: the lanes of a wave
-// come in pairs that own horizontally adjacent blocks (even lane: the left / even one), so the pair's two 8-byte row segments are
-// one aligned 16-byte unit -- the even lane stores rows 0-3 of both blocks, the odd lane rows 4-7 (a write-through store is one
-// fabric write whatever its size: per byte an 8-byte one costs 2.7 x a 16-byte one, MI355X_MICROARCH.md).
-template <bool kShared, class PreStore>
+// The per-block body of k_recon: plain loads of the reference frame, plain 8-byte row stores.
 __device__ __forceinline__ void recon_group(uint32_t* __restrict__ lds, const uint32_t* __restrict__ coefs,
                                             const uint32_t* __restrict__ qt_custom, uint8_t* __restrict__ frames, int ring_depth,
-                                            int pic, int pos0, int first_pts, int epoch, int s, int g, const uint4 rw,
-                                            PreStore&& pre_store EFX_PROBE_PARAM)
+                                            int pic, int pos0, int first_pts, int epoch, int s, int g,
+                                            const uint4 rw EFX_PROBE_PARAM)
 {
     int16_t* const cfh = reinterpret_cast<int16_t*>(lds);
     uint16_t* const s_pre = reinterpret_cast<uint16_t*>(lds + 64 * kLaneDwords);  // entries before the block in the wave
@@ -210,11 +196,6 @@ __device__ __forceinline__ void recon_group(uint32_t* __restrict__ lds, const ui
     uint8_t* const ring = frames + (size_t)s * ring_depth * kFrameBytes;  // the stream's frames (wave-uniform)
     uint8_t* cur = ring + (size_t)cur_slot * kFrameBytes;
     const uint8_t* ref = ring + (size_t)ref_slot * kFrameBytes;
-    // (kShared) the stream's ring as a buffer: offsets are 32-bit, the cache policy rides on the instruction.  The range
-    // includes the slack behind the last frame that the window rows may over-read (the pool ends with it).
-    const __amdgpu_buffer_rsrc_t ring_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(ring, 0, (int)(ring_depth * kFrameBytes + 8192), 0x00020000);
-    const uint32_t cur_off = cur_slot * (uint32_t)kFrameBytes, ref_off = ref_slot * (uint32_t)kFrameBytes;
 
     const uint32_t w_base = rw.x, w_cnt = rw.y, w_misc = rw.z, w_mv = rw.w;
     EFX_PROBE_STAMP_AFTER(3, w_base);  // the record has arrived
@@ -268,17 +249,10 @@ __device__ __forceinline__ void recon_group(uint32_t* __restrict__ lds, const ui
 #pragma unroll
             for (int r = 0; r < 9; r++) {
                 const uint32_t off = off0 + (uint32_t)(r * kStride) + ((uint32_t)r >= jump ? 8u * kStride : 0u);
-                if constexpr (kShared) {
-                    const u32x3 v = __builtin_amdgcn_raw_buffer_load_b96(ring_rsrc, (int)(ref_off + off), 0, kAuxSc1);
-                    wa[r] = v.x;
-                    wb[r] = v.y;
-                    wc[r] = v.z;
-                } else {
-                    const uint32_t* p = reinterpret_cast<const uint32_t*>(ref + off);
-                    wa[r] = p[0];
-                    wb[r] = p[1];
-                    wc[r] = p[2];
-                }
+                const uint32_t* p = reinterpret_cast<const uint32_t*>(ref + off);
+                wa[r] = p[0];
+                wb[r] = p[1];
+                wc[r] = p[2];
             }
         }
     } else {
@@ -295,8 +269,7 @@ __device__ __forceinline__ void recon_group(uint32_t* __restrict__ lds, const ui
                 for (int k = 0; k < 4; k++) {
                     const int yy = clampi(py0 + r, 0, ph - 1), xx = clampi((px0 & ~3) + d * 4 + k, 0, pw - 1);
                     const uint32_t o = (uint32_t)(row_off(yy) + xx);
-                    const uint32_t byte = kShared ? (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(ring_rsrc, (int)(ref_off + o), 0, kAuxSc1)
-                                                  : (uint32_t)ref[o];
+                    const uint32_t byte = (uint32_t)ref[o];
                     word |= (byte & 0xFF) << (k * 8);
                 }
             w32[i] = word;
@@ -384,7 +357,7 @@ __device__ __forceinline__ void recon_group(uint32_t* __restrict__ lds, const ui
             // is its DC value << 6
             const int n = e & 63;
             const int level = (o_intra && n == 0) ? (int)e >> 6 : tm_level(e);
-            // scan/quantiser table entry: zz | premultiplier << 8 | intra q << 16 | non-intra q << 24
+            // scan/quantiser table entry: zz | slot in the paired block layout << 8 | intra q << 16 | non-intra q << 24
             uint32_t t = lds[n * kLaneDwords + kLaneData];
             if (f & 0x80)
                 t = qt_custom[n];
@@ -577,8 +550,6 @@ __device__ __forceinline__ void recon_group(uint32_t* __restrict__ lds, const ui
     flat4 |= flat4 << 16;
     uint32_t clamped_m = clamped ? ~0u : 0u;
     asm volatile("" : "+v"(clamped_m));
-    pre_store();  // (k_recon_all: the place where the previous item's stores are known to have left)
-    uint32_t out_lo[8], out_hi[8];
 #pragma unroll
     for (int r = 0; r < 8; r++) {
         const uint32_t p_lo = pr_lo[r], p_hi = pr_hi[r];
@@ -594,41 +565,9 @@ __device__ __forceinline__ void recon_group(uint32_t* __restrict__ lds, const ui
             w[h] = __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, b), __builtin_bit_cast(uint32_t, a), 0x06040200u);
         }
         // prediction only (skipped macroblock, block without coefficients) / intra DC-only replica / the clamped sum
-        out_lo[r] = bitop3<0xCA>(clamped_m, w[0], flat4);
-        out_hi[r] = bitop3<0xCA>(clamped_m, w[1], flat4);
-        if constexpr (!kShared) {
-            if (stored)
-                *reinterpret_cast<uint2*>(cur + dst0 + r * kStride) = make_uint2(out_lo[r], out_hi[r]);
-        }
-    }
-    if constexpr (kShared) {
-        // lanes 2k, 2k + 1 own the left and the right half of a 16-byte aligned unit of every row they write (block_at: luma
-        // blocks alternate left / right, chroma blocks run along the macroblock row and a row of them starts on an even lane)
-        const bool odd = lane & 1;
-        const bool partner_stored = __builtin_amdgcn_update_dpp(0, (int)stored, 0xB1, 0xF, 0xF, false) != 0;  // quad_perm [1,0,3,2]
-        const bool both = stored && partner_stored;
-        const uint32_t unit0 = cur_off + (uint32_t)dst0 - (odd ? 8u : 0u) + (odd ? 4u * kStride : 0u);  // first row this lane stores
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            // what the partner needs from this lane: the even lane's rows 4-7, the odd lane's rows 0-3
-            const uint32_t give_lo = odd ? out_lo[k] : out_lo[4 + k], give_hi = odd ? out_hi[k] : out_hi[4 + k];
-            const uint32_t got_lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)give_lo, 0xB1, 0xF, 0xF, false);
-            const uint32_t got_hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)give_hi, 0xB1, 0xF, 0xF, false);
-            const uint32_t own_lo = odd ? out_lo[4 + k] : out_lo[k], own_hi = odd ? out_hi[4 + k] : out_hi[k];
-            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-            const u32x4 unit = {odd ? got_lo : own_lo, odd ? got_hi : own_hi, odd ? own_lo : got_lo, odd ? own_hi : got_hi};
-            if (both)
-                __builtin_amdgcn_raw_buffer_store_b128(unit, ring_rsrc, (int)(unit0 + (uint32_t)(k * kStride)), 0, kAuxSc1);
-        }
-        if (__any(stored && !partner_stored)) {  // (damaged or incomplete pictures only: a block whose neighbour is not written)
-            if (stored && !partner_stored) {
-#pragma unroll
-                for (int r = 0; r < 8; r++) {
-                    const u32x2 o2 = {out_lo[r], out_hi[r]};
-                    __builtin_amdgcn_raw_buffer_store_b64(o2, ring_rsrc, (int)(cur_off + (uint32_t)(dst0 + r * kStride)), 0, kAuxSc1);
-                }
-            }
-        }
+        const uint32_t out_lo = bitop3<0xCA>(clamped_m, w[0], flat4), out_hi = bitop3<0xCA>(clamped_m, w[1], flat4);
+        if (stored)
+            *reinterpret_cast<uint2*>(cur + dst0 + r * kStride) = make_uint2(out_lo, out_hi);
     }
 }
 
@@ -658,234 +597,15 @@ __global__ __launch_bounds__(64) void k_recon(const MbRec* __restrict__ mbrecs, 
     EFX_PROBE_STAMP(1);
     EFX_PROBE_CYCLES_BEGIN();
     EFX_PROBE_SET(6, (unsigned long long)pic | (unsigned long long)(epoch & 0xFF) << 8 | (unsigned long long)stream0 << 16);
-    // scan/quantiser table entry: zz | premultiplier << 8 | intra q << 16 | non-intra q << 24
+    // scan/quantiser table entry: zz | slot in the paired block layout << 8 | intra q << 16 | non-intra q << 24
     lds[lane * kLaneDwords + kLaneData] = scan_tab[lane];
     const BlockAt at = block_at(blockIdx.y, lane);
     const uint4 rw = *reinterpret_cast<const uint4*>(mbrecs + ((size_t)s * max_pictures + pic) * kMbCount + at.mb);
     EFX_PROBE_STAMP_AFTER(3, rw.x);  // the record has arrived
-    recon_group<false>(lds, coefs, qtab_custom + ((size_t)s * max_pictures + pic) * 64, frames, ring_depth, pic, call_pos[2 * s],
-                       call_pos[2 * s + 1], epoch, s, blockIdx.y, rw, [] {} EFX_PROBE_PASS);
+    recon_group(lds, coefs, qtab_custom + ((size_t)s * max_pictures + pic) * 64, frames, ring_depth, pic, call_pos[2 * s],
+                call_pos[2 * s + 1], epoch, s, blockIdx.y, rw EFX_PROBE_PASS);
     EFX_PROBE_STAMP(4);
     EFX_PROBE_CYCLES_END(2);
-}
-
-// ---- all pictures of a decode call in ONE launch ----------------------------------------------------------------------------
-// The per-picture launches above each pay one wave life of filling and draining (a launch of waves that live 10 us costs
-// its work plus about 10 us: 12 x that per call, profiles/r4_ablations.md section 2), and every wave starts with an exposed
-// round trip for its macroblock record.  Here the waves are persistent: the grid is what the chip holds, and a wave pulls
-// ITEMS -- (picture, stream, group of 64 blocks) -- off a counter until none is left.
-//   * Order: picture-major, so the item a P picture depends on -- the same stream's previous picture, all 25 groups of it --
-//     was handed out a whole picture's worth of items earlier.  What orders them is a per-stream counter of finished items:
-//     a wave polls done[s] >= 25 * picture (one relaxed sc1 load, issued an item ahead; a spin only near the end of
-//     small batches), and adds 1 when its stores have left (s_waitcnt vmcnt(0), then one relaxed agent-scope atomic).
-//     A wave only ever waits for items handed out BEFORE its own, each of which is in the hands of a running wave: no
-//     cycle, whatever the residency and whatever else shares the chip.
-//   * Eight queues, one per XCD: queue x holds the streams stream0 + x + 8 j, and a wave serves the queue of the XCD it runs
-//     on (HW_REG_XCC_ID) until that is empty, then helps the next one -- a stream's frames stay in one L2, and eight heads
-//     take the dequeue traffic (one head saturates at ~88 per us: MI355X_MICROARCH.md, "dequeue").  Placement is for speed
-//     only: every frame access is sc1 on both sides (recon_group<true>), correct wherever an item runs.
-//   * A wave works ahead of itself: the next item's macroblock record and its stream's counter are requested, and the index
-//     of the item after that is claimed, before the current item's first instruction -- the record's round trip (1.5 of a
-//     wave's 10.6 us under load) is off the chain, and so are the dequeue and the poll.
-// sync: queue heads, a spin count (diagnostics), an abort word, and per stream the count of its finished items -- EVERY word
-// in its own 128-byte line: agent-scope atomics on one line take their turns at the memory side (~88 per us per line,
-// MI355X_MICROARCH.md "dequeue"); with the eight heads in one line the whole launch ran at that rate, 5.7 instead of
-// 0.9 ms per 307 200 items.  Zeroed by the host before every launch.  Restates, for a whole call, the order MpegDecoder::run() gives one stream: picture after picture
-// (player.cpp:692-702).
-// Ordering (round-5 ADVICE asked for release / acquire or the reason they are not needed): the hand-over is correct with
-// RELAXED agent-scope atomics because no plain cached access is involved on either side -- every frame store of an item is a
-// write-through `sc1` store and the signal goes out only after `s_waitcnt vmcnt(0)` has seen them complete (drain(); memory
-// operations of a wave complete in issue order), every frame load of the dependent item is an L1-bypassing `sc1` load issued
-// after the poll returned the count, and both go to the same L2 / fabric point of coherence.  A release fence would write back
-// an L2 that holds no dirty frame line, an acquire would invalidate an L1 that holds no frame line (MI355X_MICROARCH.md,
-// "Valid forms": {sc0 sc1 stores and loads both sides}); the plain-access build, which does need them, fails parity.
-constexpr unsigned long long kReconAllPatienceTicks = 1000000000ull;  // 10 s of the 100 MHz wall clock
-constexpr int kGroupsPerPicture = (kBlocksPerPicture + 63) / 64;  // 25
-constexpr uint32_t kSyncLine = 32;  // words per line
-constexpr uint32_t kSyncHeads = 0, kSyncSpins = 8 * kSyncLine, kSyncAbort = 9 * kSyncLine, kSyncDone = 64 * kSyncLine;
-
-struct ItemAt {
-    int pic, s, g;
-};
-
-__device__ __forceinline__ void recon_all_body(uint32_t* __restrict__ lds, const MbRec* __restrict__ mbrecs,
-                                               const uint32_t* __restrict__ coefs, const uint32_t* __restrict__ scan_tab,
-                                               const uint32_t* __restrict__ qtab_custom, uint8_t* __restrict__ frames,
-                                               int max_pictures, int ring_depth, int n_pictures,
-                                               const int32_t* __restrict__ call_pos, int epoch, int stream0, int n_streams,
-                                               uint32_t* __restrict__ sync, uint32_t* __restrict__ status, int max_items)
-{
-    const int lane = threadIdx.x;
-    lds[lane * kLaneDwords + kLaneData] = scan_tab[lane];  // (once per wave: the items leave the 33rd dword alone)
-    uint32_t xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    // queue q: streams stream0 + q + 8 j, j < per_queue(q); its items picture by picture, inside a picture stream by stream, a
-    // stream's 25 groups together: the last group of a stream's picture p and the first of its picture p + 1 are a whole
-    // picture of the queue apart (with the streams innermost they were per_queue(q) items apart -- fewer than the waves in
-    // flight: every picture began with a wait)
-    auto per_queue = [&](uint32_t q) { return (uint32_t)(n_streams > (int)q ? (n_streams - (int)q + 7) >> 3 : 0); };
-    auto items_of = [&](uint32_t q) { return per_queue(q) * (uint32_t)(kGroupsPerPicture * n_pictures); };
-    uint32_t q = xcc & 7, visited = 0;
-    auto decode = [&](uint32_t qq, uint32_t idx) {
-        const uint32_t per_pic = per_queue(qq) * kGroupsPerPicture;
-        const uint32_t p = idx / per_pic, rem = idx - p * per_pic, j = rem / kGroupsPerPicture, g = rem - j * kGroupsPerPicture;
-        return ItemAt{(int)p, stream0 + (int)(qq + 8 * j), (int)g};
-    };
-    // a returning agent-scope add on the queue head, by lane 0; the value is waited for where it is used
-    auto claim_issue = [&](uint32_t qq) {
-        uint32_t v = 0;
-        if (lane == 0)
-            v = __hip_atomic_fetch_add(sync + kSyncHeads + qq * kSyncLine, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return v;
-    };
-    // walk the queues until one hands out an item (a synchronous claim: the start of a wave, the end of a queue); false when
-    // all eight are empty
-    auto claim_walk = [&](uint32_t& idx) {
-        while (visited < 8) {
-            idx = (uint32_t)__builtin_amdgcn_readfirstlane((int)claim_issue(q));
-            if (idx < items_of(q))
-                return true;
-            q = (q + 1) & 7;
-            visited++;
-        }
-        return false;
-    };
-    auto record_of = [&](const ItemAt& it) {
-        const BlockAt at = block_at(it.g, lane);
-        return *reinterpret_cast<const uint4*>(mbrecs + ((size_t)it.s * max_pictures + it.pic) * kMbCount + at.mb);
-    };
-    auto done_of = [&](const ItemAt& it) {
-        return __hip_atomic_load(sync + kSyncDone + (uint32_t)(it.s - stream0) * kSyncLine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
-    auto signal = [&](int s_done) {  // one more finished item of the stream (the caller knows that its stores have left)
-        if (lane == 0)
-            __hip_atomic_fetch_add(sync + kSyncDone + (uint32_t)(s_done - stream0) * kSyncLine, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
-    auto drain = [] { __builtin_amdgcn_s_waitcnt(0x0F70); };  // s_waitcnt vmcnt(0), as a builtin: the compiler's own bookkeeping
-                                                               // learns that every load and atomic issued so far has returned
-
-    // A wave takes at most `max_items` items and ends (0: as many as there are): the grid is then items / max_items
-    // workgroups and wave slots keep coming free -- a grid of waves that live for the whole call would hold every CU's LDS
-    // until its last item, and the parse kernel of the NEXT call (which must run beside this one, efx_api.hip) would find no
-    // room.  An item that has been claimed is always processed: claims go out only while the budget has room.
-    //
-    // The pipeline of a wave, three items deep: A is worked on; B's macroblock record and its stream's counter were requested
-    // at the top of A's turn; C's index is being claimed.  ALL of that is waited for at ONE place -- just before A's first store,
-    // where every load of A has long been consumed and the wait is free -- and there the hand-over signal of the item BEFORE A
-    // goes out too (memory operations complete in issue order: its stores have left).  A wait anywhere else would sit out A's
-    // stores: the counter of outstanding memory operations cannot tell an old atomic from a new store.
-    uint32_t budget = max_items > 0 ? (uint32_t)max_items : 0xFFFFFFFFu;
-    uint32_t idx = 0;
-    if (!claim_walk(idx))
-        return;
-    budget--;
-    ItemAt a = decode(q, idx);
-    bool have_b = budget > 0 && claim_walk(idx);
-    ItemAt b = a;
-    if (have_b) {
-        budget--;
-        b = decode(q, idx);
-    }
-    uint4 rw_a = record_of(a);
-    uint32_t seen_a = (uint32_t)__builtin_amdgcn_readfirstlane((int)done_of(a));
-    int pending_signal = -1;  // stream of the item whose stores are still on their way
-    for (;;) {
-        // ---- requests for the items behind this one (consumed at this item's pre-store point) -----------------------------------
-        uint4 rw_b = rw_a;
-        uint32_t done_b = 0, claim_c = 0;
-        const uint32_t q_c = q;
-        const bool pending_c = have_b && budget > 0;
-        if (have_b) {
-            rw_b = record_of(b);
-            done_b = done_of(b);
-        }
-        if (pending_c)
-            claim_c = claim_issue(q_c);
-        // ---- this item's predecessor: every group of the stream's previous pictures is in memory ---------------------------
-        const uint32_t need = (uint32_t)(kGroupsPerPicture * a.pic);
-        if (seen_a < need) {
-            // (the tail of a small batch: the predecessor is still in the hands of another wave -- or of THIS one: the item
-            // whose signal is still held back may be what this item waits for)
-            if (pending_signal >= 0) {
-                drain();
-                signal(pending_signal);
-                pending_signal = -1;
-            }
-            // The wait is bounded by WALL-CLOCK time (round-5 ADVICE: a count of polls -- 2^19 x s_sleep(8), 0.1-0.2 s -- can run
-            // out under a legitimate wait on a shared or preempted GPU): kReconAllPatienceTicks of the 100 MHz counter = 10 s,
-            // looked at every 1024 polls.  When it does run out the stream is flagged EFX_STREAM_INTERNAL and the launch
-            // gives up: the frames of that call are NOT valid (include/efx.h).
-            uint32_t spins = 0;
-            bool abort = false;
-            const unsigned long long t_wait0 = wall_clock64();
-            do {
-                __builtin_amdgcn_s_sleep(8);
-                seen_a = (uint32_t)__builtin_amdgcn_readfirstlane((int)done_of(a));
-                if ((++spins & 1023) == 0)
-                    abort = __builtin_amdgcn_readfirstlane((int)__hip_atomic_load(sync + kSyncAbort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0 ||
-                            wall_clock64() - t_wait0 > kReconAllPatienceTicks;
-            } while (seen_a < need && !abort);
-            if (seen_a < need && lane == 0) {
-                // never observed: a lost hand-over must not hang the device -- the stream is flagged, every other wait of the
-                // launch gives up at its next look, the call ends
-                atomicOr(status + a.s, EFX_STREAM_INTERNAL);
-                __hip_atomic_store(sync + kSyncAbort, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            if (lane == 0)
-                __hip_atomic_fetch_add(sync + kSyncSpins, spins, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        uint32_t seen_b = 0, idx_c = 0;
-        recon_group<true>(lds, coefs, qtab_custom + ((size_t)a.s * max_pictures + a.pic) * 64, frames, ring_depth, a.pic,
-                          call_pos[2 * a.s], call_pos[2 * a.s + 1], epoch, a.s, a.g, rw_a, [&] {
-                              drain();
-                              if (pending_signal >= 0)
-                                  signal(pending_signal);
-                              seen_b = (uint32_t)__builtin_amdgcn_readfirstlane((int)done_b);
-                              idx_c = (uint32_t)__builtin_amdgcn_readfirstlane((int)claim_c);
-                          } EFX_PROBE_PASS_NONE);
-        pending_signal = a.s;
-        if (!have_b)
-            break;
-        // ---- rotate: B becomes the item worked on, C (if its claim found one) the item behind it --------------------------
-        bool have_c = false;
-        ItemAt c = b;
-        if (pending_c) {
-            have_c = idx_c < items_of(q_c);
-            if (!have_c) {  // that queue is empty: on to the next ones (synchronous, a handful of times per wave at most)
-                if (q == q_c) {
-                    q = (q + 1) & 7;
-                    visited++;
-                }
-                have_c = claim_walk(idx_c);
-            }
-            if (have_c) {
-                budget--;
-                c = decode(q, idx_c);
-            }
-        }
-        a = b;
-        rw_a = rw_b;
-        seen_a = seen_b;
-        b = c;
-        have_b = have_c;
-    }
-    drain();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the last item's stores)
-    signal(pending_signal);
-}
-
-// waves per SIMD the register allocation aims at: 4 (123 registers, nothing spilled; with 5 the 96 registers spill 14 and the
-// launch is a quarter slower) -- 16 waves per CU
-constexpr int kReconAllWaves = 4;
-__global__ __launch_bounds__(64, kReconAllWaves) void k_recon_all(
-    const MbRec* __restrict__ mbrecs, const uint32_t* __restrict__ coefs, const uint32_t* __restrict__ scan_tab,
-    const uint32_t* __restrict__ qtab_custom, uint8_t* __restrict__ frames, int max_pictures, int ring_depth, int n_pictures,
-    const int32_t* __restrict__ call_pos, int epoch, int stream0, int n_streams, uint32_t* __restrict__ sync,
-    uint32_t* __restrict__ status, int max_items)
-{
-    __shared__ uint32_t lds[64 * kLaneDwords + 32 + 16];
-    recon_all_body(lds, mbrecs, coefs, scan_tab, qtab_custom, frames, max_pictures, ring_depth, n_pictures, call_pos, epoch, stream0,
-                   n_streams, sync, status, max_items);
 }
 
 // FNV-1a-64 of whole ring frames, one lane per frame (verification helper, not on the timed path)

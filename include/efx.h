@@ -65,10 +65,8 @@ typedef enum efx_status {
                                          of them is also damaged or short -- the parity claim does not cover a stream with \
                                          this bit */
 
-#define EFX_STREAM_INTERNAL 256u      /* never expected: a reconstruction wave gave up waiting for the stream's previous picture \
-                                         (k_recon_all's hand-over counter, optional EFX_OPT_RECON_MODE only; patience: 10 s \
-                                         of wall-clock time) -- the launch was abandoned: NO frame of that call is valid, \
-                                         for this stream or any other */
+/* (bit 256 of the status word is reserved and never set: it belonged to a reconstruction path that was removed, and no later
+ * flag takes it) */
 
 typedef enum efx_format {
     EFX_FORMAT_ES = 0, /* raw ISO 11172-2 video elementary stream */
@@ -1542,8 +1540,7 @@ typedef struct efx_timing {
     uint16_t mixed;    /* 1: the averaged calls did not all run with the newest call's structure (a call that found the GPU
                           idle is split into groups, one queued behind another is not): per-launch figures derived from
                           the means are off */
-    uint32_t recon_launches; /* reconstruction kernel launches of the newest call: groups x pictures with one k_recon launch per
-                                picture index, groups with one k_recon_all per group (EFX_OPT_RECON_MODE) */
+    uint32_t recon_launches; /* reconstruction kernel launches of the newest call: groups x pictures */
 } efx_timing;
 /* Enable HIP-event timing of the decode stages (events recorded on the kernels' own streams);
  * enabling (again) starts a new averaging window. */
@@ -1556,26 +1553,17 @@ int efx_get_timing(efx_ctx* ctx, efx_timing* out);
 typedef enum efx_option {
     EFX_OPT_GROUPS = 1,      /* reconstruction groups per efx_decode: 0 = automatic (above), n >= 1 = always n */
     EFX_OPT_PARSE_CAP = 2,   /* k_parse's residency cap: 0 = only while reconstruction is queued, 1 = always, 2 = never */
-    EFX_OPT_RECON_MODE = 3,  /* 0 = one k_recon launch per picture index (default); 1 or 2 = ONE launch per group for all picture
-                                indices (k_recon_all: a stream's pictures ordered by a per-stream counter -- bit-identical, on a
-                                par one call at a time, 8 % slower back to back: profiles/r5_recon_all.md) */
-    EFX_OPT_RECON_WAVES = 4, /* k_recon_all with EFX_OPT_RECON_ITEMS = 0: workgroups (waves) per compute unit; 0 = default (18) */
-    EFX_OPT_RECON_ITEMS = 6, /* k_recon_all: items -- (picture, stream, 64 blocks) -- a wave takes before it ends and frees its
-                                slot (default 16); 0 = as many as there are (a grid of what the chip holds) */
-    EFX_OPT_SBC_SERIAL = 7,  /* 1 = efx_sbc_decode runs every stream through the one-wave-per-stream kernel (the comparison the tests
+    EFX_OPT_SBC_SERIAL = 7   /* 1 = efx_sbc_decode runs every stream through the one-wave-per-stream kernel (the comparison the tests
                                 run the frame-parallel kernels against); 0 = default */
-    /* (8 selected a one-pass demultiplexer that was measured slower and was removed: EFX_ERR_ARG) */
-    EFX_OPT_RECON_SPINS = 5  /* read only: polls the reconstruction waves of the most recent call spent waiting for a predecessor
-                                picture (synchronises) */
+    /* The numbers 3, 4, 5, 6 and 8 are not reused: 3 ... 6 drove a single-launch reconstruction and 8 selected a one-pass
+     * demultiplexer, both measured slower and removed (tools/exp/rejected/README.md).  efx_set_option and efx_get_option
+     * return EFX_ERR_ARG for them. */
 } efx_option;
 /* Debugging aid of the guard-page allocator (EFX_GUARD=1 / 2 in the environment: every device buffer of the library and of
  * efx_device_alloc becomes its own mapping that ends -- mode 2: starts -- on an unmapped page, so that a kernel reading or
  * writing past a buffer faults at once): writes one word at `offset_bytes` from the start of a buffer (negative: in front of
  * it).  tools/guard_selftest.py uses it to show that the allocator catches what it is there to catch. */
 int efx_debug_poke(efx_ctx* ctx, void* dptr, size_t bytes, long long offset_bytes);
-/* Debugging aid: word 0 of each of the 64 header lines of k_recon_all's hand-over words after the most recent call (queue
- * heads 0-7, spins 8, abort 9; the rest zero). */
-int efx_debug_recon_stats(efx_ctx* ctx, uint32_t out[64]);
 int efx_set_option(efx_ctx* ctx, int option, int value);
 int efx_get_option(efx_ctx* ctx, int option, int* value);
 

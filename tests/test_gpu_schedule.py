@@ -1,6 +1,5 @@
 """Every launch structure on purpose (efx_set_option): results must not depend on how a call is cut into launches -- one
-k_recon launch per picture index or one k_recon_all per group (eager / deferred hand-over signal, any number of items per wave),
-one reconstruction group or several, a capped or an uncapped parse kernel -- and the in-place ingest path must deliver the
+reconstruction group or several, a capped or an uncapped parse kernel -- and the in-place ingest path must deliver the
 same batch as the staged one.  Goldens: the unmodified reference decoder's per-picture hashes (tests/golden/bench_gop12.u64)."""
 import os
 
@@ -34,13 +33,14 @@ def all_pictures(efx, dec, n):
     return np.stack([h[:n, dec.picture_slot(p)] for p in range(P)], axis=1)
 
 
-@pytest.mark.parametrize("mode,items", [(0, 16), (1, 16), (2, 16), (2, 1), (2, 3), (2, 0), (1, 0)])
+@pytest.mark.parametrize("groups", [0, 1, 2, 4, 16])
 @pytest.mark.parametrize("n", [1, 5, 8, 128])
-def test_reconstruction_structures_every_picture(efx, batch, mode, items, n):
+def test_reconstruction_structures_every_picture(efx, batch, groups, n):
+    """All 12 pictures of every stream under every group count (the library clamps it to max(1, n / 8): the small batches run
+    as one group, 128 streams as 1, 2, 4 and 16)."""
     streams, golden = batch
     dec = efx.Decoder(n, P, P + 1, max_stream_bytes=sum(s.size for s in streams[:n]) + 4096)
-    dec.set_option(efx.OPT_RECON_MODE, mode)
-    dec.set_option(efx.OPT_RECON_ITEMS, items)
+    dec.set_option(efx.OPT_GROUPS, groups)
     dec.upload(streams[:n], efx.FORMAT_ES)
     dec.decode()
     assert np.array_equal(all_pictures(efx, dec, n), golden[:n])
@@ -69,7 +69,9 @@ def test_groups_and_parse_cap_pinned(efx, batch, groups, cap):
 
 
 def test_decode_range_small_budgets_through_the_single_launch(efx, batch):
-    """efx_decode_range asks for one or two pictures at a time (the streaming adapter): k_recon_all with n_pictures = 1, 2."""
+    """efx_decode_range asks for a few pictures at a time (the streaming adapter): calls of 1, 2, 3 and 5 picture indices, each
+    continuing where the one before stopped.  Each call is one k_recon launch per picture index asked for; the name dates
+    from when a single-launch kernel existed beside that, which this test never selected."""
     streams, golden = batch
     n = 16
     dec = efx.Decoder(n, P, P + 1, max_stream_bytes=sum(s.size for s in streams[:n]) + 4096)
@@ -87,11 +89,14 @@ def test_decode_range_small_budgets_through_the_single_launch(efx, batch):
 
 
 def test_removed_option_number_is_refused(efx):
-    """Option 8 selected the one-pass demultiplexer that was removed; its number is not reused and not accepted."""
+    """Options 3 ... 6 drove the single-launch reconstruction and 8 selected the one-pass demultiplexer, all removed; their
+    numbers are not reused and not accepted, neither to set nor to read."""
     dec = efx.Decoder(1, P, 2, max_stream_bytes=4096)
-    with pytest.raises(efx.EfxError) as e:
-        dec.set_option(8, 0)
-    assert e.value.status == -1  # EFX_ERR_ARG
+    for number in (3, 4, 5, 6, 8):
+        for call in (lambda: dec.set_option(number, 0), lambda: dec.get_option(number)):
+            with pytest.raises(efx.EfxError) as e:
+                call()
+            assert e.value.status == -1, number  # EFX_ERR_ARG
     dec.close()
 
 

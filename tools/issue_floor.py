@@ -33,7 +33,7 @@ SIMDS = 256 * 4
 
 # kernel (mangled-name fragment) -> (source file, extra flags)
 KERNELS = {
-    "k_recon": ("k_recon.hip", "_ZN3efx7k_reconE", ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]),
+    "k_recon": ("k_recon.hip", "_ZN3efx7k_reconE", []),
     "k_parse": ("k_parse.hip", "_ZN3efx7k_parseE", []),
     "k_sbc_par_mono": ("k_sbc.hip", "_ZN3efx14k_sbc_par_monoE", []),
     "k_pdm": ("k_video.hip", "_ZN3efx5k_pdmE", []),
