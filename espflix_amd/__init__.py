@@ -17,7 +17,7 @@ from fractions import Fraction
 import numpy as np
 
 # the C-ABI's structs, record dtypes and signatures live in _abi.py; they are part of this module's surface
-from ._abi import (ENC_PICTURE_INFO_DTYPE, LOUDNESS_REC_DTYPE, LOUDNESS_STEP_DTYPE, TELECINE_INFO, _P, _SYMBOLS,  # noqa: F401
+from ._abi import (DENOISE_OPTS_DTYPE, ENC_PICTURE_INFO_DTYPE, LOUDNESS_REC_DTYPE, LOUDNESS_STEP_DTYPE, TELECINE_INFO, _P, _SYMBOLS,  # noqa: F401
                    _AdaptiveQuant, _CompareOpts, _CompareRec, _Config, _ConformOpts, _CropOpts, _DeintOpts, _DetelecineOpts,
                    _EncodeOpts, _EncodeRate, _EncPictureInfo, _ExportOpts, _FieldOpts, _IdxRec, _ImportColour, _ImportHdr,
                    _ImportOpts, _ImportPcmOpts, _LoudnessGateOpts, _LoudnessStepsOpts, _MuxOpts, _PcmGainOpts, _SbcEncodeOpts,
@@ -489,6 +489,19 @@ def detelecine_count(n_frames: int, *, lead: bool = False) -> int:
     """Film frames per stream a detelecine call makes of n_frames offered frames (efx_detelecine_count; -1 for arguments
     the call rejects): of the n = n_frames - lead processed frames one in every whole cycle of five is dropped."""
     return int(load_library().efx_detelecine_count(n_frames, 1 if lead else 0))
+
+
+DENOISE_MAX_THRESHOLD = 64   # efx_denoise_opts: every threshold lies in 0 .. 64
+
+
+def denoise_thresholds(sigma: float) -> tuple:
+    """(luma_spatial, chroma_spatial, luma_temporal, chroma_temporal) for noise of standard deviation sigma, in levels:
+    (2 sigma, 2 sigma, 4 sigma, 4 sigma), rounded and clamped to 64 -- the settings measured in profiles/denoise.md.
+    Host only."""
+    if not sigma >= 0:
+        raise ValueError(f"sigma must be >= 0, got {sigma!r}")
+    t = lambda v: int(min(DENOISE_MAX_THRESHOLD, v + 0.5))
+    return t(2 * sigma), t(2 * sigma), t(4 * sigma), t(4 * sigma)
 
 
 def sbc_state_bytes() -> int:
@@ -1159,6 +1172,58 @@ class Decoder:
 
         out, records = self._frames_to_pictures(src, fmt, width, height, pitch, plane_rows, n_streams, count, queue)
         return (out, records) if info else out
+
+    # -- noisy sources (efx_denoise) ----------------------------------------------------------
+    def denoise_to(self, src: DeviceBuffer | int, dst: DeviceBuffer | int, *, surface: _Surface, n_streams: int = 1, n_frames: int,
+                   luma_spatial: int = 0, chroma_spatial: int = 0, luma_temporal: int = 0, chroma_temporal: int = 0,
+                   prev: DeviceBuffer | int | None = None, src_stride: int = 0, dst_stride: int = 0, prev_stride: int = 0) -> int:
+        """efx_denoise on raw device memory (DeviceBuffers or pointers), asynchronous on the library's stream: frame j of
+        stream i, read as `surface` (surface_layout(): I420, YV12, NV12, NV21, pitched or packed) describes it, at src +
+        (i * n_frames + j) * src_stride (0 = surface.bytes rounded up to 16); the filtered pictures, packed I420 of the
+        surface's size, at dst + (i * n_frames + j) * dst_stride (0 = width * height * 3 / 2 rounded up to 16).  The
+        thresholds, 0 .. 64 in levels (denoise_thresholds(sigma)): a neighbour further than *_spatial from a sample stays
+        out of its 3 x 3 average; a sample that moved by *_temporal or more against the stream's previous output takes
+        the new value whole, a smaller change is blended.  prev: stream i's last output of the previous piece, packed
+        I420, at prev + i * prev_stride -- a pointer into that call's dst; None = the title's start.  The rule:
+        include/efx.h, "noisy sources".  Returns n_frames, the pictures per stream."""
+        o = np.zeros(1, dtype=DENOISE_OPTS_DTYPE)
+        o[0] = (n_streams, n_frames, luma_spatial, chroma_spatial, luma_temporal, chroma_temporal, src_stride, dst_stride, prev_stride)
+        _check(self._ctx, self._lib.efx_denoise(self._ctx, C.byref(surface), o.ctypes.data, _ptr(src), _ptr(prev), _ptr(dst)))
+        return n_frames
+
+    def denoise(self, src, *, fmt: str = "i420", width: int, height: int, pitch: int = 0, plane_rows: int = 0,
+                luma_spatial: int = 0, chroma_spatial: int = 0, luma_temporal: int = 0, chroma_temporal: int = 0,
+                n_streams: int = 1, prev=None):
+        """Noisy frames as filtered pictures of the same size, made on the device (denoise_to).  src: a NumPy array or a
+        uint8 torch tensor on the decoder's device of shape (n_streams * n_frames, bytes), stream by stream, bytes being
+        surface_layout(fmt, width, height, pitch, plane_rows).bytes; fmt "i420", "yv12", "nv12" or "nv21", width and
+        height even.  prev: the streams' last pictures of the previous piece, (n_streams, width * height * 3 / 2) as
+        this method returned them (array or tensor), None at a title's start.  Returns (n_streams * n_frames, width *
+        height * 3 / 2) uint8 packed I420 pictures: what import_pictures(fmt="i420", width=, height=), detect_crop(),
+        deinterlace() and detelecine() take; a tensor for a tensor (no host round trip), an array for an array.
+        Synchronises: torch's current stream before (tensor input), the library's after."""
+        surf, total, src = _surface_source(src, fmt, width, height, pitch, plane_rows)
+        if n_streams < 1 or total < 1 or total % n_streams:
+            raise ValueError(f"{total} source images do not make {n_streams} streams of equal length")
+        for name, t in (("luma_spatial", luma_spatial), ("chroma_spatial", chroma_spatial), ("luma_temporal", luma_temporal),
+                        ("chroma_temporal", chroma_temporal)):
+            if not 0 <= t <= DENOISE_MAX_THRESHOLD:
+                raise ValueError(f"{name}={t!r}: a threshold lies in 0 .. {DENOISE_MAX_THRESHOLD}")
+        image = width * height * 3 // 2
+        if prev is not None and tuple(prev.shape) != (n_streams, image):
+            raise ValueError(f"prev must have shape ({n_streams}, {image}), got {tuple(prev.shape)}")
+        stride, dstride = _r16(surf.bytes), _r16(image)
+        with self._scratch() as s:
+            src_ptr, is_array, _ = self._stage(s, src, total, surf.bytes, stride=stride)
+            prev_ptr = self._stage(s, prev, n_streams, image, stride=dstride, what="prev")[0] if prev is not None else None
+            if not is_array or not (prev is None or isinstance(prev, np.ndarray)):
+                self._wait_for_torch(own_stream_ok=True)
+            dst_ptr, fetch = self._rows_out(s, is_array, total, image, dstride)
+            self.denoise_to(src_ptr, dst_ptr, surface=surf, n_streams=n_streams, n_frames=total // n_streams, luma_spatial=luma_spatial,
+                            chroma_spatial=chroma_spatial, luma_temporal=luma_temporal, chroma_temporal=chroma_temporal, prev=prev_ptr,
+                            src_stride=stride, dst_stride=dstride, prev_stride=dstride)
+            self.sync()
+            return fetch()
 
     # -- black borders (efx_detect_crop) ----------------------------------------------------
     def detect_crop_to(self, src: DeviceBuffer | int, rects: DeviceBuffer | int, *, n_streams: int, images_per_stream: int,

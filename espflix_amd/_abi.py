@@ -169,6 +169,11 @@ LOUDNESS_REC_DTYPE = np.dtype([("gated_mean", "<u8"), ("max_block", "<u8"), ("n_
 TELECINE_INFO = np.dtype([("comb_c", "<u8"), ("comb_p", "<u8"), ("diff", "<u8"), ("match", "<i4"), ("out", "<i4")])
 # efx_enc_picture_info: the record efx_encode_picture_info gives per picture
 ENC_PICTURE_INFO_DTYPE = np.dtype([("cut_i", "<u4"), ("cut_p", "<u4"), ("type", "u1"), ("pad", "u1", 3)])
+# efx_denoise_opts: the options of one efx_denoise call, passed by the address of a one-element record array (fixed-width
+# fields only, so the record is the struct)
+DENOISE_OPTS_DTYPE = np.dtype([("n_streams", "<i4"), ("n_frames", "<i4"), ("luma_spatial", "<i4"), ("chroma_spatial", "<i4"),
+                               ("luma_temporal", "<i4"), ("chroma_temporal", "<i4"), ("src_stride", "<u8"), ("dst_stride", "<u8"),
+                               ("prev_stride", "<u8")])
 
 # every symbol include/efx.h declares: (name, restype, argtypes)
 _P = C.c_void_p
@@ -219,6 +224,7 @@ _SYMBOLS = {
     "efx_deinterlace_count": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "efx_detelecine": (C.c_int, [_P, C.POINTER(_Surface), C.POINTER(_DetelecineOpts), _P, _P, _P]),
     "efx_detelecine_count": (C.c_int, [C.c_int, C.c_int]),
+    "efx_denoise": (C.c_int, [_P, C.POINTER(_Surface), _P, _P, _P, _P]),
     "efx_import_set_colour": (C.c_int, [_P, C.POINTER(_ImportColour)]),
     "efx_import_colour_coefs": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
     "efx_import_set_hdr": (C.c_int, [_P, C.POINTER(_ImportHdr)]),

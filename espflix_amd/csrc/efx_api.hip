@@ -26,6 +26,7 @@
 #include "import_px.h"
 #include "crop_px.h"
 #include "deint_px.h"
+#include "denoise_px.h"
 #include "telecine_px.h"
 #include "surface_px.h"
 #include "quality_px.h"
@@ -88,6 +89,7 @@ template <int SOURCE>
 __global__ void k_trick(TrickArgs);  // (k_trick.hip: the I420 and the ring instance)
 __global__ void k_conform(ConformArgs);  // (k_conform.hip)
 __global__ void k_deint(DeintArgs);      // (k_deint.hip)
+__global__ void k_denoise(DenoiseArgs);  // (k_denoise.hip)
 __global__ void k_telecine_measure(TelecineArgs);  // (k_telecine.hip)
 __global__ void k_telecine_decide(TelecineArgs);
 __global__ void k_telecine_weave(TelecineArgs);
@@ -2088,6 +2090,50 @@ int efx_detelecine(efx_ctx* ctx, const efx_surface* s, const efx_detelecine_opts
     hipLaunchKernelGGL(k_telecine_decide, dim3((unsigned)std::min((cycles + 255) / 256, cap)), dim3(256), 0, ctx->stream, a);
     const size_t wgs = (frames * a.weave_items + tpx::kWeaveWaves - 1) / tpx::kWeaveWaves;
     hipLaunchKernelGGL(k_telecine_weave, dim3((unsigned)std::min(wgs, cap)), dim3(64 * tpx::kWeaveWaves), 0, ctx->stream, a);
+    EFX_HIP(hipGetLastError());
+    return EFX_OK;
+}
+
+// ---- noisy sources (k_denoise.hip) ----------------------------------------------------------------------------------------------
+int efx_denoise(efx_ctx* ctx, const efx_surface* s, const efx_denoise_opts* o, const void* src_device, const uint8_t* prev_device,
+                uint8_t* dst_device)
+{
+    bind_device(ctx);
+    if (!ctx || !s || !o)
+        return EFX_ERR_ARG;
+    if (const char* what = surface_fault(s, EFX_PIX_I420, s->width, s->height))
+        return fail(ctx, EFX_ERR_ARG, (std::string("efx_denoise: ") + what).c_str());
+    if (!npx::surface_ok(*s))
+        return fail(ctx, EFX_ERR_ARG, "efx_denoise: the surface must be EFX_SURF_PLANAR8 or EFX_SURF_SEMI8");
+    if (!src_device || ((uintptr_t)src_device & 15) || !dst_device || ((uintptr_t)dst_device & 15) || ((uintptr_t)prev_device & 15))
+        return fail(ctx, EFX_ERR_ARG, "efx_denoise: src_device, dst_device and prev_device (when given) must be 16-byte aligned device pointers");
+    if (!npx::threshold_ok(o->luma_spatial) || !npx::threshold_ok(o->chroma_spatial) || !npx::threshold_ok(o->luma_temporal) ||
+        !npx::threshold_ok(o->chroma_temporal))
+        return fail(ctx, EFX_ERR_ARG, "efx_denoise: every threshold must be 0 .. 64");
+    if (o->n_streams < 1 || o->n_frames < 1 || (int64_t)o->n_streams * o->n_frames > INT32_MAX)
+        return fail(ctx, EFX_ERR_ARG, "efx_denoise: n_streams and n_frames must be >= 1, the images below 2^31");
+    DenoiseArgs a{};
+    a.src = static_cast<const uint8_t*>(src_device), a.prev = prev_device, a.dst = dst_device;
+    const size_t image = (size_t)s->width * s->height * 3 / 2;
+    a.src_stride = o->src_stride ? (size_t)o->src_stride : (s->bytes + 15) / 16 * 16;
+    a.dst_stride = o->dst_stride ? (size_t)o->dst_stride : (image + 15) / 16 * 16;
+    a.prev_stride = (size_t)o->prev_stride;
+    if (a.src_stride < s->bytes || (a.src_stride & 15))
+        return fail(ctx, EFX_ERR_ARG, "efx_denoise: src_stride must be a multiple of 16 and hold an image");
+    if (a.dst_stride < image || (a.dst_stride & 15))
+        return fail(ctx, EFX_ERR_ARG, "efx_denoise: dst_stride must be a multiple of 16 and hold an image");
+    if ((a.prev_stride & 15) || (prev_device && o->n_streams > 1 && a.prev_stride < image))
+        return fail(ctx, EFX_ERR_ARG, "efx_denoise: prev_stride must be a multiple of 16 and, with prev_device and several streams, hold an image");
+    a.s = *s;
+    a.n_streams = o->n_streams, a.n_frames = o->n_frames;
+    a.ts[0] = o->luma_spatial, a.ts[1] = o->chroma_spatial;
+    a.tt[0] = o->luma_temporal, a.tt[1] = o->chroma_temporal;
+    a.q[0] = npx::blend_q(a.tt[0]), a.q[1] = npx::blend_q(a.tt[1]);
+    a.stream_items = npx::stream_items(s->width, s->height);
+    // one launch whatever the counts are (a workgroup takes further items when there are more than the grid's)
+    const size_t items = (size_t)a.n_streams * a.stream_items;
+    const size_t wgs = (items + npx::kWaves - 1) / npx::kWaves;
+    hipLaunchKernelGGL(k_denoise, dim3((unsigned)std::min(wgs, (size_t)1 << 20)), dim3(64 * npx::kWaves), 0, ctx->stream, a);
     EFX_HIP(hipGetLastError());
     return EFX_OK;
 }

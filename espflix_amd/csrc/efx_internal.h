@@ -457,6 +457,19 @@ struct TelecineArgs {
     int measure_items, weave_items;  // tpx::measure_items(width, height), tpx::weave_items(surface)
 };
 
+// k_denoise (k_denoise.hip) launch arguments (by value): efx_denoise_opts, checked, and the surface, checked (denoise_px.h)
+struct DenoiseArgs {
+    const uint8_t* src;   // stream i, frame j of the call at src + (i * n_frames + j) * src_stride
+    const uint8_t* prev;  // stream i's last output of the previous piece at prev + i * prev_stride: packed I420; NULL = none
+    uint8_t* dst;         // stream i, output j at dst + (i * n_frames + j) * dst_stride: packed I420, width x height
+    size_t src_stride, dst_stride, prev_stride;
+    efx_surface s;
+    int n_streams, n_frames;
+    int ts[2], tt[2];     // the spatial and temporal thresholds of luma [0] and chroma [1]
+    uint32_t q[2];        // npx::blend_q of tt
+    int stream_items;     // npx::stream_items(width, height)
+};
+
 // k_sbc_enc launch arguments (by value): efx_sbc_encode_opts, checked, with the context's tables
 namespace sbcenc {
 struct Tables;

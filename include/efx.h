@@ -613,6 +613,70 @@ int efx_detelecine(efx_ctx* ctx, const efx_surface* surface, const efx_detelecin
 /* outputs per stream of such a call; -1 for arguments it rejects.  Host only. */
 int efx_detelecine_count(int n_frames, int lead);
 
+/* -- noisy sources: spatial and temporal noise reduction (k_denoise) ------------------------ */
+/* Film grain and analogue or sensor noise are the part of a picture that motion compensation cannot predict, and at 1.5
+ * Mbit/s every bit spent on noise is taken from the picture.  DVD-size sources are scaled down only 2 to 2.5 times by
+ * the import, so their noise survives it.  efx_denoise filters the source pictures at their own size, before anything
+ * is scaled: the step the reference indexer leaves to ffmpeg's hqdn3d.  The rule is this library's own exact integer
+ * rule (espflix_amd/csrc/denoise_px.h), bit-reproducible anywhere.  Byte compatibility with ffmpeg is not promised.
+ *
+ * The rule is applied to each of the three planes of the canonical image of a surface ("surfaces" above), each with its
+ * own w, h (luma: width x height; Cb, Cr: half of each).  Luma uses (Ts, Tt) = (luma_spatial, luma_temporal), Cb and Cr
+ * use (chroma_spatial, chroma_temporal); every threshold lies in 0 .. 64.  All values are int, >> is arithmetic.
+ *
+ *   Spatial step.  Row and column indices are clamped to the plane.  With F the plane of the frame, c = F[y][x] and the
+ *   weights K = [[1, 2, 1], [2, 4, 2], [1, 2, 1]]:
+ *     v(i, j) = F[y+i][x+j]  if |F[y+i][x+j] - c| <= Ts,  else c               (i, j in -1, 0, 1)
+ *     s = (sum of K[i][j] v(i, j) + 8) >> 4
+ *   A thresholded 3 x 3 binomial filter: a neighbour across an edge is replaced by the centre.  Ts = 0 gives s = c.
+ *   Temporal step.  Recursive over a stream's frames: P is the output sample at the same place of the stream's previous
+ *   output picture.  For a stream's first picture with no `prev` (a title's start) out = s; with Tt = 0, out = s;
+ *   otherwise
+ *     d = s - P;  a = |d|
+ *     k = 256                       if a >= Tt
+ *     k = 64 + ((a a Q) >> 16)      otherwise, with Q = 12582912 / (Tt Tt)      (integer division; 12582912 = 192 x 65536)
+ *     out = P + sgn(d) ((a k + 128) >> 8)
+ *   out lies between s and P, so in 0 .. 255; out = P with s != P only for a = 1, so the recursion never lags a static
+ *   value by more than one level; a a Q < 2^24; the rounding is symmetric in the sign of d (no brightness drift); a
+ *   sample that moved by Tt or more takes the new value whole, which is why moving edges leave no trail.
+ *   Layout.  Source image i * n_frames + j is stream i's frame j, at src_device + (i * n_frames + j) * src_stride.  Outputs
+ *   are packed I420 pictures of the surface's width x height at dst_device + (i * n_frames + j) * dst_stride, as
+ *   efx_deinterlace writes them: efx_import_frames, efx_detect_crop, efx_deinterlace and efx_detelecine (through
+ *   efx_surface_layout(EFX_KIND_I420)) read them as they are.
+ *   Pieces.  prev_device + i * prev_stride is stream i's last output picture of the previous piece, packed I420: a caller
+ *   passes dst_prev + (n_prev - 1) * dst_stride with prev_stride = n_prev * dst_stride.  There is no copy and no state
+ *   buffer, and the concatenated outputs of the pieces equal those of one long call, byte for byte.  prev_device = NULL
+ *   is the title's start.  Streams never see each other's frames.
+ *   Surfaces.  EFX_SURF_PLANAR8 (YV12 by swapped offsets; pitched) and EFX_SURF_SEMI8 (NV12 / NV21, de-interleaved on
+ *   load); width and height even, 2 .. 4096.
+ *   Settings.  Thresholds of (2 sigma, 2 sigma, 4 sigma, 4 sigma) for noise of standard deviation sigma are the measured
+ *   ones (profiles/denoise.md).
+ *
+ * Memory contract (efx_deinterlace's).  For source image k the kernel reads only bytes in [src + k * src_stride, src + k
+ * * src_stride + bytes rounded up to 16), 16 bytes at a time wherever a plane's rows begin, and only rows of the three
+ * planes; of a previous output only [prev + i * prev_stride, ... + width x height x 3 / 2 rounded up to 16).  Bytes in
+ * pitch padding, between planes and between images are fetched at most as part of such an access and never influence a
+ * result.  It writes only the width x height x 3 / 2 bytes of each output image.  All offsets are computed in 64 bits.
+ * The source, previous-output and destination regions must not overlap.
+ *
+ * Out of scope: the 16-bit layouts, motion-compensated filtering, a noise estimate that chooses the thresholds, state
+ * at more than 8 bits, chaining into the import or the title builder, efx_multi_*. */
+typedef struct efx_denoise_opts {     /* fixed-width fields only: a binding can mirror it as a packed record */
+    int32_t  n_streams;               /* >= 1 */
+    int32_t  n_frames;                /* frames per stream in this call, >= 1 */
+    int32_t  luma_spatial, chroma_spatial, luma_temporal, chroma_temporal;   /* 0 .. 64 */
+    uint64_t src_stride, dst_stride;  /* as efx_deint_opts: 0 = default, multiples of 16 */
+    uint64_t prev_stride;             /* bytes between the streams' previous output pictures; multiple of 16 */
+} efx_denoise_opts;
+/* Asynchronous on the context's stream: no host synchronisation, one launch whatever the counts are, no scratch, and no
+ * decoder, encoder, SBC, import or other state is touched.
+ * EFX_ERR_ARG: everything efx_import_surfaces rejects about a surface, a 16-bit layout, a threshold outside 0 .. 64,
+ * n_streams or n_frames below 1, more than 2^31 - 1 images, a NULL or misaligned (16 bytes) src_device or dst_device, a
+ * misaligned prev_device, a stride that is too small or not a multiple of 16, prev_stride of 0 with prev_device given
+ * and n_streams > 1.  A refused call writes nothing. */
+int efx_denoise(efx_ctx* ctx, const efx_surface* surface, const efx_denoise_opts* opts, const void* src_device,
+                const uint8_t* prev_device /* NULL: the title's start */, uint8_t* dst_device);
+
 /* -- source colour: BT.709, full-range and other YCbCr sources to BT.601 (k_import) -------- */
 /* MPEG-1 carries BT.601 studio-swing YCbCr, and efx_import_frames / efx_import_surfaces copy a YCbCr source's samples
  * through.  What a decoder hands over today is mostly HD with BT.709 matrix coefficients, and phone or JPEG-derived
