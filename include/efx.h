@@ -1556,7 +1556,10 @@ int efx_loudness_step_count(int rate, int64_t first_sample, int n_samples);
  *  - the unit of interleaving is a PES: its packets stay together, video packets are copied unchanged.  Units appear in
  *    PTS order, audio first at equal PTS, the order inside each kind kept; a video PES without PTS counts as having its
  *    predecessor's (before the first PTS: as earlier than all audio); audio later than the last video PES follows it.
- *    PTS are compared as written, without unwrapping at 2^33;
+ *    Nothing is unwrapped at 2^33: a video PTS is compared as written (its 33 bits), an audio PTS as audio_first_pts +
+ *    floor(frame x samples_per_frame x 90000 / sample_rate) BEFORE it is masked to the 33 bits that are written.  Audio PTS
+ *    therefore never decrease (the placement is a binary search over them), and once they pass 2^33 the remaining audio
+ *    PES count as later than every video PES and follow the last one, whatever the video's wrapped PTS say;
  *  - no PAT / PMT: the reference player does not read them (its own clips carry them on PIDs 0 and 0x1000, it skips them). */
 #define EFX_MUX_FULL      1024u  /* status bit: the output region is too small; the stream's length is 0 */
 #define EFX_MUX_BAD_VIDEO 2048u  /* status bit: video_len not a multiple of 188, a packet without 0x47 or not on PID 0x100,

@@ -42,13 +42,14 @@ def r16(v):
     return (v + 15) // 16 * 16
 
 
-def device_mux(efx, dec, videos, frames, dst_stride=None, **opt):
-    """videos: list of uint8 arrays; frames [n, n_frames x FB].  Returns (titles, status, the output regions [n, stride])."""
+def prepare_mux(efx, dec, videos, frames, dst_stride=None, frame_bytes=FB, **opt):
+    """videos: list of uint8 arrays; frames [n, n_frames x frame_bytes].  Allocates and uploads the buffers of one efx_mux_av
+    (every upload synchronises the library's stream first: efx_memcpy_h2d) and returns what launch_mux and collect_mux need."""
     n = len(videos)
-    n_frames = frames.shape[1] // FB
+    n_frames = frames.shape[1] // frame_bytes
     v_stride, a_stride = r16(max(1, max(v.size for v in videos))) + 16, r16(max(1, frames.shape[1])) + 16
     fpp = opt.get("frames_per_pes", 8)
-    stride = dst_stride or efx.mux_bound(v_stride, n_frames, FB, fpp)
+    stride = dst_stride or efx.mux_bound(v_stride, n_frames, frame_bytes, fpp)
     host_v = np.full((n, v_stride), 0xEE, dtype=np.uint8)
     for i, v in enumerate(videos):
         host_v[i, :v.size] = v
@@ -61,18 +62,39 @@ def device_mux(efx, dec, videos, frames, dst_stride=None, **opt):
     meta = np.full(3 * r16(4 * n) // 4, 0xFFFFFFFF, dtype=np.uint32)
     meta[:n] = [v.size for v in videos]
     d_meta.upload(meta)
+    args = dict(n_streams=n, frame_bytes=frame_bytes, n_frames=n_frames, video_stride=v_stride, audio_stride=a_stride,
+                dst_stride=stride, **opt)
+    return n, stride, (d_v, d_a, d_dst, d_meta), args
+
+
+def launch_mux(dec, prepared):
+    """efx_mux_av on prepared buffers: one asynchronous launch, no copy and nothing synchronised."""
+    n, _, (d_v, d_a, d_dst, d_meta), args = prepared
     p_len, p_st = d_meta.ptr + r16(4 * n), d_meta.ptr + 2 * r16(4 * n)
-    dec.mux_to(d_v, d_meta.ptr, d_a if n_frames else None, d_dst, p_len, p_st, n_streams=n, frame_bytes=FB, n_frames=n_frames,
-               video_stride=v_stride, audio_stride=a_stride, dst_stride=stride, **opt)
-    dec.sync()
-    meta = d_meta.download(np.uint32, meta.size)
+    dec.mux_to(d_v, d_meta.ptr, d_a if args["n_frames"] else None, d_dst, p_len, p_st, **args)
+
+
+def collect_mux(dec, prepared):
+    """(titles, status, the output regions [n, stride]) of a launch_mux, after a dec.sync()."""
+    n, stride, (d_v, d_a, d_dst, d_meta), _ = prepared
+    try:
+        meta = d_meta.download(np.uint32, 3 * r16(4 * n) // 4)
+        region = d_dst.download(np.uint8, n * stride).reshape(n, stride)
+    finally:
+        for b in (d_v, d_a, d_dst, d_meta):
+            b.free()
     lens, st = meta[r16(4 * n) // 4:][:n], meta[2 * r16(4 * n) // 4:][:n]
-    region = d_dst.download(np.uint8, n * stride).reshape(n, stride)
-    for b in (d_v, d_a, d_dst, d_meta):
-        b.free()
     for i in range(n):
         assert (region[i, lens[i]:] == 0xA5).all(), f"stream {i}: bytes behind the title were written"
     return [region[i, :lens[i]].tobytes() for i in range(n)], st, region
+
+
+def device_mux(efx, dec, videos, frames, dst_stride=None, frame_bytes=FB, **opt):
+    """prepare_mux, launch_mux, a synchronisation, collect_mux."""
+    prepared = prepare_mux(efx, dec, videos, frames, dst_stride, frame_bytes, **opt)
+    launch_mux(dec, prepared)
+    dec.sync()
+    return collect_mux(dec, prepared)
 
 
 @pytest.mark.parametrize("fpp,pid", [(8, 0x101), (1, 0x102), (32, 0x102)])

@@ -1,11 +1,14 @@
 """The A/V multiplexer's rules (include/efx.h: efx_mux_av) as tests/mux_model.py restates them, no GPU: a multiplexed title
 plays like its video alone plus exactly its audio -- through the test oracle, and through the unmodified reference player
 where oracle/_ref is built."""
+import os
+
 import numpy as np
 import pytest
 
 import encode_model as E
 import mux_model as X
+import mux_streams as S
 import oracle
 
 FB = 64  # mono, 48 kHz, 16 blocks, bitpool 28: the frames the player plays
@@ -26,6 +29,31 @@ def audio_for(video: np.ndarray, seed: int):
     n_frames = int(np.ceil((max(pts) + 3003 - pts[0]) * 48000 / 90000 / 128))
     rng = np.random.default_rng(seed)
     return rng.integers(0, 256, size=n_frames * FB, dtype=np.uint8), pts[0]
+
+
+def ordering_holds(units, title_size):
+    """PES units in PTS order, audio first at ties, the order inside each kind kept, the title gapless."""
+    at, reach, last_audio = 0, -1, -1
+    for kind, pts, start, n in units:
+        assert start == at
+        at += n
+        if kind == "v":
+            reach = max(reach, pts if pts is not None else reach)
+        else:
+            assert pts > last_audio
+            last_audio = pts
+    assert at * 188 == title_size
+    last_video_pts = -1
+    for k, (kind, pts, start, n) in enumerate(units):
+        if kind == "v":
+            if pts is not None:
+                # no audio at or before this PTS comes later
+                assert all(u[1] > pts for u in units[k + 1:] if u[0] == "a")
+                last_video_pts = max(last_video_pts, pts)
+        else:
+            # an audio PES follows only video that is strictly earlier, unless no video is left
+            later_video = [u for u in units[k + 1:] if u[0] == "v"]
+            assert last_video_pts < pts or not later_video
 
 
 @pytest.mark.parametrize("name", ["splash", "vmedia", "encoded"])
@@ -55,28 +83,7 @@ def test_title_plays_like_its_parts(videos, name, fpp, pid):
     v_units = [u for u in units if u[0] == "v"]
     first_of = {u[0]: k for k, u in enumerate(X.video_units(video))}
     assert [v_units[first_of[int(o)]][2] for o in so0] == [int(o) for o in so1]
-    # PES units in PTS order, audio first at ties, the order inside each kind kept, the title gapless
-    at, reach, last_audio = 0, -1, -1
-    for kind, pts, start, n in units:
-        assert start == at
-        at += n
-        if kind == "v":
-            reach = max(reach, pts if pts is not None else reach)
-        else:
-            assert pts > last_audio
-            last_audio = pts
-    assert at * 188 == title.size
-    last_video_pts = -1
-    for k, (kind, pts, start, n) in enumerate(units):
-        if kind == "v":
-            if pts is not None:
-                # no audio at or before this PTS comes later
-                assert all(u[1] > pts for u in units[k + 1:] if u[0] == "a")
-                last_video_pts = max(last_video_pts, pts)
-        else:
-            # an audio PES follows only video that is strictly earlier, unless no video is left
-            later_video = [u for u in units[k + 1:] if u[0] == "v"]
-            assert last_video_pts < pts or not later_video
+    ordering_holds(units, title.size)
     # continuity counters per PID
     pk = title.reshape(-1, 188)
     pids = ((pk[:, 1].astype(int) & 0x1F) << 8) | pk[:, 2]
@@ -127,3 +134,100 @@ def test_statuses_and_continuation(videos):
                  cc=(3 + X.audio_packets(half, FB, 8)) & 15)
     both, _ = X.mux(video[:0], frames, frame_bytes=FB, first_pts=first, cc=3)
     assert a + b == both
+
+
+# ---- the packetiser of enc_core.h against the model's, and the hand-built video of tests/mux_streams.py ---------------------
+
+@pytest.fixture(scope="module")
+def ts_packets_exe(tmp_path_factory):
+    """tests/ts_packets_main.cpp: enc_core.h's ts_byte and pes_header_byte on the host (built as encode_model.build builds)."""
+    import shutil
+    import subprocess
+    cxx = shutil.which("g++") or shutil.which("c++")
+    assert cxx, "a host C++ compiler is needed to build enc_core.h"
+    exe = str(tmp_path_factory.mktemp("ts_packets") / "ts_packets")
+    subprocess.run([cxx, "-O2", "-std=c++17", "-Wall", "-I", os.path.join(E.ROOT, "espflix_amd", "csrc"),
+                    os.path.join(E.ROOT, "tests", "ts_packets_main.cpp"), "-o", exe], check=True)
+    return exe
+
+
+def _run_ts_packets(exe, mode, data, tmp_path):
+    import subprocess
+    src, out = str(tmp_path / f"{mode}.in"), str(tmp_path / f"{mode}.out")
+    data.tofile(src)
+    subprocess.run([exe, mode, src, out], check=True, timeout=120)
+    return np.fromfile(out, dtype=np.uint8)
+
+
+def test_packetiser_equals_the_model(ts_packets_exe, tmp_path):
+    """k_mux.hip's audio_byte is enc::ts_byte plus the PID and the PES header: ts_byte against mux_model.packets() for every
+    PES length an audio PES can have (1 .. 14 + 2048), and all 16 starting counters at the lengths around the multiples of
+    184, where the stuffing appears, is one byte, and goes."""
+    pairs = [(n, n & 15) for n in range(1, 2063)]
+    pairs += [(n, cc) for m in range(184, 2063, 184) for n in (m - 2, m - 1, m, m + 1, m + 2) for cc in range(16)]
+    pairs += [(n, cc) for n in (1, 2, 2061, 2062) for cc in range(16)]
+    got = _run_ts_packets(ts_packets_exe, "ts", np.array(pairs, dtype=np.uint32), tmp_path).tobytes()
+    at = 0
+    for n, cc in pairs:
+        pes = bytes((k * 7 + 3) & 0xFF for k in range(n))
+        want = X.packets(pes, 0x100, cc)
+        assert got[at:at + len(want)] == want, (n, cc)
+        at += len(want)
+    assert at == len(got)
+
+
+def test_pes_header_equals_the_model(ts_packets_exe, tmp_path):
+    pts = [0, (1 << 33) - 1] + [1 << b for b in range(33)]
+    got = _run_ts_packets(ts_packets_exe, "pes", np.array(pts, dtype=np.int64), tmp_path).reshape(-1, 14)
+    for p, row in zip(pts, got):
+        assert row[:9].tobytes() == b"\x00\x00\x01\xE0\x00\x00\x80\x80\x05" and row[9:].tobytes() == X.pts_bytes(p), p
+        t = [int(v) for v in row[9:]]
+        assert (((t[0] >> 1) & 7) << 30 | t[1] << 22 | (t[2] >> 1) << 15 | t[3] << 7 | t[4] >> 1) == p  # as video_units reads it
+
+
+FAMILIES = S.families()
+HAND_BUILT = [c for cases in FAMILIES.values() for c in cases]
+
+
+@pytest.mark.parametrize("case", HAND_BUILT, ids=[c.name for c in HAND_BUILT])
+def test_hand_built_video(case):
+    """The cases the device runs in tests/test_gpu_mux_edges.py, through the model alone: what each aims at occurs (the
+    case's own coverage assertion), the ordering rules hold, the video's packets are unchanged and in order, and the
+    oracle's audio demultiplexer returns the frames."""
+    for i, (title, status, units) in enumerate(case.cover()):
+        if status:
+            assert title == b"" and units == []
+            continue
+        ordering_holds(units, len(title))
+        arr = np.frombuffer(title, dtype=np.uint8)
+        assert np.array_equal(X.video_only(arr), case.videos[i])
+        assert np.array_equal(oracle.ts_audio_es(arr), case.frames[i])
+        pk = arr.reshape(-1, 188)
+        pid = case.opt.get("audio_pid", 0x101)
+        cc = pk[(((pk[:, 1].astype(int) & 0x1F) << 8) | pk[:, 2]) == pid][:, 3] & 15
+        assert np.array_equal(cc, (case.opt.get("audio_cc", 0) + np.arange(cc.size)) & 15)
+
+
+def test_batches_cover_every_status():
+    for n in (1, 65):
+        S.batch(n).cover()
+
+
+@pytest.mark.parametrize("case", HAND_BUILT, ids=[c.name for c in HAND_BUILT])
+def test_hand_built_titles_in_the_reference_player(case):
+    """Every title of every case through the unmodified reference player's demultiplexer, where it is built.  The player
+    decodes the video it demultiplexes, so the video's filler is zeros here (mux_streams.blank says why nothing else
+    does): the packets and PES starts, all the multiplexer reads, are the same, and so is every unit's place."""
+    if not oracle.have_ref():
+        pytest.skip("oracle/_ref is not built")
+    played = 0
+    for i, (_, status, want_units) in enumerate(case.model()):
+        if status:
+            continue
+        video = S.blank(case.videos[i])
+        assert X.video_units(video) == X.video_units(case.videos[i])
+        title, status, units = case.model_one(video, case.frames[i])
+        assert status == 0 and [u[2:] for u in units] == [u[2:] for u in want_units]
+        assert np.array_equal(oracle.ref_audio_es(np.frombuffer(title, dtype=np.uint8)), case.frames[i]), i
+        played += 1
+    assert played
