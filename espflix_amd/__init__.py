@@ -17,7 +17,8 @@ from fractions import Fraction
 import numpy as np
 
 # the C-ABI's structs, record dtypes and signatures live in _abi.py; they are part of this module's surface
-from ._abi import (DENOISE_OPTS_DTYPE, ENC_PICTURE_INFO_DTYPE, LOUDNESS_REC_DTYPE, LOUDNESS_STEP_DTYPE, TELECINE_INFO, _P, _SYMBOLS,  # noqa: F401
+from ._abi import (DENOISE_OPTS_DTYPE, ENC_PICTURE_INFO_DTYPE, LOUDNESS_REC_DTYPE, LOUDNESS_STEP_DTYPE, SCAN_FRAME_DTYPE,  # noqa: F401
+                   SCAN_OPTS_DTYPE, SCAN_REC_DTYPE, TELECINE_INFO, _P, _SYMBOLS,
                    _AdaptiveQuant, _CompareOpts, _CompareRec, _Config, _ConformOpts, _CropOpts, _DeintOpts, _DetelecineOpts,
                    _EncodeOpts, _EncodeRate, _EncPictureInfo, _ExportOpts, _FieldOpts, _IdxRec, _ImportColour, _ImportHdr,
                    _ImportOpts, _ImportPcmOpts, _LoudnessGateOpts, _LoudnessStepsOpts, _MuxOpts, _PcmGainOpts, _SbcEncodeOpts,
@@ -92,6 +93,14 @@ class LoudnessResult:
     gain_q12: np.ndarray       # int32: the gain that takes the stream to the target under the peak ceiling
     n_blocks: np.ndarray       # int64: 400 ms blocks
     n_gated: np.ndarray        # int64: blocks above both gates
+
+
+@dataclass
+class ScanResult:
+    """The scan type of one stream (Decoder.detect_scan, scan_verdict; the definition: include/efx.h, "scan type")."""
+    kind: str              # "progressive", "interlaced", "telecined" or "unknown"
+    first_field: object    # "top" or "bottom" for "interlaced" and "telecined", else None
+    rec: np.ndarray        # the stream's counts: a SCAN_REC_DTYPE record
 
 
 @dataclass
@@ -489,6 +498,23 @@ def detelecine_count(n_frames: int, *, lead: bool = False) -> int:
     """Film frames per stream a detelecine call makes of n_frames offered frames (efx_detelecine_count; -1 for arguments
     the call rejects): of the n = n_frames - lead processed frames one in every whole cycle of five is dropped."""
     return int(load_library().efx_detelecine_count(n_frames, 1 if lead else 0))
+
+
+# efx_scan_frame.label / .repeat and the verdicts of efx_scan_verdict
+SCAN_NONE, SCAN_STILL, SCAN_PROGRESSIVE, SCAN_TFF, SCAN_BFF, SCAN_UNDETERMINED = range(6)
+SCAN_REPEAT_NONE, SCAN_REPEAT_TOP, SCAN_REPEAT_BOTTOM = range(3)
+_SCAN_KINDS = ("unknown", "progressive", "interlaced", "telecined")
+SCAN_DEFAULTS = dict(nt=10, still=64, prog=384, intl=266, rep=768)   # still: not measured on real material (profiles/scan.md)
+
+
+def scan_verdict(rec) -> ScanResult:
+    """The verdict of one stream's counts, a SCAN_REC_DTYPE record (efx_scan_verdict; host only)."""
+    r = np.array(rec, dtype=SCAN_REC_DTYPE).reshape(1)
+    first = C.c_int(-1)
+    kind = int(load_library().efx_scan_verdict(r.ctypes.data, C.byref(first)))
+    if not 0 <= kind < len(_SCAN_KINDS):
+        raise ValueError("not a scan record")
+    return ScanResult(_SCAN_KINDS[kind], {FIELD_TOP: "top", FIELD_BOTTOM: "bottom"}.get(first.value), r[0])
 
 
 DENOISE_MAX_THRESHOLD = 64   # efx_denoise_opts: every threshold lies in 0 .. 64
@@ -1173,6 +1199,60 @@ class Decoder:
         out, records = self._frames_to_pictures(src, fmt, width, height, pitch, plane_rows, n_streams, count, queue)
         return (out, records) if info else out
 
+    # -- scan type (efx_detect_scan) ----------------------------------------------------------
+    def detect_scan_to(self, src: DeviceBuffer | int, frames: DeviceBuffer | int, recs: DeviceBuffer | int, *, surface: _Surface,
+                       n_streams: int = 1, n_frames: int, lead: bool = False, first_frame: int = 0, accumulate: bool = False,
+                       nt: int = 10, still: int = 64, prog: int = 384, intl: int = 266, rep: int = 768, src_stride: int = 0) -> int:
+        """efx_detect_scan on raw device memory (DeviceBuffers or pointers), asynchronous on the library's stream: frame j of
+        stream i, read as `surface` (surface_layout(): I420, YV12, NV12, NV21, pitched or packed) describes it, at src +
+        (i * n_frames + j) * src_stride (0 = surface.bytes rounded up to 16); one 48-byte record (SCAN_FRAME_DTYPE) per
+        processed frame at frames + (i * n + j) * 48, n = n_frames - lead, whatever frames held before; stream i's counts
+        (SCAN_REC_DTYPE, 64 bytes) at recs + 64 i, written, or with accumulate added to what lies there.  lead: the first
+        offered frame is context only; first_frame: its number in the title, which keeps the repeat phases title-absolute
+        when a title goes through in pieces with one frame of overlap.  nt, still, prog, intl, rep: the rule's options
+        (include/efx.h, "scan type").  Returns n, the frame records per stream."""
+        o = np.zeros(1, dtype=SCAN_OPTS_DTYPE)
+        o[0] = (n_streams, n_frames, 1 if lead else 0, 1 if accumulate else 0, nt, still, prog, intl, rep, 0, first_frame, src_stride)
+        _check(self._ctx, self._lib.efx_detect_scan(self._ctx, C.byref(surface), o.ctypes.data, _ptr(src), _ptr(frames), _ptr(recs)))
+        return n_frames - (1 if lead else 0)
+
+    def detect_scan(self, src, *, fmt: str = "i420", width: int, height: int, pitch: int = 0, plane_rows: int = 0, n_streams: int = 1,
+                    lead: bool = False, first_frame: int = 0, recs=None, frames: bool = False, nt: int = 10, still: int = 64,
+                    prog: int = 384, intl: int = 266, rep: int = 768):
+        """Whether streams are progressive, interlaced or telecined, and in which field order, found on the device
+        (detect_scan_to).  src: a NumPy array or a uint8 torch tensor on the decoder's device of shape (n_streams *
+        n_frames, bytes), stream by stream, as detelecine() takes it.  recs: the records of the title's previous piece
+        (the .rec of this method's results, or a SCAN_REC_DTYPE array of n_streams), to add to; the piece then begins
+        with the previous piece's last frame (lead=True) and first_frame is that frame's number in the title.  Returns a
+        list of ScanResult(kind, first_field, rec), one per stream; with frames=True (results, frame records), the
+        records a SCAN_FRAME_DTYPE array of shape (n_streams, n_frames - lead).  Synchronises: torch's current stream
+        before (tensor input), the library's after."""
+        surf, total, src = _surface_source(src, fmt, width, height, pitch, plane_rows)
+        if n_streams < 1 or total < 1 or total % n_streams:
+            raise ValueError(f"{total} source images do not make {n_streams} streams of equal length")
+        n_frames = total // n_streams
+        n = n_frames - (1 if lead else 0)
+        if n < 1:
+            raise ValueError(f"detect_scan: {n_frames} frames with lead={lead} leave no frame to process")
+        if recs is not None:
+            recs = np.array([r.rec if isinstance(r, ScanResult) else r for r in recs], dtype=SCAN_REC_DTYPE).reshape(-1)
+            if len(recs) != n_streams:
+                raise ValueError(f"recs must hold {n_streams} records, got {len(recs)}")
+        stride = _r16(surf.bytes)
+        with self._scratch() as s:
+            src_ptr, is_array, _ = self._stage(s, src, total, surf.bytes, stride=stride)
+            if not is_array:
+                self._wait_for_torch(own_stream_ok=True)
+            fbuf = s.alloc(n_streams * n * SCAN_FRAME_DTYPE.itemsize)
+            rbuf = s.alloc(n_streams * SCAN_REC_DTYPE.itemsize)
+            if recs is not None:
+                rbuf.upload(recs)
+            self.detect_scan_to(src_ptr, fbuf, rbuf, surface=surf, n_streams=n_streams, n_frames=n_frames, lead=lead, first_frame=first_frame,
+                                accumulate=recs is not None, nt=nt, still=still, prog=prog, intl=intl, rep=rep, src_stride=stride)
+            self.sync()
+            results = [scan_verdict(r) for r in rbuf.download(SCAN_REC_DTYPE, n_streams)]
+            return (results, fbuf.download(SCAN_FRAME_DTYPE, n_streams * n).reshape(n_streams, n)) if frames else results
+
     # -- noisy sources (efx_denoise) ----------------------------------------------------------
     def denoise_to(self, src: DeviceBuffer | int, dst: DeviceBuffer | int, *, surface: _Surface, n_streams: int = 1, n_frames: int,
                    luma_spatial: int = 0, chroma_spatial: int = 0, luma_temporal: int = 0, chroma_temporal: int = 0,
@@ -1383,6 +1463,9 @@ class Decoder:
         source's size (deinterlace_to; include/efx.h, "interlaced sources") and the progressive pictures are imported
         with the arguments given, crop="auto" detecting on them.  field_rate=True makes a picture of every field: 2 n
         pictures come back, to be encoded at twice the frame rate (576i25: fps=50).  None, the default, changes nothing.
+        deinterlace="auto": the batch, taken as one stream, is scanned on the device first (detect_scan_to, default
+        options; one read-back, like crop="auto"): an interlaced stream proceeds as "tff" or "bff" says, a progressive or
+        unknown one as None, and telecined film raises ValueError -- it goes through detelecine() first.
 
         Returns a tensor for tensor input and an array for array input.  out: a preallocated contiguous uint8 tensor
         of n * 101376 elements on this device, or a DeviceBuffer (then returned as is); with out given, array input
@@ -1410,11 +1493,11 @@ class Decoder:
             raise ValueError("matrix=, src_range= and transfer= describe a YCbCr source; an RGB source is converted with BT.601 (full_range=)")
         if src_range is not None:
             crop_limit = colour_source_limit(crop_limit, src_range)
-        if deinterlace is None and field_rate:
+        if deinterlace in (None, "auto") and field_rate:
             raise ValueError("field_rate=True needs deinterlace='tff' or 'bff'")
         if deinterlace is not None:
-            if deinterlace not in ("tff", "bff"):
-                raise ValueError(f"unknown deinterlace {deinterlace!r}: 'tff', 'bff' or None")
+            if deinterlace not in ("tff", "bff", "auto"):
+                raise ValueError(f"unknown deinterlace {deinterlace!r}: 'tff', 'bff', 'auto' or None")
             if fmt != "i420" or (surface is not None and surface.layout not in (SURF_PLANAR8, SURF_SEMI8)):
                 raise ValueError("deinterlace= takes 8-bit YCbCr sources: 'i420', 'yv12', 'nv12' or 'nv21'")
             if height % 4 or height < 8:
@@ -1424,6 +1507,8 @@ class Decoder:
             src_ptr, is_array, copied = self._stage(s, src, n, image, stride=stride)
             waited = not is_array and self._wait_for_torch(own_stream_ok=True)
             sync = sync or (copied and waited)  # (torch may hand a staging copy's memory out again on its own stream)
+            if deinterlace == "auto":
+                deinterlace = self._scan_for_import(s, src_ptr, surface if surface is not None else surface_layout("i420", width, height), n, stride)
             if deinterlace is not None:
                 # the progressive pictures, packed I420 at the source's size, in a buffer of this call: the import's source
                 dstride = _r16(width * height * 3 // 2)
@@ -1467,6 +1552,21 @@ class Decoder:
             if obuf is not None:
                 result = obuf.download(np.uint8, nbytes).reshape(n, FRAME_BYTES)
             return result
+
+    def _scan_for_import(self, s: _Scratch, src_ptr, surface, n: int, stride: int):
+        """deinterlace="auto" of import_pictures: the call's n images scanned as one stream (detect_scan_to with the
+        default options, one read-back): "tff" / "bff" for an interlaced stream, None for a progressive or unknown one;
+        a telecined one is the caller's to detelecine first."""
+        if n < 2:
+            return None  # (no frame has a predecessor: unknown)
+        fbuf, rbuf = s.alloc(n * SCAN_FRAME_DTYPE.itemsize), s.alloc(SCAN_REC_DTYPE.itemsize)
+        self.detect_scan_to(src_ptr, fbuf, rbuf, surface=surface, n_frames=n, src_stride=stride)
+        self.sync()
+        res = scan_verdict(rbuf.download(SCAN_REC_DTYPE, 1)[0])
+        if res.kind == "telecined":
+            raise ValueError(f"deinterlace='auto': the pictures are telecined film ({res.first_field} field first): make the film's frames "
+                             f"with detelecine(first_field={res.first_field!r}) and import those")
+        return {"top": "tff", "bottom": "bff"}[res.first_field] if res.kind == "interlaced" else None
 
     # -- MPEG-1 encode (efx_encode) ------------------------------------------------------------
     def encode_to(self, src: DeviceBuffer | int, dst: DeviceBuffer | int, length: DeviceBuffer | int,

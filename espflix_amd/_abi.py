@@ -174,6 +174,14 @@ ENC_PICTURE_INFO_DTYPE = np.dtype([("cut_i", "<u4"), ("cut_p", "<u4"), ("type", 
 DENOISE_OPTS_DTYPE = np.dtype([("n_streams", "<i4"), ("n_frames", "<i4"), ("luma_spatial", "<i4"), ("chroma_spatial", "<i4"),
                                ("luma_temporal", "<i4"), ("chroma_temporal", "<i4"), ("src_stride", "<u8"), ("dst_stride", "<u8"),
                                ("prev_stride", "<u8")])
+# efx_scan_opts (passed like efx_denoise_opts), efx_scan_frame (one per processed frame) and efx_scan_rec (one per stream)
+SCAN_OPTS_DTYPE = np.dtype([("n_streams", "<i4"), ("n_frames", "<i4"), ("lead", "<i4"), ("accumulate", "<i4"), ("nt", "<i4"),
+                            ("still", "<i4"), ("prog", "<i4"), ("intl", "<i4"), ("rep", "<i4"), ("reserved", "<i4"),
+                            ("first_frame", "<u8"), ("src_stride", "<u8")])
+SCAN_FRAME_DTYPE = np.dtype([("comb", "<u8"), ("comb_tb", "<u8"), ("comb_bt", "<u8"), ("diff_top", "<u8"), ("diff_bottom", "<u8"),
+                             ("label", "<i4"), ("repeat", "<i4")])
+SCAN_REC_DTYPE = np.dtype([("n_still", "<u4"), ("n_prog", "<u4"), ("n_tff", "<u4"), ("n_bff", "<u4"), ("n_undet", "<u4"),
+                           ("rep_top", "<u4", 5), ("rep_bottom", "<u4", 5), ("reserved", "<u4")])
 
 # every symbol include/efx.h declares: (name, restype, argtypes)
 _P = C.c_void_p
@@ -224,6 +232,8 @@ _SYMBOLS = {
     "efx_deinterlace_count": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "efx_detelecine": (C.c_int, [_P, C.POINTER(_Surface), C.POINTER(_DetelecineOpts), _P, _P, _P]),
     "efx_detelecine_count": (C.c_int, [C.c_int, C.c_int]),
+    "efx_detect_scan": (C.c_int, [_P, C.POINTER(_Surface), _P, _P, _P, _P]),
+    "efx_scan_verdict": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "efx_denoise": (C.c_int, [_P, C.POINTER(_Surface), _P, _P, _P, _P]),
     "efx_import_set_colour": (C.c_int, [_P, C.POINTER(_ImportColour)]),
     "efx_import_colour_coefs": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int)]),

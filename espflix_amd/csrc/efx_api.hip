@@ -28,6 +28,7 @@
 #include "deint_px.h"
 #include "denoise_px.h"
 #include "telecine_px.h"
+#include "scan_px.h"
 #include "surface_px.h"
 #include "quality_px.h"
 #include "parse_tm.h"
@@ -93,6 +94,8 @@ __global__ void k_denoise(DenoiseArgs);  // (k_denoise.hip)
 __global__ void k_telecine_measure(TelecineArgs);  // (k_telecine.hip)
 __global__ void k_telecine_decide(TelecineArgs);
 __global__ void k_telecine_weave(TelecineArgs);
+__global__ void k_scan_measure(ScanArgs);  // (k_scan.hip)
+__global__ void k_scan_count(ScanArgs);
 __global__ void k_import_pcm(ImportPcmArgs);  // (k_import_pcm.hip)
 __global__ void k_import_pcm_state(ImportPcmArgs);
 __global__ void k_loud_steps(LoudStepsArgs);  // (k_loudness.hip)
@@ -2093,6 +2096,53 @@ int efx_detelecine(efx_ctx* ctx, const efx_surface* s, const efx_detelecine_opts
     EFX_HIP(hipGetLastError());
     return EFX_OK;
 }
+
+// ---- scan type (k_scan.hip) ---------------------------------------------------------------------------------------------------
+int efx_detect_scan(efx_ctx* ctx, const efx_surface* s, const efx_scan_opts* o, const void* src_device, efx_scan_frame* frames_device,
+                    efx_scan_rec* recs_device)
+{
+    bind_device(ctx);
+    if (!ctx || !s || !o)
+        return EFX_ERR_ARG;
+    if (const char* what = surface_fault(s, EFX_PIX_I420, s->width, s->height))
+        return fail(ctx, EFX_ERR_ARG, (std::string("efx_detect_scan: ") + what).c_str());
+    if (!dpx::surface_ok(*s))
+        return fail(ctx, EFX_ERR_ARG, "efx_detect_scan: the surface must be EFX_SURF_PLANAR8 or EFX_SURF_SEMI8, its height a multiple of 4 from 8");
+    if (!src_device || ((uintptr_t)src_device & 15) || !frames_device || ((uintptr_t)frames_device & 15) || !recs_device ||
+        ((uintptr_t)recs_device & 15))
+        return fail(ctx, EFX_ERR_ARG, "efx_detect_scan: src_device, frames_device and recs_device must be 16-byte aligned device pointers");
+    if (!scpx::options_ok(*o))
+        return fail(ctx, EFX_ERR_ARG,
+                    "efx_detect_scan: nt must be 0 .. 255, still 0 .. 4080, prog, intl and rep 256 .. 65535, accumulate 0 / 1");
+    const int n = tpx::processed(o->n_frames, o->lead);
+    if (n < 0)
+        return fail(ctx, EFX_ERR_ARG, "efx_detect_scan: n_frames < 1, lead not 0 / 1, or lead >= n_frames");
+    if (o->n_streams < 1 || (int64_t)o->n_streams * o->n_frames > INT32_MAX)
+        return fail(ctx, EFX_ERR_ARG, "efx_detect_scan: n_streams must be >= 1, the images in below 2^31");
+    ScanArgs a{};
+    a.src = static_cast<const uint8_t*>(src_device), a.frames = frames_device, a.recs = recs_device;
+    a.src_stride = o->src_stride ? (size_t)o->src_stride : (s->bytes + 15) / 16 * 16;
+    if (a.src_stride < s->bytes || (a.src_stride & 15))
+        return fail(ctx, EFX_ERR_ARG, "efx_detect_scan: src_stride must be a multiple of 16 and hold an image");
+    a.s = *s;
+    a.n_streams = o->n_streams, a.n_frames = o->n_frames;
+    a.lead = o->lead, a.n = n;
+    a.accumulate = o->accumulate, a.nt = o->nt;
+    a.first_frame = o->first_frame;
+    const scpx::Rule rule = scpx::rule_of(*o, s->width, s->height);
+    a.still_wh = rule.still_wh, a.prog = rule.prog, a.intl = rule.intl, a.rep = rule.rep;
+    a.measure_items = scpx::measure_items(s->width, s->height);
+    // two launches whatever the counts are (a workgroup takes further frames or streams when there are more than the
+    // grid's); the frame records carry everything from one to the next
+    const size_t frames = (size_t)a.n_streams * a.n, cap = (size_t)1 << 20;
+    hipLaunchKernelGGL(k_scan_measure, dim3((unsigned)std::min(frames, cap)), dim3(64 * scpx::kMeasureWaves), 0, ctx->stream, a);
+    const size_t wgs = ((size_t)a.n_streams + scpx::kCountWaves - 1) / scpx::kCountWaves;
+    hipLaunchKernelGGL(k_scan_count, dim3((unsigned)std::min(wgs, cap)), dim3(64 * scpx::kCountWaves), 0, ctx->stream, a);
+    EFX_HIP(hipGetLastError());
+    return EFX_OK;
+}
+
+int efx_scan_verdict(const efx_scan_rec* rec, int* first_field) { return rec ? scpx::verdict(*rec, first_field) : EFX_ERR_ARG; }
 
 // ---- noisy sources (k_denoise.hip) ----------------------------------------------------------------------------------------------
 int efx_denoise(efx_ctx* ctx, const efx_surface* s, const efx_denoise_opts* o, const void* src_device, const uint8_t* prev_device,

@@ -457,6 +457,23 @@ struct TelecineArgs {
     int measure_items, weave_items;  // tpx::measure_items(width, height), tpx::weave_items(surface)
 };
 
+// k_scan_measure / k_scan_count (k_scan.hip) launch arguments (by value): efx_scan_opts, checked, and the surface, checked
+// (scan_px.h)
+struct ScanArgs {
+    const uint8_t* src;      // stream i, frame j of the call at src + (i * n_frames + j) * src_stride
+    efx_scan_frame* frames;  // stream i, processed frame j at frames + i * n + j
+    efx_scan_rec* recs;      // stream i's counts at recs + i
+    size_t src_stride;
+    efx_surface s;
+    int n_streams, n_frames;
+    int lead, n;             // frames lead .. lead + n - 1 of a stream are processed
+    int accumulate, nt;
+    uint64_t first_frame;    // the title's frame number of the first offered frame
+    uint64_t still_wh;       // scpx::Rule: still x width x height, and the three Q8 ratios
+    uint32_t prog, intl, rep;
+    int measure_items;       // scpx::measure_items(width, height)
+};
+
 // k_denoise (k_denoise.hip) launch arguments (by value): efx_denoise_opts, checked, and the surface, checked (denoise_px.h)
 struct DenoiseArgs {
     const uint8_t* src;   // stream i, frame j of the call at src + (i * n_frames + j) * src_stride

@@ -502,8 +502,8 @@ size_t efx_surface_layout(int kind, int width, int height, size_t pitch, int pla
  * and destination regions must not overlap.
  *
  * Out of scope: the 16-bit layouts, 4:2:2, bwdif's longer filter, motion-compensated deinterlacing, inverse telecine
- * (efx_detelecine: "telecined sources" below), detecting whether a source is interlaced at all, per-frame parity flags,
- * field-sited chroma resampling, efx_multi_*. */
+ * (efx_detelecine: "telecined sources" below), per-frame parity flags, field-sited chroma resampling, efx_multi_*.
+ * Whether a source is interlaced at all, and in which field order: efx_detect_scan ("scan type" below). */
 #define EFX_FIELD_TOP    0   /* the top field (even lines) is the earlier one: tff */
 #define EFX_FIELD_BOTTOM 1   /* bff */
 #define EFX_DEINT_FRAME  0   /* one output per frame: (t, 0) */
@@ -581,10 +581,10 @@ int efx_deinterlace_count(int n_frames, int lead, int tail, int mode);
  * 3 / 2 bytes of each output image and the n_streams x n records.  All offsets are computed in 64 bits.  The source,
  * destination and record regions must not overlap.
  *
- * Out of scope: a third (next-frame) match candidate; post-deinterlacing of frames that stay combed; deciding whether a
- * title is telecined; cadences other than cycles of 5 (PAL speed-up needs none; 2:2 phase-shifted material is matched, but
- * nothing of it should be decimated: such a caller uses the records' match only); the 16-bit layouts; chaining into
- * efx_import_surfaces; efx_multi_*. */
+ * Out of scope: a third (next-frame) match candidate; post-deinterlacing of frames that stay combed; cadences other than
+ * cycles of 5 (PAL speed-up needs none; 2:2 phase-shifted material is matched, but nothing of it should be decimated: such
+ * a caller uses the records' match only); the 16-bit layouts; chaining into efx_import_surfaces; efx_multi_*.  Whether a
+ * title is telecined, and with which first_field: efx_detect_scan ("scan type" below). */
 typedef struct efx_telecine_info {
     uint64_t comb_c;      /* cc */
     uint64_t comb_p;      /* cp */
@@ -612,6 +612,129 @@ int efx_detelecine(efx_ctx* ctx, const efx_surface* surface, const efx_detelecin
                    uint8_t* dst_device, efx_telecine_info* info_device);
 /* outputs per stream of such a call; -1 for arguments it rejects.  Host only. */
 int efx_detelecine_count(int n_frames, int lead);
+
+/* -- scan type: progressive, interlaced or telecined (k_scan) -------------------------------- */
+/* efx_deinterlace and efx_detelecine take first_field from the caller, and neither says whether a title needs it at
+ * all.  A wrong guess is the costliest mistake of the source side: a woven interlaced frame that is scaled and encoded
+ * has its ghosts baked in, film that is deinterlaced where it should be detelecined keeps a repeated picture in every
+ * five, a wrong field order judders in every picture.  efx_detect_scan answers the question ffmpeg users put to idet,
+ * for a whole batch of streams, piece by piece: per frame a label and a repeated-field flag, per stream their counts,
+ * and efx_scan_verdict makes one answer of a stream's counts.  The rule is this library's own exact integer rule
+ * (espflix_amd/csrc/scan_px.h), bit-reproducible anywhere.  Byte compatibility with ffmpeg is not promised.
+ *
+ *   Setting.  Luma only, of the canonical image of a surface ("surfaces" above), width w and height h.  The top field is
+ *   the even lines.  score(W) is the comb score of "telecined sources" above, exactly as written there, with the same nt.
+ *   Per frame t that has a predecessor.  All five are uint64.
+ *     cc  = score(F[t])
+ *     ctb = score(the frame with the even lines of F[t]   and the odd lines of F[t-1])
+ *     cbt = score(the frame with the even lines of F[t-1] and the odd lines of F[t])
+ *     dt  = sum of |F[t][y][x] - F[t-1][y][x]| over even y, all x
+ *     db  = the same over odd y
+ *   cc is efx_detelecine's cc; for first_field TOP ctb is its cp and dt its D, for BOTTOM cbt is its cp and db its D.
+ *   Label of a frame.  The options still, prog, intl and rep; the last three are Q8 ratios.  The first test that holds
+ *   decides:
+ *     EFX_SCAN_STILL          16 (dt + db) < still w h
+ *     EFX_SCAN_PROGRESSIVE    256 min(ctb, cbt) > prog cc
+ *     EFX_SCAN_TFF            256 cbt > intl ctb
+ *     EFX_SCAN_BFF            256 ctb > intl cbt
+ *     EFX_SCAN_UNDETERMINED   otherwise
+ *   Weaving the fields of a progressive frame with those of its neighbour combs both ways; of an interlaced frame the
+ *   weave that puts the later field beside the previous frame's earlier one (two field periods apart) combs more than
+ *   the one that puts neighbours in time side by side.  The PROGRESSIVE test comes before the order tests on purpose:
+ *   on a progressive pan ctb and cbt differ by more than 1.04, so idet's own order of tests would call it interlaced.
+ *   Repeat of a frame.  None for a STILL frame.  Otherwise the first test that holds:
+ *     EFX_SCAN_REPEAT_TOP     rep dt < 256 db        (the top field repeats the previous frame's)
+ *     EFX_SCAN_REPEAT_BOTTOM  rep db < 256 dt
+ *     EFX_SCAN_REPEAT_NONE    otherwise
+ *   A frame with no predecessor (t = 0 and lead = 0) is EFX_SCAN_NONE with no repeat; its five sums are 0 and it is
+ *   counted nowhere.
+ *   Defaults.  prog = 384, intl = 266 and rep = 768 are idet's 1.5, 1.04 and 3 in Q8; nt = 10 is efx_detelecine's.
+ *   still = 64 is a mean field difference of 4 levels: that value has NOT been measured on real material, only on the
+ *   synthetic cases of the tests (profiles/scan.md).  All five are options.
+ *   Records.  One efx_scan_frame per processed frame, stream i's processed frame j (frame lead + j) at frames_device +
+ *   (i * n + j), n = n_frames - lead; one efx_scan_rec per stream at recs_device + i: how many of the call's processed
+ *   frames got each label, and rep_top[phase] / rep_bottom[phase], how many got that repeat at phase = (first_frame +
+ *   index in the call) mod 5, the index counted over the offered frames (lead + j).  first_frame is the title's frame
+ *   number of the call's first offered frame, so phases are title-absolute across pieces.
+ *   Pieces.  lead has efx_detelecine's meaning: the first offered frame is context only.  accumulate = 1 adds a stream's
+ *   counts to what recs_device holds (reserved becomes 0), accumulate = 0 overwrites: a title goes through in pieces
+ *   with one frame of overlap and no read-back, and pieces need no length rule.  Streams never see each other's frames.
+ *   Layout.  Source image i * n_frames + j is stream i's frame j, at src_device + (i * n_frames + j) * src_stride.
+ *   frames_device is required: it is the call's only scratch, and its earlier content does not matter.
+ *   Surfaces.  Those efx_detelecine accepts.
+ *   Verdict (efx_scan_verdict, a pure function of a record).  n_moving = n_prog + n_tff + n_bff + n_undet; pt is the phase
+ *   with the largest rep_top and pb the one with the largest rep_bottom, the lowest phase on a tie; m = rep_top[pt] +
+ *   rep_bottom[pb]; tot is the sum of all ten repeat counters.
+ *     EFX_SCAN_IS_TELECINED    iff rep_top[pt] >= 1, rep_bottom[pb] >= 1, m >= 4, 4 m >= 3 tot, 5 m >= n_moving and
+ *                              (pb - pt) mod 5 is 2 or 3: 2 means first_field TOP, 3 BOTTOM.  (In 2-3 pulldown with the top
+ *                              field first the bottom-field repeat comes two frames after the top-field repeat; with the
+ *                              bottom field first it is the other way round.)
+ *     EFX_SCAN_IS_INTERLACED   else iff n_tff + n_bff > n_prog and 4 min(n_tff, n_bff) <= max(n_tff, n_bff); first_field is
+ *                              TOP iff n_tff > n_bff
+ *     EFX_SCAN_IS_PROGRESSIVE  else iff n_prog >= 1 and n_prog >= n_tff + n_bff
+ *     EFX_SCAN_IS_UNKNOWN      otherwise: all still, no frames, the order unclear
+ *   These constants are part of the definition, not a tolerance; the counts are reported so that a caller can apply a
+ *   rule of its own.
+ *
+ * Memory contract (efx_detelecine's, for luma rows only).  For source image k the kernel reads only bytes in [src + k *
+ * src_stride, src + k * src_stride + bytes rounded up to 16), 16 bytes at a time wherever the luma plane's rows begin,
+ * and only luma rows, of every processed frame and of its predecessor; chroma is never read.  Bytes in pitch padding and
+ * between images are fetched at most as part of such an access and never influence a result.  The kernels write only
+ * the n_streams x n frame records and the n_streams stream records.  All offsets are computed in 64 bits.  The source
+ * and record regions must not overlap.
+ *
+ * Out of scope: phase-shifted 2:2 material (it comes out as INTERLACED); mixed titles, which get one verdict per record
+ * (a caller cuts the title and keeps a record per part); the 16-bit layouts; a next-frame candidate; efx_multi_*. */
+#define EFX_SCAN_NONE           0   /* labels: a frame with no predecessor */
+#define EFX_SCAN_STILL          1
+#define EFX_SCAN_PROGRESSIVE    2
+#define EFX_SCAN_TFF            3
+#define EFX_SCAN_BFF            4
+#define EFX_SCAN_UNDETERMINED   5
+#define EFX_SCAN_REPEAT_NONE    0   /* repeats */
+#define EFX_SCAN_REPEAT_TOP     1
+#define EFX_SCAN_REPEAT_BOTTOM  2
+#define EFX_SCAN_IS_UNKNOWN     0   /* verdicts */
+#define EFX_SCAN_IS_PROGRESSIVE 1
+#define EFX_SCAN_IS_INTERLACED  2
+#define EFX_SCAN_IS_TELECINED   3
+typedef struct efx_scan_frame {       /* 48 bytes, one per processed frame; fixed-width fields only */
+    uint64_t comb;                    /* cc */
+    uint64_t comb_tb;                 /* ctb */
+    uint64_t comb_bt;                 /* cbt */
+    uint64_t diff_top;                /* dt */
+    uint64_t diff_bottom;             /* db */
+    int32_t  label;                   /* EFX_SCAN_NONE .. EFX_SCAN_UNDETERMINED */
+    int32_t  repeat;                  /* EFX_SCAN_REPEAT_* */
+} efx_scan_frame;
+typedef struct efx_scan_rec {         /* 64 bytes, one per stream */
+    uint32_t n_still, n_prog, n_tff, n_bff, n_undet;
+    uint32_t rep_top[5];              /* frames with EFX_SCAN_REPEAT_TOP, by phase */
+    uint32_t rep_bottom[5];           /* frames with EFX_SCAN_REPEAT_BOTTOM, by phase */
+    uint32_t reserved;                /* 0 */
+} efx_scan_rec;
+typedef struct efx_scan_opts {        /* fixed-width fields only: a binding can mirror it as a packed record */
+    int32_t  n_streams;               /* >= 1 */
+    int32_t  n_frames;                /* frames per stream offered by this call, >= 1 */
+    int32_t  lead;                    /* 0 / 1: the first offered frame is context only */
+    int32_t  accumulate;              /* 0: overwrite recs_device; 1: add to it */
+    int32_t  nt;                      /* the noise threshold of the comb score in pels, 0 .. 255; default 10 */
+    int32_t  still;                   /* 0 .. 4080; default 64 (synthetic material only, see above) */
+    int32_t  prog, intl, rep;         /* Q8 ratios, 256 .. 65535; defaults 384, 266, 768 */
+    int32_t  reserved;                /* ignored */
+    uint64_t first_frame;             /* the title's frame number of the first offered frame (only its value mod 5 matters) */
+    uint64_t src_stride;              /* bytes between source images; 0 = the surface's bytes rounded up to 16; multiple of 16 */
+} efx_scan_opts;
+/* Asynchronous on the context's stream: no host synchronisation, two launches whatever the counts are -- measure, count
+ * -- nothing is allocated, and no decoder, encoder, SBC, import or other state is touched.
+ * EFX_ERR_ARG: everything efx_detelecine rejects about a surface, the counts, lead and src_stride, nt outside 0 .. 255,
+ * still outside 0 .. 4080, prog, intl or rep outside 256 .. 65535, accumulate other than 0 / 1, a NULL or misaligned
+ * (16 bytes) src_device, frames_device or recs_device.  A refused call writes nothing. */
+int efx_detect_scan(efx_ctx* ctx, const efx_surface* surface, const efx_scan_opts* opts, const void* src_device,
+                    efx_scan_frame* frames_device, efx_scan_rec* recs_device);
+/* The verdict of a stream's record (EFX_SCAN_IS_*), or EFX_ERR_ARG for a NULL record.  *first_field (may be NULL) is
+ * written only for TELECINED and INTERLACED: EFX_FIELD_TOP / EFX_FIELD_BOTTOM.  Host only. */
+int efx_scan_verdict(const efx_scan_rec* rec, int* first_field);
 
 /* -- noisy sources: spatial and temporal noise reduction (k_denoise) ------------------------ */
 /* Film grain and analogue or sensor noise are the part of a picture that motion compensation cannot predict, and at 1.5
