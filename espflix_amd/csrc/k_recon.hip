@@ -50,8 +50,9 @@ __device__ inline int mad24(int a, int k, int c)
 // The products use the full-rate 24-bit multiplier: every multiplied operand is a combination of AC
 // coefficients only -- the DC term v0 enters through dc_sum / dc_dif and is never multiplied --
 // and AC coefficients are clamped to +-2048 and scaled by a premultiplier <= 62, which bounds the
-// operands by 2^19 in the column pass and 2^22.5 in the row pass (L1 norm of the linear map).  The
-// low 32 bits of the 48-bit product equal the reference's wrapped 32-bit product.
+// operands by 2^19 in the column pass and 2^22.5 in the row pass (L1 norm of the linear map; the stream range_idct of
+// tests/syntax_streams.py stands at those extremes, 329 654 and 1 775 219, and tests/test_syntax_streams.py computes
+// them).  The low 32 bits of the 48-bit product equal the reference's wrapped 32-bit product.
 // (the butterfly from its first stage on: the sums and differences of the input pairs (0,4) (2,6) (1,7) (3,5))
 __device__ inline void idct8_paired(int dc_sum, int dc_dif, int c_sum, int c_dif, int p17, int m17, int p35, int m53, int& v0, int& v1,
                                     int& v2, int& v3, int& v4, int& v5, int& v6, int& v7, int half)
@@ -457,6 +458,13 @@ __device__ __forceinline__ void recon_group(uint32_t* __restrict__ lds, const ui
     const bool zf = (zd & 0x80) != 0;  // an entry sits at scan position 0
     // intra DC value (22 bits: a slice adds at most 1584 differentials of +-255 to the predictor)
     const int dc_raw = (int)((uint32_t)(uint16_t)mine[0] | ((uint32_t)((int)(zd << 26) >> 26) << 16));
+    // The parser hands the predictor on unclamped, and a slice can walk it far out of 0 ... 255; behind the IDCT a pixel is
+    // kept in 16 bits (pair(), below).  The 63 AC coefficients of a block move a pixel by 14 062 at the most
+    // (tests/test_syntax_streams.py, largest_ac_residual(), computes it and holds kDcBound against it), so a DC term beyond
+    // +-kDcBound ends at 0 or 248 whatever they do: bounded there it changes no stored pixel, and DC + AC stays inside
+    // +-2^15.  (One v_med3_i32.  A DC-only block does not pass here: its value is replicated whole, flat4 below.)
+    constexpr int kDcBound = 16384;
+    const int dc_idct = max(-kDcBound, min(kDcBound, dc_raw));
 
     // A block whose only coefficient sits at scan position 0 takes the reference's "n == 1"
     // shortcut (player.cpp:1133-1140): dc = b[0] >> 8 (floor), no IDCT; for intra blocks the
@@ -496,7 +504,7 @@ __device__ __forceinline__ void recon_group(uint32_t* __restrict__ lds, const ui
             // the DC term: an intra block's is the parser's value << 8 (wider than the block's int16), and a block whose only
             // coefficient it is has its low byte cleared (the reference's n == 1 shortcut, see above)
             int v0 = __mul24((int)(int16_t)(q04 & 0xFFFF), premul_at(0, 0));
-            v0 = intra ? (dc_raw << 8) : v0;
+            v0 = intra ? (dc_idct << 8) : v0;
             v0 = dc_only ? (v0 & ~0xFF) : v0;
             const int v4 = __mul24((int)q04 >> 16, premul_at(4, 0));
             dc_sum = v0 + v4;
@@ -518,7 +526,8 @@ __device__ __forceinline__ void recon_group(uint32_t* __restrict__ lds, const ui
     for (int r = 0; r < 8; r++) {
         // the final rounding "(x + 128) >> 8" (player.cpp:985-994): the first input reaches all eight outputs unscaled
         // (it is never multiplied), so the 128 is added there, once; the shift is left to the byte permutes below -- a
-        // residual fits 16 bits, so bytes 1 and 2 of x + 128 ARE the shifted value
+        // residual fits 16 bits (14 304 at the most, an intra DC term is bounded above: the same test), so bytes 1 and 2
+        // of x + 128 ARE the shifted value
         v[r * 8] += 128;
         idct8(v[r * 8], v[r * 8 + 1], v[r * 8 + 2], v[r * 8 + 3], v[r * 8 + 4], v[r * 8 + 5], v[r * 8 + 6], v[r * 8 + 7], half);
         asm volatile("" : "+v"(v[r * 8]), "+v"(v[r * 8 + 1]), "+v"(v[r * 8 + 2]), "+v"(v[r * 8 + 3]), "+v"(v[r * 8 + 4]),
@@ -545,8 +554,8 @@ __device__ __forceinline__ void recon_group(uint32_t* __restrict__ lds, const ui
     };
     const short ceiling = my_cnt == 0 ? 255 : 248;
     const pk16 zero = {0, 0}, top = {ceiling, ceiling};
-    uint32_t flat4 = (uint32_t)(v[0] >> 8);  // intra DC-only block: replicated exactly as copy_block_dc does, unclamped and
-    flat4 |= flat4 << 8;                      // unmasked (player.cpp:1175-1187)
+    uint32_t flat4 = (uint32_t)dc_raw;  // intra DC-only block: replicated exactly as copy_block_dc does, unclamped and
+    flat4 |= flat4 << 8;                // unmasked (player.cpp:1175-1187)
     flat4 |= flat4 << 16;
     uint32_t clamped_m = clamped ? ~0u : 0u;
     asm volatile("" : "+v"(clamped_m));

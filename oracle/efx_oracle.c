@@ -246,6 +246,11 @@ void efxo_tables(uint8_t zz_out[64], uint8_t premul_out[64])
     memcpy(premul_out, premul, 64);
 }
 
+void efxo_default_intra(uint8_t out[64])
+{
+    memcpy(out, intra_default, 64);
+}
+
 /* ------------------------------------------------------------------------------------ */
 /* decoder state                                                                        */
 

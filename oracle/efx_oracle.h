@@ -93,6 +93,8 @@ void efxo_color_tab(int ntsc, uint32_t out768[768]);
 
 /* zig-zag scan and IDCT pre-multiplier tables as the restatement derives them */
 void efxo_tables(uint8_t zz_out[64], uint8_t premul_out[64]);
+/* the default intra quantiser matrix, raster order */
+void efxo_default_intra(uint8_t out[64]);
 
 /* PDM: restatement of pdm_second_order (espflix.ino:73-107).  state = {_i0,_i1,_i2}. */
 void efxo_pdm_second_order(int32_t state[3], uint16_t* dst, const int16_t* src, int len);

@@ -112,8 +112,9 @@ def trace_levels(data: np.ndarray, fmt: int) -> dict:
 
 def trace_syntax(data: np.ndarray, fmt: int) -> dict:
     """Runs the oracle with its parse trace on and summarises WHICH syntax elements it decoded (trace_levels' sibling): per
-    picture its type, r_size, full_pel and every macroblock (address, type flags or "skipped", half-pel vector, pattern,
-    quantiser), and as sets over the stream
+    picture its type, r_size, full_pel, whether a loaded quantiser matrix is in force (custom) and every macroblock (address,
+    type flags or "skipped", half-pel vector, pattern, quantiser, and per coded block its [(scan position, level)], an intra
+    block's first entry being (0, DC value)), and as sets over the stream
       mba        address-increment codes 1 ... 33, 34 stuffing, 35 escape;  mba_esc: the codes read behind an escape
       types      (picture type, macroblock_type flags);  cbp: patterns;  qscale: (0 slice header / 1 macroblock, value)
       motion     (picture, component, motion code);  residual: (picture, component, r_size, residual)
@@ -135,7 +136,7 @@ def trace_syntax(data: np.ndarray, fmt: int) -> dict:
         if kind == 0:      # slice
             if a != cur["picture"]:
                 cur["picture"] = a
-                cur["pic"] = dict(type=c & 15, r_size=(c >> 8) & 0xFF, full_pel=(c >> 4) & 1, mbs=[])
+                cur["pic"] = dict(type=c & 15, r_size=(c >> 8) & 0xFF, full_pel=(c >> 4) & 1, mbs=[], custom=bool(e))
                 while len(st["pictures"]) <= a:
                     st["pictures"].append(None)
                 st["pictures"][a] = cur["pic"]
@@ -176,13 +177,13 @@ def trace_syntax(data: np.ndarray, fmt: int) -> dict:
         elif kind == 1:    # macroblock
             p = cur["pic"]
             if b & 2:
-                p["mbs"].append(dict(addr=a, type="skipped", mv=(0, 0), cbp=0, q=0))
+                p["mbs"].append(dict(addr=a, type="skipped", mv=(0, 0), cbp=0, q=0, blocks=[]))
                 cur["between"].add("skipped")
                 return
             t = cur["type"]
             cur["intra"], cur["n"] = bool(b & 1), 0
             cbp = cur["cbp"] if cur["cbp"] is not None else (63 if b & 1 else 0)
-            p["mbs"].append(dict(addr=a, type=t, mv=(c, e), cbp=cbp, q=b >> 2))
+            p["mbs"].append(dict(addr=a, type=t, mv=(c, e), cbp=cbp, q=b >> 2, blocks=[]))
             if t & 8:
                 u = 2 if p["full_pel"] else 1
                 scale = 1 << p["r_size"]
@@ -204,6 +205,9 @@ def trace_syntax(data: np.ndarray, fmt: int) -> dict:
             cur["n"] = 0
         elif kind == 2:    # coefficient: b = scan position
             first = cur["n"] == 0
+            if first:
+                cur["pic"]["mbs"][-1]["blocks"].append([])
+            cur["pic"]["mbs"][-1]["blocks"][-1].append((b, c))
             if cur["esc"] is not None:
                 st["escapes"].add(cur["esc"] + (0 if first else 1,))
             if b == 63:
@@ -291,6 +295,14 @@ def tables():
     pm = np.zeros(64, dtype=np.uint8)
     lib().efxo_tables(zz.ctypes.data, pm.ctypes.data)
     return zz, pm
+
+
+def default_intra() -> np.ndarray:
+    m = np.zeros(64, dtype=np.uint8)
+    L = lib()
+    L.efxo_default_intra.argtypes = [C.c_void_p]
+    L.efxo_default_intra(m.ctypes.data)
+    return m
 
 
 def pdm(state: np.ndarray, pcm: np.ndarray) -> np.ndarray:

@@ -1,6 +1,8 @@
 """The directed streams of tests/syntax_streams.py through the HIP decoder (espflix_amd.Decoder): every VLC code, f_code
-1 ... 7 with and without full_pel, every window alignment and edge of k_recon's fetch -- against tests/golden/syntax.json
-(what the unmodified reference decoded) and the oracle, bit-exact.  What the streams cover is asserted on the CPU side,
+1 ... 7 with and without full_pel, every window alignment and edge of k_recon's fetch, every scan position, matrix entry and
+rounding class of the dequantiser, waves of full blocks -- against tests/golden/syntax.json (what the unmodified reference
+decoded) and the oracle, bit-exact; vectors that leave the picture, saturated blocks at the extremes of the IDCT's range
+and intra DC predictors far outside 0 ... 255 against the oracle alone.  What the streams cover is asserted on the CPU side,
 tests/test_syntax_streams.py."""
 import json
 import os
@@ -15,7 +17,7 @@ import syntax_streams as ss
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEFINED = ("codes", "vectors", "windows")
+DEFINED = ("codes", "vectors", "windows", "coefs")
 
 
 @pytest.fixture(scope="module")
@@ -60,7 +62,8 @@ def results(dec, n_streams):
 
 
 def first_difference(s, k, got, want):
-    """Names the first macroblock and plane in which picture k of stream s differs, with the manifest's entry for it."""
+    """Names the first macroblock, plane and block in which picture k of stream s differs, with the manifest's entry for the
+    macroblock and the block's list of (scan position, level)."""
     g, w = ss.planes(got), ss.planes(want)
     for addr in range(ss.MBW * ss.MBH):
         for plane, (a, b) in enumerate(zip(ss.mb_pixels(g, addr), ss.mb_pixels(w, addr))):
@@ -68,7 +71,14 @@ def first_difference(s, k, got, want):
                 m = s.pictures[k]["mbs"][addr] if s.pictures[k] else None
                 text = f"{s.name} picture {k}: macroblock {addr} (column {addr % ss.MBW}, row {addr // ss.MBW}) plane {'Y Cr Cb'.split()[plane]} differs"
                 if m:
-                    text += f"; f_code {s.pictures[k]['f_code']} full_pel {s.pictures[k]['full_pel']}; manifest {m}"
+                    d = a != b
+                    blk = 4 + plane - 1 if plane else next(i for i in range(4) if d[8 * (i >> 1):8 * (i >> 1) + 8, 8 * (i & 1):8 * (i & 1) + 8].any())
+                    coded = [i for i in range(6) if m["cbp"] & (0x20 >> i)]
+                    entries = m["blocks"][coded.index(blk)] if blk in coded else "not coded"
+                    y, x = (int(v[0]) for v in np.nonzero(d))
+                    text += (f"; f_code {s.pictures[k]['f_code']} full_pel {s.pictures[k]['full_pel']}; manifest "
+                             f"{ {key: v for key, v in m.items() if key != 'blocks'} }; block {blk} (scan position, level) {entries}; "
+                             f"first differing pixel ({y}, {x}) of the plane's part: {int(a[y, x])}, expected {int(b[y, x])}")
                     if m["type"] != ss.T_SKIPPED and m["type"] & ss.T_FORWARD:
                         text += f"; windows (blk, px0, py0, hx, hy, pw, ph) {ss.block_windows(addr, m['mv'])}"
                 return text
@@ -106,7 +116,7 @@ def test_interleaved_with_generator_streams_double_buffer(efx, expected):
     pictures of every stream against the oracle."""
     from espflix_amd import gen
     directed = ss.all_streams(DEFINED)
-    b = gen.Batch(0, 8, 8, 12, 0)
+    b = gen.Batch(0, len(directed), 8, 12, 0)
     streams, names = [], []
     for i, s in enumerate(directed):
         streams += [s.array(), b.es(i)]
@@ -139,10 +149,26 @@ def test_outside_equals_oracle(efx, expected):
         assert not bad, f"{s.name}: pictures {bad} differ from the oracle"
 
 
+def test_range_equals_oracle(efx, expected):
+    """Outside the reference's clamp table (the oracle clamps plainly to 0 ... 248): blocks whose 63 AC coefficients are all
+    saturated, in the sign patterns that drive each multiplied operand of the IDCT and the residual to their extremes, and
+    intra DC predictors walked to +-40 000 and back, in DC-only blocks (replicated unmasked) and in blocks that run the IDCT.
+    What the streams hold is asserted in tests/test_syntax_streams.py."""
+    streams = ss.family("range")
+    dec = decode(efx, [s.array() for s in streams], efx.FORMAT_ES)
+    res = results(dec, len(streams))
+    dec.close()
+    for s, r in zip(streams, res):
+        assert r["status"] == 0 and r["n"] == expected[s.name][0], (s.name, r["status"], r["n"])
+        bad = [k for k in range(r["n"]) if r["hashes"][k] != expected[s.name][1][k]]
+        assert not bad, f"{s.name}: pictures {bad} differ from the oracle"
+
+
 def test_whole_frames_name_the_macroblock(efx):
     """One stream per family, whole frames: a mismatch names the first differing macroblock and plane and the manifest's
     entry for it (vector, window alignment), so a failure points at a path rather than at a 64-bit number."""
-    streams = [ss.family("codes")[-1], ss.family("vectors")[1], ss.family("windows")[1], ss.family("outside")[0]]
+    streams = [ss.family("codes")[-1], ss.family("vectors")[1], ss.family("windows")[1], ss.family("outside")[0],
+               ss.family("coefs")[0], ss.family("range")[1]]
     dec = decode(efx, [s.array() for s in streams], efx.FORMAT_ES)
     for i, s in enumerate(streams):
         n, _, _, frames = oracle.decode(s.array(), 0, want_frames=True)
