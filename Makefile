@@ -7,7 +7,7 @@ HIPCC   ?= /opt/rocm/bin/hipcc
 ARCH    ?= gfx950
 CSRC     = espflix_amd/csrc
 HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude -I$(CSRC) -Wall -Wno-unused-function
-OBJS     = $(CSRC)/efx_api.o $(CSRC)/k_demux.o $(CSRC)/k_index.o $(CSRC)/k_parse.o $(CSRC)/k_recon.o $(CSRC)/k_video.o $(CSRC)/k_sbc.o $(CSRC)/k_tsindex.o $(CSRC)/k_export.o $(CSRC)/k_import.o $(CSRC)/k_cropdetect.o $(CSRC)/k_quality.o $(CSRC)/k_trick.o $(CSRC)/k_conform.o $(CSRC)/k_deint.o $(CSRC)/k_telecine.o $(CSRC)/k_scan.o $(CSRC)/k_denoise.o $(CSRC)/k_import_pcm.o $(CSRC)/k_loudness.o $(CSRC)/k_encode.o $(CSRC)/k_sbc_enc.o $(CSRC)/k_mux.o $(CSRC)/efx_tables.o $(CSRC)/efx_multi.o
+OBJS     = $(CSRC)/efx_api.o $(CSRC)/k_demux.o $(CSRC)/k_index.o $(CSRC)/k_parse.o $(CSRC)/k_recon.o $(CSRC)/k_video.o $(CSRC)/k_sbc.o $(CSRC)/k_tsindex.o $(CSRC)/k_export.o $(CSRC)/k_import.o $(CSRC)/k_cropdetect.o $(CSRC)/k_quality.o $(CSRC)/k_trick.o $(CSRC)/k_conform.o $(CSRC)/k_deint.o $(CSRC)/k_telecine.o $(CSRC)/k_scan.o $(CSRC)/k_denoise.o $(CSRC)/k_overlay.o $(CSRC)/k_import_pcm.o $(CSRC)/k_loudness.o $(CSRC)/k_encode.o $(CSRC)/k_sbc_enc.o $(CSRC)/k_mux.o $(CSRC)/efx_tables.o $(CSRC)/efx_multi.o
 
 .PHONY: all lib gen oracle ref clean dropin scale harness
 # (`scale` links librccl: built by __graft_entry__.build() and by `make scale`, not by a plain `make`)
@@ -28,6 +28,7 @@ $(CSRC)/k_deint.o $(CSRC)/efx_api.o: $(CSRC)/deint_px.h $(CSRC)/surface_px.h $(C
 $(CSRC)/k_telecine.o $(CSRC)/efx_api.o: $(CSRC)/telecine_px.h $(CSRC)/deint_px.h $(CSRC)/surface_px.h $(CSRC)/crop_px.h $(CSRC)/import_px.h
 $(CSRC)/k_scan.o $(CSRC)/efx_api.o: $(CSRC)/scan_px.h $(CSRC)/telecine_px.h $(CSRC)/deint_px.h $(CSRC)/surface_px.h $(CSRC)/crop_px.h $(CSRC)/import_px.h
 $(CSRC)/k_denoise.o $(CSRC)/efx_api.o: $(CSRC)/denoise_px.h $(CSRC)/deint_px.h $(CSRC)/surface_px.h $(CSRC)/crop_px.h $(CSRC)/import_px.h
+$(CSRC)/k_overlay.o $(CSRC)/efx_api.o: $(CSRC)/overlay_px.h $(CSRC)/deint_px.h $(CSRC)/surface_px.h $(CSRC)/import_px.h
 $(CSRC)/k_import.o $(CSRC)/efx_api.o $(CSRC)/efx_tables.o: $(CSRC)/hdr_px.h $(CSRC)/colour_px.h $(CSRC)/import_px.h
 $(CSRC)/k_quality.o $(CSRC)/efx_api.o: $(CSRC)/quality_px.h
 $(CSRC)/k_encode.o $(CSRC)/k_mux.o $(CSRC)/efx_api.o: $(CSRC)/enc_core.h $(CSRC)/mpeg1_codebook.h

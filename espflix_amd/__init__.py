@@ -10,6 +10,7 @@ raises immediately.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from dataclasses import dataclass
 from fractions import Fraction
@@ -18,7 +19,7 @@ import numpy as np
 
 # the C-ABI's structs, record dtypes and signatures live in _abi.py; they are part of this module's surface
 from ._abi import (DENOISE_OPTS_DTYPE, ENC_PICTURE_INFO_DTYPE, LOUDNESS_REC_DTYPE, LOUDNESS_STEP_DTYPE, SCAN_FRAME_DTYPE,  # noqa: F401
-                   SCAN_OPTS_DTYPE, SCAN_REC_DTYPE, TELECINE_INFO, _P, _SYMBOLS,
+                   OVERLAY_EVENT_DTYPE, OVERLAY_OPTS_DTYPE, SCAN_OPTS_DTYPE, SCAN_REC_DTYPE, TELECINE_INFO, _P, _SYMBOLS,
                    _AdaptiveQuant, _CompareOpts, _CompareRec, _Config, _ConformOpts, _CropOpts, _DeintOpts, _DetelecineOpts,
                    _EncodeOpts, _EncodeRate, _EncPictureInfo, _ExportOpts, _FieldOpts, _IdxRec, _ImportColour, _ImportHdr,
                    _ImportOpts, _ImportPcmOpts, _LoudnessGateOpts, _LoudnessStepsOpts, _MuxOpts, _PcmGainOpts, _SbcEncodeOpts,
@@ -56,6 +57,9 @@ PICTURE_I, PICTURE_P, PICTURE_CUT_I = 1, 2, 5   # efx_enc_picture_info.type
 AQ_DEFAULT = 256          # aq=True: Test Model 5's factor (profiles/adaptive_quant.md)
 MUX_FULL = 1024           # efx_mux_av: the stream's output region is too small, nothing written (efx.h)
 MUX_BAD_VIDEO = 2048      # efx_mux_av: the video input is not a transport stream of PID 0x100 that starts with a PES (efx.h)
+OVERLAY_BAD_EVENT = 8192  # efx_overlay: the list holds an event that is not valid; it was not drawn (efx.h)
+OVL_A8, OVL_RGBA = 0, 1   # efx_overlay_event.kind
+OVERLAY_MAX_EVENTS = 4096
 PCM_FRAME_PLANAR, PCM_INTERLEAVED = 0, 1   # efx_sbc_encode_opts.pcm_layout
 PCM_PLANAR = 2                             # efx_import_pcm_opts.layout (or PCM_INTERLEAVED)
 TRICK_FROM_I420, TRICK_FROM_RING = 0, 1    # efx_trick_opts.source
@@ -528,6 +532,79 @@ def denoise_thresholds(sigma: float) -> tuple:
         raise ValueError(f"sigma must be >= 0, got {sigma!r}")
     t = lambda v: int(min(DENOISE_MAX_THRESHOLD, v + 0.5))
     return t(2 * sigma), t(2 * sigma), t(4 * sigma), t(4 * sigma)
+
+
+class Overlay:
+    """One event of Decoder.overlay() / make_title(overlays=): a bitmap shown over the pictures first .. last of a title.
+    bitmap: (h, w) uint8 alpha drawn in `colour` (R, G, B) -- what libass or Pillow's text mask gives -- or (h, w, 4)
+    uint8 R, G, B, A with straight alpha (`colour` is then not used).  x, y: the picture column and row of its top-left
+    sample; it is clipped to the picture.  stream: the stream it belongs to, -1 = every stream.  opacity: 0 .. 256.
+    fade_in, fade_out: pictures over which it comes and goes.  Events that show the same array object share its bytes."""
+    __slots__ = ("bitmap", "first", "last", "x", "y", "colour", "stream", "opacity", "fade_in", "fade_out")
+
+    def __init__(self, bitmap, first: int, last: int, x: int, y: int, colour=(255, 255, 255), stream: int = -1, opacity: int = 256,
+                 fade_in: int = 0, fade_out: int = 0):
+        self.bitmap, self.first, self.last, self.x, self.y = bitmap, first, last, x, y
+        self.colour, self.stream, self.opacity, self.fade_in, self.fade_out = colour, stream, opacity, fade_in, fade_out
+
+    def __repr__(self):
+        return (f"Overlay({tuple(np.shape(self.bitmap))}, first={self.first}, last={self.last}, x={self.x}, y={self.y}, "
+                f"stream={self.stream})")
+
+
+def overlay_span(fps, start_s, end_s) -> tuple:
+    """(first, last): the pictures of a title at fps (any constant rate, as for conform) whose display begins inside the
+    time span [start_s, end_s) in seconds -- first = ceil(start x fps), last = ceil(end x fps) - 1 -- in exact rational
+    arithmetic (times may be Fractions, "num/den" strings, ints or floats, a float counting as its exact binary value).
+    ValueError for a span that holds no picture or begins before 0."""
+    f, a, b = _rate(fps), Fraction(start_s), Fraction(end_s)
+    first, last = math.ceil(a * f), math.ceil(b * f) - 1
+    if a < 0 or last < first:
+        raise ValueError(f"the span {start_s!r} .. {end_s!r} s holds no picture at {f} pictures per second")
+    return first, last
+
+
+def overlay_pack(overlays, names=None) -> tuple:
+    """(events, atlas) of a list of Overlay: the efx_overlay_event records (OVERLAY_EVENT_DTYPE) in list order, and one
+    uint8 atlas that holds every distinct bitmap object once, row after row (pitch = the row's bytes), each at a 16-byte
+    aligned offset, its length a multiple of 16.  ValueError, naming the event, for a bitmap of another shape or type or
+    a value that does not fit its field (names: the numbers to name the events by, where they are not their places)."""
+    events = np.zeros(len(overlays), dtype=OVERLAY_EVENT_DTYPE)
+    placed, parts, size = {}, [], 0
+    for k, o in enumerate(overlays):
+        i = k if names is None else names[k]
+        b = o.bitmap
+        if not isinstance(b, np.ndarray) or b.dtype != np.uint8 or not (b.ndim == 2 or (b.ndim == 3 and b.shape[2] == 4)) or b.size == 0:
+            raise ValueError(f"event {i} ({o!r}): bitmap must be a non-empty (h, w) or (h, w, 4) uint8 array")
+        if id(b) not in placed:
+            placed[id(b)] = size
+            data = np.ascontiguousarray(b).reshape(-1)
+            parts.append(data)
+            pad = -data.size % 16
+            if pad:
+                parts.append(np.zeros(pad, dtype=np.uint8))
+            size += data.size + pad
+        rgba = b.ndim == 3
+        try:
+            r, g, bl = (0, 0, 0) if rgba else (int(v) for v in o.colour)
+            if not all(0 <= v <= 255 for v in (r, g, bl)):
+                raise OverflowError("a colour component outside 0 .. 255")
+            values = (o.first, o.last, placed[id(b)], o.stream, o.x, o.y, b.shape[1] * (4 if rgba else 1), r << 16 | g << 8 | bl,
+                      b.shape[1], b.shape[0], o.opacity, o.fade_in, o.fade_out, OVL_RGBA if rgba else OVL_A8, 0, 0)
+            events[k] = values
+            if any(int(got) != int(v) for got, v in zip(events[k].tolist(), values)):
+                raise OverflowError("a value wrapped")
+        except (OverflowError, TypeError, ValueError) as exc:
+            raise ValueError(f"event {i} ({o!r}): a value does not fit its field of efx_overlay_event") from exc
+    atlas = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)
+    return events, atlas
+
+
+def overlay_check(events, atlas_bytes: int) -> int:
+    """efx_overlay_check: the index of the first record of events (OVERLAY_EVENT_DTYPE) that is not valid for an atlas of
+    atlas_bytes, or -1."""
+    ev = np.ascontiguousarray(events, dtype=OVERLAY_EVENT_DTYPE)
+    return int(load_library().efx_overlay_check(ev.ctypes.data, len(ev), atlas_bytes))
 
 
 def sbc_state_bytes() -> int:
@@ -1304,6 +1381,69 @@ class Decoder:
                             src_stride=stride, dst_stride=dstride, prev_stride=dstride)
             self.sync()
             return fetch()
+
+    # -- subtitles and logos (efx_overlay) ----------------------------------------------------
+    def overlay_to(self, pictures: DeviceBuffer | int, events: DeviceBuffer | int | None, atlas: DeviceBuffer | int | None, *,
+                   n_streams: int, n_pictures: int, n_events: int, atlas_bytes: int, first_picture: int = 0, stride: int = 0,
+                   status: DeviceBuffer | int | None = None):
+        """efx_overlay on raw device memory (DeviceBuffers or pointers), asynchronous on the library's stream and in
+        place: the n_events records at events (OVERLAY_EVENT_DTYPE, overlay_pack()) whose bitmaps lie in the atlas_bytes
+        bytes at atlas are blended into picture j of stream i at pictures + i * stride + j * 101376 (stride 0 = packed),
+        picture j being first_picture + j of the title.  status: n_streams uint32 the caller cleared, or None; an event
+        that is not valid is not drawn and sets OVERLAY_BAD_EVENT in every word.  The rule: include/efx.h, "subtitles
+        and logos"."""
+        o = np.zeros(1, dtype=OVERLAY_OPTS_DTYPE)
+        o[0] = (n_streams, n_pictures, n_events, 0, first_picture, stride, atlas_bytes)
+        _check(self._ctx, self._lib.efx_overlay(self._ctx, o.ctypes.data, _ptr(events), _ptr(atlas), _ptr(pictures), _ptr(status)))
+
+    def overlay(self, pictures, overlays, *, first_picture: int = 0, inplace: bool = False):
+        """(n, P, 101376) I420 pictures, as encode() takes them, with a list of Overlay burnt in on the device
+        (overlay_to): a uint8 tensor on the decoder's device (a tensor is returned) or a NumPy array (an array is
+        returned).  Picture j of every stream is first_picture + j of the title, which is what Overlay.first / .last
+        count.  The bitmaps are packed into one atlas (overlay_pack: an array object shared by several events once);
+        events that no picture of this piece can show are dropped, the rest is checked on the host (ValueError naming
+        the event).  The result is a copy unless inplace=True with a packed, 16-byte aligned tensor, which is then
+        changed and returned.  EfxError if the device reports an invalid event all the same.  Synchronises: torch's
+        current stream before (tensor input), the library's after."""
+        if len(pictures.shape) != 3 or pictures.shape[-1] != FRAME_BYTES or pictures.shape[0] < 1 or pictures.shape[1] < 1:
+            raise ValueError(f"pictures must have shape (n, P, {FRAME_BYTES}), got {tuple(pictures.shape)}")
+        n, P = int(pictures.shape[0]), int(pictures.shape[1])
+        is_array = isinstance(pictures, np.ndarray)
+        kept = [(i, o) for i, o in enumerate(overlays) if not (o.last < first_picture or o.first >= first_picture + P or o.stream >= n)]
+        if len(kept) > OVERLAY_MAX_EVENTS:
+            raise ValueError(f"{len(kept)} events can show in this piece; a call takes {OVERLAY_MAX_EVENTS}")
+        events, atlas = overlay_pack([o for _, o in kept], names=[i for i, _ in kept])
+        bad = overlay_check(events, atlas.size)
+        if bad >= 0:
+            raise ValueError(f"event {kept[bad][0]} ({kept[bad][1]!r}) is not a valid efx_overlay_event (include/efx.h, "
+                             f"\"subtitles and logos\"): {events[bad]}")
+        if inplace and is_array:
+            raise ValueError("inplace=True needs a tensor on the device")
+        with self._scratch() as s:
+            if is_array:
+                buf = s.alloc(n * P * FRAME_BYTES)
+                buf.upload(np.ascontiguousarray(pictures, dtype=np.uint8))
+                ptr, out = buf.ptr, None
+            else:
+                out = pictures if inplace else pictures.clone().contiguous()
+                ptr, _, copied = self._stage(s, out, n * P, FRAME_BYTES, what="pictures")
+                if copied:
+                    raise ValueError("inplace=True needs a packed, 16-byte aligned tensor")
+                self._wait_for_torch()
+            if len(events):
+                ebuf, abuf = s.alloc(events.nbytes), s.alloc(atlas.size)
+                ebuf.upload(events)
+                abuf.upload(atlas)
+                status = s.zeros(4 * n)
+                self.overlay_to(ptr, ebuf, abuf, n_streams=n, n_pictures=P, n_events=len(events), atlas_bytes=atlas.size,
+                                first_picture=first_picture, status=status)
+                self.sync()
+                st = status.download(np.uint32, n)
+                if st.any():
+                    raise EfxError(-1, f"efx_overlay: status {st.tolist()} (OVERLAY_BAD_EVENT = {OVERLAY_BAD_EVENT})")
+            if is_array:
+                return buf.download(np.uint8, n * P * FRAME_BYTES).reshape(n, P, FRAME_BYTES)
+            return out
 
     # -- black borders (efx_detect_crop) ----------------------------------------------------
     def detect_crop_to(self, src: DeviceBuffer | int, rects: DeviceBuffer | int, *, n_streams: int, images_per_stream: int,
@@ -2354,7 +2494,7 @@ class Decoder:
             return out[0], out[1], status
 
     def make_title(self, pictures, pcm, *, speed: int = 15, trick_gop: int = 3, fps=None, fps_out=None, poster=None, aq: int | bool | None = None,
-                   **encode_av):
+                   overlays=None, **encode_av):
         """A complete title directory per stream, as the reference's indexer leaves it (indexer/indexer.cpp:292-321) and its
         player opens it (src/espflix.cpp:647,787-792): returns (list of n dicts {"video.ts", "video_fwd.ts", "video_rwd.ts",
         "video.idx"} of bytes, status: uint32 [3, n], rows video.ts (ENCODE_* | MUX_* bits), video_fwd.ts, video_rwd.ts).
@@ -2375,7 +2515,14 @@ class Decoder:
         scene_cut=, min_gop= (among **encode_av) apply to video.ts only: the trick streams keep their GOPs of trick_gop.
         aq: adaptive quantisation as for encode(), of video.ts and of both trick streams.
 
-        loudness=, peak= (among **encode_av): video.ts's sound levelled to a target in LUFS, as for encode_av()."""
+        loudness=, peak= (among **encode_av): video.ts's sound levelled to a target in LUFS, as for encode_av().
+
+        overlays: a list of Overlay (subtitles, a logo) burnt into the pictures once, on the device (overlay()), after
+        any conform: Overlay.first / .last are indices of the CODED timeline, picture 0 being the first coded picture
+        (overlay_span(fps_out or fps, start, end) gives them for times).  The burnt pictures feed both encode_av and
+        trick_streams, so the trick streams show the text too; the caller's pictures are not changed.  Without overlays
+        the bytes, launches and allocations are what they were."""
+        conformed = False
         if fps is not None and fps_out is None and not picture_rate_code(fps):
             raise ValueError(f"fps={fps!r} is not a rate MPEG-1 codes; give fps_out=, one of "
                              f"{', '.join(str(r) for r in PICTURE_RATES.values())}")
@@ -2388,7 +2535,10 @@ class Decoder:
                     import torch
                     pictures = torch.from_numpy(np.ascontiguousarray(pictures)).to(torch.device("cuda", self.device))
                 pictures = self.conform(pictures, fps, fps_out)
+                conformed = True
             fps = fps_out
+        if overlays is not None and len(overlays):
+            pictures = self.overlay(pictures, overlays, inplace=conformed)  # (conform's result is this call's own)
         titles, st = self.encode_av(pictures, pcm, fps=fps, aq=aq, **encode_av)
         keys = ("qscale", "search", "first_pts", "bitrate", "vbv_bits", "qmin", "qmax")
         fwd, rwd, tst = self.trick_streams(pictures, speed=speed, gop=trick_gop, fps=fps, aq=aq,

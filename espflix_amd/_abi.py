@@ -182,6 +182,13 @@ SCAN_FRAME_DTYPE = np.dtype([("comb", "<u8"), ("comb_tb", "<u8"), ("comb_bt", "<
                              ("label", "<i4"), ("repeat", "<i4")])
 SCAN_REC_DTYPE = np.dtype([("n_still", "<u4"), ("n_prog", "<u4"), ("n_tff", "<u4"), ("n_bff", "<u4"), ("n_undet", "<u4"),
                            ("rep_top", "<u4", 5), ("rep_bottom", "<u4", 5), ("reserved", "<u4")])
+# efx_overlay_event (one 64-byte record per event, an array of them is the list) and efx_overlay_opts (passed like
+# efx_denoise_opts)
+OVERLAY_EVENT_DTYPE = np.dtype([("first", "<i8"), ("last", "<i8"), ("offset", "<u8"), ("stream", "<i4"), ("x", "<i4"), ("y", "<i4"),
+                                ("pitch", "<u4"), ("colour", "<u4"), ("w", "<u2"), ("h", "<u2"), ("opacity", "<u2"),
+                                ("fade_in", "<u2"), ("fade_out", "<u2"), ("kind", "u1"), ("reserved0", "u1"), ("reserved", "<u8")])
+OVERLAY_OPTS_DTYPE = np.dtype([("n_streams", "<i4"), ("n_pictures", "<i4"), ("n_events", "<i4"), ("reserved", "<i4"),
+                               ("first_picture", "<i8"), ("stride", "<u8"), ("atlas_bytes", "<u8")])
 
 # every symbol include/efx.h declares: (name, restype, argtypes)
 _P = C.c_void_p
@@ -235,6 +242,8 @@ _SYMBOLS = {
     "efx_detect_scan": (C.c_int, [_P, C.POINTER(_Surface), _P, _P, _P, _P]),
     "efx_scan_verdict": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "efx_denoise": (C.c_int, [_P, C.POINTER(_Surface), _P, _P, _P, _P]),
+    "efx_overlay": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "efx_overlay_check": (C.c_int, [_P, C.c_int, C.c_uint64]),
     "efx_import_set_colour": (C.c_int, [_P, C.POINTER(_ImportColour)]),
     "efx_import_colour_coefs": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
     "efx_import_set_hdr": (C.c_int, [_P, C.POINTER(_ImportHdr)]),

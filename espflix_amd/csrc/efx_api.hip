@@ -27,6 +27,7 @@
 #include "crop_px.h"
 #include "deint_px.h"
 #include "denoise_px.h"
+#include "overlay_px.h"
 #include "telecine_px.h"
 #include "scan_px.h"
 #include "surface_px.h"
@@ -91,6 +92,7 @@ __global__ void k_trick(TrickArgs);  // (k_trick.hip: the I420 and the ring inst
 __global__ void k_conform(ConformArgs);  // (k_conform.hip)
 __global__ void k_deint(DeintArgs);      // (k_deint.hip)
 __global__ void k_denoise(DenoiseArgs);  // (k_denoise.hip)
+__global__ void k_overlay(OverlayArgs);  // (k_overlay.hip)
 __global__ void k_telecine_measure(TelecineArgs);  // (k_telecine.hip)
 __global__ void k_telecine_decide(TelecineArgs);
 __global__ void k_telecine_weave(TelecineArgs);
@@ -2186,6 +2188,50 @@ int efx_denoise(efx_ctx* ctx, const efx_surface* s, const efx_denoise_opts* o, c
     hipLaunchKernelGGL(k_denoise, dim3((unsigned)std::min(wgs, (size_t)1 << 20)), dim3(64 * npx::kWaves), 0, ctx->stream, a);
     EFX_HIP(hipGetLastError());
     return EFX_OK;
+}
+
+// ---- subtitles and logos (k_overlay.hip) ----------------------------------------------------------------------------------------
+int efx_overlay(efx_ctx* ctx, const efx_overlay_opts* o, const efx_overlay_event* events_device, const uint8_t* atlas_device,
+                uint8_t* pictures_device, uint32_t* status_device)
+{
+    bind_device(ctx);
+    if (!ctx || !o)
+        return EFX_ERR_ARG;
+    if (o->n_streams < 1 || o->n_pictures < 1 || o->n_events < 0 || o->n_events > EFX_OVERLAY_MAX_EVENTS || o->reserved != 0)
+        return fail(ctx, EFX_ERR_ARG, "efx_overlay: n_streams and n_pictures must be >= 1, n_events 0 .. 4096, reserved 0");
+    if ((int64_t)o->n_streams * o->n_pictures > INT32_MAX)
+        return fail(ctx, EFX_ERR_ARG, "efx_overlay: the pictures must be below 2^31");
+    if (o->first_picture < 0 || o->first_picture > ovx::kMaxIndex - o->n_pictures)
+        return fail(ctx, EFX_ERR_ARG, "efx_overlay: first_picture must be >= 0 and first_picture + n_pictures at most 2^40");
+    if (!pictures_device || ((uintptr_t)pictures_device & 15))
+        return fail(ctx, EFX_ERR_ARG, "efx_overlay: pictures_device must be a 16-byte aligned device pointer");
+    if (o->n_events > 0 && (!events_device || !atlas_device))
+        return fail(ctx, EFX_ERR_ARG, "efx_overlay: events_device and atlas_device must be given with n_events > 0");
+    if (((uintptr_t)events_device & 7) || ((uintptr_t)status_device & 3))
+        return fail(ctx, EFX_ERR_ARG, "efx_overlay: events_device must be 8-byte aligned, status_device (when given) 4-byte aligned");
+    OverlayArgs a{};
+    a.events = events_device, a.atlas = atlas_device, a.pictures = pictures_device, a.status = status_device;
+    const uint64_t row = (uint64_t)o->n_pictures * ovx::kPicture;
+    a.stride = o->stride ? (size_t)o->stride : (size_t)row;
+    if (a.stride < row || (a.stride & 15))
+        return fail(ctx, EFX_ERR_ARG, "efx_overlay: stride must be a multiple of 16 and hold a stream's pictures");
+    a.atlas_bytes = o->atlas_bytes, a.first_picture = o->first_picture;
+    a.n_streams = o->n_streams, a.n_pictures = o->n_pictures, a.n_events = o->n_events;
+    if (a.n_events == 0)
+        return EFX_OK;  // nothing is shown: no launch
+    // one launch whatever the counts are (a workgroup takes further pictures when there are more than the grid's)
+    const size_t pictures = (size_t)a.n_streams * (size_t)a.n_pictures;
+    hipLaunchKernelGGL(k_overlay, dim3((unsigned)std::min(pictures, (size_t)1 << 20)), dim3(ovx::kScanStep), 0, ctx->stream, a);
+    EFX_HIP(hipGetLastError());
+    return EFX_OK;
+}
+
+int efx_overlay_check(const efx_overlay_event* events, int n_events, uint64_t atlas_bytes)
+{
+    for (int i = 0; events && i < n_events; i++)
+        if (!ovx::valid(events[i], atlas_bytes))
+            return i;
+    return -1;
 }
 
 // ---- black borders (k_cropdetect.hip) -------------------------------------------------------------------------------------------

@@ -487,6 +487,18 @@ struct DenoiseArgs {
     int stream_items;     // npx::stream_items(width, height)
 };
 
+// k_overlay (k_overlay.hip) launch arguments (by value): efx_overlay_opts, checked (overlay_px.h)
+struct OverlayArgs {
+    const efx_overlay_event* events;  // n_events records
+    const uint8_t* atlas;             // the bitmaps; readable up to atlas_bytes rounded up to 16
+    uint8_t* pictures;                // stream i, picture j at pictures + i * stride + j * 101376
+    uint32_t* status;                 // n_streams words, or NULL
+    size_t stride;
+    uint64_t atlas_bytes;
+    int64_t first_picture;            // the title index of the call's picture 0
+    int n_streams, n_pictures, n_events;
+};
+
 // k_sbc_enc launch arguments (by value): efx_sbc_encode_opts, checked, with the context's tables
 namespace sbcenc {
 struct Tables;

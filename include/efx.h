@@ -800,6 +800,99 @@ typedef struct efx_denoise_opts {     /* fixed-width fields only: a binding can 
 int efx_denoise(efx_ctx* ctx, const efx_surface* surface, const efx_denoise_opts* opts, const void* src_device,
                 const uint8_t* prev_device /* NULL: the title's start */, uint8_t* dst_device);
 
+/* -- subtitles and logos: events alpha-blended into pictures (k_overlay) -------------------- */
+/* The player shows one MPEG-1 picture and nothing over it but its own progress bar: text or a station logo reaches the
+ * screen only burnt into the pictures before efx_encode reads them -- what ffmpeg does with subtitles= / ass= (alpha
+ * masks and a colour) and overlay= (an RGBA picture).  efx_overlay blends a list of events, bitmaps shown over a span of
+ * pictures, into batches of 352 x 192 I420 pictures, in place, on the device.  The rule is exact integer arithmetic
+ * (espflix_amd/csrc/overlay_px.h), bit-reproducible anywhere.  All values are int, >> is arithmetic, / is integer
+ * division of non-negative values.
+ *
+ *   Pictures.  The layout efx_encode, efx_conform_rate and efx_trick_pick read: 101376 bytes a picture (Y 192 x 352, Cb
+ *   96 x 176, Cr 96 x 176), stream i's picture j at pictures + i * stride + j * 101376.  Picture j of the call has the
+ *   title index p = first_picture + j.
+ *   Events.  One 64-byte record each (efx_overlay_event below), bitmaps in one atlas of atlas_bytes bytes.  An event is
+ *   VALID when: kind is 0 or 1; 0 <= first <= last < 2^40; stream >= -1; x and y lie in -4096 .. 4095; w and h lie in 1 ..
+ *   4096; opacity <= 256; fade_in and fade_out <= 32767; with bpp = 1 (EFX_OVL_A8) or 4 (EFX_OVL_RGBA), pitch >= w bpp;
+ *   for RGBA offset and pitch are multiples of 4; offset + (h - 1) pitch + w bpp <= atlas_bytes, computed in 64 bits;
+ *   colour < 2^24 for A8 and 0 for RGBA; both reserved fields are 0.
+ *   Activity.  Event e is active for stream s and picture j when it is valid, (stream == -1 or stream == s) and first <= p
+ *   <= last.  An event whose stream is >= n_streams is never active: one list serves every shard of a batch.  Everything
+ *   depends on p only, so the pieces of a title, concatenated, equal one long call; no state is carried.
+ *   Gain of an event at picture p.  With k = p - first: fi = 256 if fade_in == 0 or k >= fade_in, else fi = (256 (k + 1)) /
+ *   (fade_in + 1).  With k' = last - p: fo likewise from fade_out.  g = (opacity min(fi, fo) + 128) >> 8, in 0 .. 256.
+ *   fade_in = 3, fade_out = 2, opacity = 256 over pictures 10 .. 20: 64 128 192 256 256 256 256 256 256 170 85.
+ *   Sample alpha and colour.  For the picture's luma sample (X, Y) the bitmap sample is (X - x, Y - y); outside 0 .. w - 1,
+ *   0 .. h - 1 it is absent and a = 0.  Otherwise a = (A g + 128) >> 8 with A the alpha byte: 0 .. 255, and A = 255 with
+ *   g = 256 gives 255.  The colour (Cy, Ccb, Ccr) is the import's BT.601 studio-swing matrix (efx_import_frames, RGB
+ *   sources, full_range = 0) of the pixel's R, G, B for RGBA (bytes R, G, B, A, straight alpha), or of `colour`
+ *   (0x00RRGGBB) for A8 (one alpha byte a sample).
+ *   Luma.  t = Y (255 - a) + Cy a;  out = (2 t + 255) / 510, which is t / 255 rounded half up.  a = 0 leaves Y, a = 255
+ *   gives Cy.
+ *   Chroma.  Premultiplied 2 x 2 down-sampling: the site (cx, cy) covers the luma samples (2 cx + i, 2 cy + j), i, j in
+ *   0, 1, with alphas a_ij (0 where absent) and colours c_ij.  S = sum a_ij (<= 1020), N = sum a_ij c_ij, and
+ *   out = (C (1020 - S) + N + 510) / 1020, for Cb and Cr alike.  Absent samples need no colour.  out lies between the
+ *   extremes of C and the c_ij.
+ *   Order.  The active events of a picture are applied in list order, each to the 8-bit result of the one before: a
+ *   later event is on top.  With Y = 100, white (Cy = 235) at a = 128 then black (16) at a = 128 gives 92; the other
+ *   order gives 147.
+ *
+ * Memory contract.  The kernel reads events only in [events, events + n_events x 64) and the atlas only in [atlas, atlas
+ * + atlas_bytes rounded up to 16), 16 bytes at a time at any alignment, and only for bitmap rows and 16-byte groups of
+ * columns that land inside a picture; no atlas byte of an invalid event is read.  Bytes in pitch padding and between
+ * bitmaps never influence a result.  A picture with no active event is neither read nor written.  A picture with active
+ * events is read and written only in the 16-byte chunks of plane rows that an active event's clipped rectangle touches
+ * (chroma: the rectangle halved outward); bytes of those chunks outside the rectangle are written back unchanged.
+ * Bytes between pictures (stride padding) are never written.  The atlas, event and picture regions must not overlap.
+ *
+ * Out of scope: rendering text or parsing subtitle files (the caller brings bitmaps), events that move or scale, other
+ * blend modes, sources at their own size, the frame rings as destination, efx_multi_*. */
+#define EFX_OVL_A8   0
+#define EFX_OVL_RGBA 1
+#define EFX_OVERLAY_BAD_EVENT 8192u  /* status_device bit: the list holds an event that is not valid; it was not drawn */
+#define EFX_OVERLAY_MAX_EVENTS 4096
+typedef struct efx_overlay_event {     /* 64 bytes, fixed-width fields only, little endian */
+    int64_t  first;                    /* title index of the first picture that shows the event */
+    int64_t  last;                     /* ... of the last one */
+    uint64_t offset;                   /* byte offset of the bitmap in the atlas */
+    int32_t  stream;                   /* stream of the call it belongs to, -1 = every stream */
+    int32_t  x;                        /* picture column of the bitmap's top-left sample */
+    int32_t  y;                        /* picture row of it; both may be negative or beyond the picture: the bitmap is clipped */
+    uint32_t pitch;                    /* bytes between bitmap rows */
+    uint32_t colour;                   /* EFX_OVL_A8: 0x00RRGGBB; EFX_OVL_RGBA: 0 */
+    uint16_t w;                        /* bitmap width */
+    uint16_t h;                        /* bitmap height */
+    uint16_t opacity;                  /* 0 .. 256 */
+    uint16_t fade_in;                  /* fade-in length in pictures */
+    uint16_t fade_out;                 /* fade-out length in pictures */
+    uint8_t  kind;                     /* EFX_OVL_A8 or EFX_OVL_RGBA */
+    uint8_t  reserved0;                /* 0 */
+    uint64_t reserved;                 /* 0 */
+} efx_overlay_event;
+typedef struct efx_overlay_opts {      /* fixed-width fields only */
+    int32_t  n_streams;                /* >= 1 */
+    int32_t  n_pictures;               /* pictures per stream in this call, >= 1 */
+    int32_t  n_events;                 /* 0 .. 4096 */
+    int32_t  reserved;                 /* 0 */
+    int64_t  first_picture;            /* title index of the call's picture 0, 0 .. 2^40 - 1 */
+    uint64_t stride;                   /* bytes between streams; 0 = n_pictures x 101376; multiple of 16 */
+    uint64_t atlas_bytes;              /* bytes of the atlas the events may name */
+} efx_overlay_opts;
+/* Asynchronous on the context's stream: no host synchronisation, one launch whatever the counts are and none for n_events
+ * == 0 (which returns EFX_OK), no scratch, no allocation, and no decoder, encoder, SBC or import state is touched.
+ * The kernel applies the validity rule to every event it reads: an invalid event is drawn for no picture, the valid
+ * events of the same list are drawn as usual, and EFX_OVERLAY_BAD_EVENT is ORed (vector atomics; the caller clears the
+ * words) into every one of the n_streams words of status_device (may be NULL) when the list holds one.
+ * EFX_ERR_ARG: a count out of range, more than 2^31 - 1 pictures, first_picture below 0 or first_picture + n_pictures
+ * above 2^40, a non-zero reserved field, a NULL or misaligned (16 bytes) pictures_device, a NULL events_device or
+ * atlas_device with n_events > 0, events_device not 8-byte aligned, status_device not 4-byte aligned, a stride that is too
+ * small or not a multiple of 16.  A refused call writes nothing. */
+int efx_overlay(efx_ctx* ctx, const efx_overlay_opts* opts, const efx_overlay_event* events_device, const uint8_t* atlas_device,
+                uint8_t* pictures_device, uint32_t* status_device /* n_streams words, or NULL */);
+/* The index of the first event of the list that is not valid for an atlas of atlas_bytes, or -1 (also for a NULL list or
+ * n_events <= 0).  Host only. */
+int efx_overlay_check(const efx_overlay_event* events, int n_events, uint64_t atlas_bytes);
+
 /* -- source colour: BT.709, full-range and other YCbCr sources to BT.601 (k_import) -------- */
 /* MPEG-1 carries BT.601 studio-swing YCbCr, and efx_import_frames / efx_import_surfaces copy a YCbCr source's samples
  * through.  What a decoder hands over today is mostly HD with BT.709 matrix coefficients, and phone or JPEG-derived
