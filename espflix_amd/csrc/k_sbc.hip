@@ -706,6 +706,22 @@ __device__ inline void sbc_lds_barrier()
     __builtin_amdgcn_s_barrier();
 }
 
+// x / d as (x * m) >> 16 with m = 2^16 / d rounded up (or 2^16 / d + 1 where d divides 2^16).  With e = m * d - 2^16 > 0,
+// x * m / 2^16 = x / d + x * e / (d * 2^16): the quotient is floor(x / d) as long as the second term stays below the 1 / d that
+// x mod d = d - 1 leaves to the next integer, that is for every x with x * e < 2^16 -- x below sbc_recip16_bound(m, d).
+constexpr uint32_t sbc_recip16_bound(uint32_t m, uint32_t d) { return (65536u + (m * d - 65536u) - 1) / (m * d - 65536u); }
+// ... of a block number by the frame's block count, and of a quarter (four blocks) number by the frame's quarters
+constexpr uint32_t kSbcInvB4 = 16385u, kSbcInvB8 = 8193u, kSbcInvB12 = 5462u, kSbcInvB16 = 4097u;
+constexpr uint32_t kSbcInvQ1 = 65537u, kSbcInvQ2 = 32769u, kSbcInvQ3 = 21846u, kSbcInvQ4 = 16385u;
+static_assert(sbc_recip16_bound(kSbcInvB4, 4) == 16384, "inv_b, 4 blocks: 16385 * 4 - 2^16 = 4, exact for x < 2^16 / 4 = 16384");
+static_assert(sbc_recip16_bound(kSbcInvB8, 8) == 8192, "inv_b, 8 blocks: 8193 * 8 - 2^16 = 8, exact for x < 2^16 / 8 = 8192");
+static_assert(sbc_recip16_bound(kSbcInvB12, 12) == 8192, "inv_b, 12 blocks: 5462 * 12 - 2^16 = 8, exact for x < 2^16 / 8 = 8192");
+static_assert(sbc_recip16_bound(kSbcInvB16, 16) == 4096, "inv_b, 16 blocks: 4097 * 16 - 2^16 = 16, exact for x < 2^16 / 16 = 4096");
+static_assert(sbc_recip16_bound(kSbcInvQ1, 1) == 65536, "inv_q, 1 quarter: 65537 - 2^16 = 1, exact for x < 2^16");
+static_assert(sbc_recip16_bound(kSbcInvQ2, 2) == 32768, "inv_q, 2 quarters: 32769 * 2 - 2^16 = 2, exact for x < 2^16 / 2 = 32768");
+static_assert(sbc_recip16_bound(kSbcInvQ3, 3) == 32768, "inv_q, 3 quarters: 21846 * 3 - 2^16 = 2, exact for x < 2^16 / 2 = 32768");
+static_assert(sbc_recip16_bound(kSbcInvQ4, 4) == 16384, "inv_q, 4 quarters: 16385 * 4 - 2^16 = 4, exact for x < 2^16 / 4 = 16384");
+
 }  // namespace
 
 // Regular streams: every frame decodes under the geometry of frame 0, so everything has a closed form -- frame f's PCM sits at
@@ -792,7 +808,11 @@ __device__ __forceinline__ void sbc_par_body(const uint8_t* __restrict__ frames,
         // x / blocks = x * inv_b >> 16, exact for x < 4096 ONLY: it is applied to block numbers counted from the first frame
         // in reach (< FR * 16), never to a block of the call's timeline -- that grows with the number of frames of the call
         // (round-5 ADVICE: with the absolute number the quotient was first wrong at frame 688 of a 12-block stream)
-        p.inv_b = p.blocks == 4 ? 16385u : p.blocks == 8 ? 8193u : p.blocks == 12 ? 5462u : 4097u;
+        p.inv_b = p.blocks == 4 ? kSbcInvB4 : p.blocks == 8 ? kSbcInvB8 : p.blocks == 12 ? kSbcInvB12 : kSbcInvB16;
+        static_assert((uint32_t)(FR * 16) <= sbc_recip16_bound(kSbcInvB16, 16) && (uint32_t)(FR * 16) <= sbc_recip16_bound(kSbcInvB12, 12) &&
+                          (uint32_t)(FR * 16) <= sbc_recip16_bound(kSbcInvB8, 8) && (uint32_t)(FR * 16) <= sbc_recip16_bound(kSbcInvB4, 4),
+                      "inv_b divides block numbers below FR * 16 (blocks of the frames in reach): the tightest reciprocal, 4097 for "
+                      "16 blocks, is exact below 4096 only");
         p.gbase = frames + (size_t)p.s * stream_stride;
         p.inf = info + (size_t)p.s * n_frames;
         p.f0 = chunk * CH;
@@ -934,7 +954,12 @@ __device__ __forceinline__ void sbc_par_body(const uint8_t* __restrict__ frames,
         {
             const int r = tid & (PB - 1);
             const int QB = blocks >> 2;  // quarters of a frame
-            const uint32_t inv_q = QB == 1 ? 65537u : QB == 2 ? 32769u : QB == 3 ? 21846u : 16385u;
+            const uint32_t inv_q = QB == 1 ? kSbcInvQ1 : QB == 2 ? kSbcInvQ2 : QB == 3 ? kSbcInvQ3 : kSbcInvQ4;
+            // (its argument: a task number, below the FR * 4 quarters of the frames in reach; __umul24 takes it whole)
+            static_assert((uint32_t)(FR * 4) <= sbc_recip16_bound(kSbcInvQ4, 4) && (uint32_t)(FR * 4) <= sbc_recip16_bound(kSbcInvQ3, 3) &&
+                              (uint32_t)(FR * 4) <= sbc_recip16_bound(kSbcInvQ2, 2) && (uint32_t)(FR * 4) <= sbc_recip16_bound(kSbcInvQ1, 1) && FR * 4 < (1 << 24),
+                          "inv_q divides task numbers below FR * 4: the tightest reciprocal, 16385 for 4 quarters, is exact below "
+                          "16384 only");
             const int q_lo = fr_lo >= 0 ? (first_vb - fr_lo * blocks) >> 2 : 0, nq0 = QB - q_lo;
             const int n_tasks = nq0 + (n_fr - 1) * QB;
             auto tasks = [&](auto&& field) {

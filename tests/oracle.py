@@ -424,6 +424,11 @@ def sbc_tables():
 
 def sbc_decode(frames: np.ndarray, frame_bytes: int, probe: bool = False):
     """Decode concatenated frames with the restatement.  Returns (pcm int16, [(ret, decoded)])."""
+    return sbc_decode_state(frames, frame_bytes, probe)[:2]
+
+
+def sbc_decode_state(frames: np.ndarray, frame_bytes: int, probe: bool = False):
+    """sbc_decode() and the restatement's sb_sample[16][2][8] as the last frame left it: (pcm, rets, sb_sample int32)."""
     L = lib()
     L.efxo_sbc_decode.restype = C.c_int
     L.efxo_sbc_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
@@ -441,7 +446,42 @@ def sbc_decode(frames: np.ndarray, frame_bytes: int, probe: bool = False):
         r = L.efxo_sbc_decode(C.byref(st), data[fi * frame_bytes:].ctypes.data, frame_bytes, pcm.ctypes.data, C.byref(dec))
         rets.append((r, dec.value))
         out.append(pcm[:dec.value // 2].copy())
-    return (np.concatenate(out) if out else np.zeros(0, np.int16)), rets
+    return (np.concatenate(out) if out else np.zeros(0, np.int16)), rets, np.array(st.sb_sample, dtype=np.int32).reshape(16, 2, 8)
+
+
+def sbc_decode_call(streams, frame_bytes: int):
+    """Equally long streams, each through a fresh restatement decoder, without the per-frame array work of sbc_decode():
+    (list of pcm int16, int32 [stream, frame, 2]: return value and decoded bytes, int32 sb_sample [stream, 16, 2, 8])."""
+    L = lib()
+    L.efxo_sbc_decode.restype = C.c_int
+    L.efxo_sbc_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.efxo_sbc_init.argtypes = [C.c_void_p]
+    n = streams[0].size // frame_bytes
+    rets = np.zeros((len(streams), n, 2), dtype=np.int32)
+    sb = np.zeros((len(streams), 16, 2, 8), dtype=np.int32)
+    pcm = []
+    st = SbcState()
+    p_st = C.addressof(st)
+    for i, s in enumerate(streams):
+        L.efxo_sbc_init(p_st)
+        data = np.concatenate([np.ascontiguousarray(s[:n * frame_bytes], dtype=np.uint8), np.zeros(1024, np.uint8)])
+        out = np.zeros(n * 256, dtype=np.int16)
+        src, dst, r = data.ctypes.data, out.ctypes.data, rets[i].ctypes.data
+        off = 0
+        for f in range(n):
+            rets[i, f, 0] = L.efxo_sbc_decode(p_st, src + f * frame_bytes, frame_bytes, dst + off, r + 8 * f + 4)
+            off += int(rets[i, f, 1])
+        pcm.append(out[:off // 2])
+        sb[i] = np.frombuffer(st.sb_sample, dtype=np.int32).reshape(16, 2, 8)
+    return pcm, rets, sb
+
+
+def sbc_call_hashes(pcm, rets) -> dict:
+    """What tests/golden/sbc_directed.json keeps of a call: the FNV of all streams' PCM back to back and of the (return value,
+    decoded bytes) pairs of all frames."""
+    allpcm = np.ascontiguousarray(np.concatenate(pcm), dtype=np.int16).view(np.uint8)
+    r = np.ascontiguousarray(rets, dtype=np.int32).reshape(-1).view(np.uint8)
+    return {"pcm": f"{fnv1a64(allpcm):016x}", "ret": f"{fnv1a64(r):016x}"}
 
 
 def ts_audio_es(ts: np.ndarray) -> np.ndarray:
@@ -462,6 +502,10 @@ def ref_sbc_decode(frames: np.ndarray, frame_bytes: int, probe: bool = False):
                            (["probe"] if probe else []), check=True, timeout=120, stderr=subprocess.PIPE, text=True)
         rets = [(int(l.split()[2]), int(l.split()[3])) for l in p.stderr.splitlines() if l.startswith("R ")]
         return np.fromfile(out, dtype=np.int16), rets
+
+
+def have_ref_sbc() -> bool:
+    return os.path.exists(os.path.join(REF_DIR, "efx_ref_sbc"))
 
 
 def ref_sbc_tables():
