@@ -7,7 +7,7 @@ HIPCC   ?= /opt/rocm/bin/hipcc
 ARCH    ?= gfx950
 CSRC     = espflix_amd/csrc
 HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude -I$(CSRC) -Wall -Wno-unused-function
-OBJS     = $(CSRC)/efx_api.o $(CSRC)/k_demux.o $(CSRC)/k_index.o $(CSRC)/k_parse.o $(CSRC)/k_recon.o $(CSRC)/k_video.o $(CSRC)/k_sbc.o $(CSRC)/k_tsindex.o $(CSRC)/k_export.o $(CSRC)/k_import.o $(CSRC)/k_cropdetect.o $(CSRC)/k_quality.o $(CSRC)/k_trick.o $(CSRC)/k_conform.o $(CSRC)/k_deint.o $(CSRC)/k_telecine.o $(CSRC)/k_scan.o $(CSRC)/k_denoise.o $(CSRC)/k_overlay.o $(CSRC)/k_import_pcm.o $(CSRC)/k_loudness.o $(CSRC)/k_encode.o $(CSRC)/k_sbc_enc.o $(CSRC)/k_mux.o $(CSRC)/efx_tables.o $(CSRC)/efx_multi.o
+OBJS     = $(CSRC)/efx_api.o $(CSRC)/k_demux.o $(CSRC)/k_index.o $(CSRC)/k_parse.o $(CSRC)/k_recon.o $(CSRC)/k_video.o $(CSRC)/k_sbc.o $(CSRC)/k_tsindex.o $(CSRC)/k_export.o $(CSRC)/k_import.o $(CSRC)/k_cropdetect.o $(CSRC)/k_quality.o $(CSRC)/k_trick.o $(CSRC)/k_conform.o $(CSRC)/k_deint.o $(CSRC)/k_telecine.o $(CSRC)/k_scan.o $(CSRC)/k_denoise.o $(CSRC)/k_overlay.o $(CSRC)/k_import_pcm.o $(CSRC)/k_loudness.o $(CSRC)/k_limit.o $(CSRC)/k_encode.o $(CSRC)/k_sbc_enc.o $(CSRC)/k_mux.o $(CSRC)/efx_tables.o $(CSRC)/efx_multi.o
 
 .PHONY: all lib gen oracle ref clean dropin scale harness
 # (`scale` links librccl: built by __graft_entry__.build() and by `make scale`, not by a plain `make`)
@@ -33,9 +33,9 @@ $(CSRC)/k_import.o $(CSRC)/efx_api.o $(CSRC)/efx_tables.o: $(CSRC)/hdr_px.h $(CS
 $(CSRC)/k_quality.o $(CSRC)/efx_api.o: $(CSRC)/quality_px.h
 $(CSRC)/k_encode.o $(CSRC)/k_mux.o $(CSRC)/efx_api.o: $(CSRC)/enc_core.h $(CSRC)/mpeg1_codebook.h
 $(CSRC)/k_sbc_enc.o $(CSRC)/efx_api.o: $(CSRC)/sbc_enc_core.h $(CSRC)/sbc_proto.h
-$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/efx_internal.h $(CSRC)/import_pcm.h $(CSRC)/loudness_px.h $(CSRC)/enc_rate.h $(CSRC)/enc_aq.h $(CSRC)/parse_tm.h $(CSRC)/efx_probe.h include/efx.h
+$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/efx_internal.h $(CSRC)/import_pcm.h $(CSRC)/loudness_px.h $(CSRC)/limit_px.h $(CSRC)/enc_rate.h $(CSRC)/enc_aq.h $(CSRC)/parse_tm.h $(CSRC)/efx_probe.h include/efx.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(CSRC)/efx_tables.o: $(CSRC)/efx_tables.cpp $(CSRC)/efx_internal.h $(CSRC)/import_pcm.h $(CSRC)/loudness_px.h $(CSRC)/enc_rate.h $(CSRC)/enc_aq.h $(CSRC)/parse_tm.h $(CSRC)/mpeg1_codebook.h $(CSRC)/sbc_proto.h
+$(CSRC)/efx_tables.o: $(CSRC)/efx_tables.cpp $(CSRC)/efx_internal.h $(CSRC)/import_pcm.h $(CSRC)/loudness_px.h $(CSRC)/limit_px.h $(CSRC)/enc_rate.h $(CSRC)/enc_aq.h $(CSRC)/parse_tm.h $(CSRC)/mpeg1_codebook.h $(CSRC)/sbc_proto.h
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 $(CSRC)/efx_multi.o: $(CSRC)/efx_multi.cpp include/efx.h
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@

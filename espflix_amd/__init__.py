@@ -18,7 +18,7 @@ from fractions import Fraction
 import numpy as np
 
 # the C-ABI's structs, record dtypes and signatures live in _abi.py; they are part of this module's surface
-from ._abi import (DENOISE_OPTS_DTYPE, ENC_PICTURE_INFO_DTYPE, LOUDNESS_REC_DTYPE, LOUDNESS_STEP_DTYPE, SCAN_FRAME_DTYPE,  # noqa: F401
+from ._abi import (DENOISE_OPTS_DTYPE, ENC_PICTURE_INFO_DTYPE, LIMIT_OPTS_DTYPE, LIMIT_PEAKS_OPTS_DTYPE, LOUDNESS_REC_DTYPE, LOUDNESS_STEP_DTYPE, SCAN_FRAME_DTYPE,  # noqa: F401
                    OVERLAY_EVENT_DTYPE, OVERLAY_OPTS_DTYPE, SCAN_OPTS_DTYPE, SCAN_REC_DTYPE, TELECINE_INFO, _P, _SYMBOLS,
                    _AdaptiveQuant, _CompareOpts, _CompareRec, _Config, _ConformOpts, _CropOpts, _DeintOpts, _DetelecineOpts,
                    _EncodeOpts, _EncodeRate, _EncPictureInfo, _ExportOpts, _FieldOpts, _IdxRec, _ImportColour, _ImportHdr,
@@ -675,6 +675,28 @@ def loudness_state_bytes(rate: int) -> int:
 def loudness_step_count(rate: int, first_sample: int, n_samples: int) -> int:
     """Steps of 100 ms that become whole with n_samples more samples (efx_loudness_step_count; -1 for invalid arguments)."""
     return int(load_library().efx_loudness_step_count(rate, first_sample, n_samples))
+
+
+def limit_block(rate: int) -> int:
+    """Samples of a block of the peak limiter at `rate` (efx_limit_block): 16, 32, 48 or 48; 0 for a rate that is not one of
+    the four."""
+    return int(load_library().efx_limit_block(rate))
+
+
+def _limit_blocks(samples: int, rate: int) -> int:
+    """Blocks of `samples` samples at `rate`: the entries of a stream's peaks row.  ValueError for a rate that is not one of
+    the four."""
+    bk = limit_block(rate)
+    if not bk:
+        raise ValueError("rate must be 16000, 32000, 44100 or 48000")
+    return -(-samples // bk)
+
+
+def limit_gain(gated_mean: int, n_gated: int, target_ms: int, rate: int) -> int:
+    """The gain (Q12, 1 .. 32767) the limiter aims at for a stream whose efx_loudness_rec holds gated_mean and n_gated
+    (efx_limit_gain): the loudness gain to target_ms (loudness_thresholds(rate, target)[1]) without the record's peak
+    cap; 4096 when n_gated is 0.  0 for arguments out of range."""
+    return int(load_library().efx_limit_gain(int(gated_mean), int(n_gated), int(target_ms), rate))
 
 
 def mux_bound(video_bytes: int, n_frames: int, frame_bytes: int, frames_per_pes: int) -> int:
@@ -2017,6 +2039,77 @@ class Decoder:
         o = _PcmGainOpts(n_streams, n_samples, fixed_gain_q12, src_stride or r8, dst_stride or r8)
         _check(self._ctx, self._lib.efx_pcm_gain(self._ctx, C.byref(o), _ptr(src), _ptr(recs), _ptr(dst)))
 
+    # -- peak limiter (efx_limit_peaks, efx_pcm_limit) ------------------------------------------------
+    def limit_peaks_to(self, pcm: DeviceBuffer | int, peaks: DeviceBuffer | int, *, n_streams: int, n_samples: int, rate: int,
+                       first_sample: int = 0, peaks_first: int = 0, pcm_stride: int = 0, peaks_stride: int = 0):
+        """efx_limit_peaks on raw device memory (DeviceBuffers or pointers), asynchronous on the library's stream: the peak
+        (uint16, 0 .. 32768) of every block of limit_block(rate) samples of stream i's n_samples samples at pcm +
+        i x pcm_stride elements (0 = n_samples rounded up to 8) goes to entry first_sample / Bk - peaks_first onwards of
+        the stream's row of peaks_stride entries (0 = just those).  first_sample is a multiple of Bk, and so is n_samples
+        on every piece but a stream's last."""
+        bk = max(1, limit_block(rate))
+        o = np.zeros(1, dtype=LIMIT_PEAKS_OPTS_DTYPE)
+        o[0] = (n_streams, n_samples, rate, 0, first_sample, peaks_first, pcm_stride or (max(0, n_samples) + 7) // 8 * 8,
+                peaks_stride or max(0, first_sample // bk - peaks_first) + -(-max(0, n_samples) // bk))
+        _check(self._ctx, self._lib.efx_limit_peaks(self._ctx, o.ctypes.data, _ptr(pcm), _ptr(peaks)))
+
+    def pcm_limit_to(self, src: DeviceBuffer | int, peaks: DeviceBuffer | int, recs: DeviceBuffer | int | None, dst: DeviceBuffer | int,
+                     *, n_streams: int, n_samples: int, rate: int, n_peaks: int, half_window: int = 0, first_sample: int = 0,
+                     peaks_first: int = 0, target: float = -23.0, peak: float = -1.0, thresholds=None, fixed_gain_q12: int = 4096,
+                     src_stride: int = 0, dst_stride: int = 0, peaks_stride: int = 0):
+        """efx_pcm_limit on raw device memory, asynchronous on the library's stream: the look-ahead limiter of include/efx.h
+        ("peak limiter") over stream i's n_samples samples that begin at stream sample first_sample, with the block peaks
+        limit_peaks_to left: entry 0 of a row (n_peaks entries, peaks_stride apart, 0 = n_peaks) is stream block
+        peaks_first, a block outside the row counts as silent.  Each stream's gain is worked out on the device from its
+        record at recs (those of loudness_gate_to) and the target -- thresholds: (abs_thr, target_ms, ceiling) instead of
+        loudness_thresholds(rate, target, peak) -- or is fixed_gain_q12 for all when recs is None; the ceiling is `peak`
+        dBFS.  half_window: H in blocks of about 1 ms, 1 .. 64, 0 = 32.  dst may be src.  Sample strides in elements, 0 =
+        n_samples rounded up to 8.
+
+        A title fed in pieces takes two passes, as normalize() explains: loudness_steps_to and limit_peaks_to over every
+        piece (the peaks into one row for the whole title, or the caller keeps 2H + 1 blocks either side of each piece),
+        one loudness_gate_to, then pcm_limit_to per piece."""
+        _, t, c = thresholds if thresholds is not None else loudness_thresholds(rate, target, peak)
+        r8 = (max(0, n_samples) + 7) // 8 * 8
+        o = np.zeros(1, dtype=LIMIT_OPTS_DTYPE)
+        o[0] = (n_streams, n_samples, rate, half_window, c, fixed_gain_q12, n_peaks, 0, first_sample, peaks_first, t, src_stride or r8,
+                dst_stride or r8, peaks_stride or max(0, n_peaks))
+        _check(self._ctx, self._lib.efx_pcm_limit(self._ctx, o.ctypes.data, _ptr(src), _ptr(peaks), _ptr(recs), _ptr(dst)))
+
+    def _limit_queue(self, s_peaks: DeviceBuffer, src_ptr: int, recs, dst_ptr: int, n: int, samples: int, stride: int, rate: int,
+                     half_window: int, thr, fixed_gain_q12: int = 4096):
+        """peaks -> limit over whole fresh streams with a peaks buffer of n x ceil(samples / Bk) entries: launches only."""
+        nb = _limit_blocks(samples, rate)
+        self.limit_peaks_to(src_ptr, s_peaks, n_streams=n, n_samples=samples, rate=rate, pcm_stride=stride, peaks_stride=nb)
+        self.pcm_limit_to(src_ptr, s_peaks, recs, dst_ptr, n_streams=n, n_samples=samples, rate=rate, n_peaks=nb,
+                          half_window=half_window, thresholds=thr, fixed_gain_q12=fixed_gain_q12, src_stride=stride,
+                          dst_stride=stride, peaks_stride=nb)
+
+    def limit(self, pcm, rate: int, *, gain_q12: int = 4096, peak: float = -1.0, half_window: int = 32):
+        """The peak limiter alone: mono int16 PCM [n_streams, samples] at `rate` (a NumPy array or a torch tensor on the
+        decoder's device), every stream whole, scaled by gain_q12 / 4096 with the gain reduced smoothly around the samples
+        that would pass `peak` dBFS (include/efx.h, "peak limiter"): peaks -> limit queued back to back.  Returns int16
+        [n_streams, samples] of the input's kind; no output sample is above the ceiling."""
+        import torch
+        device = torch.device("cuda", self.device)
+        is_array = isinstance(pcm, np.ndarray)
+        if is_array:
+            pcm = torch.from_numpy(np.ascontiguousarray(pcm, dtype=np.int16)).to(device)
+        if len(getattr(pcm, "shape", ())) != 2 or pcm.shape[1] < 1:
+            raise ValueError(f"pcm must be int16 [n_streams, samples] on {device} (or a NumPy array)")
+        n, samples = int(pcm.shape[0]), int(pcm.shape[1])
+        n_peaks = _limit_blocks(samples, rate)
+        stride = _r8(samples)
+        thr = loudness_thresholds(rate, -23.0, peak)
+        with self._scratch() as s:
+            src_ptr, _, _ = self._stage(s, pcm, n, samples, stride=stride, dtype=np.int16, what="pcm")
+            out = torch.empty((n, stride), dtype=torch.int16, device=device)
+            d_peaks = s.alloc(_r16(2 * n * n_peaks))
+            self._wait_for_torch()
+            self._limit_queue(d_peaks, src_ptr, None, out.data_ptr(), n, samples, stride, rate, half_window, thr, gain_q12)
+            self.sync()
+        return out[:, :samples].cpu().numpy() if is_array else out[:, :samples]
+
     def _loudness_buffers(self, s: _Scratch, n: int, samples: int, rate: int, target: float, peak: float):
         """What measuring n fresh streams of `samples` samples needs, made ready in the scratch s: (state (zeroed), steps,
         records) on the device, the step count and the thresholds.  The upload synchronises the library's stream, so
@@ -2054,7 +2147,7 @@ class Decoder:
         peak no higher than `peak` dBFS.  Synchronises torch's current stream before and the library's after."""
         return self._measure(pcm, rate, target, peak, gain=False)[1]
 
-    def normalize(self, pcm, rate: int, *, target: float = -23.0, peak: float = -1.0):
+    def normalize(self, pcm, rate: int, *, target: float = -23.0, peak: float = -1.0, limiter: bool = False, half_window: int = 32):
         """loudness() and the gain applied, measure -> gate -> gain queued back to back with the gain read on the device:
         returns (pcm_out, LoudnessResult), pcm_out int16 [n_streams, samples], a NumPy array for a NumPy input, else a
         torch tensor on the device.  The result describes the input; the output sits at target (or as close as the peak
@@ -2062,11 +2155,19 @@ class Decoder:
 
         A title fed in pieces needs the whole title measured before its first sample is scaled, so it takes two passes
         over the *_to calls: loudness_steps_to over every piece (first_sample and the state carried on), one
-        loudness_gate_to over all its steps, then pcm_gain_to per piece with the records it left."""
-        out, res = self._measure(pcm, rate, target, peak, gain=True)
+        loudness_gate_to over all its steps, then pcm_gain_to per piece with the records it left.
+
+        limiter=True: steps -> gate -> peaks -> limit in place of steps -> gate -> gain.  One loud sample no longer caps
+        the gain of the whole title: every stream gets the full loudness gain -- limit_gain(gated_mean, n_gated, target_ms,
+        rate), not the result's gain_q12, which stays the capped gain of the record -- reduced smoothly within half_window
+        blocks of about 1 ms (1 .. 64) around the samples that would pass `peak` dBFS.  A stream whose cap does not bind
+        comes out bit for bit as without the limiter.  The limited title lands slightly under the target, by the energy
+        of what was limited; no second pass measures it again.  In pieces: limit_peaks_to over every piece in the first
+        pass, into a row the caller keeps, and pcm_limit_to per piece in the second (pcm_limit_to's docstring)."""
+        out, res = self._measure(pcm, rate, target, peak, gain=True, limiter=limiter, half_window=half_window)
         return (out.cpu().numpy() if isinstance(pcm, np.ndarray) else out), res
 
-    def _measure(self, pcm, rate: int, target: float, peak: float, gain: bool):
+    def _measure(self, pcm, rate: int, target: float, peak: float, gain: bool, limiter: bool = False, half_window: int = 32):
         """loudness() and normalize(): (the scaled PCM as a tensor [n_streams, samples] when gain, else None, the result)."""
         import torch
         device = torch.device("cuda", self.device)
@@ -2081,8 +2182,11 @@ class Decoder:
             out = torch.empty((n, stride), dtype=torch.int16, device=device) if gain else None
             self._wait_for_torch()
             prepared = self._loudness_buffers(s, n, samples, rate, target, peak)
+            d_peaks = s.alloc(_r16(2 * n * _limit_blocks(samples, rate))) if gain and limiter else None
             d_recs = self._loudness_queue(src_ptr, n, samples, stride, rate, prepared)
-            if gain:
+            if d_peaks is not None:
+                self._limit_queue(d_peaks, src_ptr, d_recs, out.data_ptr(), n, samples, stride, rate, half_window, prepared[2])
+            elif gain:
                 self.pcm_gain_to(src_ptr, d_recs, out.data_ptr(), n_streams=n, n_samples=samples, src_stride=stride, dst_stride=stride)
             self.sync()
             res = self._loudness_result(d_recs.download(np.uint8, 32 * n).view(LOUDNESS_REC_DTYPE), rate)
@@ -2204,7 +2308,7 @@ class Decoder:
                   audio_pid: int = 0x101, bitrate: int | None = None, vbv_bits: int = 250_000, qmin: int = 3, qmax: int = 31,
                   pcm_rate: int | None = None, pcm_layout: str = "interleaved", fps=None, scene_cut: int | bool | None = None,
                   min_gop: int | None = None, quality: bool = False, aq: int | bool | None = None, loudness: float | None = None,
-                  peak: float = -1.0):
+                  peak: float = -1.0, limiter: bool = False, half_window: int = 32):
         """Pictures + PCM -> complete titles: encode (transport streams) -> sbc_encode (mono) -> mux, queued back to back on
         the library's stream with nothing synchronised in between.  pictures: (n, P, 101376) I420 as for encode(); pcm: int16
         [n, samples], a whole number of frames of blocks x 8 samples; the audio starts at the first picture's PTS.  Every
@@ -2232,6 +2336,11 @@ class Decoder:
         to that programme loudness with its sample peak no higher than `peak` dBFS, queued in front of sbc_encode_to
         with nothing synchronised in between: the gain stays on the device.  None (the default): no launch, no
         allocation, the title's bytes are what they were without the keyword.
+
+        limiter, half_window: with loudness=, the peak limiter (limit_peaks_to, pcm_limit_to) takes pcm_gain_to's place, as
+        for normalize(limiter=True): the full loudness gain, reduced around the samples that would pass `peak` dBFS, so
+        that a few loud samples do not hold the whole title under its target.  Without loudness= they do nothing.  False
+        (the default): no launch and no allocation of the limiter's, the title's bytes are what they were.
 
         quality=True: the video's reconstruction is kept in a device buffer of the call's own and compared with the
         pictures right behind the encode, on the same stream, as for encode(); the call then returns (titles, status,
@@ -2281,6 +2390,7 @@ class Decoder:
                 # (buffers and the zeroed state now: an upload waits for what is queued on the library's stream)
                 loud_rate = {v: k for k, v in _SBC_FREQUENCY.items()}[frequency]
                 loud = self._loudness_buffers(s, n, samples, loud_rate, loudness, peak)
+                d_lpeaks = s.alloc(_r16(2 * n * _limit_blocks(samples, loud_rate))) if limiter else None
                 if imp is None:
                     pcm = pcm.clone()  # (scaled in place: the caller's tensor stays as it is)
             pic_ptr, _, _ = self._stage(s, pictures, n * P, FRAME_BYTES, what="pictures")
@@ -2299,7 +2409,10 @@ class Decoder:
                                    dst_stride=samples)
             if loud is not None:
                 d_lrecs = self._loudness_queue(pcm_ptr, n, samples, samples, loud_rate, loud)
-                self.pcm_gain_to(pcm_ptr, d_lrecs, pcm_ptr, n_streams=n, n_samples=samples, src_stride=samples, dst_stride=samples)
+                if d_lpeaks is not None:
+                    self._limit_queue(d_lpeaks, pcm_ptr, d_lrecs, pcm_ptr, n, samples, samples, loud_rate, half_window, loud[2])
+                else:
+                    self.pcm_gain_to(pcm_ptr, d_lrecs, pcm_ptr, n_streams=n, n_samples=samples, src_stride=samples, dst_stride=samples)
             if n_frames:
                 self.sbc_encode_to(pcm_ptr, d_state, d_a, n_streams=n, n_frames=n_frames, blocks=blocks, mode=0,
                                    allocation=allocation, bitpool=bitpool, frequency=frequency, pcm_stride=samples,
@@ -2515,7 +2628,8 @@ class Decoder:
         scene_cut=, min_gop= (among **encode_av) apply to video.ts only: the trick streams keep their GOPs of trick_gop.
         aq: adaptive quantisation as for encode(), of video.ts and of both trick streams.
 
-        loudness=, peak= (among **encode_av): video.ts's sound levelled to a target in LUFS, as for encode_av().
+        loudness=, peak=, limiter=, half_window= (among **encode_av): video.ts's sound levelled to a target in LUFS, with
+        the peak limiter if asked, as for encode_av().
 
         overlays: a list of Overlay (subtitles, a logo) burnt into the pictures once, on the device (overlay()), after
         any conform: Overlay.first / .last are indices of the CODED timeline, picture 0 being the first coded picture

@@ -189,6 +189,13 @@ OVERLAY_EVENT_DTYPE = np.dtype([("first", "<i8"), ("last", "<i8"), ("offset", "<
                                 ("fade_in", "<u2"), ("fade_out", "<u2"), ("kind", "u1"), ("reserved0", "u1"), ("reserved", "<u8")])
 OVERLAY_OPTS_DTYPE = np.dtype([("n_streams", "<i4"), ("n_pictures", "<i4"), ("n_events", "<i4"), ("reserved", "<i4"),
                                ("first_picture", "<i8"), ("stride", "<u8"), ("atlas_bytes", "<u8")])
+# efx_limit_peaks_opts and efx_limit_opts (passed like efx_denoise_opts)
+LIMIT_PEAKS_OPTS_DTYPE = np.dtype([("n_streams", "<i4"), ("n_samples", "<i4"), ("rate", "<i4"), ("reserved", "<i4"),
+                                   ("first_sample", "<i8"), ("peaks_first", "<i8"), ("pcm_stride", "<u8"), ("peaks_stride", "<u8")])
+LIMIT_OPTS_DTYPE = np.dtype([("n_streams", "<i4"), ("n_samples", "<i4"), ("rate", "<i4"), ("half_window", "<i4"), ("ceiling", "<i4"),
+                             ("fixed_gain_q12", "<i4"), ("n_peaks", "<i4"), ("reserved", "<i4"), ("first_sample", "<i8"),
+                             ("peaks_first", "<i8"), ("target_ms", "<u8"), ("src_stride", "<u8"), ("dst_stride", "<u8"),
+                             ("peaks_stride", "<u8")])
 
 # every symbol include/efx.h declares: (name, restype, argtypes)
 _P = C.c_void_p
@@ -292,6 +299,10 @@ _SYMBOLS = {
     "efx_loudness_coefs": (C.c_int, [C.c_int, C.POINTER(C.c_int32)]),
     "efx_loudness_state_bytes": (C.c_size_t, [C.c_int]),
     "efx_loudness_step_count": (C.c_int, [C.c_int, C.c_int64, C.c_int]),
+    "efx_limit_peaks": (C.c_int, [_P, _P, _P, _P]),
+    "efx_pcm_limit": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "efx_limit_block": (C.c_int, [C.c_int]),
+    "efx_limit_gain": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint64, C.c_int]),
     "efx_mux_av": (C.c_int, [_P, C.POINTER(_MuxOpts), _P, _P, _P, _P, _P, _P]),
     "efx_mux_bound": (C.c_size_t, [C.c_size_t, C.c_int, C.c_int, C.c_int]),
     "efx_mux_audio_packets": (C.c_int, [C.c_int, C.c_int, C.c_int]),

@@ -104,6 +104,8 @@ __global__ void k_loud_steps(LoudStepsArgs);  // (k_loudness.hip)
 __global__ void k_loud_state(LoudStepsArgs);
 __global__ void k_loud_gate(LoudGateArgs);
 __global__ void k_pcm_gain(PcmGainArgs);
+__global__ void k_limit_peaks(LimitPeaksArgs);  // (k_limit.hip)
+__global__ void k_pcm_limit(PcmLimitArgs);
 __global__ void k_enc_begin(EncArgs);
 __global__ void k_enc_aq(EncArgs);
 __global__ void k_enc_cut(EncArgs);
@@ -3476,6 +3478,112 @@ int efx_pcm_gain(efx_ctx* ctx, const efx_pcm_gain_opts* o, const int16_t* src_de
     // (grid.y is strided over by the kernel: the cap only bounds the launch)
     const int per_stream = std::max(1, std::min((o->n_samples + 2047) / 2048, (8 * ctx->n_cus + o->n_streams - 1) / o->n_streams));
     hipLaunchKernelGGL(k_pcm_gain, dim3((unsigned)o->n_streams, (unsigned)per_stream), dim3(256), 0, ctx->stream, a);
+    EFX_HIP(hipGetLastError());
+    return EFX_OK;
+}
+
+// ---- peak limiter (k_limit.hip) ---------------------------------------------------------------------------------------------------
+int efx_limit_block(int rate) { return limit::block_of(rate); }
+
+int efx_limit_gain(uint64_t gated_mean, uint32_t n_gated, uint64_t target_ms, int rate)
+{
+    if (!loud::rate_ok(rate) || target_ms >= loud::kMaxTarget)
+        return 0;
+    return loud::stream_gain_q12(gated_mean, n_gated, target_ms, loud::step_of(rate));
+}
+
+// workgroups per stream: every tile one, up to eight workgroups per compute unit over the streams (the kernels stride over
+// grid.y, so the cap only bounds the launch)
+static unsigned limit_grid_y(const efx_ctx* ctx, int n_streams, int n_samples, int bk)
+{
+    const int64_t n_tiles = ((int64_t)n_samples + (int64_t)limit::kTile * bk - 1) / ((int64_t)limit::kTile * bk);
+    const int64_t share = (8 * (int64_t)ctx->n_cus + n_streams - 1) / n_streams;
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(std::min(n_tiles, share), 65535));
+}
+
+int efx_limit_peaks(efx_ctx* ctx, const efx_limit_peaks_opts* o, const int16_t* pcm_device, uint16_t* peaks_device)
+{
+    bind_device(ctx);
+    if (!ctx || !o)
+        return EFX_ERR_ARG;
+    auto misaligned = [](const void* p) { return !p || ((uintptr_t)p & 15); };
+    if (o->n_streams < 1 || o->n_streams > ctx->cfg.max_streams)
+        return fail(ctx, EFX_ERR_ARG, "efx_limit_peaks: n_streams outside 1 .. max_streams");
+    const int bk = limit::block_of(o->rate);
+    if (!bk)
+        return fail(ctx, EFX_ERR_ARG, "efx_limit_peaks: rate must be 16000, 32000, 44100 or 48000");
+    if (o->n_samples < 1)
+        return fail(ctx, EFX_ERR_ARG, "efx_limit_peaks: n_samples must be >= 1");
+    if (o->first_sample < 0 || o->first_sample >= limit::kMaxFirstSample || o->first_sample % bk)
+        return fail(ctx, EFX_ERR_ARG, "efx_limit_peaks: first_sample outside 0 .. 2^40 - 1 or not a multiple of the block length");
+    const int64_t first_block = o->first_sample / bk, n_blocks = ((int64_t)o->n_samples + bk - 1) / bk;
+    if (o->peaks_first < 0 || o->peaks_first > first_block)
+        return fail(ctx, EFX_ERR_ARG, "efx_limit_peaks: peaks_first outside 0 .. first_sample / block length");
+    if (o->pcm_stride < (uint64_t)o->n_samples || (o->pcm_stride & 7))
+        return fail(ctx, EFX_ERR_ARG, "efx_limit_peaks: pcm_stride must be a multiple of 8 and hold n_samples elements");
+    if (o->peaks_stride < (uint64_t)(first_block - o->peaks_first + n_blocks))
+        return fail(ctx, EFX_ERR_ARG, "efx_limit_peaks: peaks_stride must hold the call's blocks behind first_sample / block length - peaks_first");
+    if (misaligned(pcm_device) || misaligned(peaks_device))
+        return fail(ctx, EFX_ERR_ARG, "efx_limit_peaks: pcm and peaks must be 16-byte aligned device pointers");
+    LimitPeaksArgs a{};
+    a.pcm = pcm_device, a.peaks = peaks_device;
+    a.pcm_stride = (size_t)o->pcm_stride, a.peaks_stride = (size_t)o->peaks_stride;
+    a.entry0 = first_block - o->peaks_first;
+    a.n_samples = o->n_samples, a.bk = bk;
+    hipLaunchKernelGGL(k_limit_peaks, dim3((unsigned)o->n_streams, limit_grid_y(ctx, o->n_streams, o->n_samples, bk)), dim3(limit::kThreads), 0,
+                       ctx->stream, a);
+    EFX_HIP(hipGetLastError());
+    return EFX_OK;
+}
+
+int efx_pcm_limit(efx_ctx* ctx, const efx_limit_opts* o, const int16_t* src_device, const uint16_t* peaks_device,
+                  const efx_loudness_rec* recs_device, int16_t* dst_device)
+{
+    bind_device(ctx);
+    if (!ctx || !o)
+        return EFX_ERR_ARG;
+    auto misaligned = [](const void* p) { return !p || ((uintptr_t)p & 15); };
+    if (o->n_streams < 1 || o->n_streams > ctx->cfg.max_streams)
+        return fail(ctx, EFX_ERR_ARG, "efx_pcm_limit: n_streams outside 1 .. max_streams");
+    const int bk = limit::block_of(o->rate);
+    if (!bk)
+        return fail(ctx, EFX_ERR_ARG, "efx_pcm_limit: rate must be 16000, 32000, 44100 or 48000");
+    if (o->n_samples < 1)
+        return fail(ctx, EFX_ERR_ARG, "efx_pcm_limit: n_samples must be >= 1");
+    if (o->half_window < 0 || o->half_window > limit::kMaxHalf)
+        return fail(ctx, EFX_ERR_ARG, "efx_pcm_limit: half_window outside 0 .. 64");
+    if (o->first_sample < 0 || o->first_sample >= limit::kMaxFirstSample || o->first_sample % bk)
+        return fail(ctx, EFX_ERR_ARG, "efx_pcm_limit: first_sample outside 0 .. 2^40 - 1 or not a multiple of the block length");
+    if (o->peaks_first < 0 || o->peaks_first >= limit::kMaxFirstSample)
+        return fail(ctx, EFX_ERR_ARG, "efx_pcm_limit: peaks_first outside 0 .. 2^40 - 1");
+    if (o->n_peaks < 1)
+        return fail(ctx, EFX_ERR_ARG, "efx_pcm_limit: n_peaks must be >= 1");
+    if (o->ceiling < 1 || o->ceiling > 32767)
+        return fail(ctx, EFX_ERR_ARG, "efx_pcm_limit: ceiling outside 1 .. 32767");
+    if (recs_device && o->target_ms >= loud::kMaxTarget)
+        return fail(ctx, EFX_ERR_ARG, "efx_pcm_limit: target_ms must be below 2^40");
+    if (!recs_device && (o->fixed_gain_q12 < 1 || o->fixed_gain_q12 > loud::kMaxGain))
+        return fail(ctx, EFX_ERR_ARG, "efx_pcm_limit: fixed_gain_q12 outside 1 .. 32767");
+    if (o->src_stride < (uint64_t)o->n_samples || (o->src_stride & 7) || o->dst_stride < (uint64_t)o->n_samples || (o->dst_stride & 7))
+        return fail(ctx, EFX_ERR_ARG, "efx_pcm_limit: the sample strides must be multiples of 8 and hold n_samples elements");
+    if (o->peaks_stride < (uint64_t)o->n_peaks)
+        return fail(ctx, EFX_ERR_ARG, "efx_pcm_limit: peaks_stride must hold n_peaks entries");
+    if (dst_device == src_device && o->dst_stride != o->src_stride)
+        return fail(ctx, EFX_ERR_ARG, "efx_pcm_limit: in place (dst == src) needs equal sample strides");
+    if (misaligned(src_device) || misaligned(dst_device) || misaligned(peaks_device) || ((uintptr_t)recs_device & 15))
+        return fail(ctx, EFX_ERR_ARG, "efx_pcm_limit: src, peaks and dst must be 16-byte aligned device pointers, recs NULL or aligned");
+    PcmLimitArgs a{};
+    a.src = src_device, a.peaks = peaks_device, a.dst = dst_device;
+    a.recs = reinterpret_cast<const loud::GateRec*>(recs_device);
+    a.src_stride = (size_t)o->src_stride, a.dst_stride = (size_t)o->dst_stride, a.peaks_stride = (size_t)o->peaks_stride;
+    a.first_block = o->first_sample / bk, a.peaks_first = o->peaks_first;
+    a.target_ms = o->target_ms;
+    a.n_samples = o->n_samples, a.n_peaks = o->n_peaks, a.bk = bk;
+    a.half = o->half_window ? o->half_window : limit::kDefaultHalf;
+    a.ceiling = o->ceiling, a.fixed_gain = o->fixed_gain_q12, a.step = loud::step_of(o->rate);
+    a.div = limit::div_of(bk);
+    hipLaunchKernelGGL(k_pcm_limit, dim3((unsigned)o->n_streams, limit_grid_y(ctx, o->n_streams, o->n_samples, bk)), dim3(limit::kThreads), 0,
+                       ctx->stream, a);
     EFX_HIP(hipGetLastError());
     return EFX_OK;
 }

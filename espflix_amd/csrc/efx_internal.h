@@ -20,6 +20,7 @@
 #include "enc_rate.h"
 #include "import_pcm.h"
 #include "loudness_px.h"
+#include "limit_px.h"
 
 namespace efx {
 
@@ -265,6 +266,28 @@ struct PcmGainArgs {
     int16_t* dst;                // stream i at dst + i * dst_stride; may be src
     size_t src_stride, dst_stride;
     int n_samples, fixed_gain;
+};
+
+// k_limit_peaks launch arguments (by value): efx_limit_peaks_opts, checked
+struct LimitPeaksArgs {
+    const int16_t* pcm;          // stream i at pcm + i * pcm_stride
+    uint16_t* peaks;             // stream i's row at peaks + i * peaks_stride
+    size_t pcm_stride, peaks_stride;
+    int64_t entry0;              // the row's entry of the call's first block: first_sample / Bk - peaks_first
+    int n_samples, bk;
+};
+
+// k_pcm_limit launch arguments (by value): efx_limit_opts, checked
+struct PcmLimitArgs {
+    const int16_t* src;          // stream i at src + i * src_stride
+    const uint16_t* peaks;       // stream i's row of n_peaks entries at peaks + i * peaks_stride; entry 0: block peaks_first
+    const loud::GateRec* recs;   // null: fixed_gain
+    int16_t* dst;                // stream i at dst + i * dst_stride; may be src
+    size_t src_stride, dst_stride, peaks_stride;
+    int64_t first_block, peaks_first;
+    uint64_t target_ms;
+    int n_samples, n_peaks, bk, half, ceiling, fixed_gain, step;
+    limit::DivBk div;
 };
 
 // per-stream result of k_ts_sequences

@@ -192,18 +192,29 @@ EFX_LOUD_HD inline uint32_t isqrt(uint64_t x)
     return (uint32_t)r;
 }
 
+// The gain that takes a stream to the target with no regard to its peak (include/efx.h): T = target_ms < 2^40; 1 .. 32767.
+// What gain_q12 caps and what the limiter (limit_px.h) aims at.
+EFX_LOUD_HD inline int stream_gain_q12(uint64_t gated_mean, uint32_t n_gated, uint64_t T, int step)
+{
+    if (n_gated == 0)
+        return kUnity;
+    uint64_t q = udiv128(((u128)T << 24) * (uint64_t)(4 * step), gated_mean ? gated_mean : 1);
+    if (q > ((uint64_t)1 << 32))
+        q = (uint64_t)1 << 32;  // (the clamp below is at 32767)
+    const uint64_t g = isqrt(q);
+    return g < 1 ? 1 : (g > (uint64_t)kMaxGain ? kMaxGain : (int)g);
+}
+
 // gain_q12 of a stream (include/efx.h): T = target_ms < 2^40, C = ceiling 1 .. 32767
 EFX_LOUD_HD inline int gain_q12(uint64_t gated_mean, uint32_t n_gated, uint32_t peak, uint64_t T, uint32_t C, int step)
 {
     if (n_gated == 0 || peak == 0)
         return kUnity;
-    uint64_t q = udiv128(((u128)T << 24) * (uint64_t)(4 * step), gated_mean ? gated_mean : 1);
-    if (q > ((uint64_t)1 << 32))
-        q = (uint64_t)1 << 32;  // (the clamp below is at 32767)
-    uint64_t g = isqrt(q);
+    // (clamping the uncapped gain to 1 .. 32767 before the cap gives what clamping after it gave: min and clamp commute)
+    uint64_t g = (uint64_t)stream_gain_q12(gated_mean, n_gated, T, step);
     const uint64_t cap = udiv128((u128)(4096ull * C), peak);
     g = g < cap ? g : cap;
-    return g < 1 ? 1 : (g > (uint64_t)kMaxGain ? kMaxGain : (int)g);
+    return g < 1 ? 1 : (int)g;
 }
 
 EFX_LOUD_HD inline int apply_gain(int x, int g)

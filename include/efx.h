@@ -1635,7 +1635,8 @@ int efx_import_pcm_filter(int32_t* out, int cap);
  * loudness, maximum momentary loudness and sample peak (ffmpeg's ebur128); derive one gain per stream for a target
  * loudness under a peak ceiling (loudnorm in linear mode); and apply it (volume) -- all on the device, the gain never
  * visits the host.  Sample peak with a ceiling of -1 dBFS stands in for true peak: no oversampling.  Not measured: true
- * peak, loudness range, short-term loudness; no limiter, no dynamic mode.
+ * peak, loudness range, short-term loudness.  A title whose peaks cap that one gain goes through the peak limiter of the
+ * next section (efx_limit_peaks, efx_pcm_limit) in efx_pcm_gain's place; there is no compressor and no dynamic mode.
  *
  * Meaning.  step = rate / 10 samples (100 ms: 1600, 3200, 4410, 4800), W = step / 2.  Step s of a stream covers samples
  * s step .. (s + 1) step - 1.  Its energy is DEFINED by a K-weighting filter that starts at rest at sample s step - W and
@@ -1670,6 +1671,8 @@ int efx_import_pcm_filter(int32_t* out, int cap);
  *     g = floor(sqrt(min(floor(2^24 T 4 step / gated_mean), 2^32)))         (128-bit dividend)
  *     g = min(g, floor(4096 C / peak)), then clamped to 1 .. 32767          (Q12: just under +18 dB)
  *     g = 4096 when n_gated = 0 or peak = 0.
+ *   (The first line, clamped to 1 .. 32767 and 4096 when n_gated = 0, is the stream gain G of the peak limiter:
+ *   efx_limit_gain.)
  *   Apply.  y = clamp16((x g + 2048) >> 12); g = 4096 returns x.
  *
  * State.  efx_loudness_state_bytes(rate) per stream, 16-byte aligned: the newest H = (W + step + 7) & ~7 samples of the
@@ -1761,6 +1764,97 @@ size_t efx_loudness_state_bytes(int rate);
 /* floor((first_sample + n_samples) / step) - floor(first_sample / step); -1 for arguments efx_loudness_steps rejects.
  * Host only. */
 int efx_loudness_step_count(int rate, int64_t first_sample, int n_samples);
+
+/* -- peak limiter (k_limit.hip) -------------------------------------------------------------------- */
+/* efx_pcm_gain gives a stream ONE gain, min(loudness gain, floor(4096 C / peak)): a single loud sample anywhere caps the
+ * gain of the whole title, and a peaky title stays far under its target.  The limiter applies the full loudness gain G
+ * everywhere and reduces it smoothly around the samples that would pass the ceiling (ffmpeg's alimiter behind volume).
+ * It looks ahead and behind by whole windows and has NO recurrence -- a sliding minimum followed by a box average, not an
+ * attack / release envelope follower -- so every block of a stream is independent work and pieces equal one long call.
+ * Sample peak, as in the section above: no oversampling, true peak is not measured.  No compressor, no dynamic mode.
+ * The limited title lands slightly UNDER the target, by the energy of what was limited (about 1.3 LU on a title whose
+ * bursts would otherwise have cost 9 LU: tests/test_limit_model.py); no second measuring pass trims that shortfall.
+ *
+ * The rule (espflix_amd/csrc/limit_px.h; tests/limit_model.py restates it), in exact integers; >> is arithmetic, floor()
+ * of non-negative operands:
+ *   Block length.  Bk = 16, 32, 48, 48 samples at 16000, 32000, 44100, 48000 Hz (efx_limit_block): about 1 ms, a whole
+ *   number of 32-byte pieces.  Block b of a stream holds samples b Bk .. b Bk + Bk - 1; the last may be partial.
+ *   Block peak.  p[b] = the largest |x| of the block's samples, 32768 for -32768, a uint16_t; blocks in front of the
+ *   stream and behind it have p = 0.
+ *   Stream gain G (Q12, 1 .. 32767).  floor(sqrt(min(floor(2^24 T 4 step / gated_mean), 2^32))) clamped to 1 .. 32767,
+ *   4096 when n_gated = 0: the loudness gain of the section above without its peak cap (efx_limit_gain), worked out on
+ *   the device from the stream's efx_loudness_rec with T = target_ms; or fixed_gain_q12 when no records are given.
+ *   Required gain.  r[b] = G where p[b] = 0, else min(G, floor(4096 C / p[b])), C = ceiling 1 .. 32767; r may be 0.
+ *   Then |x| r <= 4096 C, so (x r + 2048) >> 12 lies in -C .. C.
+ *   Nodes.  Node b is the border between blocks b - 1 and b: q[b] = min(r[b - 1], r[b]).
+ *   Smoothing.  With the half window H (1 .. 64 blocks, default 32) and W = 2 H + 1:
+ *     M[j] = min(q[j - H] .. q[j + H]),  a[b] = floor((M[b - H] + .. + M[b + H]) / W).
+ *   Every M of the sum has q[b] inside its window, so a[b] <= q[b].
+ *   Gain of sample n of block b, t = n - b Bk:  g = floor((a[b] (Bk - t) + a[b + 1] t) / Bk)  <= r[b].
+ *   Output.  y = clamp16((x g + 2048) >> 12); the clamp never acts.
+ * Two consequences.  Where no block has r < G the output is efx_pcm_gain's with gain G, bit for bit.  The samples of
+ * blocks b0 .. b1 - 1 depend on the peaks of blocks b0 - 2 H - 1 .. b1 + 2 H and on nothing else.
+ *
+ * Pieces.  The block grid is anchored at stream sample 0 and there is no state: a piece begins at a multiple of Bk and
+ * every piece but a stream's last is a whole number of blocks.  A title takes two passes, as for efx_pcm_gain: the first
+ * measures (efx_loudness_steps) and takes the peaks (efx_limit_peaks) of every piece; after efx_loudness_gate the second
+ * limits every piece (efx_pcm_limit).  The caller keeps the peaks: the whole title's row (2 bytes per millisecond), or for
+ * each piece the 2 H + 1 blocks either side of it as far as the stream has them.
+ *
+ * Memory contract.  efx_limit_peaks reads, for stream i, only the n_samples int16 from pcm + i * pcm_stride and writes only
+ * the ceil(n_samples / Bk) entries from peaks + i * peaks_stride + first_sample / Bk - peaks_first.  efx_pcm_limit reads only
+ * the n_samples samples of each stream, entries 0 .. n_peaks - 1 of each row and gated_mean and n_gated of each record, and
+ * writes only the n_samples samples of each stream: bytes of a row behind n_samples stay as they were.  Samples go in
+ * 16-byte pieces, a last partial piece element by element.  All device pointers are 16-byte aligned, the sample strides
+ * are multiples of 8 elements.  Both calls are one launch each, asynchronous on the context's stream, without allocation
+ * or host synchronisation: steps -> gate -> peaks -> limit -> efx_sbc_encode queue back to back. */
+typedef struct efx_limit_peaks_opts {  /* fixed-width fields only */
+    int32_t n_streams;      /* 1 .. max_streams */
+    int32_t n_samples;      /* samples per stream in this call, >= 1; a multiple of Bk on every piece but a stream's last */
+    int32_t rate;           /* 16000, 32000, 44100 or 48000 */
+    int32_t reserved;
+    int64_t first_sample;   /* index in the stream of this call's first sample: a multiple of Bk, 0 .. 2^40 - 1 */
+    int64_t peaks_first;    /* the stream block that entry 0 of a row holds, 0 .. first_sample / Bk */
+    uint64_t pcm_stride;    /* int16 elements between streams, >= n_samples, multiple of 8 */
+    uint64_t peaks_stride;  /* entries between rows, >= first_sample / Bk - peaks_first + ceil(n_samples / Bk) */
+} efx_limit_peaks_opts;
+/* p of the call's blocks: entry first_sample / Bk - peaks_first of stream i's row receives its first block's peak.  One
+ * launch; it reads the samples only.
+ * EFX_ERR_ARG: n_streams, n_samples, first_sample or peaks_first out of range, first_sample not a multiple of Bk, a rate
+ * that is not one of the four, a NULL or misaligned (16 bytes) pointer, pcm_stride too small or not a multiple of 8,
+ * peaks_stride too small. */
+int efx_limit_peaks(efx_ctx* ctx, const efx_limit_peaks_opts* opts, const int16_t* pcm_device, uint16_t* peaks_device);
+typedef struct efx_limit_opts {        /* fixed-width fields only */
+    int32_t n_streams;      /* 1 .. max_streams */
+    int32_t n_samples;      /* samples per stream in this call, >= 1 */
+    int32_t rate;           /* 16000, 32000, 44100 or 48000 */
+    int32_t half_window;    /* H in blocks, 1 .. 64; 0 = 32 */
+    int32_t ceiling;        /* C, 1 .. 32767 (efx_loudness_thresholds) */
+    int32_t fixed_gain_q12; /* 1 .. 32767: every stream's G when recs_device is NULL (else ignored) */
+    int32_t n_peaks;        /* entries of a row, >= 1; a block outside the row counts as p = 0 */
+    int32_t reserved;
+    int64_t first_sample;   /* index in the stream of this call's first sample: a multiple of Bk, 0 .. 2^40 - 1 */
+    int64_t peaks_first;    /* the stream block that entry 0 of a row holds, 0 .. 2^40 - 1 */
+    uint64_t target_ms;     /* T, below 2^40 (efx_loudness_thresholds); used with recs_device */
+    uint64_t src_stride;    /* int16 elements between streams, >= n_samples, multiples of 8 */
+    uint64_t dst_stride;
+    uint64_t peaks_stride;  /* entries between rows, >= n_peaks */
+} efx_limit_opts;
+/* dst[i][n] = the rule's y for stream i's samples first_sample .. first_sample + n_samples - 1, G_i from recs[i] on the
+ * device (or fixed_gain_q12), the peaks those an earlier efx_limit_peaks left.  dst_device == src_device (with equal
+ * strides) works in place -- the peaks were taken by the earlier launch, so no workgroup reads what another writes --
+ * otherwise the two must not overlap.  One launch.  It queues behind efx_loudness_gate and in front of efx_sbc_encode.
+ * EFX_ERR_ARG: n_streams, n_samples, half_window, ceiling, n_peaks, first_sample or peaks_first out of range, first_sample
+ * not a multiple of Bk, target_ms (with records) or fixed_gain_q12 (without) out of range, a rate that is not one of the
+ * four, a NULL or misaligned (16 bytes) src / peaks / dst, a misaligned recs, a sample stride too small or not a multiple
+ * of 8, peaks_stride below n_peaks, dst_device == src_device with unequal sample strides. */
+int efx_pcm_limit(efx_ctx* ctx, const efx_limit_opts* opts, const int16_t* src_device, const uint16_t* peaks_device,
+                  const efx_loudness_rec* recs_device, int16_t* dst_device);
+/* Bk: 16, 32, 48 or 48; 0 for a rate that is not one of the four.  Host only. */
+int efx_limit_block(int rate);
+/* G of a stream from the fields of its efx_loudness_rec; 0 for a rate that is not one of the four or target_ms >= 2^40.
+ * Host only. */
+int efx_limit_gain(uint64_t gated_mean, uint32_t n_gated, uint64_t target_ms, int rate);
 
 /* -- A/V multiplexer: video transport stream + SBC frames -> a title (espflix_amd/csrc/k_mux.hip) -- */
 /* The reference player takes its audio from PES packets on PID 0x101 / 0x102 of the transport stream that carries the
